@@ -212,6 +212,42 @@ def time_steps(ctx, step, steps, warmup, event_slot=None, L=None):
     return out
 
 
+def emit(fd, out):
+    """write THE result line to the real stdout, after everything buffered for fd 1 (pointed at stderr) has gone out --
+    otherwise Python's block-buffered sys.stdout is flushed at exit, after the JSON line, and the line is no longer last"""
+    import ctypes
+    sys.stdout.flush()
+    sys.stderr.flush()
+    try:
+        ctypes.CDLL(None).fflush(None)
+    except (OSError, AttributeError):
+        pass
+    os.write(fd, (json.dumps(out) + "\n").encode())
+
+
+DUMP_BUDGET = 64 << 20      # --dump-outputs: bytes of .npy payload at most
+DUMP_SAMPLE = 2_000_000     # rows of the per-splat outputs kept when the whole would not fit (fixed seed)
+
+
+def dump_sor_outputs(out_dir, mask, mean_dists, stats):
+    """--dump-outputs: what a caller of the timed SOR step receives -- survivor mask, per-splat KNN mean distance and
+    (mean, std, threshold) -- as float32 / float64 .npy files; above DUMP_BUDGET the per-splat arrays are a fixed,
+    seeded sample of rows (index.npy says which)"""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(mask)
+    if n * (4 + 4 + 8) <= DUMP_BUDGET:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    arrays = {"mask": mask[idx].astype(np.float32), "mean_dists": mean_dists[idx].astype(np.float32),
+              "index": idx.astype(np.float64), "stats": np.asarray(stats, dtype=np.float32),
+              "survivors": np.array([mask.sum()], dtype=np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def kernel_groups(ctx, L, step, slots, steps):
     """a short separate pass with every slot recording (not in a timed region)"""
     ctx.set_param("timing_mask", 0xff)
@@ -327,16 +363,21 @@ def cpu_sor(xyz_host, k, sigma, gpu_mask):
             "mask_identical_to_gpu": bool(np.array_equal(ref["mask"], gpu_mask))}
 
 
-def run_sor(L, ctx, xyz_host, k, sigma, steps, warmup, algo=0, groups=False, cpu=False, adaptive=False):
+def run_sor(L, ctx, xyz_host, k, sigma, steps, warmup, algo=0, groups=False, cpu=False, adaptive=False, dump_dir=None):
     ctx.set_param("adaptive", 1 if adaptive else 0)
     b = SorBench(L, ctx, xyz_host, k, sigma, algo)
     try:
         t = time_steps(ctx, b.step, steps, warmup, event_slot=L.T_SOR_KNN, L=L)
         mask, stats = b.results()
         n = b.n
+        dumped = None
+        if dump_dir:   # the last timed step's outputs, before any other pass reuses the buffers
+            dumped = dump_sor_outputs(dump_dir, mask, b.md.download(np.float32, n), stats)
         out = {"value": round(n * steps / t["dt"] / 1e6, 2), "unit": "Msplats/s", "ms_per_step": round(t["ms_per_step"], 4),
                "steps": steps, "warmup": warmup, "knn_kernel_ms": round(t["event_ms"], 4), "survivors": int(mask.sum()),
                "threshold": float(stats[2])}
+        if dumped:
+            out["dumped_outputs"] = dumped
         if groups:
             side = min(steps, 10)
             g = kernel_groups(ctx, L, b.step, {"bin": L.T_SOR_BIN, "fallback": L.T_SOR_FALLBACK, "stats": L.T_SOR_STATS}, side)
@@ -627,7 +668,8 @@ def main_single(args):
             sustained = run_sustained(L, ctx, xyz, args.k, args.sigma, args.algo)
         except Exception as e:   # noqa: BLE001
             sustained = {"error": repr(e)}
-    head = run_sor(L, ctx, xyz, args.k, args.sigma, args.steps, args.warmup, algo=args.algo, groups=True, cpu=want_cpu)
+    head = run_sor(L, ctx, xyz, args.k, args.sigma, args.steps, args.warmup, algo=args.algo, groups=True, cpu=want_cpu,
+                   dump_dir=args.dump_outputs)
     roof = sor_roofline(args.n, args.k, head["knn_kernel_ms"], args.algo)
     out = {
         "metric": "Msplats/sec SOR k=%d" % args.k, "value": head["value"], "unit": "Msplats/s", "n_gpus": 1, "steps": args.steps,
@@ -640,6 +682,8 @@ def main_single(args):
                    "host_runtime": "numpy + ctypes on libgsx_hip.so (gsx_dev_malloc / gsx_dev_upload); torch is not imported"},
         "roofline": roof, "kernel_ms_per_step": head["kernel_ms_per_step"], "survivors_rank0": head["survivors"],
         "threshold": head["threshold"], "grid": head["grid"]}
+    if "dumped_outputs" in head:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "files": head["dumped_outputs"]}
     if "cpu_baseline" in head:
         out["cpu_baseline"] = head["cpu_baseline"]
 
@@ -974,7 +1018,7 @@ def main_single(args):
         out["value_resident"] = out["value"]
         out["value_host_to_host"] = configs.get("host_to_host", {}).get("value")
     out["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
-    os.write(args.json_fd, (json.dumps(out) + "\n").encode())
+    emit(args.json_fd, out)
 
 
 def main_slab_one_rank(args, gsx, L, ctx):
@@ -1007,7 +1051,7 @@ def main_slab_one_rank(args, gsx, L, ctx):
            "threshold": float(stats[2])}
     ctx.check()
     comm.close()
-    os.write(args.json_fd, (json.dumps(out) + "\n").encode())
+    emit(args.json_fd, out)
 
 
 def _golden_files():
@@ -1343,7 +1387,7 @@ def main_multi(args):
             out["config3"] = config3
         if config2 is not None:
             out["config2"] = config2
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        emit(json_fd, out)
     comm.barrier()
     watchdog.done()
     comm.close()
@@ -1370,7 +1414,13 @@ def main():
     ap.add_argument("--n3", type=int, default=50_000_000, help="N>1: total splats of the configs[3] line (k=32), split over the ranks")
     ap.add_argument("--k3", type=int, default=32, help="N>1: k of the configs[3] line (tests: a size / k pair a committed reference-run hash exists for)")
     ap.add_argument("--n2", type=int, default=10_000_000, help="N>1: total splats of the configs[2] line (density 0.5 -> SOR k=16), split over the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (mask, mean distances, statistics) as "
+                         "DIR/<name>.npy; single-GPU SOR workload only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.workload != "sor"
+                              or args.exchange == "slab"):
+        ap.error("--dump-outputs supports the single-GPU SOR workload (--gpus 1 --workload sor)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 or args.gpus > 1:   # (either spawns its own ranks when no launcher did)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -44,3 +45,18 @@ def test_sor_line_has_the_contract_fields():
 def test_slab_pipeline_line_one_rank():
     d = _run("--n", "300000", "--extent", "10", "--no-secondary", "--no-cpu-baseline", "--exchange", "slab")
     assert "slab" in d["config"]["parallelism"] and d["survivors_rank0"] > 0
+
+
+def test_dump_outputs_are_the_timed_steps_results(tmp_path):
+    """--dump-outputs DIR: the last timed step's mask, mean distances and statistics == the oracle on the same cloud"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import sor as osor
+    d = _run("--n", "300000", "--extent", "10", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and sorted(d["dump_outputs"]["files"]) == ["index", "mask", "mean_dists", "stats", "survivors"]
+    ref = osor.sor(bench.synth_uniform(300000, 10.0, 0), 16, 1.0)
+    assert np.array_equal(np.load(tmp_path / "index.npy"), np.arange(300000))
+    assert np.array_equal(np.load(tmp_path / "mask.npy"), ref["mask"].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "mean_dists.npy").view(np.uint32), ref["mean_dists"].view(np.uint32))
+    assert np.float32(np.load(tmp_path / "stats.npy")[2]) == np.float32(ref["threshold"])
+    assert np.load(tmp_path / "survivors.npy")[0] == d["survivors_rank0"] == ref["mask"].sum()

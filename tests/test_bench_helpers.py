@@ -35,3 +35,27 @@ def test_bench_generator_is_the_one_the_goldens_were_made_with(golden_cases):
     for world in (2, 3, 8):
         parts = [x[r * len(x) // world:(r + 1) * len(x) // world] for r in range(world)]
         np.testing.assert_array_equal(np.concatenate(parts), x)
+
+
+def test_dump_outputs_fit_the_budget_and_sample_with_a_fixed_seed(tmp_path):
+    """--dump-outputs: float32 / float64 files only, at most 64 MB, the same rows of a large output on every run"""
+    n = 10_000_000
+    rng = np.random.default_rng(3)
+    mask, md = rng.random(n) < 0.85, rng.random(n, dtype=np.float32)
+    stats = np.array([0.5, 0.1, 0.6], dtype=np.float32)
+    names = bench.dump_sor_outputs(str(tmp_path / "a"), mask, md, stats)
+    bench.dump_sor_outputs(str(tmp_path / "b"), mask, md, stats)
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "a" / "index.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "mask.npy"), mask[idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "mean_dists.npy"), md[idx])
+    assert np.load(tmp_path / "a" / "survivors.npy")[0] == mask.sum()
+    # small outputs go out whole
+    small = bench.dump_sor_outputs(str(tmp_path / "c"), mask[:1000], md[:1000], stats)
+    assert "index" in small and np.array_equal(np.load(tmp_path / "c" / "index.npy"), np.arange(1000))

@@ -1,9 +1,11 @@
 """-m "not gpu": the drop-in boundary -- the C-ABI library loads and exports every symbol the header
 declares, the ctypes table matches the header, the product never touches oracle/ or the reference,
 and the host-side mirror of the reference API behaves like the reference without a GPU."""
+import importlib
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -145,26 +147,60 @@ def test_cluster_selection_matches_oracle(gsx):
     assert got == want
 
 
-def test_install_patches_reference_when_present(gsx):
-    from oracle import refload
-    if not refload.available():
-        pytest.skip("reference not mounted")
-    refload.load()
-    import gsconverter.processing as rp
-    import gsconverter.processing.data_processor as rdp
-    orig = rdp.DataProcessor
+_STANDIN = {   # the module layout install() rebinds, with the names the orchestrator resolves at call time (no reference code)
+    "gsconverter/__init__.py": "",
+    "gsconverter/processing/__init__.py": "from . import gpu_ops\nfrom .data_processor import DataProcessor\n",
+    "gsconverter/processing/gpu_ops.py": "HAS_TAICHI = False\n",
+    "gsconverter/processing/data_processor.py":
+        "class DataProcessor:\n"
+        "    def __init__(self, data):\n        self.data = data\n"
+        "    def later_method(self, n):\n        return ('forwarded', len(self.data), n)\n",
+    "gsconverter/converter.py": "from .processing import DataProcessor\n",
+    "gsconverter/formats/__init__.py": "",
+    "gsconverter/formats/sog.py": "from ..processing import gpu_ops\n\nclass SogFormat:\n    def write(self, data, path, **kw):\n        return 'own'\n",
+    "gsconverter/formats/compressed_ply.py": "class CompressedPlyFormat:\n    def write(self, data, path, **kw):\n        return 'own'\n",
+}
+
+
+def test_install_patches_reference_when_present(gsx, tmp_path, monkeypatch):
+    """install() on a stand-in ``gsconverter`` package with the reference's module layout: every name the orchestrator and
+    the writers resolve is rebound, a method this package does not implement is forwarded to the package's own class, and
+    uninstall() puts everything back"""
+    for rel, src in _STANDIN.items():
+        (tmp_path / rel).parent.mkdir(parents=True, exist_ok=True)
+        (tmp_path / rel).write_text(src)
+    saved = {m: sys.modules.pop(m) for m in list(sys.modules) if m == "gsconverter" or m.startswith("gsconverter.")}
+    mine = importlib.import_module("3dgsconverter_amd.processing.data_processor")
+    monkeypatch.setattr(mine, "_REFERENCE_CLASS", None)
+    monkeypatch.syspath_prepend(str(tmp_path))
     try:
-        gsx.install()
-        assert issubclass(rp.DataProcessor, gsx.DataProcessor) and issubclass(rdp.DataProcessor, gsx.DataProcessor)
-        assert rp.gpu_ops is gsx.gpu_ops
-        # a non-hot-path method is forwarded to the reference implementation
-        arr = np.zeros(5, dtype=[("x", "f4"), ("y", "f4"), ("z", "f4")])
-        arr["x"] = np.arange(5)
-        out = gsx.DataProcessor(arr).crop_by_bbox(1, -1, -1, 3, 1, 1)
-        assert len(out) == 3
+        import gsconverter.converter as rconv
+        import gsconverter.formats.compressed_ply as rcply
+        import gsconverter.formats.sog as rsog
+        import gsconverter.processing as rp
+        import gsconverter.processing.data_processor as rdp
+        orig, own_gpu_ops, own_sog_write, own_cply_write = rdp.DataProcessor, rp.gpu_ops, rsog.SogFormat.write, rcply.CompressedPlyFormat.write
+        try:
+            gsx.install()
+            assert issubclass(rp.DataProcessor, gsx.DataProcessor) and issubclass(rdp.DataProcessor, gsx.DataProcessor)
+            assert rp.gpu_ops is gsx.gpu_ops and rsog.gpu_ops is gsx.gpu_ops and sys.modules["gsconverter.processing.gpu_ops"] is gsx.gpu_ops
+            assert rconv.DataProcessor is mine.ChainedDataProcessor
+            assert rsog.SogFormat.write is not own_sog_write and rcply.CompressedPlyFormat.write is not own_cply_write
+            arr = np.zeros(5, dtype=[("x", "f4"), ("y", "f4"), ("z", "f4")])
+            arr["x"] = np.arange(5)
+            out = gsx.DataProcessor(arr).crop_by_bbox(1, -1, -1, 3, 1, 1)
+            assert len(out) == 3
+            # a method of the reference class this package does not implement is forwarded to it
+            assert gsx.DataProcessor(arr).later_method(7) == ("forwarded", 5, 7)
+        finally:
+            gsx.uninstall()
+        assert rdp.DataProcessor is orig and rp.DataProcessor is orig and rp.gpu_ops is own_gpu_ops and rsog.gpu_ops is own_gpu_ops
+        assert rsog.SogFormat.write is own_sog_write and rcply.CompressedPlyFormat.write is own_cply_write
+        assert sys.modules["gsconverter.processing.gpu_ops"] is own_gpu_ops
     finally:
-        gsx.uninstall()
-    assert rdp.DataProcessor is orig
+        for m in [m for m in sys.modules if m == "gsconverter" or m.startswith("gsconverter.")]:
+            del sys.modules[m]
+        sys.modules.update(saved)
 
 
 def test_info_struct_layout_matches_the_header(gsx, tmp_path):

@@ -1020,7 +1020,12 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                                 // word (a valid, cached address) and the result is discarded below
                                 const int i = ok[j] ? __builtin_clz(m) : 0;
                                 m &= ~(0x80000000u >> i);  // m == 0 stays 0
-                                pt[j] = refs[(MF && i >= c1 ? base2 : base) + i];
+                                const int idx = (MF && i >= c1 ? base2 : base) + i;
+                                // MF + NET kernels: a 32-bit byte offset from the kernel-argument base (one v_add_lshl_u32 and a
+                                // global_load with saddr, instead of a sign extension and a 64-bit shift-add per candidate);
+                                // dispatch_bricks runs them only for clouds of fewer than 2^28 points
+                                if constexpr (MF && NET) pt[j] = *(const float4 *)((const char *)refs + ((unsigned)idx << 4));
+                                else pt[j] = refs[idx];
                             }
 #pragma unroll
                             for (int j = 0; j < HB; ++j) {
@@ -1152,7 +1157,9 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                     const int c = w.c1 + w.c2;
                     if (c == 0) return make_float4(0.f, 0.f, 0.f, 0.f);
                     const int t = min(my_cand, c - 1);  // slots past the end repeat the last candidate (masked out below)
-                    return refs[t < w.c1 ? w.b1 + t : w.b2 + (t - w.c1)];
+                    const int idx = t < w.c1 ? w.b1 + t : w.b2 + (t - w.c1);
+                    if constexpr (NET) return *(const float4 *)((const char *)refs + ((unsigned)idx << 4));  // (as phase 2)
+                    else return refs[idx];
                 };
                 auto process = [&](const Word &w_cur, const float4 &p_cur) __attribute__((always_inline)) {
                     const bf16x8 cand = mf_candidate_operand((p_cur.x - ccx) * g_inv_h, (p_cur.y - ccy) * g_inv_h,
@@ -2623,7 +2630,9 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
         }
         return 0;
     }
-    GSX_CHECK(dispatch_bricks(ctx, a, ctx->filter_mfma != 0, ctx->phase2_net != 0));
+    // (the MFMA kernels' phase 2 addresses the sorted points with 32-bit byte offsets: 16 * n_ref < 2^32; larger clouds take the
+    //  scalar filter, which is exact as well)
+    GSX_CHECK(dispatch_bricks(ctx, a, ctx->filter_mfma != 0 && n_ref < (int64_t(1) << 28), ctx->phase2_net != 0));
 
     const bool trace = getenv("GSX_TRACE_LEVELS") != nullptr;
     GridParams hgp;

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -77,6 +78,11 @@ SOG_FIELD_NAMES = (["x", "y", "z", "rot_0", "rot_1", "rot_2", "rot_3", "scale_0"
 class SogLayout(C.Structure):
     """gsx_sog_layout (include/gsx_hip.h): where the writer's float32 fields sit inside a row of the structured table"""
     _fields_ = [("row_bytes", C.c_int64), ("n_rest", C.c_int32), ("offset", C.c_int32 * SOG_FIELDS)]
+
+
+class SpzLayout(C.Structure):
+    """gsx_spz_layout (include/gsx_hip.h): the SPZ writer's fields inside a row, -1 = absent"""
+    _fields_ = [("row_bytes", C.c_int64), ("offset", C.c_int32 * SOG_FIELDS)]
 
 
 class SogScan(C.Structure):
@@ -200,6 +206,8 @@ SIGNATURES = {
     "gsx_kmeans_lloyd_dev": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P]),
     "gsx_kmeans_lloyd_batch_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "gsx_quantize_sorted_codebook_dev": (_I, [_P, _P, _I64, _P, _I, _P]),
+    "gsx_spz_rest_nonzero_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsx_spz_pack_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, _I, _P, _P, _I64, _P]),
 }
 
 _lib = None
@@ -321,6 +329,66 @@ def host_gather_columns(vertices: np.ndarray, names) -> np.ndarray:
     check(load().gsx_host_gather_columns_f32(vertices.ctypes.data, vertices.dtype.itemsize, n, offs, len(names), out.ctypes.data),
           "gsx_host_gather_columns_f32")
     return out
+
+
+SPZ_HEADER_BYTES = 16   # <IIIBBBB: magic, version, n, SH degree, fractional bits, flags, reserved (spz.py:95-97)
+SPZ_SH_DIM = {0: 0, 1: 3, 2: 8, 3: 15}   # spz.py _dim_for_degree
+
+
+def spz_layout(dtype: np.dtype) -> SpzLayout:
+    """gsx_spz_layout of a structured dtype: byte offsets of the fields in SOG_FIELD_NAMES' order, -1 where absent"""
+    fields = dtype.fields or {}
+    lay = SpzLayout()
+    lay.row_bytes = dtype.itemsize
+    for i, nm in enumerate(SOG_FIELD_NAMES):
+        lay.offset[i] = int(fields[nm][1]) if nm in fields else -1
+    return lay
+
+
+def spz_alpha_bytes(opacity: np.ndarray) -> np.ndarray:
+    """spz.py:121 with numpy's own float32 exp, for the rows the device lists"""
+    with np.errstate(all="ignore"):
+        return (1.0 / (1.0 + np.exp(-np.clip(opacity, -20, 20))) * 255.0).astype(np.uint8)
+
+
+def spz_patch_rotations(rot: np.ndarray, rows: np.ndarray, quats: np.ndarray) -> None:
+    """spz.py:298-343 for the rows the device lists (a component other than the largest is NaN).  rot: the body's n packed
+    words, the other rows already final; quats: (len(rows), 4) float32 rot_0..3 of the listed rows.
+
+    The reference quantises component j of every row whose largest component is not j in ONE array, and numpy's float32 ->
+    uint32 cast of a NaN gives a value that depends on the position in that array (vector lanes and scalar remainder
+    differ).  The position comes from the largest-component index of every row (bits 30-31 of the words), the value from
+    numpy's own cast of a NaN array of that length."""
+    rows = np.asarray(rows, dtype=np.int64)
+    w, x, y, z = (np.ascontiguousarray(quats[:, c], dtype=np.float32) for c in range(4))
+    with np.errstate(all="ignore"):
+        norm = np.sqrt(w * w + x * x + y * y + z * z + 1e-9)
+        r = np.column_stack((x / norm, y / norm, z / norm, w / norm))
+    mi = np.argmax(np.abs(r), axis=1)
+    mi_all = rot >> np.uint32(30)
+    mi_all[rows] = mi
+    should_neg = r[np.arange(len(rows)), mi] < 0
+    packed = mi.astype(np.uint32) << np.uint32(30)
+    scale = 511.0 / 0.707106781186547524401
+    for j in range(4):
+        m = mi != j
+        if not np.any(m):
+            continue
+        val = r[m, j]
+        with np.errstate(all="ignore"):
+            mag_f = np.clip(np.abs(val) * scale + 0.5, 0, 511)
+            mag = mag_f.astype(np.uint32)
+        nan = np.isnan(mag_f)
+        if np.any(nan):
+            ne = mi_all != j
+            pos = np.cumsum(ne, dtype=np.int64)[rows[m][nan]] - 1
+            with np.errstate(all="ignore"):
+                probe = np.full(int(np.count_nonzero(ne)), np.nan, np.float32).astype(np.uint32)
+            mag[nan] = probe[pos]
+        negbit = ((val < 0) != should_neg[m]).astype(np.uint32)
+        shift = ((2 - (j - (mi[m] < j))) * 10).astype(np.uint32)
+        packed[m] |= ((negbit << np.uint32(9)) | mag) << shift
+    rot[rows] = packed
 
 
 def host_compact_rows(rows: np.ndarray, mask: np.ndarray) -> np.ndarray:
@@ -1074,6 +1142,112 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
             ctx.close()
 
 
+def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict | None" = None, listed: "dict | None" = None,
+                   device: int = 0):
+    """The SPZ writer's body on a whole splat table (formats/spz.py:49-173, :298-343): the raw rows are uploaded ONCE through the
+    staging lanes, the SH-degree scan and the packer read their fields straight out of them (any row size up to 512 bytes, fields
+    at any byte offset), and the body comes back through the staging lanes into the buffer the file is written from.
+
+    data: 1-D C-contiguous structured table whose fields named in SOG_FIELD_NAMES are little-endian float32 where present, with
+    x y z, scale_0..2 and rot_0..3 among them (formats/spz_writer.py checks).  sh_degree: the degree, or a function (highest
+    f_rest index of `scan_fields` holding a value != 0, -1 for none) -> degree, answered by one device pass over the resident rows.
+    listed: a dict that receives the rows whose alpha byte ("alpha") or rotation word ("rotation") numpy evaluated.
+    -> (out, degree): out = uint8[16 + (20 + 3 sh_dim) n], the body behind SPZ_HEADER_BYTES left for the caller's header.
+
+    Runs on the process's arena (grow-only buffers, no allocation on a repeated call) while it holds the arena's "spz" lease;
+    a second call at the same moment (another thread) takes a context and buffers of its own."""
+    lib = require_hip()
+    n = len(data)
+    if data.dtype.itemsize > 512:          # only the fields this writer reads: at most 59 x 4 bytes per row
+        import numpy.lib.recfunctions as rfn
+        data = rfn.repack_fields(data[[nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields]])
+    data = np.ascontiguousarray(data)
+    ar = arena(device)
+    leased = ar.lease("spz")
+    own = not leased
+    ctx = ar.ctx if leased else Context(device)
+    bufs = []
+    import time as _time
+    _t = [_time.perf_counter()]
+
+    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
+        if stage_ms is not None:
+            ctx.synchronize()
+            now = _time.perf_counter()
+            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
+            _t[0] = now
+
+    def alloc(nbytes, name):
+        if leased:
+            return ar.buf("spz_" + name, nbytes)
+        b = ctx.alloc(max(int(nbytes), 16))
+        bufs.append(b)
+        return b
+    try:
+        lay = spz_layout(data.dtype)
+        d_rows = alloc(data.nbytes + 64, "rows")        # (the kernels read up to 15 bytes past the last row)
+        if n:
+            upload_table(lib, ctx, d_rows.ptr, data)
+        mark("upload")
+        degree = sh_degree
+        if callable(sh_degree):
+            word = C.c_uint64(0)
+            want = sum(1 << int(i) for i in scan_fields)
+            check(lib.gsx_spz_rest_nonzero_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, want, C.byref(word)), "gsx_spz_rest_nonzero_dev")
+            hit = [int(i) for i in scan_fields if (word.value >> int(i)) & 1]
+            degree = int(sh_degree(max(hit) if hit else -1))
+            mark("sh_detect")
+        body_bytes = (20 + 3 * SPZ_SH_DIM[degree]) * n
+        out = np.empty(SPZ_HEADER_BYTES + body_bytes, np.uint8)
+        toucher = prefault(out) if body_bytes >= (1 << 22) else None
+        d_body = alloc(body_bytes, "body")
+        cap = n // 64 + 4096
+        d_list, d_cnt = alloc(8 * cap, "list"), alloc(16, "count")
+
+        def pack():
+            check(lib.gsx_spz_pack_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, degree, d_body.ptr, d_list.ptr, cap, d_cnt.ptr),
+                  "gsx_spz_pack_dev")
+            return int(d_cnt.download(np.uint32, 1)[0])
+        cnt = pack()
+        if cnt > cap:                      # more listed rows than room: again, with room for every one of them
+            cap = cnt
+            d_list = alloc(8 * cap, "list")
+            cnt = pack()
+        mark("pack")
+        if toucher is not None:
+            toucher.join()
+        if body_bytes:
+            check(lib.gsx_dev_download_staged(ctx.handle, out.ctypes.data + SPZ_HEADER_BYTES, d_body.ptr, body_bytes), "gsx_dev_download_staged")
+        lst = d_list.download(np.uint32, 2 * cnt).reshape(cnt, 2) if cnt else np.zeros((0, 2), np.uint32)
+        mark("download")
+        a_rows = lst[lst[:, 1] == 0, 0].astype(np.int64)
+        r_rows = lst[lst[:, 1] == 1, 0].astype(np.int64)
+        body = out[SPZ_HEADER_BYTES:]
+        if len(a_rows):
+            body[9 * n + a_rows] = spz_alpha_bytes(data["opacity"][a_rows])
+        if len(r_rows):
+            q = np.column_stack([data["rot_%d" % c][r_rows] for c in range(4)])
+            spz_patch_rotations(body[16 * n:20 * n].view("<u4"), r_rows, q)
+        if cnt:
+            mark("host_patch")
+        if listed is not None:
+            listed["alpha"], listed["rotation"] = a_rows, r_rows
+        return out, degree
+    except GsxError:
+        if leased:
+            ar.unlease("spz")
+            leased = False
+            release_arenas()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if leased:
+            ar.unlease("spz")
+        if own:
+            ctx.close()
+
+
 class DeviceArray:
     """A raw HBM allocation owned by a Context (only used where no other allocator is around)."""
 
@@ -1238,10 +1412,11 @@ class DeviceArena:
     def lease(self, who: str) -> bool:
         """one user of the buffers named after `who` at a time (a second DeviceChain alive at the same moment gets a context and
         buffers of its own)"""
-        if who in self._leases:
-            return False
-        self._leases.add(who)
-        return True
+        with _arena_lock:               # (two threads asking at once: exactly one of them gets it)
+            if who in self._leases:
+                return False
+            self._leases.add(who)
+            return True
 
     def unlease(self, who: str):
         self._leases.discard(who)
@@ -1267,23 +1442,26 @@ class DeviceArena:
 
 
 _arenas = {}
+_arena_lock = threading.RLock()
 
 
 def arena(device: int = 0) -> DeviceArena:
-    a = _arenas.get(int(device))
-    if a is None or a.ctx is None:
-        a = _arenas[int(device)] = DeviceArena(device)
-    return a
+    with _arena_lock:
+        a = _arenas.get(int(device))
+        if a is None or a.ctx is None:
+            a = _arenas[int(device)] = DeviceArena(device)
+        return a
 
 
 def release_arenas():
     """free every cached work buffer and context of the writers' arenas (they are re-created on the next call)"""
-    for dev, a in list(_arenas.items()):
-        if a._leases:            # a device chain is alive on this arena's context (a lazy DataProcessor with pending filters): it keeps it
-            continue
-        if a.ctx is not None:
-            a.release()
-        del _arenas[dev]
+    with _arena_lock:
+        for dev, a in list(_arenas.items()):
+            if a._leases:            # a device chain is alive on this arena's context (a lazy DataProcessor with pending filters): it keeps it
+                continue
+            if a.ctx is not None:
+                a.release()
+            del _arenas[dev]
 
 
 class DeviceChain:

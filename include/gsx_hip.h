@@ -615,6 +615,33 @@ int gsx_cply_pack_opacity_dev(gsx_ctx *ctx, const float *const *cols14_dev, cons
                               int64_t n, float *chunk_out_dev, uint32_t *vertex_out_dev, uint32_t *list_dev, int64_t cap,
                               uint32_t *count_dev);
 
+
+/* ---- the SPZ v3 writer's body on a DEVICE-RESIDENT splat table (csrc/spz.hip) ----
+ * gsconverter/formats/spz.py:49-173 and :298-343.  The raw rows are uploaded once; the body the reference assembles in
+ * `_pack_v3` -- positions 9n | alpha n | colours 3n | scales 3n | rotations 4n | SH 3*sh_dim*n bytes, sh_dim = 0, 3, 8, 15 for
+ * degree 0..3 -- is written to one device buffer, byte for byte. */
+typedef struct gsx_spz_layout {
+    int64_t row_bytes;                 /* itemsize of the structured dtype: 1 ... 512, any size (251: the table widened by the three
+                                          u1 colour fields of data_processor.py:262-274).  rows_dev must be 16-byte aligned and
+                                          readable up to 15 bytes past the last row */
+    int32_t offset[GSX_SOG_FIELDS];    /* byte offset of the float32 (little-endian) fields x y z | rot_0..3 | scale_0..2 | f_dc_0..2 |
+                                          opacity | f_rest_0..44 inside a row (gsx_sog_layout's order; any offset); -1 = the field
+                                          is absent (allowed for f_dc_*, opacity and f_rest_*) */
+} gsx_spz_layout;
+/* spz.py:60-77 `np.any(data[f'f_rest_{i}'] != 0)`, the loop of the SH-degree refinement: bit i of *mask_out (HOST word) is set iff
+ * some row holds f_rest_i != 0 (NaN counts, -0.0 does not), for the f_rest fields whose bit is set in `fields` (all present).
+ * One pass over the rows for every field at once.  Synchronises the context's stream. */
+int gsx_spz_rest_nonzero_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_layout *layout, int64_t n, uint64_t fields,
+                             uint64_t *mask_out);
+/* spz.py:111-170 (`_pack_v3`) and :298-343 (`_pack_rot_v3`): the whole body, (20 + 3 * sh_dim) * n bytes at body_dev (16-byte
+ * aligned), for the given SH degree (f_rest_i, f_rest_{i+15}, f_rest_{i+30} must be present for i < sh_dim: spz.py:152-154).
+ * list_dev receives `cap` entries of two uint32 (row, kind) for the bytes the caller fills with numpy's own expression: kind 0 =
+ * the alpha byte (spz.py:121: NaN, or numpy's float32 exp within the certificate's bracket of a byte boundary), kind 1 = the
+ * rotation word (a non-largest component is NaN: numpy's float32 -> uint32 cast of a NaN depends on its position in the array);
+ * *count_dev (zeroed by the call) keeps counting past cap.  Asynchronous. */
+int gsx_spz_pack_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_layout *layout, int64_t n, int sh_degree, uint8_t *body_dev,
+                     uint32_t *list_dev, int64_t cap, uint32_t *count_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,10 @@ SIGNATURES = {
     "gsx_quantize_sorted_codebook_dev": (_I, [_P, _P, _I64, _P, _I, _P]),
     "gsx_spz_rest_nonzero_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "gsx_spz_pack_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, _I, _P, _P, _I64, _P]),
+    "gsx_ksplat_centres_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, _I64, _P, _P, _I64, _P]),
+    "gsx_ksplat_pack_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, _I, _I, _I64, C.c_float, _P, _P, _I64, _P, _I64, _P]),
+    "gsx_ksplat_math_dev": (_I, [_P, _P, _I64, _P, _P]),
+    "gsx_np_expf_host": (_I, [_P, _P, _I64]),
 }
 
 _lib = None
@@ -1244,6 +1248,254 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
             b.free()
         if leased:
             ar.unlease("spz")
+        if own:
+            ctx.close()
+
+
+KSPLAT_HEADER_BYTES = 4096 + 1024   # file header + the one section header (ksplat.py:370-413)
+KSPLAT_SH_C0 = 0.28209479177387814  # ksplat.py:478
+
+
+def ksplat_row_dtype(level: int, sh_count: int) -> np.dtype:
+    """one interleaved .ksplat row (ksplat.py:502-515); level: 0, 1, 2, or 3 for every level >= 3"""
+    if level == 0:
+        fields = [("pos", "<f4", (3,)), ("scale", "<f4", (3,)), ("rot", "<f4", (4,)), ("color", "u1", (4,))]
+        sh = "<f4"
+    else:
+        fields = [("pos", "<u2", (3,)), ("scale", "<f2", (3,)), ("rot", "<f2", (4,)), ("color", "u1", (4,))]
+        sh = "<f2" if level == 1 else "u1"
+    if sh_count:
+        fields.append(("sh", sh, (sh_count,)))
+    return np.dtype(fields)
+
+
+def ksplat_exp_fields(data: np.ndarray, rows, level: int):
+    """ksplat.py:464-468 and :482 with numpy's own exp, for `rows` -> (scales (m, 3) float32 / float16, alpha uint8[m])"""
+    with np.errstate(all="ignore"):
+        s = np.column_stack([np.exp(data["scale_%d" % a][rows]) for a in range(3)])
+        a = np.clip((1 / (1 + np.exp(-data["opacity"][rows]))) * 255, 0, 255).astype(np.uint8)
+        return (s if level == 0 else s.astype(np.float16)), a
+
+
+def ksplat_rows_host(data: np.ndarray, rows, level: int, sh_count: int, centres: "np.ndarray | None", bucket_size: int,
+                     sf_inv: float) -> np.ndarray:
+    """ksplat.py:452-536 with numpy's own expressions for the rows the device lists -> their interleaved rows
+    (ksplat_row_dtype).  centres: (n_buckets, 3) float32, final (levels >= 1); sf_inv: the Python float of :452."""
+    rows = np.asarray(rows, dtype=np.int64)
+    out = np.zeros(len(rows), ksplat_row_dtype(level, sh_count))
+    with np.errstate(all="ignore"):
+        xyz = np.column_stack([data[a][rows] for a in "xyz"])
+        if level == 0:
+            out["pos"] = xyz
+        else:
+            c = centres[rows // bucket_size]
+            out["pos"] = np.clip(np.round((xyz - c) * sf_inv) + 32767, 0, 65535).astype(np.uint16)
+        out["scale"], alpha = ksplat_exp_fields(data, rows, level)
+        out["rot"] = np.column_stack([data["rot_%d" % a][rows] for a in range(4)]).astype(out.dtype["rot"].base)
+        rgb = [np.clip((0.5 + KSPLAT_SH_C0 * data["f_dc_%d" % a][rows]) * 255, 0, 255).astype(np.uint8) for a in range(3)]
+        out["color"] = np.column_stack(rgb + [alpha])
+        if sh_count:
+            sh = np.stack([data["f_rest_%d" % j][rows] for j in range(sh_count)], axis=1)
+            if level == 2:
+                out["sh"] = np.clip((sh - -2.0) / (2.0 - -2.0) * 255, 0, 255).astype(np.uint8)
+            else:                          # levels >= 3 cast the values themselves (ksplat.py:527-533)
+                out["sh"] = sh.astype(out.dtype["sh"].base)
+    return out
+
+
+def ksplat_centres_host(data: np.ndarray, bucket_size: int) -> np.ndarray:
+    """ksplat.py:428-444 with numpy's own reductions (its order decides the sign of an all-zero bucket's centre) -> (nb, 3)"""
+    idx = np.arange(0, len(data), bucket_size)
+    cols = []
+    with np.errstate(all="ignore"):
+        for a in "xyz":
+            v = data[a]
+            cols.append((np.minimum.reduceat(v, idx) + np.maximum.reduceat(v, idx)) / 2.0)
+    return np.column_stack(cols).astype(np.float32)
+
+
+def np_exp_host(x: np.ndarray) -> np.ndarray:
+    """csrc/np_exp.h on the host (gsx_np_expf_host): the twin of the device's exp"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    check(load().gsx_np_expf_host(x.ctypes.data, out.ctypes.data, x.size), "gsx_np_expf_host")
+    return out
+
+
+def np_exp_probe_vector() -> np.ndarray:
+    """~64K float32 inputs: the hard case 0xc2781e37, both ends of numpy's range (+inf above 0x1.62e430p+6, +0 below
+    -0x1.9fe368p+6) and their neighbours, denormal results, |x| near 0, NaN / +-inf / +-0, uniform values and raw bit patterns"""
+    rng = np.random.default_rng(0x6B73)
+    f = np.float32
+    edges = []
+    for e in (f(88.72283935546875), f(-103.972084045410156), f(-87.33654), f(0.0)):
+        v = e
+        for _ in range(64):
+            v = np.nextafter(v, f(-np.inf), dtype=np.float32)
+        for _ in range(129):
+            edges.append(v)
+            v = np.nextafter(v, f(np.inf), dtype=np.float32)
+    bits = np.array([0xC2781E37, 0x7FC00000, 0xFFC00000, 0x7F800001, 0x7F800000, 0xFF800000, 0x80000000, 0, 0x00000001, 0x7F7FFFFF,
+                     0xFF7FFFFF], np.uint32).view(np.float32)
+    parts = [bits, np.array(edges, np.float32),
+             rng.uniform(-103.98, -87.3, 12288).astype(np.float32),             # denormal and smallest normal results
+             rng.uniform(-110.0, 90.0, 24576).astype(np.float32),
+             rng.uniform(-1e-3, 1e-3, 4096).astype(np.float32),
+             rng.integers(0, 1 << 32, 16384, dtype=np.uint64).astype(np.uint32).view(np.float32)]
+    return np.concatenate(parts)
+
+
+_np_exp_checked = None
+
+
+def np_exp_probe() -> bool:
+    """The .ksplat writer stores np.exp's float32 bits, so the device's exp (csrc/np_exp.h) must be THIS process's numpy's.  Probed
+    once per process: the host twin against np.exp on np_exp_probe_vector().  On a mismatch: a RuntimeWarning and False (the
+    writer then takes every exp-derived result -- scales, alpha -- from numpy on the host, and stays exact), or under
+    GSX_STRICT_NUMPY=1 a GsxError."""
+    global _np_exp_checked
+    if _np_exp_checked is not None:
+        return _np_exp_checked
+    import warnings
+    x = np_exp_probe_vector()
+    with np.errstate(all="ignore"):
+        want = np.exp(x).view(np.uint32)
+    got = np_exp_host(x).view(np.uint32)
+    bad = np.nonzero(got != want)[0]
+    _np_exp_checked = not len(bad)
+    if len(bad):
+        i = int(bad[0])
+        msg = ("numpy %s's float32 exp differs from the one libgsx_hip reproduces (numpy 2.x's AVX512F / AVX2 routine) on %d of %d "
+               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): the .ksplat writer takes scales and alpha from numpy "
+               "on the host.  GSX_STRICT_NUMPY=1 turns this warning into an error."
+               % (np.__version__, len(bad), len(x), int(x.view(np.uint32)[i]), int(got[i]), int(want[i])))
+        if os.environ.get("GSX_STRICT_NUMPY") == "1":
+            _np_exp_checked = None
+            raise GsxError(msg)
+        warnings.warn(msg, RuntimeWarning, stacklevel=2)
+    return _np_exp_checked
+
+
+def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms: "dict | None" = None, listed: "dict | None" = None,
+                      device: int = 0):
+    """The .ksplat writer's payload on a whole splat table (formats/ksplat.py:319-544): the raw rows are uploaded ONCE, the SH-degree
+    scan (gsx_spz_rest_nonzero_dev), the bucket centres and the row packer read their fields straight out of them, and the payload
+    comes back into the buffer the file is written from.
+
+    data: 1-D C-contiguous structured table, its fields in SOG_FIELD_NAMES little-endian float32 where present
+    (formats/ksplat_writer.py checks).  degree: the SH degree, or a function (bits of the f_rest fields in scan_fields holding a
+    value != 0) -> degree.  geometry(degree) -> (out, g): the whole file's buffer with both headers (and the first payload word)
+    written, and a dict with level (0 / 1 / 2), sh_count, bucket_size, sf_inv, n_buckets, row_base, payload_bytes, head (the
+    first payload word's bytes); it may raise (the reference's struct errors) before anything is packed.
+    listed: a dict that receives the rows ("rows") and buckets ("buckets") numpy evaluated, and "exp_host" (True when the numpy
+    probe failed and every scale and alpha came from numpy).  -> (out, degree)
+
+    Runs on the process's arena while it holds the "ksplat" lease; a second call at the same moment (another thread) takes a
+    context and buffers of its own."""
+    lib = require_hip()
+    n = len(data)
+    exp_ok = np_exp_probe()
+    src = data                               # the caller's table: numpy's host patches run on it, as the reference's expressions do
+    if data.dtype.itemsize > 512:            # only the fields this writer reads: at most 59 x 4 bytes per row
+        import numpy.lib.recfunctions as rfn
+        data = rfn.repack_fields(data[[nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields]])
+    data = np.ascontiguousarray(data)
+    ar = arena(device)
+    leased = ar.lease("ksplat")
+    own = not leased
+    ctx = ar.ctx if leased else Context(device)
+    bufs = []
+    import time as _time
+    _t = [_time.perf_counter()]
+
+    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
+        if stage_ms is not None:
+            ctx.synchronize()
+            now = _time.perf_counter()
+            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
+            _t[0] = now
+
+    def alloc(nbytes, name):
+        if leased:
+            return ar.buf("ksplat_" + name, nbytes)
+        b = ctx.alloc(max(int(nbytes), 16))
+        bufs.append(b)
+        return b
+    try:
+        lay = spz_layout(data.dtype)
+        d_rows = alloc(data.nbytes + 64, "rows")        # (the kernels read up to 15 bytes past the last row)
+        if n:
+            upload_table(lib, ctx, d_rows.ptr, data)
+        mark("upload")
+        if callable(degree):
+            word = C.c_uint64(0)
+            want = sum(1 << int(i) for i in scan_fields)
+            check(lib.gsx_spz_rest_nonzero_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, want, C.byref(word)), "gsx_spz_rest_nonzero_dev")
+            degree = int(degree(word.value))
+            mark("sh_detect")
+        out, g = geometry(degree)
+        level, sh_count, bs, nb, row_base = g["level"], g["sh_count"], g["bucket_size"], g["n_buckets"], g["row_base"]
+        pay = out[KSPLAT_HEADER_BYTES:]
+        toucher = prefault(pay) if pay.nbytes >= (1 << 22) else None
+        d_pay = alloc(g["payload_bytes"] + 64, "payload")
+        cap = n // 64 + 4096
+        d_list, d_cnt = alloc(8 * cap, "list"), alloc(16, "count")
+        centres_ptr = d_pay.ptr + len(g["head"])
+
+        def pack():
+            check(lib.gsx_dev_memset(ctx.handle, d_cnt.ptr, 0, 4), "gsx_dev_memset")
+            if level >= 1 and n:
+                check(lib.gsx_ksplat_centres_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, bs, centres_ptr, d_list.ptr, cap, d_cnt.ptr),
+                      "gsx_ksplat_centres_dev")
+                mark("centres")
+            check(lib.gsx_ksplat_pack_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, level, sh_count, bs if level else 1, g["sf_inv"],
+                                          centres_ptr if level else None, d_pay.ptr, row_base, d_list.ptr, cap, d_cnt.ptr),
+                  "gsx_ksplat_pack_dev")
+            return int(d_cnt.download(np.uint32, 1)[0])
+        cnt = pack()
+        if cnt > cap:                      # more listed entries than room: again, with room for every one of them
+            cap = cnt
+            d_list = alloc(8 * cap, "list")
+            cnt = pack()
+        mark("pack")
+        if toucher is not None:
+            toucher.join()
+        if g["payload_bytes"]:
+            check(lib.gsx_dev_download_staged(ctx.handle, pay.ctypes.data, d_pay.ptr, g["payload_bytes"]), "gsx_dev_download_staged")
+        pay[:len(g["head"])] = np.frombuffer(g["head"], np.uint8)
+        lst = d_list.download(np.uint32, 2 * cnt).reshape(cnt, 2) if cnt else np.zeros((0, 2), np.uint32)
+        mark("download")
+        rows = lst[lst[:, 1] == 0, 0].astype(np.int64)
+        buckets = np.unique(lst[lst[:, 1] == 2, 0].astype(np.int64))
+        body = pay[row_base:row_base + n * ksplat_row_dtype(level, sh_count).itemsize].view(ksplat_row_dtype(level, sh_count))
+        cen = None
+        if level >= 1 and (len(rows) or len(buckets)):
+            cen = pay[len(g["head"]):row_base].view("<f4").reshape(nb, 3)
+        if len(buckets):
+            cen[buckets] = ksplat_centres_host(src, bs)[buckets]
+            starts = buckets * bs
+            rows = np.concatenate([rows] + [np.arange(a, min(a + bs, n)) for a in starts])
+        if not exp_ok and n:               # the probe found another exp: every exp-derived result from numpy
+            body["scale"], body["color"][:, 3] = ksplat_exp_fields(src, slice(None), level)
+        if len(rows):
+            rows = np.unique(rows)
+            body[rows] = ksplat_rows_host(src, rows, level, sh_count, cen, bs, g["py_sf_inv"])
+        if cnt or not exp_ok:
+            mark("host_patch")
+        if listed is not None:
+            listed["rows"], listed["buckets"], listed["exp_host"] = rows, buckets, not exp_ok
+        return out, degree
+    except GsxError:
+        if leased:
+            ar.unlease("ksplat")
+            leased = False
+            release_arenas()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if leased:
+            ar.unlease("ksplat")
         if own:
             ctx.close()
 

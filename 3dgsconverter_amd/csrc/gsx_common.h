@@ -195,6 +195,7 @@ struct gsx_ctx {
     gsx::DevBuf scratch3;
     gsx::DevBuf scratch4;
     gsx::DevBuf scratch5;
+    gsx::DevBuf ksplat_keys; // u32[7 * tiles]: the straddling buckets' min / max keys and NaN flags (ksplat.hip)
 };
 
 namespace gsx {

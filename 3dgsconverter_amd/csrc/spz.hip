@@ -20,55 +20,17 @@
 //           depends on where in its array the value sits: vector lanes and scalar remainder differ)
 #include "gsx_common.h"
 #include "sog_math.h"
+#include "row_tile.h"
 
 namespace gsx {
 
-constexpr int SPZ_FIELDS = 59;   // x y z | rot_0..3 | scale_0..2 | f_dc_0..2 | opacity | f_rest_0..44 (gsx_sog_layout's order)
-constexpr int SPZ_F_ROT = 3, SPZ_F_SCALE = 7, SPZ_F_DC = 10, SPZ_F_OPACITY = 13, SPZ_F_REST = 14;
-constexpr int SPZ_MAX_ROW_BYTES = 512;
-
-struct SpzLayoutDev {
-    int row_bytes;
-    int off[SPZ_FIELDS];   // byte offset inside a row, -1 = absent
-};
-
 __host__ __device__ constexpr int spz_sh_dim(int degree) { return degree == 1 ? 3 : degree == 2 ? 8 : degree == 3 ? 15 : 0; }
 __host__ __device__ constexpr int spz_row_out_bytes(int sh_dim) { return 20 + 3 * sh_dim; }
-
-// rows per tile (= threads per workgroup): the staged input stays within 32 KiB
-static inline int spz_tile_rows(int row_bytes) { return row_bytes <= 256 ? 128 : 64; }
-
-// LDS bytes of a tile: the staged rows (16-byte aligned window, one spare quad) + the output image (+16 spare bytes)
-__host__ __device__ inline size_t spz_in_bytes(int tr, int row_bytes) { return ((size_t)tr * row_bytes + 15 + 15) / 16 * 16 + 16; }
-
-// the tile's rows [t0, t0 + cnt) -> LDS, from the 16-byte boundary at or below the first byte; -> that boundary's offset.
-// Reads at most 15 bytes past the last row (the caller's allocation has that slack).
-__device__ __forceinline__ int spz_stage_tile(const uint4 *__restrict__ rows, int row_bytes, int64_t t0, int cnt, uint4 *lds)
-{
-    const int64_t b0 = t0 * row_bytes, b1 = (t0 + cnt) * row_bytes;
-    const int64_t q0 = b0 >> 4, q1 = (b1 + 15) >> 4;
-    const int nq = (int)(q1 - q0);
-    for (int k = threadIdx.x; k < nq; k += blockDim.x) lds[k] = rows[q0 + k];
-    return (int)(b0 & 15);
-}
-
-// the float32 at LDS byte index q (any alignment)
-__device__ __forceinline__ float spz_lds_f32(const unsigned *lds, int q)
-{
-    const unsigned lo = lds[q >> 2], hi = lds[(q >> 2) + 1];
-    return __uint_as_float(__builtin_amdgcn_alignbyte(hi, lo, (unsigned)(q & 3)));
-}
 
 // numpy's float32 -> int32 cast on x86 (cvttss2si): NaN, +-inf and values outside [-2^31, 2^31) give INT_MIN
 __device__ __forceinline__ int spz_f32_to_i32(float t)
 {
     return (t == t && t >= -2147483648.0f && t < 2147483648.0f) ? (int)t : (int)0x80000000u;
-}
-
-// np.clip(t, 0, 255).astype(np.uint8): NaN stays NaN through the clip and casts to 0
-__device__ __forceinline__ unsigned spz_u8(float t)
-{
-    return t == t ? (unsigned)fminf(fmaxf(t, 0.0f), 255.0f) : 0u;
 }
 
 // quant_sh (spz.py:162-170) for one value: round(v * 128 + 128) -> int32, (q + bs/2) // bs * bs, clip 0..255; bs = 1 << shift

@@ -19,13 +19,15 @@ import sys
 _saved = {}
 
 
-def install(sog_writer: bool = True, spz_writer: bool = True):
+def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
     formats/compressed_ply_writer.py:write_compressed_ply (Morton order, chunk bounds and packers on the GPU).
     spz_writer: also rebind ``gsconverter.formats.spz.SpzFormat.write`` to formats/spz_writer.py:write_spz (SH-degree scan and
-    the whole body on the GPU; identical file bytes).  A reference without that module is left as it is."""
+    the whole body on the GPU; identical file bytes).  A reference without that module is left as it is.
+    ksplat_writer: also rebind ``gsconverter.formats.ksplat.KSplatFormat.write`` to formats/ksplat_writer.py:write_ksplat (SH-degree
+    scan, bucket centres and every row on the GPU; identical file bytes).  A reference without that module is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -75,6 +77,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True):
             from .formats.spz_writer import write_spz
             _saved.setdefault(("spzformat", "write"), spzmod.SpzFormat.write)
             spzmod.SpzFormat.write = lambda self, data, path, **kw: write_spz(data, path, **kw)
+    if ksplat_writer:
+        try:
+            ksmod = importlib.import_module("gsconverter.formats.ksplat")
+        except ImportError:
+            ksmod = None
+        if ksmod is not None:
+            from .formats.ksplat_writer import write_ksplat
+            _saved.setdefault(("ksplatformat", "write"), ksmod.KSplatFormat.write)
+            ksmod.KSplatFormat.write = lambda self, data, path, compression_level=0, **kw: write_ksplat(data, path, compression_level, **kw)
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -91,6 +102,9 @@ def uninstall():
             continue
         if modname == "spzformat":
             importlib.import_module("gsconverter.formats.spz").SpzFormat.write = val
+            continue
+        if modname == "ksplatformat":
+            importlib.import_module("gsconverter.formats.ksplat").KSplatFormat.write = val
             continue
         if modname == "sys.modules":
             if val is None:

@@ -642,6 +642,34 @@ int gsx_spz_rest_nonzero_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_l
 int gsx_spz_pack_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_layout *layout, int64_t n, int sh_degree, uint8_t *body_dev,
                      uint32_t *list_dev, int64_t cap, uint32_t *count_dev);
 
+
+/* ---- the .ksplat writer's payload on a DEVICE-RESIDENT splat table (csrc/ksplat.hip) ----
+ * gsconverter/formats/ksplat.py:319-544 (KSplatFormat.write).  The payload behind the 4096 + 1024 header bytes is
+ * [u32 N % bucket_size] | [bucket_count x 3 f32 centres, levels >= 1] | N interleaved rows; the host writes the headers and the
+ * first word, these calls the rest.  The rows use gsx_spz_layout (x y z, rot_0..3, scale_0..2, f_dc_0..2 and opacity required).
+ * Both pack calls APPEND (index, kind) entries to list_dev and count on in *count_dev (zero it first: gsx_dev_memset); kind 0 =
+ * row `index`, whose bytes the caller fills with numpy's own expressions (a NaN reaches a float -> u8 / u16 / f16 cast), kind 2 =
+ * bucket `index`, whose centre and rows the caller takes from numpy (a NaN centre, or an axis of zeros of both signs, where
+ * numpy's reduction order picks the sign).  Asynchronous. */
+/* ksplat.py:426-450: the centre (min + max) / 2.0 per axis of every bucket of `bucket_size` consecutive rows (the last one may be
+ * partial; any bucket_size >= 1), written as n_buckets x 3 float32 at centres_dev (4-byte aligned: its payload slot). */
+int gsx_ksplat_centres_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_layout *layout, int64_t n, int64_t bucket_size,
+                           float *centres_dev, uint32_t *list_dev, int64_t cap, uint32_t *count_dev);
+/* ksplat.py:452-536: every interleaved row -- level 0: 3 f32 position, 3 f32 np.exp(scale), 4 f32 rotation, 4 u8 colour, sh_count
+ * f32; level 1: 3 u16 quantised position (sf_inv = float32(32767 / (block_size / 2.0)), against centres_dev), 3 f16, 4 f16, 4 u8,
+ * sh_count f16; level 2: the same with sh_count u8 clip((v + 2) / 4 * 255, 0, 255); level 3 (every level >= 3): sh_count u8
+ * astype(np.uint8) of the values themselves (ksplat.py:527-533 quantise at level 2 only).  sh_count = 0, 9 or 24:
+ * f_rest_0 .. f_rest_{sh_count-1} in index order (ksplat.py:488).  Rows land at payload_dev + row_base (payload_dev 16-byte aligned). */
+int gsx_ksplat_pack_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_layout *layout, int64_t n, int level, int sh_count,
+                        int64_t bucket_size, float sf_inv, const float *centres_dev, uint8_t *payload_dev, int64_t row_base,
+                        uint32_t *list_dev, int64_t cap, uint32_t *count_dev);
+/* ksplat.py:464 and :482 np.exp, ksplat.py:468 astype(np.float16): numpy's float32 exp (csrc/np_exp.h) and the device's
+ * float32 -> float16 cast of every x_dev[i], as bits.  Synchronises the context's stream (the proofs of tests/devtools). */
+int gsx_ksplat_math_dev(gsx_ctx *ctx, const float *x_dev, int64_t n, uint32_t *exp_out_dev, uint16_t *half_out_dev);
+/* ksplat.py:464 np.exp on the HOST: the twin of the device's exp (csrc/np_exp.h), for the writer's runtime probe against this
+ * process's numpy.  HOST pointers. */
+int gsx_np_expf_host(const float *x, float *out, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,14 +289,67 @@ def _xyz_pointers(xyz_or_cols):
     return a, base, base + 4, base + 8, 3, a.shape[0]
 
 
-def host_gather_xyz(vertices: np.ndarray, names=("x", "y", "z"), out: "np.ndarray | None" = None) -> np.ndarray:
+def is_f4(dt: np.dtype) -> bool:
+    """a float32 field of either byte order: its float32 copy is the same numbers"""
+    return dt.kind == "f" and dt.itemsize == 4
+
+
+def f32_inexact_field(vertices: np.ndarray, names):
+    """The first field of `names` (those the table has) whose values float32 does not hold exactly -> (name, dtype), or None.
+    float32 fields of either byte order and float16 fields hold float32 values by their dtype; a float64 field is checked value
+    by value (one host pass: back from float32 it must be the column again, NaN for NaN).  Any other dtype counts as inexact."""
+    fields = vertices.dtype.fields or {}
+    for nm in names:
+        if nm not in fields:
+            continue
+        dt = fields[nm][0]
+        if dt.kind == "f" and dt.itemsize in (2, 4):
+            continue
+        if dt.kind == "f" and dt.itemsize == 8:
+            col = vertices[nm]
+            with np.errstate(over="ignore", invalid="ignore"):
+                if np.array_equal(col.astype(np.float32).astype(np.float64), col, equal_nan=True):
+                    continue
+        return nm, dt
+    return None
+
+
+def require_f4_fields(data: np.ndarray, names, who: str):
+    """TypeError naming the first field of `names` (those the table has) that is not float32: a writer whose arithmetic the
+    reference does in the table's own dtype refuses other dtypes instead of casting them"""
+    fields = data.dtype.fields or {}
+    for nm in names:
+        if nm in fields and not is_f4(fields[nm][0]):
+            raise TypeError(f"{who}: field {nm!r} is {fields[nm][0].str}; the GPU writer computes in float32 as the reference does for "
+                            f"float32 fields, and takes float32 ('<f4' or '>f4') fields only")
+
+
+def native_f4(data: np.ndarray, names) -> np.ndarray:
+    """`data` with its big-endian float32 fields among `names` made little-endian (a new table, same layout, same numbers), or
+    `data` itself when it has none"""
+    fields = data.dtype.fields or {}
+    flip = [nm for nm in names if nm in fields and fields[nm][0] == np.dtype(">f4")]
+    if not flip:
+        return data
+    dt = np.dtype({"names": list(data.dtype.names),
+                   "formats": [np.dtype("<f4") if nm in flip else fields[nm][0] for nm in data.dtype.names],
+                   "offsets": [fields[nm][1] for nm in data.dtype.names], "itemsize": data.dtype.itemsize})
+    return np.ascontiguousarray(data.astype(dt))
+
+
+def host_gather_xyz(vertices: np.ndarray, names=("x", "y", "z"), out: "np.ndarray | None" = None, exact: bool = True) -> np.ndarray:
     """coords = np.column_stack((v['x'], v['y'], v['z'])) (data_processor.py:38,139) as float32 (N,3),
     threaded (C ABI gsx_host_gather_f32).  Any layout the C routine cannot take goes through numpy.  out: a C-contiguous
-    (N, len(names)) float32 array to fill (a pinned staging buffer)"""
+    (N, len(names)) float32 array to fill (a pinned staging buffer).  exact: a field whose values float32 does not hold raises
+    TypeError (f32_inexact_field); False = cast it (DeviceChain: the caller decides where the copy may stand in for the table)"""
     fields = vertices.dtype.fields or {}
     ok = (vertices.ndim == 1 and vertices.flags.c_contiguous and
           all(nm in fields and fields[nm][0] == np.dtype("<f4") for nm in names))
     if not ok:
+        bad = f32_inexact_field(vertices, names) if exact else None
+        if bad is not None:
+            raise TypeError(f"field {bad[0]!r} is {bad[1].str} and holds values float32 does not; the device computes on float32 "
+                            f"coordinates")
         res = np.column_stack([np.asarray(vertices[nm], dtype=np.float32) for nm in names])
         if out is not None:
             out[...] = res
@@ -919,8 +972,12 @@ def cply_pack(columns: dict, order: "np.ndarray | None", sh_columns=(), ctx: "Co
     """formats/compressed_ply.py:205-241 on the GPU (C ABI gsx_cply_pack_dev / gsx_cply_sh_dev).
     columns: the 14 float32 columns named in CPLY_COLUMNS (original table order; 'alpha' = numpy's sigmoid of the opacity);
     order: uint32 Morton order or None.  -> (chunks (ceil(n/256), 18) f32, vertices (n, 4) u32, sh (n, m) u8 or None)"""
+    for name, c in [(nm, columns[nm]) for nm in CPLY_COLUMNS] + [("sh_columns[%d]" % i, c) for i, c in enumerate(sh_columns)]:
+        if not is_f4(np.asarray(c).dtype):
+            raise TypeError(f"cply_pack: column {name!r} is {np.asarray(c).dtype.str}; float32 columns only (the reference computes in "
+                            f"the column's dtype)")
     require_hip()
-    cols = [np.ascontiguousarray(columns[name], dtype=np.float32) for name in CPLY_COLUMNS]
+    cols = [np.ascontiguousarray(columns[name], dtype=np.float32) for name in CPLY_COLUMNS]     # (byte order only)
     n = len(cols[0])
     nchunks = (n + 255) // 256
     own = ctx is None
@@ -1000,10 +1057,14 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
     out of them (element stride = row_bytes / 4: gsx_cply_pack_strided_dev / gsx_cply_sh_strided_dev) -- round 5 gathered the 59
     columns on the host (one threaded pass, 472 MB of freshly faulted pages per 2M splats) and uploaded that.  The alpha byte comes
     from the opacity field on the device (float64 exp + the rounding certificate of the SOG textures; numpy's own sigmoid only for
-    the ~1e-4 listed splats: gsx_cply_pack_opacity_dev); results come back through the staging lanes.  Tables the row path does not take (fields that are
-    not float32, rows that are not a multiple of 4 bytes, f_rest fields that are not consecutive) and calls with a caller's
-    context gather their columns on the host as before.
+    the ~1e-4 listed splats: gsx_cply_pack_opacity_dev); results come back through the staging lanes.  Tables the row path does not take (views that
+    are not C-contiguous, rows that are not a multiple of 4 bytes, f_rest fields that are not consecutive) and calls with a caller's
+    context gather their columns on the host as before.  A field the writer reads that is not float32 raises TypeError before the
+    device is touched (the reference computes in the field's dtype); big-endian float32 fields are made little-endian first.
     -> (chunks (ceil(n/256), 18) f32, vertices (n, 4) u32, sh (n, m) u8 or None, order u32[n], recursion levels or None)"""
+    reads = ["opacity" if c == "alpha" else c for c in CPLY_COLUMNS] + ["f_rest_%d" % i for i in range(45)]
+    require_f4_fields(data, reads, "Compressed PLY writer")
+    data = native_f4(data, reads)
     lib = require_hip()
     n = len(data)
     fields = data.dtype.fields or {}
@@ -1732,10 +1793,12 @@ class DeviceChain:
             require_hip()
             ar0 = arena(device)
             n_t = len(table)
+            # (exact=False: a row filter may start the chain on any table; DataProcessor checks f32_inexact_field before SOR, the
+            #  density filter or the box take the float32 copy for the table's values)
             if n_t >= 4096 and "chain" not in ar0._leases:
-                a = host_gather_xyz(table, out=ar0.pinned("chain_xyz", 12 * n_t)[:12 * n_t].view(np.float32).reshape(n_t, 3))
+                a = host_gather_xyz(table, out=ar0.pinned("chain_xyz", 12 * n_t)[:12 * n_t].view(np.float32).reshape(n_t, 3), exact=False)
             else:
-                a = host_gather_xyz(table)
+                a = host_gather_xyz(table, exact=False)
         else:
             a = np.ascontiguousarray(xyz_rows, dtype=np.float32)
         if a.ndim != 2 or a.shape[1] != 3:

@@ -46,6 +46,11 @@ class NotEligible(Exception):
     """the table (or the request) is one the device-resident path does not take; the caller uses the host-staged path"""
 
 
+class FieldTypeError(NotEligible, TypeError):
+    """a field the writer reads is not float32: neither core takes the table (the reference computes in the field's dtype), and
+    sog_writer.encode raises this before either is tried"""
+
+
 def _log_transform(v):
     return np.sign(v) * np.log(np.abs(v) + 1.0)          # formats/sog.py:280-281, numpy's own float32 arithmetic
 

@@ -23,8 +23,10 @@ Same bundle layout and the same bytes wherever the reference is deterministic; w
 
 Round 6: the table is DEVICE-RESIDENT for the whole core (formats/sog_device.py, csrc/sog_table.hip): the raw rows are uploaded
 once, lexsort / ``data[indices]`` / texels / codebooks / palette run in HBM, texels come back.  The host-staged core below (one
-upload / download per stage) remains for the tables that path does not take (non-float32 fields, fewer than 1024 rows,
-non-finite coordinates) and for a palette dealt out across GPUs.
+upload / download per stage) remains for the tables that path does not take (views that are not C-contiguous, fewer than 1024
+rows, non-finite coordinates) and for a palette dealt out across GPUs.  A field the writer reads that is not float32 raises
+TypeError (sog_device.FieldTypeError) before either core runs: the reference computes in the field's own dtype.  Big-endian
+float32 fields are made little-endian first (the same numbers).
 
 ``install(sog_writer=True)`` rebinds ``gsconverter.formats.sog.SogFormat.write`` to this function, which also makes the
 GPU quantiser reachable from the reference's CLI (in the reference it is a closure inside ``write``).
@@ -136,8 +138,8 @@ def _sh_bands(data, ds):
 
 
 def _encode_host(data: np.ndarray, level: int, comm=None, be=None) -> dict:
-    """The numeric core with the table on the HOST: one upload / download per stage (round 3's writer).  Takes every table the
-    reference takes (any dtype, tiny tables with their k >= N shortcuts, a palette dealt out across GPUs through comm / be);
+    """The numeric core with the table on the HOST: one upload / download per stage (round 3's writer).  Takes every float32 table
+    the reference takes (any layout, tiny tables with their k >= N shortcuts, a palette dealt out across GPUs through comm / be);
     returns what sog_device.encode returns."""
     n = len(data)
     width, height = _texture_size(n)
@@ -206,6 +208,11 @@ def encode(data: np.ndarray, level: int = 0, comm=None, be=None, device_resident
     """every array SogFormat.write hands to write_webp + the numbers of its meta.json (sog.py:249-600 without the packaging).
     device_resident: None = the device-resident core (formats/sog_device.py) whenever the table and the request allow it,
     True = insist (NotEligible propagates), False = the host-staged core."""
+    try:                        # before any device work, for both cores: float32 fields only (DESIGN.md, "Field dtypes")
+        _lib.require_f4_fields(data, _lib.SOG_FIELD_NAMES, "SOG writer")
+    except TypeError as e:
+        raise sog_device.FieldTypeError(str(e)) from None
+    data = _lib.native_f4(data, _lib.SOG_FIELD_NAMES)
     if device_resident is None:
         device_resident = DEVICE_RESIDENT
     if device_resident is not False and comm is None:

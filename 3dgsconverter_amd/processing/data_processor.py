@@ -12,6 +12,9 @@ Differences from the reference, all deliberate:
     (SURVEY.md F4/F5); any k up to 2047 (k <= 64 on the fast kernels).
   * there is NO CPU fallback: if the HIP library or the GPU is missing the call raises
     ``GsxError`` (a RuntimeError).
+  * coordinates the device cannot take without changing the answer raise ``TypeError`` (before any device work): SOR
+    takes x/y/z that float32 holds exactly, the density filter x/y/z that numpy promotes to float32 ("Field
+    dtypes").  The row filters run the reference's numpy expressions on columns that are not float32.
 Every method of the reference class is implemented here (round 3: ``cap_sh_degree``, ``add_rgb_from_sh``,
 ``apply_auto_bbox`` too -- SURVEY.md 8(f) rank 4); ``__getattr__`` only forwards names a FUTURE reference version
 might add.
@@ -25,6 +28,7 @@ from ..utils import debug_print, status_print
 from . import clusters as _clusters
 
 
+XYZ = ("x", "y", "z")
 MAX_SOR_K = 2047  # include/gsx_hip.h: 1 <= k <= 64 on the fast kernels, 65..2047 through the exact list-free kernel (slow)
 
 
@@ -161,6 +165,31 @@ class DataProcessor:
     def _column(self, name):
         return self._columns((name,))[0]
 
+    def _require_sor_dtypes(self):
+        """remove_flyers' refusal ("Field dtypes"): the reference's cKDTree measures in float64 whatever the table holds
+        (:139,156), so the device's float32 coordinates give its mask exactly when float32 holds every coordinate -- float32 fields
+        of either byte order, float16, float64 fields whose values all come back from float32 (one host pass).  Anything else
+        raises TypeError here, before the device or the table or the chain is touched"""
+        bad = _lib.f32_inexact_field(self._data, XYZ)
+        if bad is not None:
+            raise TypeError(f"remove_flyers: field {bad[0]!r} is {bad[1].str} and holds values float32 does not; the reference's "
+                            f"KD-tree measures them in float64, the MI355X path in float32 -- cast the table to float32 first "
+                            f"if that is what is wanted")
+
+    def _require_density_dtypes(self):
+        """apply_density_filter's refusal: the reference divides np.column_stack((x, y, z)) -- numpy's promotion of the three
+        dtypes -- by the voxel size (:38-39).  The device divides in float32, so only tables whose coordinates promote to float32
+        (float32 of either byte order, float16 next to float32) are taken; anything else raises TypeError before any device work"""
+        fields = self._data.dtype.fields or {}
+        dts = [fields[f][0] for f in XYZ if f in fields]
+        if len(dts) < 3 or _lib.is_f4(np.result_type(*dts)):
+            return                      # (a missing field: numpy's own error, where the reference meets it)
+        promoted = np.result_type(*dts)
+        nm = next(f for f in XYZ if not _lib.is_f4(fields[f][0]))
+        raise TypeError(f"apply_density_filter: field {nm!r} is {fields[nm][0].str}; the reference divides the coordinates in "
+                        f"{promoted} (np.column_stack of x, y, z), the MI355X path in float32 -- a float64 division mode is not "
+                        f"implemented")
+
     def _xyz_is_f32(self):
         names = self._data.dtype.names or ()
         return all(f in names and self._data.dtype[f] == np.float32 for f in ("x", "y", "z"))
@@ -179,6 +208,7 @@ class DataProcessor:
         self._flush_rgb()
         if not isinstance(self._data, np.ndarray):
             raise TypeError("self.data must be a numpy structured array.")
+        self._require_sor_dtypes()
         if intensity is not None:
             k, threshold_factor = sor_params_from_intensity(intensity)
         debug_print(f"SOR Filter (Remove Flyers) Params: K={k}, Sigma={threshold_factor:.2f}")
@@ -217,6 +247,7 @@ class DataProcessor:
         self._flush_rgb()
         if not isinstance(self._data, np.ndarray):
             raise TypeError("self.data must be a numpy structured array.")
+        self._require_density_dtypes()
         if sensitivity is not None:
             voxel_size, threshold_percentage = density_params_from_sensitivity(sensitivity)
         debug_print(f"Density Filter Params: Voxel={voxel_size:.4f}, Thresh={threshold_percentage:.4f}%, "
@@ -428,9 +459,9 @@ class DataProcessor:
         if len(self) == 0:
             status_print("Auto-BBox: No points remaining. Bounding box is undefined.")
             return
-        if self._chain is not None:
+        if self._chain is not None and _lib.f32_inexact_field(self._data, XYZ) is None:
             lo, hi = self._chain.bbox()
-        else:
+        else:   # (a chain over coordinates float32 does not hold -- a row filter's -- is materialised: the reduction runs on the table)
             # the reference's reductions (:348-349) on contiguous copies of the columns (one threaded gather; six numpy reductions
             # over 248-byte-stride views took 92 ms at 10M splats)
             cols = self._columns(("x", "y", "z"))

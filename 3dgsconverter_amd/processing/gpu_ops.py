@@ -66,6 +66,7 @@ def filter_sor_gpu(data_np: np.ndarray, k: int = 25, threshold_factor: float = 1
         raise ValueError("Requires 3D data")
     if not 1 <= int(k) <= 2047:
         raise ValueError(f"SOR: k={k} is outside the supported range 1..2047 of the MI355X path")
+    # float32 whatever the caller's dtype: the reference's Taichi path casts too (gpu_ops.py:200 `pos_np = data_np.astype(np.float32)`)
     res = _lib.sor_filter(np.ascontiguousarray(data_np, dtype=np.float32), int(k), float(threshold_factor),
                           want_mean=False)
     if verbose:

@@ -27,6 +27,14 @@ def voxel_keys(xyz: np.ndarray, voxel_size: float) -> np.ndarray:
     return np.floor(coords / voxel_size).astype(np.int64)
 
 
+def voxel_keys_table(table: np.ndarray, voxel_size: float) -> np.ndarray:
+    """data_processor.py:38-39 in the table's own dtypes: np.column_stack of x, y, z as they are (numpy promotes: float64
+    anywhere -> float64, float16 only -> float16), divided by the voxel size in that dtype.  ``voxel_keys`` casts to float32
+    first and so stands for tables whose coordinates promote to float32 only."""
+    coords = np.column_stack((table["x"], table["y"], table["z"]))
+    return np.floor(coords / voxel_size).astype(np.int64)
+
+
 def min_points_for(n: int, threshold_percentage: float) -> int:
     """data_processor.py:48."""
     return int(n * (threshold_percentage / 100.0))
@@ -81,8 +89,19 @@ def density_filter(xyz: np.ndarray, voxel_size: float = 1.0, threshold_percentag
     """-> dict(mask bool[N], unique_voxels, min_points, kept_clusters, max_len, voxel_size, threshold_percentage)."""
     if sensitivity is not None:
         voxel_size, threshold_percentage = params_from_sensitivity(sensitivity)
-    n = len(xyz)
-    keys = voxel_keys(xyz, voxel_size)
+    return _filter_keys(voxel_keys(xyz, voxel_size), voxel_size, threshold_percentage, keep_multicluster)
+
+
+def density_filter_table(table: np.ndarray, voxel_size: float = 1.0, threshold_percentage: float = 0.32,
+                         sensitivity=None, keep_multicluster: bool = False):
+    """``density_filter`` with the voxel keys computed in the table's own dtypes (voxel_keys_table)."""
+    if sensitivity is not None:
+        voxel_size, threshold_percentage = params_from_sensitivity(sensitivity)
+    return _filter_keys(voxel_keys_table(table, voxel_size), voxel_size, threshold_percentage, keep_multicluster)
+
+
+def _filter_keys(keys, voxel_size, threshold_percentage, keep_multicluster):
+    n = len(keys)
     uniq, inverse, counts = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
     inverse = np.asarray(inverse).reshape(-1)
     min_points = min_points_for(n, threshold_percentage)

@@ -54,6 +54,11 @@ def reference_sor(xyz, k=25, threshold_factor=10.5, intensity=None):
     """Run the reference's own ``DataProcessor.remove_flyers`` CPU branch and capture the
     locals of its frame (the function computes ``mask`` at data_processor.py:180 but returns
     the unfiltered data)."""
+    return reference_sor_table(xyz_to_struct(xyz, False), k, threshold_factor, intensity)
+
+
+def reference_sor_table(table, k=25, threshold_factor=10.5, intensity=None):
+    """``reference_sor`` on a structured table as it is (its x, y, z in their own dtypes)"""
     import numpy as np
     DataProcessor, gpu_ops, dpmod = load()
     assert not gpu_ops.HAS_TAICHI
@@ -75,7 +80,7 @@ def reference_sor(xyz, k=25, threshold_factor=10.5, intensity=None):
     dpmod.status_print = spy
     try:
         with np.errstate(invalid="ignore"):
-            DataProcessor(xyz_to_struct(xyz, False)).remove_flyers(k, threshold_factor, intensity=intensity)
+            DataProcessor(table).remove_flyers(k, threshold_factor, intensity=intensity)
     finally:
         dpmod.status_print = saved
     return cap

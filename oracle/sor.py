@@ -77,6 +77,33 @@ def sor(xyz: np.ndarray, k: int = 25, threshold_factor: float = 10.5, intensity=
             "threshold_factor": threshold_factor}
 
 
+def table_coords(table: np.ndarray) -> np.ndarray:
+    """data_processor.py:139 as written: np.column_stack of the table's own x, y, z -- numpy's promotion of their dtypes, no cast"""
+    return np.column_stack((table["x"], table["y"], table["z"]))
+
+
+def sor_table(table: np.ndarray, k: int = 25, threshold_factor: float = 10.5, workers=None):
+    """``sor`` in the table's own dtypes (data_processor.py:139-180): cKDTree on np.column_stack of the columns as they are (the
+    tree measures in float64 whatever it is given), row means stored into float32 as the reference does.  ``sor`` casts the
+    coordinates to float32 first and so stands for a float32 table only."""
+    from scipy.spatial import cKDTree
+
+    coords = table_coords(table)
+    n = len(coords)
+    if workers is None:
+        workers = max(1, (os.cpu_count() or 2) - 1)
+    tree = cKDTree(coords)
+    md = np.zeros(n, dtype=np.float32)
+    for i in range(0, n, 50000):
+        end = min(i + 50000, n)
+        dists, _ = tree.query(coords[i:end], k=k + 1, workers=workers)
+        md[i:end] = np.mean(dists[:, 1:], axis=1)
+    m, s, t = threshold_numpy(md, threshold_factor)
+    with np.errstate(invalid="ignore"):
+        mask = md < t
+    return {"mean_dists": md, "mean": m, "std": s, "threshold": t, "mask": mask, "k": k, "threshold_factor": threshold_factor}
+
+
 def mean_dists_brute_c(xyz: np.ndarray, k: int) -> np.ndarray:
     """O(N^2) scalar C restatement of the cKDTree arithmetic (no scipy)."""
     coords = np.ascontiguousarray(xyz, dtype=np.float32)

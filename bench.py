@@ -1,9 +1,16 @@
 #!/usr/bin/env python
-"""bench.py -- the point-cloud filtering hot path of 3dgsconverter on MI355X, every BASELINE.json config on one line.
+"""bench.py -- the point-cloud filtering hot path of 3dgsconverter on MI355X; with --full every BASELINE.json config on one line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n SPLATS_PER_GPU] [--k 16]      (N > 1: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (ranks from a launcher)
     python bench.py --workload kmeans [--gpus N]   # BASELINE.json configs[4] alone (strong scaling over the chunks)
+    python bench.py --full [...]                   # everything below: other configurations, CPU baselines, per-kernel passes
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, --dump-outputs if given, the
+result line.  Its roofline is priced from the HIP events inside the timed region, so it costs no extra pass.  --full adds
+what takes runs of its own: the other configurations and the sustained headline (N=1) or configs[3] / configs[2] (N>1),
+the CPU baselines, the per-kernel passes (kernel_ms_per_step beyond knn, phases_ms_per_step) and the grid description.
+--no-secondary and --no-cpu-baseline take parts of that out again.
 
 HEADLINE (the top-level fields; BASELINE.json's metric): one SOR step = one pass of the hot path over one batch of
 synthetic splats whose xyz is already resident in HBM: grid binning -> exact KNN mean distance (knn_brick +
@@ -12,7 +19,7 @@ quoted on -- 10M uniform-random splats (L=5, seed 0: SURVEY.md 8(d) config 3's c
 GPU adds one more 10M-splat index shard (weak scaling) and the step is the slab exchange of
 3dgsconverter_amd/dist_slab.py (RCCL from the C library).
 
-At N=1 the same run also times, and reports under "configs", every other BASELINE.json configuration and the clouds a
+At N=1 a --full run also times, and reports under "configs", every other BASELINE.json configuration and the clouds a
 uniform grid is bad at -- each with its own roofline and CPU baseline:
     config1       1M splats SOR k=16 (configs[1])
     config2       10M splats: density filter (sensitivity 0.5) -> SOR k=16 on the survivors, rows resident in HBM across
@@ -363,7 +370,7 @@ def cpu_sor(xyz_host, k, sigma, gpu_mask):
             "mask_identical_to_gpu": bool(np.array_equal(ref["mask"], gpu_mask))}
 
 
-def run_sor(L, ctx, xyz_host, k, sigma, steps, warmup, algo=0, groups=False, cpu=False, adaptive=False, dump_dir=None):
+def run_sor(L, ctx, xyz_host, k, sigma, steps, warmup, algo=0, groups=False, cpu=False, adaptive=False, dump_dir=None, grid=True):
     ctx.set_param("adaptive", 1 if adaptive else 0)
     b = SorBench(L, ctx, xyz_host, k, sigma, algo)
     try:
@@ -384,7 +391,8 @@ def run_sor(L, ctx, xyz_host, k, sigma, steps, warmup, algo=0, groups=False, cpu
             out["kernel_ms_per_step"] = dict({"knn": round(t["event_ms"], 4)}, **g,
                                              note="knn: HIP events inside the timed region (every %d-th step); the others: a "
                                                   "separate pass of %d steps" % (EVENT_EVERY, side))
-        out["grid"] = b.info()
+        if grid:   # (one more KNN launch)
+            out["grid"] = b.info()
         ctx.synchronize()
         if cpu:
             out["cpu_baseline"] = cpu_sor(xyz_host, k, sigma, mask)
@@ -654,7 +662,8 @@ def main_single(args):
     for kv in args.param:
         name, val = kv.split("=")
         ctx.set_param(name, float(val))
-    want_cpu = not args.no_cpu_baseline
+    want_cpu = args.full and not args.no_cpu_baseline
+    secondary = args.full and not args.no_secondary
     small = max(3, min(args.steps, 5))
     t_start = time.perf_counter()
 
@@ -663,13 +672,13 @@ def main_single(args):
 
     xyz = synth_uniform(args.n, args.extent, 0)
     sustained = None
-    if not args.no_secondary:   # FIRST: a utilisation sampler that looks at the first seconds of this process sees the GPU busy
+    if secondary:   # FIRST: a utilisation sampler that looks at the first seconds of this process sees the GPU busy
         try:
             sustained = run_sustained(L, ctx, xyz, args.k, args.sigma, args.algo)
         except Exception as e:   # noqa: BLE001
             sustained = {"error": repr(e)}
-    head = run_sor(L, ctx, xyz, args.k, args.sigma, args.steps, args.warmup, algo=args.algo, groups=True, cpu=want_cpu,
-                   dump_dir=args.dump_outputs)
+    head = run_sor(L, ctx, xyz, args.k, args.sigma, args.steps, args.warmup, algo=args.algo, groups=args.full, cpu=want_cpu,
+                   dump_dir=args.dump_outputs, grid=args.full)
     roof = sor_roofline(args.n, args.k, head["knn_kernel_ms"], args.algo)
     out = {
         "metric": "Msplats/sec SOR k=%d" % args.k, "value": head["value"], "unit": "Msplats/s", "n_gpus": 1, "steps": args.steps,
@@ -680,14 +689,16 @@ def main_single(args):
                    "splats_per_gpu": args.n, "k": args.k, "sigma": args.sigma,
                    "algo": "grid-binned exact KNN" if args.algo != 1 else "LDS-tiled brute force", "parallelism": "single GPU",
                    "host_runtime": "numpy + ctypes on libgsx_hip.so (gsx_dev_malloc / gsx_dev_upload); torch is not imported"},
-        "roofline": roof, "kernel_ms_per_step": head["kernel_ms_per_step"], "survivors_rank0": head["survivors"],
-        "threshold": head["threshold"], "grid": head["grid"]}
+        "roofline": roof, "kernel_ms_per_step": head.get("kernel_ms_per_step", {"knn": head["knn_kernel_ms"]}),
+        "survivors_rank0": head["survivors"], "threshold": head["threshold"]}
+    if "grid" in head:
+        out["grid"] = head["grid"]
     if "dumped_outputs" in head:
         out["dump_outputs"] = {"dir": args.dump_outputs, "files": head["dumped_outputs"]}
     if "cpu_baseline" in head:
         out["cpu_baseline"] = head["cpu_baseline"]
 
-    if not args.no_secondary:
+    if secondary:
         configs = {}
 
         def attempt(name, fn):
@@ -1040,7 +1051,9 @@ def main_slab_one_rank(args, gsx, L, ctx):
     res["r"].check()
     mask = be.to_host(res["r"]["mask"], np.uint8, args.n)
     stats = be.to_host(res["r"]["stats"], np.float32, 3)
-    g = kernel_groups(ctx, L, step, {"bin": L.T_SOR_BIN, "fallback": L.T_SOR_FALLBACK, "stats": L.T_SOR_STATS}, min(args.steps, 10))
+    g = {}
+    if args.full:
+        g = kernel_groups(ctx, L, step, {"bin": L.T_SOR_BIN, "fallback": L.T_SOR_FALLBACK, "stats": L.T_SOR_STATS}, min(args.steps, 10))
     roof = sor_roofline(args.n, args.k, t["event_ms"], single=False)
     out = {"metric": "Msplats/sec SOR k=%d" % args.k, "value": round(args.n * args.steps / t["dt"] / 1e6, 2), "unit": "Msplats/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(t["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak",
@@ -1196,7 +1209,7 @@ def main_multi(args):
         # ---- where a step's time goes: a separate pass with every slot recording (HIP events on this rank's stream; not in
         # the timed region), the slowest rank's figure per phase
         phases = None
-        if exchange["path"] == "slab":
+        if exchange["path"] == "slab" and args.full:
             slots = {"knn_ms": L.T_SOR_KNN, "bin_ms": L.T_SOR_BIN, "fallback_ms": L.T_SOR_FALLBACK, "stats_ms": L.T_SOR_STATS,
                      "slab_kernels_ms": L.T_SLAB_PREP, "exchange_rows_ms": L.T_SLAB_ROWS, "exchange_means_ms": L.T_SLAB_MEANS,
                      "collectives_ms": L.T_SLAB_COLL}
@@ -1241,7 +1254,7 @@ def main_multi(args):
         main_run = run(args.n, args.extent, args.steps, args.warmup)
         watchdog.stage("headline timed")
         config3 = None
-        if not args.no_secondary:
+        if args.full and not args.no_secondary:
             # BASELINE.json configs[3]: 50M splats, SOR k=32, sharded by index across the GPUs of the job (the 8-GPU case; at
             # other N the same 50M are split N ways).  Reported next to the headline, never instead of it.
             try:
@@ -1277,7 +1290,7 @@ def main_multi(args):
         ctx.check()
         watchdog.stage("configs[3] timed")
         config2 = None
-        if not args.no_secondary:
+        if args.full and not args.no_secondary:
             # BASELINE.json configs[2] across the GPUs of the job: density (per-rank voxel histograms merged, dist_density.py) ->
             # device compaction of each rank's rows -> SOR k=16 on the survivors (slab exchange), on the GLOBAL seed-0 cloud, with
             # both masks checked against the hashes of the reference's own run of that chain
@@ -1345,7 +1358,7 @@ def main_multi(args):
         watchdog.stage("configs[2] timed")
         # cpu_baseline leg (rank 0, its own shard: what one GPU of the job replaces), while the other ranks wait at the barrier
         cpu = None
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             from oracle import sor as osor
             xyz0 = synth_uniform(args.n, args.extent, 0)
             workers = max(1, (os.cpu_count() or 2) - 1)
@@ -1404,8 +1417,11 @@ def main():
     ap.add_argument("--sigma", type=float, default=1.0)
     ap.add_argument("--extent", type=float, default=5.0)
     ap.add_argument("--algo", type=int, default=0, help="0 auto (grid), 1 brute force, 2 grid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only: skip the other configurations (N=1) / the 50M k=32 configs[3] line (N>1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the other configurations (N=1) / the configs[3] and configs[2] lines "
+                         "(N>1), the CPU baselines, the per-kernel passes and the grid description")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other configurations (N=1) / the configs[3] and configs[2] lines (N>1)")
     ap.add_argument("--param", action="append", default=[], help="name=value library knob (A/B runs)")
     ap.add_argument("--lanes", type=int, default=0, help="config4: concurrent contexts for the independent K-Means chunks (0 = the library's default)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "slab", "replicated"],

@@ -21,8 +21,23 @@ def _run(*extra):
     return json.loads(lines[0])
 
 
+def test_plain_line_is_the_headline_alone():
+    """no --full: set-up, warm-up, the timed steps and the line -- no other configuration, CPU baseline or per-kernel pass"""
+    d = _run("--n", "300000", "--extent", "10")
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline", "survivors_rank0", "threshold"):
+        assert key in d, key
+    for key in ("cpu_baseline", "configs", "grid", "value_resident"):
+        assert key not in d, key
+    assert list(d["kernel_ms_per_step"]) == ["knn"]      # the HIP events inside the timed region; no separate pass
+    assert d["metric"] == "Msplats/sec SOR k=16" and d["dtype"] == "f32 select / f64 finalize" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Msplats/s"
+    assert abs(d["value"] - 300000 / (d["ms_per_step"] * 1e-3) / 1e6) < 0.02 * d["value"]
+    assert d["roofline"]["kernel"] == "knn_brick_kernel" and d["roofline"]["kernel_ms"] > 0
+
+
 def test_sor_line_has_the_contract_fields():
-    d = _run("--n", "300000", "--extent", "10", "--no-secondary")
+    d = _run("--n", "300000", "--extent", "10", "--full", "--no-secondary")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key

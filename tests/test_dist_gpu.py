@@ -428,7 +428,7 @@ def test_bench_gpus_2_end_to_end(launcher, tmp_path):
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--n", "400000", "--n3", "1000000", "--k3", "16",
-           "--n2", "1000000"]
+           "--n2", "1000000", "--full"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "GSX_RDZV_FILE"):
         env.pop(k, None)

@@ -140,7 +140,7 @@ def main(args):
         "kernel_ms_per_step": {"assign (operands + mfma + exact list)": round(ms_as / steps, 3),
                                "update (label sort + segmented reduce)": round(ms_up / steps, 3)},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # the reference's CPU path for the same call (gpu_ops.py:48-52: MiniBatchKMeans, batch 16384, n_init auto), ONE chunk
         from sklearn.cluster import MiniBatchKMeans
         x = first_host

@@ -8,15 +8,15 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
-timeout 900 python bench.py > $OUT/bench_${R}_10m.json 2> $OUT/bench_${R}.err
-timeout 600 python bench.py --exchange slab --steps 20 --no-cpu-baseline > $OUT/bench_${R}_slab_1rank.json 2>> $OUT/bench_${R}.err
-timeout 600 python bench.py --n 50000000 --extent 10 --k 32 --steps 10 --no-cpu-baseline --no-secondary > $OUT/bench_${R}_50m_k32.json 2>> $OUT/bench_${R}.err
+timeout 900 python bench.py --full > $OUT/bench_${R}_10m.json 2> $OUT/bench_${R}.err
+timeout 600 python bench.py --exchange slab --steps 20 --full --no-cpu-baseline > $OUT/bench_${R}_slab_1rank.json 2>> $OUT/bench_${R}.err
+timeout 600 python bench.py --n 50000000 --extent 10 --k 32 --steps 10 --full --no-cpu-baseline --no-secondary > $OUT/bench_${R}_50m_k32.json 2>> $OUT/bench_${R}.err
 # the N-rank code path on this one-GPU box: bench.py starts its own ranks, which share the GPU over the hostwire transport
 # (round 6: the secondary lines run BASELINE's own sizes -- 50M k=32, 10M density -> SOR -- on the GLOBAL seed-0 clouds and check the
 #  gathered masks against the reference-run hashes of tests/golden/large_cases.json: mask_matches_reference_run)
-timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --n 2000000 --no-cpu-baseline > $OUT/bench_${R}_gpus2_hostwire.json 2>> $OUT/bench_${R}.err
+timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --n 2000000 --full --no-cpu-baseline > $OUT/bench_${R}_gpus2_hostwire.json 2>> $OUT/bench_${R}.err
 cd /tmp
-B="--steps 20 --warmup 3 --no-cpu-baseline --no-secondary"
+B="--steps 20 --warmup 3 --full --no-cpu-baseline --no-secondary"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${R} -o trace -- python $ROOT/bench.py $B > $OUT/prof_${R}.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${R}_km -o trace -- python $ROOT/tools/probe_kmeans.py > $OUT/prof_${R}_km.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${R}_slab -o trace -- python $ROOT/bench.py --exchange slab $B > $OUT/prof_${R}_slab.log 2>&1
@@ -28,7 +28,7 @@ rm -rf $OUT/prof_${R}_sog
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_${R}_dens -o trace -- python $ROOT/tools/probe_density.py > $OUT/prof_${R}_dens.log 2>&1
 python $ROOT/tools/rocpd_summary.py $OUT/prof_${R}_dens/trace_results.db > $OUT/kernel_stats_${R}_density.txt 2>&1
 rm -rf $OUT/prof_${R}_dens
-P="--steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
+P="--steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary"
 timeout 600 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch_${R} -o pmc -- python $ROOT/bench.py $P > /dev/null 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write_${R} -o pmc -- python $ROOT/bench.py $P > /dev/null 2>&1
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM_RD -d $OUT/pmc_sq1_${R} -o pmc -- python $ROOT/bench.py $P > /dev/null 2>&1
@@ -64,7 +64,7 @@ python $ROOT/tools/rocpd_summary.py --pmc $OUT/calib_fetch_${R}/pmc_results.db $
 rm -rf $OUT/calib_fetch_${R} $OUT/calib_write_${R}
 timeout 120 $ROOT/tools/ubench/mfma_valu_overlap > $OUT/mfma_valu_overlap_${R}.txt 2>&1
 cd $ROOT
-timeout 1200 python bench.py --gpus 8 --steps 5 --warmup 2 --n 1000000 --no-cpu-baseline > $OUT/bench_${R}_gpus8_hostwire.json 2>> $OUT/bench_${R}.err
+timeout 1200 python bench.py --gpus 8 --steps 5 --warmup 2 --n 1000000 --full --no-cpu-baseline > $OUT/bench_${R}_gpus8_hostwire.json 2>> $OUT/bench_${R}.err
 for T in "" _km _slab; do python tools/rocpd_summary.py $OUT/prof_${R}${T}/trace_results.db > $OUT/kernel_stats_${R}${T}.txt 2>&1; done
 python tools/rocpd_summary.py --pmc $OUT/pmc_fetch_${R}/pmc_results.db $OUT/pmc_write_${R}/pmc_results.db > $OUT/pmc_${R}_tcc.txt 2>&1
 python tools/rocpd_summary.py --pmc $OUT/pmc_sq1_${R}/pmc_results.db $OUT/pmc_sq2_${R}/pmc_results.db $OUT/pmc_sq3_${R}/pmc_results.db $OUT/pmc_sq4_${R}/pmc_results.db $OUT/pmc_grbm_${R}/pmc_results.db > $OUT/pmc_${R}_sq.txt 2>&1

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out; mkdir -p $OUT
 TAGS=${1:-}
-ARGS=${2:---steps 20 --no-cpu-baseline --no-secondary}
+ARGS=${2:---steps 20 --full --no-cpu-baseline --no-secondary}
 NAME=${3:-var}
 : > $OUT/${NAME}_summary.txt
 for tag in default $TAGS; do

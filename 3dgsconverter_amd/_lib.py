@@ -212,6 +212,10 @@ SIGNATURES = {
     "gsx_ksplat_pack_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I64, _I, _I, _I64, C.c_float, _P, _P, _I64, _P, _I64, _P]),
     "gsx_ksplat_math_dev": (_I, [_P, _P, _I64, _P, _P]),
     "gsx_np_expf_host": (_I, [_P, _P, _I64]),
+    "gsx_splat_pack_dev": (_I, [_P, _P, C.POINTER(SpzLayout), _I, _I, _I, _I64, _P, _P, _P]),
+    "gsx_splat_keys_dev": (_I, [_P, _P, _I64, _P]),
+    "gsx_splat_order_dev": (_I, [_P, _P, _I64, _P]),
+    "gsx_splat_permute_dev": (_I, [_P, _P, _P, _I64, _P]),
 }
 
 _lib = None
@@ -1410,7 +1414,7 @@ _np_exp_checked = None
 
 
 def np_exp_probe() -> bool:
-    """The .ksplat writer stores np.exp's float32 bits, so the device's exp (csrc/np_exp.h) must be THIS process's numpy's.  Probed
+    """The .ksplat and .splat writers store np.exp's float32 bits, so the device's exp (csrc/np_exp.h) must be THIS process's numpy's.  Probed
     once per process: the host twin against np.exp on np_exp_probe_vector().  On a mismatch: a RuntimeWarning and False (the
     writer then takes every exp-derived result -- scales, alpha -- from numpy on the host, and stays exact), or under
     GSX_STRICT_NUMPY=1 a GsxError."""
@@ -1427,8 +1431,8 @@ def np_exp_probe() -> bool:
     if len(bad):
         i = int(bad[0])
         msg = ("numpy %s's float32 exp differs from the one libgsx_hip reproduces (numpy 2.x's AVX512F / AVX2 routine) on %d of %d "
-               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): the .ksplat writer takes scales and alpha from numpy "
-               "on the host.  GSX_STRICT_NUMPY=1 turns this warning into an error."
+               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): the .ksplat and .splat writers take every exp-derived "
+               "value from numpy on the host.  GSX_STRICT_NUMPY=1 turns this warning into an error."
                % (np.__version__, len(bad), len(x), int(x.view(np.uint32)[i]), int(got[i]), int(want[i])))
         if os.environ.get("GSX_STRICT_NUMPY") == "1":
             _np_exp_checked = None
@@ -1557,6 +1561,123 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
             b.free()
         if leased:
             ar.unlease("ksplat")
+        if own:
+            ctx.close()
+
+
+SPLAT_RECORD = np.dtype([("pos", "<f4", (3,)), ("scale", "<f4", (3,)), ("color", "u1", (4,)), ("rot", "u1", (4,))])   # splat.py:155-160
+
+
+def splat_metric_host(data: np.ndarray) -> np.ndarray:
+    """splat.py:92-94 with numpy's own exp: the float32 visibility metric of every row"""
+    with np.errstate(all="ignore"):
+        return np.exp((data["scale_0"] + data["scale_1"]) + data["scale_2"]) * (1 / (1 + np.exp(-data["opacity"])))
+
+
+def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None" = None, listed: "dict | None" = None,
+                     variant: str = "pack", device: int = 0) -> np.ndarray:
+    """The .splat writer's whole file on a splat table (formats/splat.py:82-166): the raw rows are uploaded ONCE; one device pass
+    keys every row by -metric and packs its 32-byte record in input order (gsx_splat_pack_dev), a stable radix sort orders the
+    keys (gsx_splat_order_dev) and the records are permuted into that order (gsx_splat_permute_dev) -> uint8[32 n], the file.
+
+    data: 1-D structured table, x y z, scale_0..2, rot_0..3, opacity and (rgb False) f_dc_0..2 little-endian float32, or (rgb
+    True) the u1 fields red, green, blue (formats/splat_writer.py checks).  variant "gather": the sort-first alternative (keys
+    pass, sort, records gathered from the raw rows in sorted order), kept for the measurement of tools/probe_splat.py.
+    listed: a dict that receives "exp_host" (True when the numpy probe failed: the metric, the scales and alpha then come from
+    numpy, the sort and the rest from the device).
+
+    Runs on the process's arena while it holds the "splat" lease; a second call at the same moment (another thread) takes a
+    context and buffers of its own."""
+    lib = require_hip()
+    n = len(data)
+    exp_ok = np_exp_probe()
+    src = data
+    names = [nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields] + (["red", "green", "blue"] if rgb else [])
+    if data.dtype.itemsize > 512:            # only the fields this writer reads
+        import numpy.lib.recfunctions as rfn
+        data = rfn.repack_fields(data[names])
+    data = np.ascontiguousarray(data)
+    fields = data.dtype.fields
+    colour = [int(fields[c][1]) for c in ("red", "green", "blue")] if rgb else [-1, -1, -1]
+    ar = arena(device)
+    leased = ar.lease("splat")
+    own = not leased
+    ctx = ar.ctx if leased else Context(device)
+    bufs = []
+    import time as _time
+    _t = [_time.perf_counter()]
+
+    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
+        if stage_ms is not None:
+            ctx.synchronize()
+            now = _time.perf_counter()
+            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
+            _t[0] = now
+
+    def alloc(nbytes, name):
+        if leased:
+            return ar.buf("splat_" + name, nbytes)
+        b = ctx.alloc(max(int(nbytes), 16))
+        bufs.append(b)
+        return b
+    try:
+        out = np.empty(32 * n, np.uint8)
+        if n == 0:
+            return out
+        toucher = prefault(out) if out.nbytes >= (1 << 22) else None
+        lay = spz_layout(data.dtype)
+        d_rows = alloc(data.nbytes + 64, "rows")        # (the pack kernel reads up to 15 bytes past the last row)
+        upload_table(lib, ctx, d_rows.ptr, data)
+        mark("upload")
+        d_keys, d_order = alloc(4 * n, "keys"), alloc(4 * n, "order")
+        d_recs, d_out = alloc(32 * n, "recs"), alloc(32 * n, "out")
+
+        def pack(order, keys, recs):
+            check(lib.gsx_splat_pack_dev(ctx.handle, d_rows.ptr, C.byref(lay), *colour, n, order, keys, recs), "gsx_splat_pack_dev")
+        if variant == "gather":
+            pack(None, d_keys.ptr, None)
+            mark("keys")
+        else:
+            pack(None, d_keys.ptr, d_recs.ptr)
+            mark("key_pack")
+        if not exp_ok:                       # another exp than numpy's: numpy's metric, keyed and sorted on the device
+            d_metric = alloc(4 * n, "metric")
+            d_metric.upload(np.ascontiguousarray(splat_metric_host(src), np.float32))
+            check(lib.gsx_splat_keys_dev(ctx.handle, d_metric.ptr, n, d_keys.ptr), "gsx_splat_keys_dev")
+            mark("host_metric")
+        check(lib.gsx_splat_order_dev(ctx.handle, d_keys.ptr, n, d_order.ptr), "gsx_splat_order_dev")
+        mark("sort")
+        if variant == "gather":
+            pack(d_order.ptr, None, d_out.ptr)
+            mark("gather_pack")
+        else:
+            check(lib.gsx_splat_permute_dev(ctx.handle, d_recs.ptr, d_order.ptr, n, d_out.ptr), "gsx_splat_permute_dev")
+            mark("permute")
+        if toucher is not None:
+            toucher.join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.ctypes.data, d_out.ptr, out.nbytes), "gsx_dev_download_staged")
+        mark("download")
+        if not exp_ok:                       # the exp-derived bytes (scales, alpha) from numpy, in the device's order
+            order = d_order.download(np.uint32, n).astype(np.int64)
+            rec = out.view(SPLAT_RECORD)
+            with np.errstate(all="ignore"):
+                rec["scale"] = np.column_stack([np.exp(src["scale_%d" % a][order]) for a in range(3)])
+                rec["color"][:, 3] = np.clip((1 / (1 + np.exp(-src["opacity"][order]))) * 255, 0, 255).astype(np.uint8)
+            mark("host_patch")
+        if listed is not None:
+            listed["exp_host"] = not exp_ok
+        return out
+    except GsxError:
+        if leased:
+            ar.unlease("splat")
+            leased = False
+            release_arenas()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if leased:
+            ar.unlease("splat")
         if own:
             ctx.close()
 

@@ -196,6 +196,7 @@ struct gsx_ctx {
     gsx::DevBuf scratch4;
     gsx::DevBuf scratch5;
     gsx::DevBuf ksplat_keys; // u32[7 * tiles]: the straddling buckets' min / max keys and NaN flags (ksplat.hip)
+    gsx::DevBuf splat_sort;  // u32[n] sorted keys + rocprim temporary storage (splat.hip)
 };
 
 namespace gsx {

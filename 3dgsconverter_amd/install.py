@@ -19,7 +19,7 @@ import sys
 _saved = {}
 
 
-def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True):
+def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -27,7 +27,10 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     spz_writer: also rebind ``gsconverter.formats.spz.SpzFormat.write`` to formats/spz_writer.py:write_spz (SH-degree scan and
     the whole body on the GPU; identical file bytes).  A reference without that module is left as it is.
     ksplat_writer: also rebind ``gsconverter.formats.ksplat.KSplatFormat.write`` to formats/ksplat_writer.py:write_ksplat (SH-degree
-    scan, bucket centres and every row on the GPU; identical file bytes).  A reference without that module is left as it is."""
+    scan, bucket centres and every row on the GPU; identical file bytes).  A reference without that module is left as it is.
+    splat_writer: also rebind ``gsconverter.formats.splat.SplatFormat.write`` to formats/splat_writer.py:write_splat (metric, sort
+    and every record on the GPU; the reference's records, equal metrics kept in input order).  A reference without that module
+    is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -86,6 +89,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.ksplat_writer import write_ksplat
             _saved.setdefault(("ksplatformat", "write"), ksmod.KSplatFormat.write)
             ksmod.KSplatFormat.write = lambda self, data, path, compression_level=0, **kw: write_ksplat(data, path, compression_level, **kw)
+    if splat_writer:
+        try:
+            spmod = importlib.import_module("gsconverter.formats.splat")
+        except ImportError:
+            spmod = None
+        if spmod is not None:
+            from .formats.splat_writer import write_splat
+            _saved.setdefault(("splatformat", "write"), spmod.SplatFormat.write)
+            spmod.SplatFormat.write = lambda self, data, path, **kw: write_splat(data, path, **kw)
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -105,6 +117,9 @@ def uninstall():
             continue
         if modname == "ksplatformat":
             importlib.import_module("gsconverter.formats.ksplat").KSplatFormat.write = val
+            continue
+        if modname == "splatformat":
+            importlib.import_module("gsconverter.formats.splat").SplatFormat.write = val
             continue
         if modname == "sys.modules":
             if val is None:

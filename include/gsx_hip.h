@@ -670,6 +670,29 @@ int gsx_ksplat_math_dev(gsx_ctx *ctx, const float *x_dev, int64_t n, uint32_t *e
  * process's numpy.  HOST pointers. */
 int gsx_np_expf_host(const float *x, float *out, int64_t n);
 
+
+/* ---- the .splat writer on a DEVICE-RESIDENT splat table (csrc/splat.hip) ----
+ * gsconverter/formats/splat.py:82-166 (SplatFormat.write).  The file is n records of 32 bytes -- 3 f32 position, 3 f32
+ * np.exp(scale), 4 u8 colour (r g b alpha), 4 u8 rotation -- in the order np.argsort(-metric, kind="stable") (the reference's
+ * sort is numpy's unstable default; equal keys keep input order here).  The rows use gsx_spz_layout: x y z, rot_0..3,
+ * scale_0..2 and opacity required, f_dc_0..2 too unless the colour comes from u1 fields.  All calls are asynchronous. */
+/* splat.py:92-94 and :104-161: for every row, the sort key of -metric (metric = np.exp((s0 + s1) + s2) * (1 / (1 + np.exp(-opacity))),
+ * float32; -0 keyed as +0, every NaN as 0xffffffff) and the row's record.  red_off / green_off / blue_off: byte offsets of the u1
+ * fields red, green, blue (splat.py:140-143), or all -1 for the colour of :134-138 from f_dc_0..2.
+ *   order_dev NULL, keys_dev and recs_dev set: rows in input order, tiles staged in LDS -> keys_dev[i], recs_dev + 32 i;
+ *   order_dev NULL, recs_dev NULL: keys only;
+ *   order_dev set, keys_dev NULL: the record of row order_dev[i] at recs_dev + 32 i (the sort-first variant).
+ * rows_dev and recs_dev 16-byte aligned; rows_dev readable up to 15 bytes past the last row. */
+int gsx_splat_pack_dev(gsx_ctx *ctx, const void *rows_dev, const gsx_spz_layout *layout, int red_off, int green_off, int blue_off, int64_t n,
+                       const uint32_t *order_dev, uint32_t *keys_dev, uint8_t *recs_dev);
+/* splat.py:93-98 from a given float32 metric: keys_dev[i] = the sort key of -metric_dev[i], as gsx_splat_pack_dev keys it. */
+int gsx_splat_keys_dev(gsx_ctx *ctx, const float *metric_dev, int64_t n, uint32_t *keys_dev);
+/* splat.py:98 `np.argsort(-metric)`, made stable: order_dev = the row indices sorted by key, equal keys in ascending index order
+ * (a stable radix sort of (key, index) pairs; n < 2^32).  keys_dev is left as it is. */
+int gsx_splat_order_dev(gsx_ctx *ctx, const uint32_t *keys_dev, int64_t n, uint32_t *order_dev);
+/* splat.py:101 `data[sorted_indices]` on the records: out_dev + 32 i = recs_dev + 32 order_dev[i] (both 16-byte aligned). */
+int gsx_splat_permute_dev(gsx_ctx *ctx, const uint8_t *recs_dev, const uint32_t *order_dev, int64_t n, uint8_t *out_dev);
+
 #ifdef __cplusplus
 }
 #endif

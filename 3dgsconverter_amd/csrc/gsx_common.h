@@ -58,7 +58,9 @@ struct KnnWs {
     DevBuf packed;      // float4[n_ref]  (brute: original order; grid: cell-sorted refs)
     DevBuf qsorted;     // float4[q_count] cell-sorted queries when q != all refs
     DevBuf bucketpts;   // float4[n_ref] points grouped by bucket (between the two sort levels)
-    DevBuf bkcnt;       // u32 bucket sizes | starts | cursors
+    DevBuf bkcnt;       // u32 bucket sizes | starts
+    DevBuf tilecnt;     // u16[slot][bucket]: points of each coarse-pass tile in each bucket
+    DevBuf tileoff;     // u32[slot][bucket]: where each tile's run starts inside its bucket
     DevBuf cellstart;   // u32[cap+1]
     DevBuf qcellstart;
     DevBuf gridparams;  // GridParams + work counters
@@ -78,7 +80,7 @@ struct KnnWs {
     uint64_t refined_total = 0;  // host-side: points gathered into sub-clouds by the current call
     void release_all()
     {
-        DevBuf *all[] = {&packed, &qsorted, &bucketpts, &bkcnt, &cellstart, &qcellstart, &gridparams, &bboxpart,
+        DevBuf *all[] = {&packed, &qsorted, &bucketpts, &bkcnt, &tilecnt, &tileoff, &cellstart, &qcellstart, &gridparams, &bboxpart,
                          &faillist, &extraitems, &deferred, &cellflag, &subxyz, &submap, &submean, &subkth,
                          &heavylist, &heavypart, &probe};
         for (auto b : all) b->release();

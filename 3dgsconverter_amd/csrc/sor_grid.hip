@@ -7,7 +7,7 @@
 //
 // Pipeline (all on one stream, no host round trip):
 //   bbox_partial -> grid_params            per-axis min/max, cell edge h for ~m pts/cell
-//   bucket_hist / bucket_scan / bucket_scatter / bucket_sort
+//   bucket_hist / bucket_offsets / bucket_scatter / bucket_sort
 //                                          two-level counting sort into float4 {x,y,z,orig}: every
 //                                          per-point atomic is an LDS atomic (see the kernels)
 //   knn_brick                              one WAVE per 2x2x2-cell brick (~56 queries)
@@ -342,60 +342,73 @@ __device__ __forceinline__ int bucket_of(const GridParams &g, int cy, int cz)
 // The points arrive in arbitrary order.  A one-level counting sort needs one returning device-scope
 // atomic and one random 16-byte write per point (measured 0.69 ms per 10M points: the L2 atomic
 // units, not HBM, are the limit).  Two levels keep every per-point atomic in LDS:
-//   A1 bucket_hist    tile of 16k points -> LDS histogram over <= 4096 buckets -> one global
-//                     atomic per (tile, non-empty bucket)
-//   A0 bucket_scan    exclusive scan of the bucket sizes (one workgroup)
-//   A2 bucket_scatter same tiles: reserve a run per (tile, bucket) with ONE returning atomic, rank
-//                     inside the run with LDS atomics, write float4 {x,y,z,orig} runs
+//   A1 bucket_hist    one BIN_TILE-point tile per workgroup -> LDS histogram over <= 4096 buckets ->
+//                     the tile's row of u16 counts in tile_cnt[slot][bucket] (plain stores, no atomics)
+//   A2 bucket_offsets one workgroup per strip of 16 buckets: exclusive scan down each bucket's column of
+//                     tile counts -> tile_off[slot][bucket] and the bucket's size; the last workgroup
+//                     scans the sizes into bk_start
+//   A3 bucket_scatter same tiles: rank inside the (tile, bucket) run with LDS atomics, stage the float4
+//                     {x,y,z,orig} records in LDS in bucket order, write them to bk_start[b] +
+//                     tile_off[slot][b] + rank run by run -- no global atomic
 //   B  bucket_sort    one workgroup per bucket: LDS histogram over the bucket's cells, LDS scan ->
 //                     cell_start (bucket base + local prefix, no global scan), LDS cursors -> final
 //                     position; reads are contiguous, writes stay inside the bucket's ~64 KiB window.
-__device__ void bucket_scan_body(int nb, unsigned *bk_cnt, unsigned *bk_start, unsigned *bk_cursor);
+// Inside a bucket the runs of the tiles are laid out in SLOT order: the tiles of one XCD (workgroup i runs on XCD i % 8)
+// first, in tile order.  A run is ~2.5 points (40 B), so a 128-B line of the bucket-grouped array holds the runs of
+// ~3 tiles; in slot order these tiles run on the same XCD at about the same time and their partial lines merge in that
+// XCD's L2 before they are written back (runs reserved by device atomics, in arrival order, left L2 as 32-B pieces:
+// 2.2x the payload; plain tile order costs ~35 us per 10M points, profiles/r08_binning_ab.txt).  The order only decides
+// where a point lands inside its bucket; bucket_sort re-sorts the bucket.
+#ifndef GSX_BIN_XCDS
+#define GSX_BIN_XCDS 8
+#endif
+constexpr int BIN_XCDS = GSX_BIN_XCDS;   // (1: the runs in plain tile order)
+
+// the ONE partition of [0, n) into tiles that bucket_hist, bucket_offsets and bucket_scatter share: tile t = workgroup t
+// covers [t * BIN_TILE, min(n, (t + 1) * BIN_TILE)) and owns row slot(t) of tile_cnt / tile_off
+struct BinTiles {
+    int ntiles, per_xcd;   // slots = BIN_XCDS * per_xcd >= ntiles; the slots past the last tile hold no tile
+    __host__ __device__ static BinTiles of(int n)
+    {
+        const int nt = (n + BIN_TILE - 1) / BIN_TILE;
+        return BinTiles{nt, (nt + BIN_XCDS - 1) / BIN_XCDS};
+    }
+    __host__ __device__ int slots() const { return BIN_XCDS * per_xcd; }
+    __host__ __device__ int slot(int t) const { return (t % BIN_XCDS) * per_xcd + t / BIN_XCDS; }
+    __host__ __device__ int tile(int s) const { return (s % per_xcd) * BIN_XCDS + s / per_xcd; }   // >= ntiles: empty slot
+};
 
 __global__ __launch_bounds__(256) void bucket_hist_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                           const float *__restrict__ z, int64_t stride, int first, int n,
-                                                          GridParams *__restrict__ gp,
-                                                          unsigned *__restrict__ bk_cnt, unsigned *__restrict__ bk_start,
-                                                          unsigned *__restrict__ bk_cursor)
+                                                          const GridParams *__restrict__ gp, unsigned short *__restrict__ tile_cnt)
 {
     __shared__ unsigned hist[MAX_BUCKETS];
     const GridParams g = *gp;
     if (g.bad_input) return;
-    const int ntiles = (n + BIN_TILE - 1) / BIN_TILE;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        for (int i = threadIdx.x; i < g.bk_count; i += 256) hist[i] = 0;
-        __syncthreads();
-        const int lo = t * BIN_TILE, hi = min(n, lo + BIN_TILE);
-        for (int i0 = lo + threadIdx.x; i0 < hi; i0 += 2048) {   // 16 independent loads in flight per lane
-            float py[8], pz[8];
+    const BinTiles bt = BinTiles::of(n);
+    const int t = blockIdx.x;
+    if (t >= bt.ntiles) return;
+    for (int i = threadIdx.x; i < g.bk_count; i += 256) hist[i] = 0;
+    __syncthreads();
+    const int lo = t * BIN_TILE, hi = min(n, lo + BIN_TILE);
+    for (int i0 = lo + threadIdx.x; i0 < hi; i0 += 2048) {   // 16 independent loads in flight per lane
+        float py[8], pz[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = min(i0 + 256 * u, hi - 1);
-                const int64_t s = (int64_t)(first + i) * stride;
-                py[u] = y[s];
-                pz[u] = z[s];
-            }
+        for (int u = 0; u < 8; ++u) {
+            const int i = min(i0 + 256 * u, hi - 1);
+            const int64_t s = (int64_t)(first + i) * stride;
+            py[u] = y[s];
+            pz[u] = z[s];
+        }
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (i0 + 256 * u < hi)
-                    atomicAdd(&hist[bucket_of(g, cell_coord(py[u], g.oy, g.inv_h, g.ny), cell_coord(pz[u], g.oz, g.inv_h, g.nz))], 1u);
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < g.bk_count; i += 256) {
-            const unsigned c = hist[i];
-            if (c) atomicAdd(&bk_cnt[i], c);
-        }
-        __syncthreads();
+        for (int u = 0; u < 8; ++u)
+            if (i0 + 256 * u < hi)
+                atomicAdd(&hist[bucket_of(g, cell_coord(py[u], g.oy, g.inv_h, g.ny), cell_coord(pz[u], g.oz, g.inv_h, g.nz))], 1u);
     }
-    // the last workgroup to arrive scans the bucket sizes (formerly a one-workgroup launch of its own)
-    __shared__ unsigned s_last;
-    __builtin_amdgcn_s_waitcnt(0);   // this workgroup's device-scope atomics have completed
     __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(&gp->ticket_hist, 1u) == gridDim.x - 1 ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) gp->ticket_hist = 0;
-    bucket_scan_body(g.bk_count, bk_cnt, bk_start, bk_cursor);
+    static_assert(BIN_TILE <= 65535, "a tile's per-bucket count is stored as u16");
+    unsigned short *row = tile_cnt + (size_t)bt.slot(t) * g.bk_count;
+    for (int i = threadIdx.x; i < g.bk_count; i += 256) row[i] = (unsigned short)hist[i];
 }
 
 __device__ __forceinline__ unsigned block_exclusive_scan_256(unsigned v, unsigned *total, unsigned *wsum /*[4]*/)
@@ -422,35 +435,131 @@ __device__ __forceinline__ unsigned block_exclusive_scan_256(unsigned v, unsigne
     return base + inc - v;
 }
 
-// bk_start[0..bk_count] = exclusive scan of bk_cnt; bk_cursor = copy of bk_start; bk_cnt re-zeroed for the next call.
-// Run by the 256 threads of bucket_hist's last workgroup; bk_cnt was accumulated with device-scope atomics (L2).
-__device__ void bucket_scan_body(int nb, unsigned *bk_cnt, unsigned *bk_start, unsigned *bk_cursor)
+constexpr int OFFSETS_THREADS = 1024;
+constexpr int OFFSETS_BUCKETS = 16;                                       // buckets of one workgroup (a strip of the tables)
+constexpr int OFFSETS_CHUNKS = OFFSETS_THREADS / OFFSETS_BUCKETS;         // slot ranges of a strip, one per lane of a bucket
+
+// bk_start[0..bk_count] = exclusive scan of bk_size.
+// Run by the OFFSETS_THREADS threads of bucket_offsets' last workgroup; bk_size was written with agent-scope (write-through) stores.
+__device__ void bucket_scan_body(int nb, const unsigned *bk_size, unsigned *bk_start)
 {
-    __shared__ unsigned wsum[4];
-    static_assert(MAX_BUCKETS <= 256 * 16, "bucket_scan_body preloads 16 values per thread");
-    unsigned vals[16];   // every bucket size requested before the first scan round (one round trip, not nb/256)
+    constexpr int T = OFFSETS_THREADS, W = T / 64, PER = MAX_BUCKETS / T;
+    static_assert(PER * T == MAX_BUCKETS, "bucket_scan_body preloads MAX_BUCKETS / T values per thread");
+    __shared__ unsigned wsum[W];
+    unsigned vals[PER];   // every bucket size requested before the first scan round (one round trip)
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        const int i = 256 * u + (int)threadIdx.x;
-        vals[u] = i < nb ? __hip_atomic_load(&bk_cnt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    for (int u = 0; u < PER; ++u) {
+        const int i = T * u + (int)threadIdx.x;
+        vals[u] = i < nb ? __hip_atomic_load(&bk_size[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     }
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned carry = 0;
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        const int b = 256 * u;
-        if (b >= nb) break;
-        const int i = b + threadIdx.x;
+    for (int u = 0; u < PER; ++u) {
+        if (T * u >= nb) break;   // block-uniform
         const unsigned v = vals[u];
-        unsigned tot;
-        const unsigned ex = block_exclusive_scan_256(v, &tot, wsum);
-        if (i < nb) {
-            bk_start[i] = carry + ex;
-            bk_cursor[i] = carry + ex;
-            bk_cnt[i] = 0;
+        unsigned inc = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned o = __shfl_up(inc, off);
+            if (lane >= off) inc += o;
         }
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        unsigned base = 0, tot = 0;
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+            const unsigned x = wsum[i];
+            if (i < w) base += x;
+            tot += x;
+        }
+        __syncthreads();
+        const int i = T * u + (int)threadIdx.x;
+        if (i < nb) bk_start[i] = carry + base + inc - v;
         carry += tot;
     }
     if (threadIdx.x == 0) bk_start[nb] = carry;
+}
+
+constexpr int OFFSETS_UNROLL = 24;   // table loads in flight per lane
+
+// One workgroup per strip of OFFSETS_BUCKETS buckets: lane (chunk c, bucket j) sums tile_cnt[s][b0 + j] over its
+// contiguous range of slots (16 lanes read 32 contiguous bytes of a row), the chunk sums are scanned in LDS, and a second
+// sweep over the same rows (now L2 hits) writes the running sums to tile_off[s][b0 + j] (64 contiguous bytes per row).
+// Workgroup i runs on XCD i % 8: the strips are dealt so that each XCD owns one contiguous range of buckets.  The last
+// workgroup to arrive (ticket in GridParams) turns the bucket sizes into bk_start.
+__global__ __launch_bounds__(OFFSETS_THREADS) void bucket_offsets_kernel(int n, GridParams *__restrict__ gp,
+                                                                         const unsigned short *__restrict__ tile_cnt,
+                                                                         unsigned *__restrict__ tile_off, unsigned *__restrict__ bk_size,
+                                                                         unsigned *__restrict__ bk_start)
+{
+    __shared__ unsigned part[OFFSETS_CHUNKS][OFFSETS_BUCKETS];
+    const GridParams g = *gp;
+    if (g.bad_input) return;
+    const int nb = g.bk_count;
+    const BinTiles bt = BinTiles::of(n);
+    const int strips = (nb + OFFSETS_BUCKETS - 1) / OFFSETS_BUCKETS;
+    const int per_xcd = (strips + BIN_XCDS - 1) / BIN_XCDS;   // (the grid has room for all: MAX_BUCKETS / OFFSETS_BUCKETS)
+    const int strip = (int)(blockIdx.x % BIN_XCDS) * per_xcd + (int)(blockIdx.x / BIN_XCDS);
+    const int j = threadIdx.x % OFFSETS_BUCKETS, c = threadIdx.x / OFFSETS_BUCKETS;
+    const int b = strip * OFFSETS_BUCKETS + j;
+    const bool active = (int)(blockIdx.x / BIN_XCDS) < per_xcd && strip < strips;   // block-uniform
+    if (active) {
+        const bool own = b < nb;
+        const int slots = bt.slots(), per_chunk = (slots + OFFSETS_CHUNKS - 1) / OFFSETS_CHUNKS;
+        const int s_lo = min(slots, c * per_chunk), s_hi = min(slots, s_lo + per_chunk);
+        auto count = [&](int s) -> unsigned {
+            return own && s < s_hi && bt.tile(s) < bt.ntiles ? (unsigned)tile_cnt[(size_t)s * nb + b] : 0u;
+        };
+        // a chunk of at most OFFSETS_UNROLL slots (10M points: 20) is loaded once and kept in registers for the second sweep
+        const bool held = per_chunk <= OFFSETS_UNROLL;   // block-uniform
+        unsigned hv[OFFSETS_UNROLL];
+        unsigned sum = 0;
+        for (int s0 = s_lo; s0 < s_hi; s0 += OFFSETS_UNROLL) {
+#pragma unroll
+            for (int u = 0; u < OFFSETS_UNROLL; ++u) hv[u] = count(s0 + u);
+#pragma unroll
+            for (int u = 0; u < OFFSETS_UNROLL; ++u) sum += hv[u];
+        }
+        part[c][j] = sum;
+        __syncthreads();
+        if (threadIdx.x < 64 * OFFSETS_BUCKETS) {   // wave jj scans the OFFSETS_CHUNKS (= 64) chunk sums of bucket jj
+            static_assert(OFFSETS_CHUNKS == 64, "one wave scans the chunk sums of one bucket");
+            const int jj = threadIdx.x >> 6, lane = threadIdx.x & 63;
+            const unsigned v = part[lane][jj];
+            unsigned inc = v;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned o = __shfl_up(inc, off);
+                if (lane >= off) inc += o;
+            }
+            part[lane][jj] = inc - v;
+            const int bb = strip * OFFSETS_BUCKETS + jj;
+            if (lane == 63 && bb < nb) __hip_atomic_store(&bk_size[bb], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through
+        }
+        __syncthreads();
+        unsigned run = part[c][j];
+        for (int s0 = s_lo; s0 < s_hi; s0 += OFFSETS_UNROLL) {
+            unsigned v[OFFSETS_UNROLL];
+#pragma unroll
+            for (int u = 0; u < OFFSETS_UNROLL; ++u) v[u] = held ? hv[u] : count(s0 + u);
+#pragma unroll
+            for (int u = 0; u < OFFSETS_UNROLL; ++u) {
+                const int s = s0 + u;
+                if (own && s < s_hi && bt.tile(s) < bt.ntiles) tile_off[(size_t)s * nb + b] = run;
+                run += v[u];
+            }
+        }
+    }
+    if (!active) return;   // (only the workgroups that own a strip take a ticket: one returning atomic each on one word)
+    __shared__ unsigned s_last;
+    __builtin_amdgcn_s_waitcnt(0);   // the write-through stores above have completed before the ticket (no L2 write-back needed)
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(&gp->ticket_hist, 1u) == (unsigned)strips - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!s_last) return;
+    if (threadIdx.x == 0) gp->ticket_hist = 0;
+    bucket_scan_body(nb, bk_size, bk_start);
 }
 
 #ifndef GSX_SCATTER_THREADS
@@ -458,57 +567,112 @@ __device__ void bucket_scan_body(int nb, unsigned *bk_cnt, unsigned *bk_start, u
 #endif
 constexpr int SCATTER_THREADS = GSX_SCATTER_THREADS;
 constexpr int SCATTER_PPT = BIN_TILE / SCATTER_THREADS;  // points per thread, kept in registers
+static_assert(SCATTER_PPT * SCATTER_THREADS == BIN_TILE, "a scatter workgroup covers exactly one tile");
 
-// One 8192-point tile per workgroup of 1024 threads, every point read ONCE: coordinates, bucket and the rank the
-// returning LDS atomic hands out stay in registers across the two barriers (count -> reserve the tile's run per bucket
-// with one global atomic -> write).  (Round 1 swept the tile twice with 256 threads: 0.21 ms per 10M points.)
+// One BIN_TILE-point tile per workgroup of 1024 threads, every point read ONCE: coordinates, bucket and the rank the
+// returning LDS atomic hands out stay in registers across the count.  The base of every run of the tile,
+// bk_start[b] + tile_off[slot][b], is loaded with the points: nothing waits on another workgroup.  The records are then
+// staged in LDS in bucket order (local prefix of the tile's histogram + rank) and streamed out in that order: the lanes of
+// one store instruction write whole runs, one L1 -> L2 request per run and line instead of one per record (a run is
+// ~2.5 records).  (Round 1 swept the tile twice with 256 threads: 0.21 ms per 10M points.)
 __global__ __launch_bounds__(SCATTER_THREADS) void bucket_scatter_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                              const float *__restrict__ z, int64_t stride, int first, int n,
-                                                             const GridParams *__restrict__ gp,
-                                                             unsigned *__restrict__ bk_cursor, float4 *__restrict__ out,
+                                                             const GridParams *__restrict__ gp, const unsigned *__restrict__ bk_start,
+                                                             const unsigned *__restrict__ tile_off, float4 *__restrict__ out,
                                                              int ref_only_from)
 {
-    __shared__ unsigned hist[MAX_BUCKETS];   // per-bucket count of this tile
-    __shared__ unsigned base[MAX_BUCKETS];   // start of this tile's run inside the bucket's region
+    constexpr int BPT = MAX_BUCKETS / SCATTER_THREADS;   // buckets per thread
+    static_assert(BIN_TILE * sizeof(float4) + MAX_BUCKETS * sizeof(unsigned) <= 160 * 1024, "the stage and the table fit the LDS");
+    static_assert(BPT * SCATTER_THREADS == MAX_BUCKETS, "every thread owns the same number of buckets");
+    __shared__ float4 stage[BIN_TILE];        // the tile's records in bucket order
+    __shared__ unsigned tab[MAX_BUCKETS];     // count -> local start -> global start minus local start, per bucket
+    unsigned *wsum = reinterpret_cast<unsigned *>(stage);   // scan scratch: the stage is written after the scan
     const GridParams g = *gp;
     if (g.bad_input) return;
-    const int ntiles = (n + BIN_TILE - 1) / BIN_TILE;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        for (int i = threadIdx.x; i < g.bk_count; i += SCATTER_THREADS) hist[i] = 0;
-        __syncthreads();
-        const int lo = t * BIN_TILE, hi = min(n, lo + BIN_TILE);
-        float px[SCATTER_PPT], py[SCATTER_PPT], pz[SCATTER_PPT];
-        int bk[SCATTER_PPT];
-        unsigned rk[SCATTER_PPT];
+    const int nb = g.bk_count;
+    const BinTiles bt = BinTiles::of(n);
+    const int t = blockIdx.x;
+    if (t >= bt.ntiles) return;
+    const unsigned *off = tile_off + (size_t)bt.slot(t) * nb;
+    unsigned gb[BPT];
 #pragma unroll
-        for (int u = 0; u < SCATTER_PPT; ++u) {   // all loads of the tile in flight
-            const int i = min(lo + u * SCATTER_THREADS + (int)threadIdx.x, hi - 1);
-            const int64_t sidx = (int64_t)(first + i) * stride;
-            px[u] = x[sidx];
-            py[u] = y[sidx];
-            pz[u] = z[sidx];
-        }
+    for (int u = 0; u < BPT; ++u) {
+        const int i = u * SCATTER_THREADS + (int)threadIdx.x;
+        gb[u] = i < nb ? bk_start[i] + off[i] : 0u;
+        if (i < nb) tab[i] = 0;
+    }
+    const int lo = t * BIN_TILE, hi = min(n, lo + BIN_TILE);
+    float px[SCATTER_PPT], py[SCATTER_PPT], pz[SCATTER_PPT];
+    int bk[SCATTER_PPT];
+    unsigned rk[SCATTER_PPT];
 #pragma unroll
-        for (int u = 0; u < SCATTER_PPT; ++u) {
-            bk[u] = bucket_of(g, cell_coord(py[u], g.oy, g.inv_h, g.ny), cell_coord(pz[u], g.oz, g.inv_h, g.nz));
-            rk[u] = lo + u * SCATTER_THREADS + (int)threadIdx.x < hi ? atomicAdd(&hist[bk[u]], 1u) : 0u;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < g.bk_count; i += SCATTER_THREADS) {
-            const unsigned c = hist[i];
-            if (c) base[i] = atomicAdd(&bk_cursor[i], c);
-        }
-        __syncthreads();
+    for (int u = 0; u < SCATTER_PPT; ++u) {   // all loads of the tile in flight
+        const int i = min(lo + u * SCATTER_THREADS + (int)threadIdx.x, hi - 1);
+        const int64_t sidx = (int64_t)(first + i) * stride;
+        px[u] = x[sidx];
+        py[u] = y[sidx];
+        pz[u] = z[sidx];
+    }
+    __syncthreads();
 #pragma unroll
-        for (int u = 0; u < SCATTER_PPT; ++u) {
-            const int i = lo + u * SCATTER_THREADS + (int)threadIdx.x;
-            if (i < hi)
-                // points from ref_only_from on are REFERENCE-ONLY (the halo of a multi-GPU slab): bit 31 of
-                // the index word keeps their lanes dead in knn_brick
-                out[base[bk[u]] + rk[u]] = make_float4(px[u], py[u], pz[u],
-                                                       __uint_as_float((unsigned)(first + i) | (i >= ref_only_from ? 0x80000000u : 0u)));
+    for (int u = 0; u < SCATTER_PPT; ++u) {
+        bk[u] = bucket_of(g, cell_coord(py[u], g.oy, g.inv_h, g.ny), cell_coord(pz[u], g.oz, g.inv_h, g.nz));
+        rk[u] = lo + u * SCATTER_THREADS + (int)threadIdx.x < hi ? atomicAdd(&tab[bk[u]], 1u) : 0u;
+    }
+    __syncthreads();
+    // exclusive scan of the tile's histogram in place (each entry is read and rewritten by the thread that owns it)
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned carry = 0;
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        if (u * SCATTER_THREADS >= nb) break;   // block-uniform
+        const int i = u * SCATTER_THREADS + (int)threadIdx.x;
+        const unsigned v = i < nb ? tab[i] : 0u;
+        unsigned inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned up = __shfl_up(inc, o);
+            if (lane >= o) inc += up;
+        }
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        unsigned base = 0, tot = 0;
+#pragma unroll
+        for (int k = 0; k < SCATTER_THREADS / 64; ++k) {
+            const unsigned q = wsum[k];
+            if (k < w) base += q;
+            tot += q;
         }
         __syncthreads();
+        const unsigned ex = carry + base + inc - v;
+        if (i < nb) tab[i] = ex;
+        gb[u] -= ex;   // record j of the stage goes to gb + j
+        carry += tot;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < SCATTER_PPT; ++u) {
+        const int i = lo + u * SCATTER_THREADS + (int)threadIdx.x;
+        if (i < hi)
+            // points from ref_only_from on are REFERENCE-ONLY (the halo of a multi-GPU slab): bit 31 of
+            // the index word keeps their lanes dead in knn_brick
+            stage[tab[bk[u]] + rk[u]] = make_float4(px[u], py[u], pz[u],
+                                                    __uint_as_float((unsigned)(first + i) | (i >= ref_only_from ? 0x80000000u : 0u)));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        const int i = u * SCATTER_THREADS + (int)threadIdx.x;
+        if (i < nb) tab[i] = gb[u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < SCATTER_PPT; ++u) {
+        const int j = u * SCATTER_THREADS + (int)threadIdx.x;
+        if (j < hi - lo) {
+            const float4 r = stage[j];
+            out[tab[bucket_of(g, cell_coord(r.y, g.oy, g.inv_h, g.ny), cell_coord(r.z, g.oz, g.inv_h, g.nz))] + j] = r;
+        }
     }
 }
 
@@ -2418,22 +2582,42 @@ int launch_knn_tree(gsx_ctx *ctx, const float *x, const float *y, const float *z
 
 int64_t grid_cell_cap(int64_t n_ref) { return std::max<int64_t>(n_ref / 2, 64) + 64; }
 
+// The coarse histogram of (x,y,z)[first, first+n): per-tile bucket counts, their per-bucket scans and bk_start.
+static int bin_hist(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, const float *z, int64_t stride, int64_t first,
+                    int64_t n, GridParams *gp)
+{
+    const BinTiles bt = BinTiles::of((int)n);
+    if ((size_t)bt.slots() * MAX_BUCKETS * sizeof(unsigned) > w.tileoff.cap) GSX_FAIL("sor: bin tables not reserved for %lld points", (long long)n);
+    unsigned *bk_size = w.bkcnt.as<unsigned>();
+    hipLaunchKernelGGL(bucket_hist_kernel, dim3(std::max(bt.ntiles, 1)), dim3(256), 0, ctx->stream, x, y, z, stride, (int)first, (int)n, gp,
+                       w.tilecnt.as<unsigned short>());
+    hipLaunchKernelGGL(bucket_offsets_kernel, dim3(MAX_BUCKETS / OFFSETS_BUCKETS), dim3(OFFSETS_THREADS), 0, ctx->stream, (int)n, gp, w.tilecnt.as<unsigned short>(),
+                       w.tileoff.as<unsigned>(), bk_size, bk_size + MAX_BUCKETS);   // its last workgroup scans the bucket sizes
+    GSX_HIP(hipGetLastError());
+    return 0;
+}
+
+// the tables of bin_hist for up to n points (grow-only)
+static int reserve_bin_tables(KnnWs &w, int64_t n)
+{
+    const size_t slots = (size_t)BinTiles::of((int)n).slots();
+    GSX_CHECK(w.tilecnt.reserve(sizeof(unsigned short) * slots * MAX_BUCKETS));
+    GSX_CHECK(w.tileoff.reserve(sizeof(unsigned) * slots * MAX_BUCKETS));
+    return 0;
+}
+
 // Sort (x,y,z)[first, first+n) by cell of the grid in gp: `sorted` and `start` (cell_start) are outputs.
+// hist_done: bin_hist has already run on these points.
 static int bin_points(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, const float *z, int64_t stride, int64_t first,
                       int64_t n, GridParams *gp, unsigned *start, float4 *sorted, int64_t cell_cap = 0, unsigned *cursor = nullptr,
                       int64_t ref_only_from = INT32_MAX, bool hist_done = false)
 {
     const bool big_path = cursor != nullptr;  // adaptive mode: oversized buckets are sorted by all workgroups
-    unsigned *bk_cnt = w.bkcnt.as<unsigned>();
-    unsigned *bk_start = bk_cnt + MAX_BUCKETS;
-    unsigned *bk_cursor = bk_start + MAX_BUCKETS + 1;
+    unsigned *bk_start = w.bkcnt.as<unsigned>() + MAX_BUCKETS;
     float4 *tmp = w.bucketpts.as<float4>();
-    const int tiles = (int)std::min<int64_t>(div_up(n, BIN_TILE), (int64_t)ctx->num_cu * 4);
-    if (!hist_done)
-        hipLaunchKernelGGL(bucket_hist_kernel, dim3(tiles), dim3(256), 0, ctx->stream, x, y, z, stride, (int)first, (int)n, gp,
-                           bk_cnt, bk_start, bk_cursor);   // its last workgroup scans the bucket sizes
-    hipLaunchKernelGGL(bucket_scatter_kernel, dim3(tiles), dim3(SCATTER_THREADS), 0, ctx->stream, x, y, z, stride, (int)first, (int)n,
-                       gp, bk_cursor, tmp, (int)std::min<int64_t>(ref_only_from, INT32_MAX));
+    if (!hist_done) GSX_CHECK(bin_hist(ctx, w, x, y, z, stride, first, n, gp));
+    hipLaunchKernelGGL(bucket_scatter_kernel, dim3(std::max(BinTiles::of((int)n).ntiles, 1)), dim3(SCATTER_THREADS), 0, ctx->stream, x, y, z, stride,
+                       (int)first, (int)n, gp, bk_start, w.tileoff.as<unsigned>(), tmp, (int)std::min<int64_t>(ref_only_from, INT32_MAX));
     if (big_path) GSX_HIP(hipMemsetAsync(start, 0, sizeof(unsigned) * (size_t)(cell_cap + 1), ctx->stream));  // counts of big buckets
     hipLaunchKernelGGL(bucket_sort_kernel, dim3(MAX_BUCKETS), dim3(SORT_THREADS), 0, ctx->stream, gp, bk_start, tmp, sorted, start,
                        big_path ? BIG_BUCKET : 0xffffffffu);
@@ -2509,10 +2693,11 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
     GSX_CHECK(w.packed.reserve(sizeof(float4) * (size_t)n_ref));
     GSX_CHECK(w.bucketpts.reserve(sizeof(float4) * (size_t)n_ref));
     GSX_CHECK(w.cellstart.reserve(sizeof(unsigned) * (size_t)(cap + 1)));
-    if (!w.bkcnt.p) {  // bucket sizes | bucket starts | bucket cursors; sizes are re-zeroed by bucket_scan_kernel
-        GSX_CHECK(w.bkcnt.reserve(sizeof(unsigned) * (3 * MAX_BUCKETS + 8)));
-        GSX_HIP(hipMemsetAsync(w.bkcnt.p, 0, sizeof(unsigned) * (3 * MAX_BUCKETS + 8), ctx->stream));
+    if (!w.bkcnt.p) {  // bucket sizes | bucket starts
+        GSX_CHECK(w.bkcnt.reserve(sizeof(unsigned) * (2 * MAX_BUCKETS + 8)));
+        GSX_HIP(hipMemsetAsync(w.bkcnt.p, 0, sizeof(unsigned) * (2 * MAX_BUCKETS + 8), ctx->stream));
     }
+    GSX_CHECK(reserve_bin_tables(w, n_ref));   // (the queries of a partial call are a subset of the refs: fewer tiles)
     if (!w.gridparams.p) {   // the arrival tickets inside must start at zero (they reset themselves afterwards)
         GSX_CHECK(w.gridparams.reserve(sizeof(GridParams)));
         GSX_HIP(hipMemsetAsync(w.gridparams.p, 0, sizeof(GridParams), ctx->stream));
@@ -2555,13 +2740,9 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
     bool tree_ok = (adaptive || (slab && ctx->adaptive)) && ctx->tree && level == 0 && kk <= 65 && n_ref > k;
     bool hist_done = false;
     if (tree_ok) {
-        unsigned *bk_cnt = w.bkcnt.as<unsigned>();
-        const int tiles = (int)std::min<int64_t>(div_up(n_ref, BIN_TILE), (int64_t)ctx->num_cu * 4);
-        hipLaunchKernelGGL(bucket_hist_kernel, dim3(tiles), dim3(256), 0, ctx->stream, x, y, z, stride, 0, (int)n_ref, gp, bk_cnt,
-                           bk_cnt + MAX_BUCKETS, bk_cnt + 2 * MAX_BUCKETS + 1);
-        GSX_HIP(hipGetLastError());
+        GSX_CHECK(bin_hist(ctx, w, x, y, z, stride, 0, n_ref, gp));
         static thread_local std::vector<unsigned> starts(MAX_BUCKETS + 1);
-        GSX_HIP(hipMemcpyAsync(starts.data(), bk_cnt + MAX_BUCKETS, sizeof(unsigned) * (MAX_BUCKETS + 1), hipMemcpyDeviceToHost, ctx->stream));
+        GSX_HIP(hipMemcpyAsync(starts.data(), w.bkcnt.as<unsigned>() + MAX_BUCKETS, sizeof(unsigned) * (MAX_BUCKETS + 1), hipMemcpyDeviceToHost, ctx->stream));
         GSX_HIP(hipStreamSynchronize(ctx->stream));
         unsigned mx = 0, nonzero = 0;
         for (int b = 0; b < MAX_BUCKETS; ++b) {

@@ -41,7 +41,7 @@ struct GridParams {
     unsigned ring_ctr[8 * 32];
     unsigned ringf_ctr[8 * 32];
     // arrival tickets of the kernels whose last workgroup finishes the job of a former one-workgroup launch
-    // (bbox_partial -> grid parameters, bucket_hist -> bucket scan); never touched by grid_params, self-resetting
+    // (bbox_partial -> grid parameters, bucket_offsets -> bucket scan); never touched by grid_params, self-resetting
     unsigned ticket_bbox, ticket_hist;
     // multi-GPU slab step: the certificate of csrc/dist_slab.hip evaluated where the k-th distance is produced (instead
     // of an 8-byte array written here and read back by a kernel of its own).  cert_axis < 0: off

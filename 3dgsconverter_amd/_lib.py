@@ -7,6 +7,7 @@ raise ``GsxError`` (a RuntimeError).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -1091,9 +1092,13 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
         m = len(sh_names)
         names = base_names + sh_names
     nchunks = (n + 255) // 256
-    own = ctx is None and not resident
+    # resident rows: the arena's grow-only cply_* buffers while this call holds the "cply" lease; a second call at the same moment
+    # (another thread) takes the same path on a context and buffers of its own
     ar = arena(0) if resident else None
-    ctx = ar.ctx if resident else (ctx or Context(0))
+    leased = ar is not None and ar.lease("cply")
+    if not leased:
+        ar = None
+    own = ctx is None and not leased
     bufs = []
     import time as _time
     _t = [_time.perf_counter()]
@@ -1106,12 +1111,13 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
             _t[0] = now
 
     def alloc(nbytes, name):
-        if ar is not None:
+        if leased:
             return ar.buf("cply_" + name, nbytes)
         b = ctx.alloc(max(int(nbytes), 16))
         bufs.append(b)
         return b
     try:
+        ctx = ar.context("cply") if leased else (ctx or Context(0))
         verts = np.empty((n, 4), np.uint32)
         sh = np.empty((n, m), np.uint8) if m and not (resolve and resident) else None
         toucher = prefault(*(a for a in (verts, sh) if a is not None)) if resident and n >= (1 << 18) else None
@@ -1201,13 +1207,17 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
             mark("host_patch")
         return chunks, verts, sh, order, levels
     except GsxError:
-        if ar is not None:
-            release_arenas()
+        if leased:
+            ar.unlease("cply")
+            leased = False
+            release_arenas()    # a failed HIP call: do not keep a context in an unknown state
         raise
     finally:
         for b in bufs:
             b.free()
-        if own:
+        if leased:
+            ar.unlease("cply")
+        if own and ctx is not None:
             ctx.close()
 
 
@@ -1234,7 +1244,7 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
     ar = arena(device)
     leased = ar.lease("spz")
     own = not leased
-    ctx = ar.ctx if leased else Context(device)
+    ctx = None
     bufs = []
     import time as _time
     _t = [_time.perf_counter()]
@@ -1253,6 +1263,7 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
         bufs.append(b)
         return b
     try:
+        ctx = ar.context("spz") if leased else Context(device)
         lay = spz_layout(data.dtype)
         d_rows = alloc(data.nbytes + 64, "rows")        # (the kernels read up to 15 bytes past the last row)
         if n:
@@ -1313,7 +1324,7 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
             b.free()
         if leased:
             ar.unlease("spz")
-        if own:
+        if own and ctx is not None:
             ctx.close()
 
 
@@ -1468,7 +1479,7 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
     ar = arena(device)
     leased = ar.lease("ksplat")
     own = not leased
-    ctx = ar.ctx if leased else Context(device)
+    ctx = None
     bufs = []
     import time as _time
     _t = [_time.perf_counter()]
@@ -1487,6 +1498,7 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
         bufs.append(b)
         return b
     try:
+        ctx = ar.context("ksplat") if leased else Context(device)
         lay = spz_layout(data.dtype)
         d_rows = alloc(data.nbytes + 64, "rows")        # (the kernels read up to 15 bytes past the last row)
         if n:
@@ -1561,7 +1573,7 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
             b.free()
         if leased:
             ar.unlease("ksplat")
-        if own:
+        if own and ctx is not None:
             ctx.close()
 
 
@@ -1602,7 +1614,7 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
     ar = arena(device)
     leased = ar.lease("splat")
     own = not leased
-    ctx = ar.ctx if leased else Context(device)
+    ctx = None
     bufs = []
     import time as _time
     _t = [_time.perf_counter()]
@@ -1621,6 +1633,7 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
         bufs.append(b)
         return b
     try:
+        ctx = ar.context("splat") if leased else Context(device)
         out = np.empty(32 * n, np.uint8)
         if n == 0:
             return out
@@ -1678,7 +1691,7 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
             b.free()
         if leased:
             ar.unlease("splat")
-        if own:
+        if own and ctx is not None:
             ctx.close()
 
 
@@ -1803,57 +1816,97 @@ class DeviceArena:
     anything from 3 to 300 ms in the allocator (measured on MI355X, 20 allocations of a 10M-splat SOG encode: 3 ms when the
     runtime still holds the address ranges of the previous call's frees, 308 ms when it does not), and the first DMA into a
     freshly mapped range runs at half the link rate.  A writer that is called again (a converter working through a directory
-    of scenes, bench.py's repetitions) finds its buffers here; ``release_arenas()`` gives the memory back."""
+    of scenes, bench.py's repetitions) finds its buffers here; ``release_arenas()`` gives the memory back.
+
+    Every named buffer belongs to a LEASE GROUP, the part of its name before the first "_" ("sog_rows" -> "sog", "rgb_in" ->
+    "rgb"), and every group runs on a context of its own (``context(group)``: its stream and the library's per-context work
+    buffers).  ``buf()``, ``pinned()`` and ``context()`` serve a group only while it is leased (``lease`` / ``leased``): one user
+    of a group at a time, so a buffer never grows -- and frees its old allocation -- under another thread that still reads it.
+    A caller that does not win its lease (another thread holds it) takes private allocations instead."""
 
     def __init__(self, device: int = 0):
         self.device = int(device)
-        self.ctx = Context(device)
-        self._side = None
+        self.closed = False
+        self._ctxs = {}                 # lease group -> Context
+        self._sides = {}                # lease group -> second Context with a stream of its own
         self._bufs = {}
         self._pinned = {}
         self._leases = set()
 
-    @property
-    def side(self) -> "Context":
-        """a second context with a stream of its own (copies that overlap the first one's kernels)"""
-        if self._side is None:
-            self._side = Context(self.device, own_stream=True)
-        return self._side
+    @staticmethod
+    def group(name: str) -> str:
+        return name.split("_", 1)[0]
+
+    def _require(self, group: str, what: str):
+        if group not in self._leases:   # (one set lookup: a user that skips the lease fails at once instead of racing)
+            raise RuntimeError("DeviceArena: %s used without holding the %r lease" % (what, group))
+
+    def context(self, group: str) -> "Context":
+        """the context of lease group `group` (created on first use, kept until release())"""
+        self._require(group, "context(%r)" % group)
+        c = self._ctxs.get(group)
+        if c is None:
+            c = self._ctxs[group] = Context(self.device)
+        return c
+
+    def side(self, group: str) -> "Context":
+        """a second context of lease group `group` with a stream of its own (copies that overlap the first one's kernels)"""
+        self._require(group, "side(%r)" % group)
+        c = self._sides.get(group)
+        if c is None:
+            c = self._sides[group] = Context(self.device, own_stream=True)
+        return c
 
     def buf(self, name: str, nbytes: int) -> DeviceArray:
+        group = self.group(name)
+        self._require(group, "buf(%r)" % name)
         nbytes = max(int(nbytes), 16)
         cur = self._bufs.get(name)
         if cur is None or cur.nbytes < nbytes:
             if cur is not None:
                 cur.free()
-            cur = self.ctx.alloc(nbytes + 256)
+            cur = self.context(group).alloc(nbytes + 256)
             self._bufs[name] = cur
         return cur
 
     def pinned(self, name: str, nbytes: int) -> np.ndarray:
         """a named grow-only PAGE-LOCKED host buffer as a uint8 array (hipHostMalloc: the DMA engines read it at link rate)"""
+        group = self.group(name)
+        self._require(group, "pinned(%r)" % name)
         nbytes = max(int(nbytes), 16)
+        ctx = self.context(group)
         cur = self._pinned.get(name)
         if cur is None or cur[1] < nbytes:
             if cur is not None:
-                self.ctx.lib.gsx_host_pinned_free(self.ctx.handle, C.c_void_p(cur[0]))
+                ctx.lib.gsx_host_pinned_free(ctx.handle, C.c_void_p(cur[0]))
                 del self._pinned[name]
             p = C.c_void_p()
-            check(self.ctx.lib.gsx_host_pinned_alloc(self.ctx.handle, nbytes, C.byref(p)), "gsx_host_pinned_alloc")
+            check(ctx.lib.gsx_host_pinned_alloc(ctx.handle, nbytes, C.byref(p)), "gsx_host_pinned_alloc")
             cur = self._pinned[name] = (p.value, nbytes)
         return np.ctypeslib.as_array((C.c_uint8 * cur[1]).from_address(cur[0]))
 
     def lease(self, who: str) -> bool:
-        """one user of the buffers named after `who` at a time (a second DeviceChain alive at the same moment gets a context and
-        buffers of its own)"""
-        with _arena_lock:               # (two threads asking at once: exactly one of them gets it)
-            if who in self._leases:
+        """one user of lease group `who` at a time -> True when this caller got it (False: another user holds it, or the arena
+        has been released; the caller then takes allocations of its own)"""
+        with _arena_lock:               # (two threads asking at once: exactly one of them gets it; release_arenas() takes it too)
+            if self.closed or who in self._leases:
                 return False
             self._leases.add(who)
             return True
 
     def unlease(self, who: str):
-        self._leases.discard(who)
+        with _arena_lock:
+            self._leases.discard(who)
+
+    @contextlib.contextmanager
+    def leased(self, who: str):
+        """``with ar.leased("sog") as won:`` -- the lease of `who` for the block when `won`, given back on every exit path"""
+        won = self.lease(who)
+        try:
+            yield won
+        finally:
+            if won:
+                self.unlease(who)
 
     def held_bytes(self) -> int:
         return sum(b.nbytes for b in self._bufs.values())
@@ -1862,17 +1915,19 @@ class DeviceArena:
         return sum(nb for _, nb in self._pinned.values())
 
     def release(self):
+        self.closed = True
         for b in self._bufs.values():
             b.free()
         self._bufs.clear()
-        for ptr, _ in self._pinned.values():
-            if self.ctx is not None and self.ctx.handle:
-                self.ctx.lib.gsx_host_pinned_free(self.ctx.handle, C.c_void_p(ptr))
+        for name, (ptr, _) in self._pinned.items():
+            c = self._ctxs.get(self.group(name))
+            if c is not None and c.handle:
+                c.lib.gsx_host_pinned_free(c.handle, C.c_void_p(ptr))
         self._pinned.clear()
-        for c in (self._side, self.ctx):
-            if c is not None:
-                c.close()
-        self._side = self.ctx = None
+        for c in (*self._sides.values(), *self._ctxs.values()):
+            c.close()
+        self._sides.clear()
+        self._ctxs.clear()
 
 
 _arenas = {}
@@ -1882,7 +1937,7 @@ _arena_lock = threading.RLock()
 def arena(device: int = 0) -> DeviceArena:
     with _arena_lock:
         a = _arenas.get(int(device))
-        if a is None or a.ctx is None:
+        if a is None or a.closed:
             a = _arenas[int(device)] = DeviceArena(device)
         return a
 
@@ -1891,9 +1946,9 @@ def release_arenas():
     """free every cached work buffer and context of the writers' arenas (they are re-created on the next call)"""
     with _arena_lock:
         for dev, a in list(_arenas.items()):
-            if a._leases:            # a device chain is alive on this arena's context (a lazy DataProcessor with pending filters): it keeps it
+            if a._leases:            # some user holds a lease (a writer mid-call, a lazy DataProcessor with pending filters): it keeps it
                 continue
-            if a.ctx is not None:
+            if not a.closed:
                 a.release()
             del _arenas[dev]
 
@@ -1910,38 +1965,37 @@ class DeviceChain:
         """xyz_rows: (n, 3) coordinates, or table: the structured splat table itself -- its x, y, z are then gathered (threaded, C ABI
         gsx_host_gather_f32) straight into a page-locked staging buffer of the arena: no 12n-byte temporary whose pages are faulted
         in, copied from at pageable rate and unmapped again (9 + 5 + 9 ms of configs.dropin_e2e_10m's 37)"""
-        if table is not None:
-            require_hip()
-            ar0 = arena(device)
-            n_t = len(table)
-            # (exact=False: a row filter may start the chain on any table; DataProcessor checks f32_inexact_field before SOR, the
-            #  density filter or the box take the float32 copy for the table's values)
-            if n_t >= 4096 and "chain" not in ar0._leases:
-                a = host_gather_xyz(table, out=ar0.pinned("chain_xyz", 12 * n_t)[:12 * n_t].view(np.float32).reshape(n_t, 3), exact=False)
-            else:
-                a = host_gather_xyz(table, exact=False)
-        else:
+        if table is None:
             a = np.ascontiguousarray(xyz_rows, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError("Requires 3D data")
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("Requires 3D data")
         # round 6: the process-wide arena's context and named buffers when no other chain holds them -- a chain per filter run used
         # to create a context, hipMalloc its ~37 bytes per row and, inside the context, the whole KNN workspace, and free it all
         # again at close(): 10-12 of the 37 ms of configs.dropin_e2e_10m.  release_arenas() gives the memory back.
         require_hip()
         ar = arena(device)
+        # the lease is taken BEFORE chain_xyz is touched: a chain that does not win it never writes the buffer another chain is
+        # still uploading from
         self._ar = ar if ar.lease("chain") else None
         self.ctx = None
         self.rows = self.spare = self.orig = self.mask = self.pristine = self._md = self._st = None
         self._pool = []
         try:
+            if table is not None:
+                n_t = len(table)
+                # (exact=False: a row filter may start the chain on any table; DataProcessor checks f32_inexact_field before SOR, the
+                #  density filter or the box take the float32 copy for the table's values)
+                if n_t >= 4096 and self._ar is not None:
+                    a = host_gather_xyz(table, out=ar.pinned("chain_xyz", 12 * n_t)[:12 * n_t].view(np.float32).reshape(n_t, 3), exact=False)
+                else:
+                    a = host_gather_xyz(table, exact=False)
             self._setup(a, device, keep_pristine, table is not None)
         except BaseException:
             self.close()                    # (gives the lease back; a private context and its buffers are freed)
             raise
 
     def _setup(self, a, device, keep_pristine, pinned_source):
-        ar = self._ar
-        self.ctx = ar.ctx if self._ar is not None else Context(device)
+        self.ctx = self._ar.context("chain") if self._ar is not None else Context(device)
         self._names = iter(range(1 << 30))
         self.ctx.set_param("adaptive", 1)   # every step below synchronises anyway
         self.n0 = self.n = int(a.shape[0])
@@ -2114,7 +2168,7 @@ class DeviceChain:
     def close(self):
         if self._ar is not None:             # the arena keeps the buffers and the context (and its KNN workspace) for the next chain
             ar, self._ar = self._ar, None
-            healthy = False
+            healthy = self.ctx is None      # (nothing ran on the context yet: a failed gather)
             if self.ctx is not None and self.ctx.handle:
                 try:
                     self.ctx.set_param("adaptive", 0)

@@ -153,9 +153,10 @@ def encode(data: np.ndarray, compression_level: int = 0, device: int = 0, profil
     texels = width * height
     t_enter = time.perf_counter()
     ar = _lib.arena(device)        # work buffers and contexts outlive the call (DeviceArena: no hipMalloc / hipFree in a repeated write)
-    ctx = ar.ctx
-    st = _Stages(ctx, profile)
-    st.t = t_enter
+    shared = ar.lease("sog")       # (its contexts and every sog_* buffer, for the whole device section)
+    if not shared:                 # another SOG write holds them: a private arena for this call, freed at its end
+        ar = _lib.DeviceArena(device)
+        ar.lease("sog")
     names = iter(range(1 << 30))
 
     def alloc(nbytes, name=None):
@@ -163,6 +164,9 @@ def encode(data: np.ndarray, compression_level: int = 0, device: int = 0, profil
 
     out = {"n": n, "width": width, "height": height, "textures": {}, "stats": {}}
     try:
+        ctx = ar.context("sog")
+        st = _Stages(ctx, profile)
+        st.t = t_enter
         n_img = 5 + (1 if coeffs_present else 0)
         host_tex_all = np.empty((n_img, texels, 4), np.uint8)
         # (touching the result pages during the upload -- _lib.prefault, what the compressed-PLY writer does -- slowed the upload's own
@@ -328,7 +332,7 @@ def encode(data: np.ndarray, compression_level: int = 0, device: int = 0, profil
             worker = threading.Thread(target=run_palette, name="gsx-sog-palette")
             worker.start()
         try:
-            ctx2 = ar.side if worker else ctx
+            ctx2 = ar.side("sog") if worker else ctx
             _lib.check(lib.gsx_dev_download_staged(ctx2.handle, host_tex.ctypes.data, d_tex.ptr, 5 * 4 * texels), "gsx_dev_download_staged")
             with np.errstate(all="ignore"):
                 if len(pos_list):
@@ -360,7 +364,7 @@ def encode(data: np.ndarray, compression_level: int = 0, device: int = 0, profil
 
             def fetch_labels():
                 try:
-                    _lib.check(lib.gsx_dev_download_staged(ar.side.handle, host_tex[5].ctypes.data, tex["shN_labels"].ptr, 4 * texels),
+                    _lib.check(lib.gsx_dev_download_staged(ar.side("sog").handle, host_tex[5].ctypes.data, tex["shN_labels"].ptr, 4 * texels),
                                "gsx_dev_download_staged")
                 except BaseException as e:
                     lerr.append(e)
@@ -386,5 +390,13 @@ def encode(data: np.ndarray, compression_level: int = 0, device: int = 0, profil
             out["stage_ms"] = {k_: round(v_, 3) for k_, v_ in st.ms.items()}
         return out
     except _lib.GsxError:
-        _lib.release_arenas()      # a failed HIP call: do not keep a context in an unknown state
+        if shared:                 # a failed HIP call: do not keep a context in an unknown state (the lease first, or the
+            ar.unlease("sog")      # arena would be skipped; another user's lease still keeps its arena alive)
+            shared = False
+            _lib.release_arenas()
         raise
+    finally:
+        if shared:
+            ar.unlease("sog")
+        else:
+            ar.release()

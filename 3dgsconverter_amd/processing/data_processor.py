@@ -21,6 +21,8 @@ might add.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 from .. import _lib
@@ -60,18 +62,22 @@ def _reference_class():
     return _REFERENCE_CLASS
 
 
-def _xyz_rows(vertices):
-    """reference :38/:139 `coords` -- (N,3) float32, gathered from the AoS table by the threaded C routine.  Large tables: into a
-    page-locked staging buffer the arena keeps (round 6: a fresh 12n-byte array costs as much to fault in, copy from at pageable rate and
-    unmap again as the filter itself) -- the result is only valid until the next call and is used at once by the eager methods"""
+@contextlib.contextmanager
+def _xyz_rows(vertices, names=("x", "y", "z"), buf_name="eager_xyz"):
+    """reference :38/:139 `coords` -- ``with _xyz_rows(vertices) as xyz:`` (N,3) float32, gathered from the AoS table by the threaded C
+    routine.  Large tables: into a page-locked staging buffer the arena keeps (round 6: a fresh 12n-byte array costs as much to fault
+    in, copy from at pageable rate and unmap again as the filter itself), under the lease of the buffer's group for the whole block --
+    another thread's filter at the same moment gathers into a fresh array instead of over (or, growing the buffer, freeing) this one"""
     n = len(vertices)
-    if n >= 65536 and isinstance(vertices, np.ndarray):
-        try:
-            buf = _lib.arena(0).pinned("eager_xyz", 12 * n)[:12 * n].view(np.float32).reshape(n, 3)
-            return _lib.host_gather_xyz(vertices, out=buf)
-        except _lib.GsxError:
-            pass                        # no device: the callers' device entry points say so themselves
-    return _lib.host_gather_xyz(vertices)
+    ar = _lib.arena(0) if n >= 65536 and isinstance(vertices, np.ndarray) else None
+    with ar.leased(ar.group(buf_name)) if ar is not None else contextlib.nullcontext(False) as won:
+        out = None
+        if won:
+            try:
+                out = ar.pinned(buf_name, 12 * n)[:12 * n].view(np.float32).reshape(n, 3)
+            except _lib.GsxError:
+                out = None              # no device: the callers' device entry points say so themselves
+        yield _lib.host_gather_xyz(vertices, names, out=out)
 
 
 class DataProcessor:
@@ -234,7 +240,8 @@ class DataProcessor:
             raise ValueError(f"SOR: k={k} is outside the supported range 1..{MAX_SOR_K} of the MI355X path "
                              f"(--sor_intensity maps to k = 10..50, the CLI default is 25)")
         status_print("[SOR] Determining outliers on GPU (HIP gfx950, exact KNN)...")
-        res = _lib.sor_filter(_xyz_rows(vertices), int(k), float(threshold_factor), want_mean=False)
+        with _xyz_rows(vertices) as xyz:
+            res = _lib.sor_filter(xyz, int(k), float(threshold_factor), want_mean=False)
         self.last_sor = {"mean": res["mean"], "std": res["std"], "threshold": res["threshold"]}
         self.data = _lib.host_compact_rows(vertices, res["mask"])  # reference :149
         status_print(f"After removing flyers (GPU), retained {len(self.data)} out of {num_points} vertices.")
@@ -262,20 +269,20 @@ class DataProcessor:
             status_print("Warning: Density filter removed all points.")
             self.data = self.data[:0]
             return self.data
-        cols = _xyz_rows(vertices)
-        occ = _lib.density_voxels(cols, float(voxel_size), min_points)
-        debug_print(f"[DEBUG] Found {occ['n_unique']} unique voxels.")
-        if len(occ["dense_keys"]) == 0:
-            status_print("Warning: Density filter removed all points.")
-            self.data = self.data[:0]
-            return self.data
-        comps = _clusters.connected_clusters(map(tuple, occ["dense_keys"].tolist()))
-        kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
-        if not kept:
-            self.data = self.data[:0]
-            return self.data
-        kept_keys = np.array(sorted(kept), dtype=np.int64).reshape(-1, 3)
-        mask = _lib.density_mask(cols, float(voxel_size), kept_keys)
+        with _xyz_rows(vertices) as cols:        # (the staging buffer is held across both device calls)
+            occ = _lib.density_voxels(cols, float(voxel_size), min_points)
+            debug_print(f"[DEBUG] Found {occ['n_unique']} unique voxels.")
+            if len(occ["dense_keys"]) == 0:
+                status_print("Warning: Density filter removed all points.")
+                self.data = self.data[:0]
+                return self.data
+            comps = _clusters.connected_clusters(map(tuple, occ["dense_keys"].tolist()))
+            kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
+            if not kept:
+                self.data = self.data[:0]
+                return self.data
+            kept_keys = np.array(sorted(kept), dtype=np.int64).reshape(-1, 3)
+            mask = _lib.density_mask(cols, float(voxel_size), kept_keys)
         self.data = _lib.host_compact_rows(vertices, mask)  # reference :114
         status_print(f"Density Filter: Kept {kept_clusters} clusters (largest: {max_len} voxels).")
         status_print(f"After density filter, retained {len(self.data)} out of {len(vertices)} vertices.")
@@ -407,15 +414,9 @@ class DataProcessor:
         #  numpy copies of a 248-byte-stride column cost ~50 ms each at 10M splats)
         names3 = [prefix + "f_dc_%d" % c for c in range(3)]
         n = len(vertices)
-        mat = None
-        if n >= 65536:      # (n, 3), the colours' own layout, into a page-locked staging buffer of the arena (as _xyz_rows does)
-            try:
-                mat = _lib.host_gather_xyz(vertices, names3, out=_lib.arena(0).pinned("rgb_in", 12 * n)[:12 * n].view(np.float32).reshape(n, 3))
-            except _lib.GsxError:
-                mat = None
-        if mat is None:
-            mat = _lib.host_gather_xyz(vertices, names3)
-        return _lib.rgb_from_sh(mat.reshape(-1)).reshape(n, 3)
+        # (n, 3), the colours' own layout; large tables into the arena's page-locked "rgb_in" under the "rgb" lease (as _xyz_rows does)
+        with _xyz_rows(vertices, names3, buf_name="rgb_in") as mat:
+            return _lib.rgb_from_sh(mat.reshape(-1)).reshape(n, 3)
 
     def add_rgb_from_sh(self):
         """reference :233-274: append (red, green, blue) u1 fields computed from the SH DC term"""

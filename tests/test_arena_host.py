@@ -1,0 +1,352 @@
+"""CPU: the process-wide DeviceArena (3dgsconverter_amd/_lib.py) and its users under concurrency, without a GPU.
+
+The arena keeps named GROW-ONLY buffers: growing one frees the old allocation.  Every buffer belongs to a lease group (the part
+of its name before the first "_") and is only served while that group is leased, so two threads never share one.  Here the
+device calls are stubbed and only the allocator is faked (numpy memory; a "freed" block is poisoned with NaN bytes but stays
+mapped): the real grow-only and lease logic, the real threaded host gathers and the real DataProcessor / DeviceChain code run.
+threading.Event forces the one interleaving that hurts: thread A gathers, thread B gathers and finishes, then A reads."""
+import importlib
+import threading
+
+import numpy as np
+import pytest
+
+L = importlib.import_module("3dgsconverter_amd._lib")
+dp = importlib.import_module("3dgsconverter_amd.processing.data_processor")
+
+WAIT = 20.0     # seconds an event may take before the test gives up (a wrong lock would otherwise hang the suite)
+
+
+class _StubArray:
+    """a device allocation: remembers what was uploaded into it"""
+
+    def __init__(self, ctx, nbytes):
+        self.ctx, self.nbytes, self.ptr, self.freed, self.uploaded = ctx, int(nbytes), 1, False, None
+
+    def upload(self, arr):
+        self.uploaded = np.array(arr, copy=True)
+        return self
+
+    def free(self):
+        self.freed, self.ptr = True, None
+
+
+class _StubLib:
+    """page-locked host memory as numpy blocks; a free fills the block with 0xff (NaN as float32) and keeps it alive"""
+
+    def __init__(self):
+        self.blocks, self.freed = {}, []
+
+    def gsx_host_pinned_alloc(self, handle, nbytes, pref):
+        a = np.zeros(int(nbytes), np.uint8)
+        self.blocks[a.ctypes.data] = a
+        pref._obj.value = a.ctypes.data
+        return 0
+
+    def gsx_host_pinned_free(self, handle, ptr):
+        a = self.blocks.pop(ptr.value)
+        a[:] = 0xFF
+        self.freed.append(a)
+        return 0
+
+
+@pytest.fixture
+def fake(monkeypatch):
+    """_lib.Context -> a stub (no GPU); a fresh, empty arena registry"""
+    stub_lib = _StubLib()
+
+    class StubContext:
+        lib = stub_lib
+        made = []
+
+        def __init__(self, device=0, stream=None, own_stream=False):
+            self.handle, self.own_stream, self.params = 1, own_stream, {}
+            StubContext.made.append(self)
+
+        def alloc(self, nbytes):
+            return _StubArray(self, nbytes)
+
+        def set_param(self, name, value):
+            self.params[name] = value
+
+        def synchronize(self):
+            pass
+
+        def close(self):
+            self.handle = None
+
+    monkeypatch.setattr(L, "Context", StubContext)
+    monkeypatch.setattr(L, "_arenas", {})
+    return StubContext
+
+
+def _table(n, seed):
+    dt = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("f_dc_0", "<f4"), ("f_dc_1", "<f4"), ("f_dc_2", "<f4"),
+                   ("opacity", "<f4")])
+    rng = np.random.default_rng(seed)
+    t = np.zeros(n, dt)
+    for nm in dt.names:
+        t[nm] = rng.standard_normal(n).astype(np.float32) * 10
+    return t
+
+
+def _cols(t, names):
+    return np.column_stack([t[nm] for nm in names]).astype(np.float32)
+
+
+# ---- the arena's rule ---------------------------------------------------------------------------------------------------
+
+def test_lease_groups_are_the_name_before_the_first_underscore():
+    g = L.DeviceArena.group
+    assert [g(n) for n in ("eager_xyz", "rgb_in", "chain_list3", "sog_12", "cply_unc_count", "spz_rows", "ksplat_body",
+                           "splat_rows")] == ["eager", "rgb", "chain", "sog", "cply", "spz", "ksplat", "splat"]
+
+
+def test_unleased_group_is_refused(fake):
+    ar = L.DeviceArena(0)
+    for call in (lambda: ar.buf("sog_rows", 64), lambda: ar.pinned("eager_xyz", 64), lambda: ar.context("cply"),
+                 lambda: ar.side("sog")):
+        with pytest.raises(RuntimeError, match="lease"):
+            call()
+    assert not ar._bufs and not ar._pinned and not fake.made       # nothing was allocated on the way to the refusal
+    with ar.leased("sog") as won:
+        assert won
+        with pytest.raises(RuntimeError, match="'cply'"):          # another group's lease does not cover it
+            ar.buf("cply_rows", 64)
+        with pytest.raises(RuntimeError, match="'eager'"):
+            ar.pinned("eager_xyz", 64)
+
+
+def test_leased_group_grows_and_keeps_its_buffers(fake):
+    ar = L.DeviceArena(0)
+    with ar.leased("sog") as won:
+        assert won
+        assert not ar.lease("sog")                                 # one holder at a time
+        b = ar.buf("sog_rows", 1000)
+        assert b.nbytes >= 1000 and ar.buf("sog_rows", 10) is b     # grow-only: a smaller request is the same buffer
+        b2 = ar.buf("sog_rows", 5000)
+        assert b.freed and not b2.freed and b2.nbytes >= 5000
+        assert b2.ctx is ar.context("sog")                         # allocated on the group's own context ...
+        p = ar.pinned("sog_host", 100)
+        assert p.dtype == np.uint8 and len(p) >= 100
+        with ar.leased("cply"):
+            assert ar.context("cply") is not ar.context("sog")     # ... which no other group shares
+            assert ar.side("sog") is not ar.context("sog") and ar.side("sog").own_stream
+    assert not ar._leases
+
+
+def test_context_manager_returns_the_lease_on_an_exception(fake):
+    ar = L.DeviceArena(0)
+    with pytest.raises(ZeroDivisionError):
+        with ar.leased("spz") as won:
+            assert won
+            ar.buf("spz_rows", 64)
+            1 / 0
+    assert "spz" not in ar._leases
+    with ar.leased("spz") as won:
+        assert won
+    with ar.leased("spz") as won:
+        with ar.leased("spz") as won2:                            # a second user at the same moment does not get it ...
+            assert won and not won2
+        assert "spz" in ar._leases                                 # ... and leaving its block does not take the first one's
+
+
+def test_release_arenas_spares_a_leased_arena(fake):
+    ar = L.arena(0)
+    assert ar.lease("cply")
+    b = ar.buf("cply_rows", 256)
+    ar.unlease("cply")
+    assert ar.lease("eager")
+    p = ar.pinned("eager_xyz", 1200)
+    p[:] = 7
+    L.release_arenas()
+    assert L.arena(0) is ar and not b.freed and np.all(p == 7)    # the eager lease keeps the whole arena: cply_rows too
+    ar.unlease("eager")
+    L.release_arenas()
+    assert b.freed and len(fake.lib.freed) == 1 and np.all(p == 0xFF)
+    assert all(c.handle is None for c in fake.made)                # every context of the arena closed
+    assert not ar.lease("eager")                                   # a released arena hands out no more leases
+    assert L.arena(0) is not ar
+
+
+# ---- eager DataProcessors on two threads --------------------------------------------------------------------------------
+
+class _Race:
+    """the first stub call of thread A blocks until thread B has run its whole method; every stub records a copy of what it
+    was handed AFTER that point, i.e. what A's device call would read"""
+
+    def __init__(self):
+        self.a_in, self.b_done = threading.Event(), threading.Event()
+        self.seen, self.errors = [], []
+
+    def hit(self, stub, arr):
+        if threading.current_thread().name == "A" and not self.a_in.is_set():
+            self.a_in.set()
+            if not self.b_done.wait(WAIT):
+                raise AssertionError("thread B did not finish")
+        self.seen.append((threading.current_thread().name, stub, np.array(arr, copy=True)))
+
+    def run(self, method_a, method_b):
+        def a():
+            try:
+                method_a()
+            except BaseException as e:      # noqa: BLE001
+                self.errors.append(("A", repr(e)))
+
+        def b():
+            try:
+                if not self.a_in.wait(WAIT):
+                    raise AssertionError("thread A never reached its device call")
+                method_b()
+            except BaseException as e:      # noqa: BLE001
+                self.errors.append(("B", repr(e)))
+            finally:
+                self.b_done.set()
+        th = [threading.Thread(target=a, name="A"), threading.Thread(target=b, name="B")]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join(3 * WAIT)
+        assert not any(t.is_alive() for t in th), "a thread hangs"
+        assert not self.errors, self.errors
+
+
+@pytest.fixture
+def stubs(monkeypatch, fake):
+    race = _Race()
+
+    def sor_filter(xyz, k, threshold_factor, want_mean=False):
+        race.hit("sor_filter", xyz)
+        return {"mean": 0.0, "std": 0.0, "threshold": 0.0, "mask": np.ones(len(xyz), bool)}
+
+    def density_voxels(cols, voxel_size, min_points):
+        race.hit("density_voxels", cols)
+        return {"n_unique": 1, "dense_keys": np.zeros((1, 3), np.int64), "dense_counts": np.array([len(cols)], np.int64)}
+
+    def density_mask(cols, voxel_size, kept_keys):
+        race.hit("density_mask", cols)
+        return np.ones(len(cols), bool)
+
+    def rgb_from_sh(f_dc):
+        race.hit("rgb_from_sh", np.asarray(f_dc).reshape(-1, 3))
+        return np.zeros(len(f_dc), np.uint8)
+
+    for nm, f in (("sor_filter", sor_filter), ("density_voxels", density_voxels), ("density_mask", density_mask),
+                  ("rgb_from_sh", rgb_from_sh)):
+        monkeypatch.setattr(L, nm, f)
+    monkeypatch.setattr(L, "require_hip", L.load)                 # (add_rgb_from_sh asks for the device before it gathers)
+    return race
+
+
+@pytest.mark.parametrize("method,stub_names,cols", [
+    ("remove_flyers", ["sor_filter"], ("x", "y", "z")),
+    ("apply_density_filter", ["density_voxels", "density_mask"], ("x", "y", "z")),
+    ("add_rgb_from_sh", ["rgb_from_sh"], ("f_dc_0", "f_dc_1", "f_dc_2")),
+])
+def test_two_eager_processors_each_see_their_own_rows(stubs, method, stub_names, cols):
+    """A gathers (>= 65 536 rows: the arena's page-locked buffer), B -- a larger table, so the buffer would grow and free A's --
+    gathers and finishes, then A's device call reads its input: it must still be A's columns"""
+    ta, tb = _table(70_001, 1), _table(100_003, 2)
+    pa, pb = dp.DataProcessor(ta), dp.DataProcessor(tb)
+    stubs.run(getattr(pa, method), getattr(pb, method))
+    want = {"A": _cols(ta, cols), "B": _cols(tb, cols)}
+    for who in "AB":
+        got = [(stub, arr) for w, stub, arr in stubs.seen if w == who]
+        assert [s for s, _ in got] == stub_names, (who, got)
+        for stub, arr in got:
+            np.testing.assert_array_equal(arr, want[who], err_msg="%s's %s read another table's rows" % (who, stub))
+    ar = L.arena(0)
+    name = "rgb_in" if method == "add_rgb_from_sh" else "eager_xyz"
+    assert ar._pinned[name][1] == 12 * len(ta)       # the lease holder's buffer, never grown under it
+    assert not ar._leases                            # every lease given back
+
+
+def test_lone_eager_processor_gathers_into_the_arena(stubs):
+    """one caller at a time always wins the lease: the page-locked path of round 6, unchanged"""
+    t = _table(80_000, 3)
+    stubs.a_in.set()
+    stubs.b_done.set()
+    dp.DataProcessor(t).remove_flyers()
+    dp.DataProcessor(t).add_rgb_from_sh()
+    ar = L.arena(0)
+    assert ar._pinned["eager_xyz"][1] == ar._pinned["rgb_in"][1] == 12 * len(t)
+    assert not ar._leases
+    np.testing.assert_array_equal(stubs.seen[0][2], _cols(t, ("x", "y", "z")))
+
+
+def test_small_eager_tables_do_not_touch_the_arena(stubs):
+    t = _table(1000, 4)
+    stubs.a_in.set()
+    stubs.b_done.set()
+    dp.DataProcessor(t).remove_flyers()
+    assert not L._arenas or not L.arena(0)._pinned
+
+
+# ---- DeviceChain: the lease before the gather ---------------------------------------------------------------------------
+
+def test_two_device_chains_built_at_once_upload_their_own_rows(fake, monkeypatch):
+    """A's chain gathers its coordinates, B's chain (larger table) gathers too, then A uploads: B must not have written (or
+    grown and freed) the pinned chain_xyz buffer A uploads from.  The lease is taken before the gather; the loser gathers
+    into an array of its own and runs on a private context"""
+    monkeypatch.setattr(L, "require_hip", L.load)
+    real = L.host_gather_xyz
+    a_gathered, b_gathered = threading.Event(), threading.Event()
+
+    def gather(vertices, names=("x", "y", "z"), out=None, exact=True):
+        r = real(vertices, names, out=out, exact=exact)
+        if threading.current_thread().name == "A":
+            a_gathered.set()
+            if not b_gathered.wait(WAIT):
+                raise AssertionError("thread B never gathered")
+        else:
+            b_gathered.set()
+        return r
+    monkeypatch.setattr(L, "host_gather_xyz", gather)
+    ta, tb = _table(5000, 5), _table(9000, 6)
+    chains, errors = {}, []
+
+    def build(name, t, wait):
+        try:
+            if wait is not None and not wait.wait(WAIT):
+                raise AssertionError("thread A never gathered")
+            chains[name] = L.DeviceChain(table=t)
+        except BaseException as e:      # noqa: BLE001
+            errors.append((name, repr(e)))
+            b_gathered.set()
+    th = [threading.Thread(target=build, args=("A", ta, None), name="A"),
+          threading.Thread(target=build, args=("B", tb, a_gathered), name="B")]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(3 * WAIT)
+    try:
+        assert not any(t.is_alive() for t in th) and not errors, errors
+        for name, t in (("A", ta), ("B", tb)):
+            np.testing.assert_array_equal(chains[name].rows.uploaded, _cols(t, ("x", "y", "z")),
+                                          err_msg="chain %s uploaded another table's rows" % name)
+        ar = L.arena(0)
+        assert ar._pinned["chain_xyz"][1] == 12 * len(ta)
+        assert sum(c._ar is not None for c in chains.values()) == 1 and ar._leases == {"chain"}
+    finally:
+        for c in chains.values():
+            c.close()
+    assert not L.arena(0)._leases
+
+
+def test_device_chain_that_loses_the_lease_leaves_chain_xyz_alone(fake, monkeypatch):
+    monkeypatch.setattr(L, "require_hip", L.load)
+    ta, tb = _table(6000, 7), _table(12000, 8)
+    first = L.DeviceChain(table=ta)
+    try:
+        held = L.arena(0).pinned("chain_xyz", 1).copy()            # (the lease holder may look)
+        second = L.DeviceChain(table=tb)
+        try:
+            assert second._ar is None and first._ar is not None
+            np.testing.assert_array_equal(L.arena(0).pinned("chain_xyz", 1), held)
+            np.testing.assert_array_equal(second.rows.uploaded, _cols(tb, ("x", "y", "z")))
+        finally:
+            second.close()
+        assert second.ctx is None and all(b.freed for b in (second.rows, second.spare, second.mask))
+    finally:
+        first.close()
+    assert not L.arena(0)._leases

@@ -86,6 +86,15 @@ class SpzLayout(C.Structure):
     _fields_ = [("row_bytes", C.c_int64), ("offset", C.c_int32 * SOG_FIELDS)]
 
 
+CPLY_READ_MAX_SH = 256   # GSX_CPLY_READ_MAX_SH
+
+
+class CplyReadLayout(C.Structure):
+    """gsx_cply_read_layout (include/gsx_hip.h): where the compressed-PLY reader's properties sit inside the file's rows"""
+    _fields_ = [("chunk_stride", C.c_int64), ("vertex_stride", C.c_int64), ("sh_stride", C.c_int64), ("chunk_offset", C.c_int32 * 18),
+                ("vertex_offset", C.c_int32 * 4), ("n_sh", C.c_int32), ("sh_offset", C.c_int32 * CPLY_READ_MAX_SH)]
+
+
 class SogScan(C.Structure):
     """gsx_sog_scan (include/gsx_hip.h)"""
     _fields_ = [("vmin", C.c_float * 3), ("vmax", C.c_float * 3), ("nonfinite", C.c_uint32), ("reserved", C.c_uint32),
@@ -217,6 +226,7 @@ SIGNATURES = {
     "gsx_splat_keys_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_splat_order_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_splat_permute_dev": (_I, [_P, _P, _P, _I64, _P]),
+    "gsx_cply_unpack_dev": (_I, [_P, _P, _I64, _P, _I64, _P, C.POINTER(CplyReadLayout), _P, _P]),
 }
 
 _lib = None
@@ -1691,6 +1701,125 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
             b.free()
         if leased:
             ar.unlease("splat")
+        if own and ctx is not None:
+            ctx.close()
+
+
+_cply_tables = None
+
+
+def cply_read_tables() -> np.ndarray:
+    """The compressed-PLY reader's quotient tables (GSX_CPLY_TAB_*), each entry numpy's own result for the reference's statement
+    on that input -- so the device divides only in the colour's `/ SH_C0` and takes no log.  -> uint8[GSX_CPLY_TAB_BYTES]"""
+    global _cply_tables
+    if _cply_tables is None:
+        with np.errstate(all="ignore"):
+            q2047 = np.arange(2048, dtype=np.uint32) / 2047                                     # compressed_ply.py:346
+            q1023 = np.arange(1024, dtype=np.uint32) / 1023
+            q255 = np.arange(256, dtype=np.uint32) / 255.0                                      # :359
+            dq = (np.arange(1024, dtype=np.uint32) / 1023.0 - 0.5) / 0.7071067811865476        # :370-371
+            a = np.clip(np.arange(256, dtype=np.uint32) / 255.0, 1e-6, 1.0 - 1e-6)             # :361, :118-119
+            opa = np.log(a / (1.0 - a)).astype(np.float32)
+            sh = ((np.arange(256, dtype=np.uint8) / 256.0 - 0.5) * 8.0).astype(np.float32)     # :126
+        _cply_tables = np.concatenate([np.concatenate([q2047, q1023, q255, dq]).view(np.uint8), opa.view(np.uint8), sh.view(np.uint8)])
+        assert _cply_tables.nbytes == 8 * 4352 + 4 * 512
+    return _cply_tables
+
+
+def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunks: int, n_vertices: int, dtype: np.dtype,
+                      stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+    """The compressed-PLY reader's rows (formats/compressed_ply.py:14-124) from a binary little-endian file: the elements' bodies
+    are read from `path` (segments: "chunk", "vertex", "sh" -> (file offset, bytes) or None) straight into page-locked staging,
+    uploaded once, decoded by gsx_cply_unpack_dev and downloaded into a prefaulted array of `dtype` (68 + 4 n_sh bytes of
+    float32 per row; formats/compressed_ply_reader.py builds it).  Rows past 256 n_chunks stay zero, as in the reference.
+
+    Runs on the process's arena while it holds the "cplyread" lease; a second call at the same moment (another thread) takes a
+    context and buffers of its own."""
+    lib = require_hip()
+    n = int(n_vertices)
+    n_dec = min(n, 256 * int(n_chunks))
+    out = np.empty(n, dtype)
+    if n_dec == 0:
+        out.view(np.uint8)[:] = 0
+        return out
+    parts = [(k, segments.get(k)) for k in ("chunk", "vertex", "sh")]
+    place, total = {}, 0
+    for k, seg in parts:                     # each body at a 16-byte boundary of one staging buffer, 16 spare bytes after it
+        if seg is not None:
+            place[k] = total
+            total += (int(seg[1]) + 16 + 15) & ~15
+    ar = arena(device)
+    leased = ar.lease("cplyread")
+    own = not leased
+    ctx = None
+    bufs = []
+    import time as _time
+    _t = [_time.perf_counter()]
+
+    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
+        if stage_ms is not None:
+            ctx.synchronize()
+            now = _time.perf_counter()
+            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
+            _t[0] = now
+
+    def alloc(nbytes, name):
+        if leased:
+            return ar.buf("cplyread_" + name, nbytes)
+        b = ctx.alloc(max(int(nbytes), 16))
+        bufs.append(b)
+        return b
+    try:
+        ctx = ar.context("cplyread") if leased else Context(device)
+        rb = dtype.itemsize
+        toucher = prefault(out) if out.nbytes >= (1 << 22) else None
+        host = ar.pinned("cplyread_in", total)[:total] if leased else np.empty(total, np.uint8)
+        with open(path, "rb") as f:
+            for k, seg in parts:
+                if seg is None:
+                    continue
+                f.seek(int(seg[0]))
+                view = memoryview(host[place[k]:place[k] + int(seg[1])])
+                got = 0
+                while got < len(view):
+                    r = f.readinto(view[got:])
+                    if not r:
+                        raise ValueError("%s: early end of file in element %r (%d of %d bytes)" % (path, k, got, len(view)))
+                    got += r
+        host_tab = cply_read_tables()
+        mark("file_read")
+        d_in = alloc(total, "in")
+        d_tab = alloc(host_tab.nbytes, "tables")
+        if leased:                           # page-locked already: the runtime's plain copy runs at link rate
+            check(lib.gsx_dev_upload(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload")
+        else:
+            check(lib.gsx_dev_upload_staged(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload_staged")
+        d_tab.upload(host_tab)
+        mark("upload")
+        d_out = alloc(n_dec * rb, "out")
+        ptr = {k: d_in.ptr + place[k] for k in place}
+        check(lib.gsx_cply_unpack_dev(ctx.handle, ptr["chunk"], int(n_chunks), ptr["vertex"], n, ptr.get("sh"), C.byref(layout), d_tab.ptr,
+                                      d_out.ptr), "gsx_cply_unpack_dev")
+        mark("kernel")
+        if toucher is not None:
+            toucher.join()
+        flat = out.view(np.uint8)
+        check(lib.gsx_dev_download_staged(ctx.handle, flat.ctypes.data, d_out.ptr, n_dec * rb), "gsx_dev_download_staged")
+        if n_dec < n:
+            flat[n_dec * rb:] = 0
+        mark("download")
+        return out
+    except GsxError:
+        if leased:
+            ar.unlease("cplyread")
+            leased = False
+            release_arenas()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if leased:
+            ar.unlease("cplyread")
         if own and ctx is not None:
             ctx.close()
 

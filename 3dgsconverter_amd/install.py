@@ -19,7 +19,8 @@ import sys
 _saved = {}
 
 
-def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True):
+def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
+            cply_reader: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -30,7 +31,11 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     scan, bucket centres and every row on the GPU; identical file bytes).  A reference without that module is left as it is.
     splat_writer: also rebind ``gsconverter.formats.splat.SplatFormat.write`` to formats/splat_writer.py:write_splat (metric, sort
     and every record on the GPU; the reference's records, equal metrics kept in input order).  A reference without that module
-    is left as it is."""
+    is left as it is.
+    cply_reader: also rebind ``gsconverter.formats.compressed_ply.CompressedPlyFormat.read`` to formats/compressed_ply_reader.py
+    (the decode on the GPU, no plyfile; the reference's rows and ``self.metadata``).  Files the device path does not take -- no
+    `chunk` element, ascii or big-endian bodies, list properties -- go to the reference's own read.  A reference without that
+    module is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -98,6 +103,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.splat_writer import write_splat
             _saved.setdefault(("splatformat", "write"), spmod.SplatFormat.write)
             spmod.SplatFormat.write = lambda self, data, path, **kw: write_splat(data, path, **kw)
+    if cply_reader:
+        try:
+            cpmod = importlib.import_module("gsconverter.formats.compressed_ply")
+        except ImportError:
+            cpmod = None
+        if cpmod is not None and getattr(cpmod.CompressedPlyFormat, "read", None) is not None:
+            from .formats.compressed_ply_reader import bind_read
+            _saved.setdefault(("cplyformat", "read"), cpmod.CompressedPlyFormat.read)
+            cpmod.CompressedPlyFormat.read = bind_read(_saved[("cplyformat", "read")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -110,7 +124,7 @@ def uninstall():
             importlib.import_module("gsconverter.formats.sog").SogFormat.write = val
             continue
         if modname == "cplyformat":
-            importlib.import_module("gsconverter.formats.compressed_ply").CompressedPlyFormat.write = val
+            setattr(importlib.import_module("gsconverter.formats.compressed_ply").CompressedPlyFormat, attr, val)
             continue
         if modname == "spzformat":
             importlib.import_module("gsconverter.formats.spz").SpzFormat.write = val

@@ -693,6 +693,40 @@ int gsx_splat_order_dev(gsx_ctx *ctx, const uint32_t *keys_dev, int64_t n, uint3
 /* splat.py:101 `data[sorted_indices]` on the records: out_dev + 32 i = recs_dev + 32 order_dev[i] (both 16-byte aligned). */
 int gsx_splat_permute_dev(gsx_ctx *ctx, const uint8_t *recs_dev, const uint32_t *order_dev, int64_t n, uint8_t *out_dev);
 
+
+/* ---- the compressed-PLY reader (csrc/cply_read.hip) ----
+ * gsconverter/formats/compressed_ply.py:14-124 (CompressedPlyFormat.read) with :342-378 (_unpack_and_denormalize_11_10_11,
+ * _unpack_and_denormalize_8888, _unpack_quaternions): the elements `chunk`, `vertex` and `sh` as they lie in a binary
+ * little-endian file -> the reference's rows, x y z nx ny nz f_dc_0..2 opacity scale_0..2 rot_0..3 and the sh properties in
+ * file order, all float32, bit for bit (NaN bits included: x86's). */
+#define GSX_CPLY_READ_MAX_SH 256
+typedef struct gsx_cply_read_layout {
+    int64_t chunk_stride;               /* bytes per row of each element */
+    int64_t vertex_stride;
+    int64_t sh_stride;
+    int32_t chunk_offset[18];           /* byte offsets of the float32 chunk properties min_x min_y min_z max_x max_y max_z
+                                           min_scale_x..z max_scale_x..z min_r min_g min_b max_r max_g max_b (any alignment) */
+    int32_t vertex_offset[4];           /* ... of the uint32 packed_position packed_rotation packed_scale packed_color */
+    int32_t n_sh;                       /* uint8 sh properties (0 ... GSX_CPLY_READ_MAX_SH) and their byte offsets */
+    int32_t sh_offset[GSX_CPLY_READ_MAX_SH];
+} gsx_cply_read_layout;
+/* the host-built tables (numpy's own results), one buffer: float64 nv / 2047 [2048] | nv / 1023 [1024] | n / 255.0 [256] |
+ * (v / 1023.0 - 0.5) / 0.7071067811865476 [1024], then float32 opacity logit of byte na [256] | (u8 / 256.0 - 0.5) * 8.0 [256] */
+#define GSX_CPLY_TAB_Q2047 0
+#define GSX_CPLY_TAB_Q1023 2048
+#define GSX_CPLY_TAB_Q255 3072
+#define GSX_CPLY_TAB_DQ 3328
+#define GSX_CPLY_TAB_DOUBLES 4352
+#define GSX_CPLY_TAB_OPA 0
+#define GSX_CPLY_TAB_SH 256
+#define GSX_CPLY_TAB_BYTES (8 * 4352 + 4 * 512)
+/* The first min(n_vertices, 256 n_chunks) rows -> out_dev (68 + 4 n_sh bytes per row, 16-byte aligned); the rows after them
+ * are the caller's (the reference leaves them zero).  Row i of the sh element belongs to vertex i (the sh element must have at
+ * least that many rows).  chunk_dev, vertex_dev and sh_dev (16-byte aligned) readable up to 16 bytes past their last row.
+ * Asynchronous. */
+int gsx_cply_unpack_dev(gsx_ctx *ctx, const void *chunk_dev, int64_t n_chunks, const void *vertex_dev, int64_t n_vertices, const void *sh_dev,
+                        const gsx_cply_read_layout *layout, const void *tables_dev, float *out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2183,7 +2183,17 @@ class DeviceChain:
         return p, p + 4, p + 8, 3
 
     def bbox(self):
-        """per-axis (min, max) of the surviving rows (gsx_slab_bbox_dev: the multi-GPU path's box kernel) -> ([3], [3]) float32"""
+        """per-axis (min, max) of the surviving rows -> ([3], [3]) float32: by value what np.min / np.max give on each column (the
+        sign of a zero extreme is not defined).  gsx_slab_bbox_dev (the multi-GPU path's box kernel) drops NaNs: when its flag
+        reports a non-finite coordinate, the rows come back and numpy reduces them -- an axis that holds a NaN is nan"""
+        lo, hi = self._bbox_dev()
+        if self.bbox_nonfinite:
+            rows = self.rows.download(np.float32, 3 * self.n).reshape(-1, 3)
+            lo, hi = list(np.min(rows, axis=0)), list(np.max(rows, axis=0))
+        return lo, hi
+
+    def _bbox_dev(self):
+        """the box kernel's answer as it is: per-axis (min, max) of the surviving rows without their NaNs, and bbox_nonfinite"""
         out = self._alloc(32, "bbox")
         try:
             x, y, z, st = self._xyz()
@@ -2210,7 +2220,7 @@ class DeviceChain:
         """the whole density filter on the device (gsx_density_filter_dev) -> dict(status, n_unique, kept_clusters, largest,
         left: rows after the compaction) ; status DENSITY_HOST: nothing was applied, take the host path"""
         if self._box is None:     # box of the rows as they are now: a superset of whatever survives later filters
-            lo, hi = self.bbox()
+            lo, hi = self._bbox_dev()
             self._box = np.array(list(lo) + list(hi), dtype=np.float32)
             if self.orig is None and not self.empty:     # nothing has been removed yet: this IS the box of the uploaded rows
                 self._pristine_box = self._box

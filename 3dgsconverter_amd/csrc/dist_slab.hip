@@ -28,9 +28,11 @@
 namespace gsx {
 
 // ---------------------------------------------------------------- slab kernels
-__device__ __forceinline__ void amax_f32(float *addr, float v)  // finite v; *addr starts at -inf
+// Split on the sign BIT, not on v >= 0: -0.0f as an int is INT_MIN, so an atomicMax would never store it (a box whose
+// maximum is -0.0 came back as the next lower value, or -inf); as an unsigned it is the smallest of the negatives.
+__device__ __forceinline__ void amax_f32(float *addr, float v)  // non-NaN v; *addr starts at -inf
 {
-    if (v >= 0.0f) atomicMax(reinterpret_cast<int *>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int *>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned *>(addr), __float_as_uint(v));
 }
 

@@ -160,8 +160,10 @@ class DataProcessor:
 
     def _columns(self, names):
         """the named columns of the (materialised) table as contiguous arrays: one threaded pass (gsx_host_gather_columns_f32) for
-        float32 fields of a plain table, numpy's own copies otherwise.  Same values, so numpy's expressions on them give what they
-        give on the strided views the reference uses"""
+        float32 fields of a plain table, numpy's own copies otherwise.  Same values, so numpy's elementwise expressions on them give
+        what they give on the strided views the reference uses.  Reductions only by value: np.min / np.max over zeros of both signs
+        may return a different zero for a contiguous array than for a strided view of the same values (numpy 2.2.6), so a zero
+        extreme is taken from the strided view (apply_auto_bbox)"""
         d = self.data
         fields = d.dtype.fields or {}
         if isinstance(d, np.ndarray) and d.ndim == 1 and len(d) >= 4096 and all(nm in fields and fields[nm][0] == np.dtype("<f4") for nm in names):
@@ -233,6 +235,9 @@ class DataProcessor:
         vertices = self.data
         num_points = len(vertices)
         if num_points == 0:
+            # the reference's GPU branch slices the empty table with an empty mask and reports it (:146-150)
+            status_print("[SOR] Determining outliers on GPU (HIP gfx950, exact KNN)...")
+            status_print("After removing flyers (GPU), retained 0 out of 0 vertices.")
             return self.data
         if not 1 <= int(k) <= MAX_SOR_K:
             # the reference's cKDTree path takes any k and its Taichi kernel silently caps K at 50 (gpu_ops.py:244); here
@@ -455,19 +460,27 @@ class DataProcessor:
 
     def apply_auto_bbox(self):
         """reference :345-354: prints the tight bounding box of what is left (no change to the data).  On the device chain
-        the box comes from the rows in HBM (no materialisation)."""
+        the box comes from the rows in HBM (no materialisation) unless it has a zero extreme."""
         debug_print("[DEBUG] Auto-Correction of Bounding Box (Calculating tight fit)...")
         if len(self) == 0:
             status_print("Auto-BBox: No points remaining. Bounding box is undefined.")
             return
         if self._chain is not None and _lib.f32_inexact_field(self._data, XYZ) is None:
-            lo, hi = self._chain.bbox()
+            lo, hi = self._chain.bbox()     # (numpy's values, `nan` on an axis that holds a NaN)
         else:   # (a chain over coordinates float32 does not hold -- a row filter's -- is materialised: the reduction runs on the table)
             # the reference's reductions (:348-349) on contiguous copies of the columns (one threaded gather; six numpy reductions
             # over 248-byte-stride views took 92 ms at 10M splats)
-            cols = self._columns(("x", "y", "z"))
+            cols = self._columns(XYZ)
             lo = [np.min(c) for c in cols]
             hi = [np.max(c) for c in cols]
+        # a zero extreme prints as 0.0000 or -0.0000: which zero numpy returns depends on the layout it reduces (a contiguous copy
+        # and the reference's strided field view can differ) and the device box's zero has no defined sign -- so that one value
+        # is the reference's own expression on the strided view
+        for a, nm in enumerate(XYZ):
+            if lo[a] == 0:
+                lo[a] = np.min(self.data[nm])
+            if hi[a] == 0:
+                hi[a] = np.max(self.data[nm])
         status_print(f"Auto-BBox Applied: [{lo[0]:.4f}, {lo[1]:.4f}, {lo[2]:.4f}] to [{hi[0]:.4f}, {hi[1]:.4f}, {hi[2]:.4f}]")
 
     # ------------------------------------------------------------------ names a newer reference might add

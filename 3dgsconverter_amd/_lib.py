@@ -95,6 +95,14 @@ class CplyReadLayout(C.Structure):
                 ("vertex_offset", C.c_int32 * 4), ("n_sh", C.c_int32), ("sh_offset", C.c_int32 * CPLY_READ_MAX_SH)]
 
 
+class KsplatReadSection(C.Structure):
+    """gsx_ksplat_read_section (include/gsx_hip.h): one section of a .ksplat file as the reader's kernel walks it"""
+    _fields_ = [("rows_offset", C.c_int64), ("centres_offset", C.c_int64), ("n_rows", C.c_int64), ("out_row", C.c_int64),
+                ("full_rows", C.c_int64), ("prefix_offset", C.c_int64), ("bucket_size", C.c_uint32), ("n_full", C.c_uint32),
+                ("n_partial", C.c_uint32), ("n_buckets", C.c_uint32), ("sh_count", C.c_int32), ("scale_range", C.c_float),
+                ("scale_factor", C.c_float)]
+
+
 class SogScan(C.Structure):
     """gsx_sog_scan (include/gsx_hip.h)"""
     _fields_ = [("vmin", C.c_float * 3), ("vmax", C.c_float * 3), ("nonfinite", C.c_uint32), ("reserved", C.c_uint32),
@@ -227,6 +235,7 @@ SIGNATURES = {
     "gsx_splat_order_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_splat_permute_dev": (_I, [_P, _P, _P, _I64, _P]),
     "gsx_cply_unpack_dev": (_I, [_P, _P, _I64, _P, _I64, _P, C.POINTER(CplyReadLayout), _P, _P]),
+    "gsx_ksplat_unpack_dev": (_I, [_P, _P, _I64, _I, C.POINTER(KsplatReadSection), _I, _P, _I64, _P, _I, _P, _I64]),
 }
 
 _lib = None
@@ -1820,6 +1829,118 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
             b.free()
         if leased:
             ar.unlease("cplyread")
+        if own and ctx is not None:
+            ctx.close()
+
+
+_ksplat_read_tables = None
+
+
+def ksplat_read_tables() -> np.ndarray:
+    """The .ksplat reader's colour tables, numpy's own results for the reference's statements on every byte: float32
+    (b / 255.0 - 0.5) / SH_C0 [256] (formats/ksplat.py:230-233) | log(a / (1 - a)), a = clip(b / 255.0, 1e-7, 1 - 1e-7) [256]
+    (:24-27) -- so the device takes no log.  -> float32[512]"""
+    global _ksplat_read_tables
+    if _ksplat_read_tables is None:
+        with np.errstate(all="ignore"):
+            b = np.arange(256, dtype=np.uint8)
+            rgba_f = b.astype(np.float32) / 255.0
+            f_dc = (rgba_f - 0.5) / 0.28209479177387814
+            alpha = np.clip(b.astype(np.float32) / 255.0, 1e-7, 1.0 - 1e-7)
+            opa = np.log(alpha / (1.0 - alpha))
+        assert f_dc.dtype == np.float32 and opa.dtype == np.float32
+        _ksplat_read_tables = np.concatenate([f_dc, opa])
+    return _ksplat_read_tables
+
+
+def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int, sections, prefix: np.ndarray, n_coeffs: int,
+                        n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+    """The .ksplat reader's rows (formats/ksplat.py:104-317) from a file whose headers the caller has parsed and checked
+    (formats/ksplat_reader.py): `body_bytes` bytes from file offset `body_offset` are read straight into page-locked staging,
+    uploaded once, decoded by gsx_ksplat_unpack_dev (sections: KsplatReadSection records with offsets inside that body; prefix:
+    uint32 prefix sums of the partially filled buckets' lengths) and downloaded into a prefaulted array of `dtype`
+    (68 + 4 n_coeffs bytes of float32 per row).
+
+    Runs on the process's arena while it holds the "ksread" lease; a second call at the same moment (another thread) takes a
+    context and buffers of its own."""
+    lib = require_hip()
+    n = int(n_rows)
+    out = np.empty(n, dtype)
+    rb = dtype.itemsize
+    if rb != 68 + 4 * int(n_coeffs):
+        raise ValueError("ksplat_unpack_table: rows of %d bytes for %d f_rest fields" % (rb, n_coeffs))
+    if n == 0:
+        return out
+    total = int(body_bytes)
+    secs = (KsplatReadSection * max(len(sections), 1))(*sections)
+    prefix = np.ascontiguousarray(prefix, dtype=np.uint32)
+    ar = arena(device)
+    leased = ar.lease("ksread")
+    own = not leased
+    ctx = None
+    bufs = []
+    import time as _time
+    _t = [_time.perf_counter()]
+
+    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
+        if stage_ms is not None:
+            ctx.synchronize()
+            now = _time.perf_counter()
+            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
+            _t[0] = now
+
+    def alloc(nbytes, name):
+        if leased:
+            return ar.buf("ksread_" + name, nbytes)
+        b = ctx.alloc(max(int(nbytes), 16))
+        bufs.append(b)
+        return b
+    try:
+        ctx = ar.context("ksread") if leased else Context(device)
+        toucher = prefault(out) if out.nbytes >= (1 << 22) else None
+        host = ar.pinned("ksread_in", total)[:total] if leased else np.empty(total, np.uint8)
+        with open(path, "rb") as f:
+            f.seek(int(body_offset))
+            view = memoryview(host)
+            got = 0
+            while got < total:
+                r = f.readinto(view[got:])
+                if not r:
+                    raise ValueError("%s: early end of file (%d of %d payload bytes)" % (path, got, total))
+                got += r
+        host_tab = ksplat_read_tables()
+        mark("file_read")
+        d_in = alloc(total + 32, "in")             # the kernel's 16-byte loads reach up to 15 bytes past the last row
+        d_tab = alloc(host_tab.nbytes, "tables")
+        d_prefix = alloc(max(prefix.nbytes, 16), "prefix")
+        if leased:                                 # page-locked already: the runtime's plain copy runs at link rate
+            check(lib.gsx_dev_upload(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload")
+        else:
+            check(lib.gsx_dev_upload_staged(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload_staged")
+        d_tab.upload(host_tab)
+        if prefix.size:
+            d_prefix.upload(prefix)
+        mark("upload")
+        d_out = alloc(n * rb, "out")
+        check(lib.gsx_ksplat_unpack_dev(ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
+                                        d_tab.ptr, int(n_coeffs), d_out.ptr, n), "gsx_ksplat_unpack_dev")
+        mark("kernel")
+        if toucher is not None:
+            toucher.join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        mark("download")
+        return out
+    except GsxError:
+        if leased:
+            ar.unlease("ksread")
+            leased = False
+            release_arenas()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+        if leased:
+            ar.unlease("ksread")
         if own and ctx is not None:
             ctx.close()
 

@@ -20,7 +20,7 @@ _saved = {}
 
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
-            cply_reader: bool = True):
+            cply_reader: bool = True, ksplat_reader: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -35,7 +35,11 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     cply_reader: also rebind ``gsconverter.formats.compressed_ply.CompressedPlyFormat.read`` to formats/compressed_ply_reader.py
     (the decode on the GPU, no plyfile; the reference's rows and ``self.metadata``).  Files the device path does not take -- no
     `chunk` element, ascii or big-endian bodies, list properties -- go to the reference's own read.  A reference without that
-    module is left as it is."""
+    module is left as it is.
+    ksplat_reader: also rebind ``gsconverter.formats.ksplat.KSplatFormat.read`` to formats/ksplat_reader.py (header walk on the
+    host, every row decoded on the GPU; the reference's rows, ``self.metadata`` and its exceptions on malformed files).  Files the
+    device path does not take -- a section of SH degree above 3, thousands of section headers, rows broadcast against a single
+    bucket assignment -- go to the reference's own read.  A reference without that module is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -112,6 +116,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.compressed_ply_reader import bind_read
             _saved.setdefault(("cplyformat", "read"), cpmod.CompressedPlyFormat.read)
             cpmod.CompressedPlyFormat.read = bind_read(_saved[("cplyformat", "read")])
+    if ksplat_reader:
+        try:
+            ksmod = importlib.import_module("gsconverter.formats.ksplat")
+        except ImportError:
+            ksmod = None
+        if ksmod is not None and getattr(ksmod.KSplatFormat, "read", None) is not None:
+            from .formats.ksplat_reader import bind_read as bind_ksplat_read
+            _saved.setdefault(("ksplatformat", "read"), ksmod.KSplatFormat.read)
+            ksmod.KSplatFormat.read = bind_ksplat_read(_saved[("ksplatformat", "read")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -130,7 +143,7 @@ def uninstall():
             importlib.import_module("gsconverter.formats.spz").SpzFormat.write = val
             continue
         if modname == "ksplatformat":
-            importlib.import_module("gsconverter.formats.ksplat").KSplatFormat.write = val
+            setattr(importlib.import_module("gsconverter.formats.ksplat").KSplatFormat, attr, val)
             continue
         if modname == "splatformat":
             importlib.import_module("gsconverter.formats.splat").SplatFormat.write = val

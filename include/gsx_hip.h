@@ -727,6 +727,38 @@ typedef struct gsx_cply_read_layout {
 int gsx_cply_unpack_dev(gsx_ctx *ctx, const void *chunk_dev, int64_t n_chunks, const void *vertex_dev, int64_t n_vertices, const void *sh_dev,
                         const gsx_cply_read_layout *layout, const void *tables_dev, float *out_dev);
 
+
+/* ---- the .ksplat reader (csrc/ksplat_read.hip) ----
+ * gsconverter/formats/ksplat.py:29-317 (KSplatFormat.read) with :24-27 (_linear_u8_to_logit): the per-row decode of :148-156
+ * (row -> bucket), :197-261 (position, scale, rotation, colour, opacity, sh at compression level 0, 1 and >= 2) and the
+ * consolidation of :266-315 -- the sections' interleaved rows as they lie in the file -> the reference's rows in
+ * GaussianStruct.define_dtype's order, x y z nx ny nz f_dc_0..2 f_rest_0..n_coeffs-1 opacity scale_0..2 rot_0..3, all
+ * float32, bit for bit (NaN bits included: x86's).  The headers are parsed and checked by the caller
+ * (formats/ksplat_reader.py). */
+typedef struct gsx_ksplat_read_section {
+    int64_t rows_offset;     /* byte offset inside body_dev of the section's first splat row (any alignment) */
+    int64_t centres_offset;  /* ... of its bucket centres, 3 float32 each (any alignment; level >= 1) */
+    int64_t n_rows;          /* rows to decode (< 2^32) */
+    int64_t out_row;         /* where its first row goes in the output */
+    int64_t full_rows;       /* rows of the full buckets, min(fullBucketCount x bucketSize, n_rows): row i < full_rows lies in
+                                bucket i / bucket_size (level >= 1) */
+    int64_t prefix_offset;   /* first of its n_partial entries in prefix_dev: entry j = the section's rows up to and including
+                                partially filled bucket j (capped at 2^32 - 1); row i >= full_rows lies in bucket n_full + the
+                                first j whose entry is > i.  The entries must cover n_rows. */
+    uint32_t bucket_size, n_full, n_partial, n_buckets;   /* every bucket index the rows reach must be < n_buckets */
+    int32_t sh_count;        /* f_rest values per row in the file: 0, 9 or 24, <= n_coeffs; float32 at level 0, float16 at
+                                level 1, uint8 at level >= 2 */
+    float scale_range;       /* float32(compressionScaleRange) (ksplat.py:207) */
+    float scale_factor;      /* float32((bucketBlockSize / 2.0) / compressionScaleRange), the quotient in float64 (:206) */
+} gsx_ksplat_read_section;
+/* tables_dev: float32 (b / 255 - 0.5) / 0.28209479177387814 [256] | the opacity logit of byte b [256], numpy's own results.
+ * body_dev: the file from its first payload byte, 16-byte aligned and readable up to 16 bytes past body_bytes.  out_dev:
+ * out_rows rows of 68 + 4 n_coeffs bytes (n_coeffs = 0, 9, 24, 45), 16-byte aligned; the sections' rows must tile it (every
+ * row is written by exactly one section, whole).  One launch per section with rows.  Asynchronous. */
+int gsx_ksplat_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t body_bytes, int level, const gsx_ksplat_read_section *sections,
+                          int n_sections, const uint32_t *prefix_dev, int64_t n_prefix, const float *tables_dev, int n_coeffs,
+                          float *out_dev, int64_t out_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ import contextlib
 import ctypes as C
 import os
 import threading
+import time
 
 import numpy as np
 
@@ -1037,12 +1038,15 @@ def cply_pack(columns: dict, order: "np.ndarray | None", sh_columns=(), ctx: "Co
             ctx.close()
 
 
-def prefault(*arrays):
+def prefault(large: bool, *arrays):
     """touch every page of freshly allocated result arrays on a helper thread WHILE the device works (numpy's strided fill releases
     the GIL; the caller sits in ctypes calls anyway): the download that follows then writes into mapped pages -- 610 MB of texels
     / vertices arrive at 28-34 GB/s through the staging lanes when every 8 MiB chunk first has to fault its 2048 pages in, at link
-    rate when the pages are there.  -> join() handle"""
-    import threading
+    rate when the pages are there.  Only when `large` (the caller's rule: a thread costs more than a small result's faults) and
+    for the arrays that are not None.  -> join(), to be called before the download (nothing to wait for when nothing was started)"""
+    arrays = [a for a in arrays if a is not None]
+    if not large or not arrays:
+        return lambda: None
 
     def run():
         for a in arrays:
@@ -1050,7 +1054,7 @@ def prefault(*arrays):
             flat[::4096] = 0
     th = threading.Thread(target=run, name="gsx-prefault", daemon=True)
     th.start()
-    return th
+    return th.join
 
 
 def file_backed(a) -> bool:
@@ -1073,6 +1077,54 @@ def upload_table(lib, ctx, dev_ptr: int, rows: np.ndarray):
         check(lib.gsx_dev_upload(ctx.handle, dev_ptr, rows.ctypes.data, rows.nbytes), "gsx_dev_upload")
     else:
         check(lib.gsx_dev_upload_staged(ctx.handle, dev_ptr, rows.ctypes.data, rows.nbytes), "gsx_dev_upload_staged")
+
+
+def narrow_rows(data: np.ndarray, extra=()) -> np.ndarray:
+    """the table a writer uploads: rows wider than 512 bytes (the kernels' limit) keep only the fields the writer reads -- those of
+    SOG_FIELD_NAMES, at most 59 x 4 bytes per row, and `extra`; C-contiguous either way"""
+    if data.dtype.itemsize > 512:
+        import numpy.lib.recfunctions as rfn
+        data = rfn.repack_fields(data[[nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields] + list(extra)])
+    return np.ascontiguousarray(data)
+
+
+def rest_nonzero_word(lib, ctx, d_rows, lay: SpzLayout, n: int, scan_fields) -> int:
+    """one device pass over resident rows -> bit i set when field f_rest_i, i in `scan_fields`, holds a value != 0"""
+    word = C.c_uint64(0)
+    want = sum(1 << int(i) for i in scan_fields)
+    check(lib.gsx_spz_rest_nonzero_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, want, C.byref(word)), "gsx_spz_rest_nonzero_dev")
+    return word.value
+
+
+def pack_listed(s: "ArenaSession", n: int, run):
+    """run(d_list, cap, d_cnt) launches a packer that lists the entries it leaves to numpy in d_list, `cap` of them at most, and
+    counts all of them in d_cnt.  More listed entries than room: once more, with room for every one of them.
+    -> (d_list, count); listed_rows() downloads them"""
+    cap = n // 64 + 4096
+    d_list, d_cnt = s.buf("list", 8 * cap), s.buf("count", 16)
+    run(d_list, cap, d_cnt)
+    cnt = int(d_cnt.download(np.uint32, 1)[0])
+    if cnt > cap:
+        d_list = s.buf("list", 8 * cnt)
+        run(d_list, cnt, d_cnt)
+        cnt = int(d_cnt.download(np.uint32, 1)[0])
+    return d_list, cnt
+
+
+def listed_rows(d_list, cnt: int) -> np.ndarray:
+    """-> the (cnt, 2) uint32 entries a packer listed"""
+    return d_list.download(np.uint32, 2 * cnt).reshape(cnt, 2) if cnt else np.zeros((0, 2), np.uint32)
+
+
+def read_exact(f, view, path: str, where: str = "", unit: str = "bytes"):
+    """fill the writable buffer `view` from the open binary file `f`, or ValueError about the file's early end"""
+    view = memoryview(view)
+    got = 0
+    while got < len(view):
+        r = f.readinto(view[got:])
+        if not r:
+            raise ValueError("%s: early end of file%s (%d of %d %s)" % (path, where, got, len(view), unit))
+        got += r
 
 
 def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = None, ctx: "Context | None" = None, stage_ms: "dict | None" = None):
@@ -1111,46 +1163,23 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
         m = len(sh_names)
         names = base_names + sh_names
     nchunks = (n + 255) // 256
-    # resident rows: the arena's grow-only cply_* buffers while this call holds the "cply" lease; a second call at the same moment
-    # (another thread) takes the same path on a context and buffers of its own
-    ar = arena(0) if resident else None
-    leased = ar is not None and ar.lease("cply")
-    if not leased:
-        ar = None
-    own = ctx is None and not leased
-    bufs = []
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
-        if stage_ms is not None:
-            ctx.synchronize()
-            now = _time.perf_counter()
-            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
-            _t[0] = now
-
-    def alloc(nbytes, name):
-        if leased:
-            return ar.buf("cply_" + name, nbytes)
-        b = ctx.alloc(max(int(nbytes), 16))
-        bufs.append(b)
-        return b
-    try:
-        ctx = ar.context("cply") if leased else (ctx or Context(0))
+    # only resident rows go to the arena (the "cply" lease, ArenaSession); a caller's context is used as it is
+    with ArenaSession("cply", 0, stage_ms, ctx=ctx, shared=resident) as s:
+        ctx = s.ctx
         verts = np.empty((n, 4), np.uint32)
         sh = np.empty((n, m), np.uint8) if m and not (resolve and resident) else None
-        toucher = prefault(*(a for a in (verts, sh) if a is not None)) if resident and n >= (1 << 18) else None
-        toucher2 = None
+        large = resident and n >= (1 << 18)
+        joins = [prefault(large, verts, sh)]
         if resident:
             pitch = (data.dtype.itemsize + 3) & ~3
             rd = pitch // 4
-            d_rows = alloc(data.nbytes + 16, "rows")
+            d_rows = s.buf("rows", data.nbytes + 16)
             upload_table(lib, ctx, d_rows.ptr, data)
-            mark("upload")
+            s.mark("upload")
             if pitch != data.dtype.itemsize:
-                d_raw, d_rows = d_rows, alloc(n * pitch, "rows_aligned")
+                d_raw, d_rows = d_rows, s.buf("rows_aligned", n * pitch)
                 check(lib.gsx_rows_repack_dev(ctx.handle, d_raw.ptr, data.dtype.itemsize, n, d_rows.ptr, pitch), "gsx_rows_repack_dev")
-                mark("repack")
+                s.mark("repack")
             if resolve:
                 word = C.c_uint64(0)
                 if m:
@@ -1161,9 +1190,8 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
                 m = len(sh_names)
                 names = base_names + sh_names
                 sh = np.empty((n, m), np.uint8) if m else None
-                if sh is not None and toucher is not None:
-                    toucher2 = prefault(sh)
-                mark("sh_detect")
+                joins.append(prefault(large, sh))
+                s.mark("sh_detect")
             # (round 6: the sigmoid's byte is decided on the device from the opacity field, with a rounding certificate; numpy only
             #  evaluates the listed ~1e-4 of the splats, below)
             col = lambda i: d_rows.ptr + int(fields[names[i]][1])
@@ -1173,71 +1201,57 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
             mat = host_gather_columns(data, names)                     # (14 + m, n), row 9 = opacity
             with np.errstate(over="ignore"):
                 mat[9] = 1.0 / (1.0 + np.exp(-mat[9]))                 # :200-203 (float32 in, float32 out, as in the reference)
-            d_mat = alloc(max(mat.nbytes, 16), "mat")
+            d_mat = s.buf("mat", max(mat.nbytes, 16))
             d_mat.upload(mat)
             col = lambda i: d_mat.ptr + 4 * n * i
             strides = (_I64 * 14)(*([1] * 14))
             xyz_stride, sh_ptr, sh_col_stride, sh_elem_stride = 1, col(14), n, 1
         levels = None
-        d_order = alloc(4 * n, "order")
+        d_order = s.buf("order", 4 * n)
         if order is None:
             lv = C.c_int()
             check(lib.gsx_morton_order_dev(ctx.handle, col(0), col(1), col(2), xyz_stride, n, d_order.ptr, C.byref(lv)), "gsx_morton_order_dev")
             levels = int(lv.value)
-            mark("morton")
+            s.mark("morton")
             order = d_order.download(np.uint32, n) if n else np.zeros(0, np.uint32)
         else:
             order = np.ascontiguousarray(order, dtype=np.uint32)
             d_order.upload(order)
         ptrs = (C.c_void_p * 14)(*[col(i) for i in range(14)])
-        d_chunk, d_vert = alloc(72 * nchunks, "chunk"), alloc(16 * n, "vert")
+        d_chunk, d_vert = s.buf("chunk", 72 * nchunks), s.buf("vert", 16 * n)
         unc_cap = n // 64 + 4096
-        d_list, d_cnt = (alloc(8 * unc_cap, "unc"), alloc(16, "unc_count")) if resident else (None, None)
+        d_list, d_cnt = (s.buf("unc", 8 * unc_cap), s.buf("unc_count", 16)) if resident else (None, None)
         check(lib.gsx_cply_pack_opacity_dev(ctx.handle, ptrs, strides, d_order.ptr, n, d_chunk.ptr, d_vert.ptr, d_list.ptr if resident else None,
                                             unc_cap if resident else 0, d_cnt.ptr if resident else None), "gsx_cply_pack_opacity_dev")
         d_out = None
         if m:
-            d_out = alloc(n * m, "sh")
+            d_out = s.buf("sh", n * m)
             check(lib.gsx_cply_sh_strided_dev(ctx.handle, sh_ptr, m, sh_col_stride, sh_elem_stride, d_order.ptr, n, d_out.ptr), "gsx_cply_sh_strided_dev")
-        mark("pack")
+        s.mark("pack")
         chunks = d_chunk.download(np.float32, 18 * nchunks).reshape(nchunks, 18)
-        for th in (toucher, toucher2):
-            if th is not None:
-                th.join()
+        for join in joins:
+            join()
         dl = lib.gsx_dev_download_staged if resident else lib.gsx_dev_download
         if n:
             check(dl(ctx.handle, verts.ctypes.data, d_vert.ptr, verts.nbytes), "gsx_dev_download")
             if m:
                 check(dl(ctx.handle, sh.ctypes.data, d_out.ptr, sh.nbytes), "gsx_dev_download")
-        mark("download")
+        s.mark("download")
         if resident:
             m_unc = int(d_cnt.download(np.uint32, 1)[0])
             if m_unc > unc_cap:      # (thousands of opacities beyond +-80, or NaNs: numpy's expression for the whole column)
                 pos = np.arange(n, dtype=np.int64)
                 x = np.ascontiguousarray(data["opacity"])[order]
             else:
-                lst = d_list.download(np.uint32, 2 * m_unc).reshape(m_unc, 2) if m_unc else np.zeros((0, 2), np.uint32)
+                lst = listed_rows(d_list, m_unc)
                 pos, x = lst[:, 0].astype(np.int64), lst[:, 1].copy().view(np.float32)
             if len(pos):
                 with np.errstate(all="ignore"):
                     a = 1.0 / (1.0 + np.exp(-x))                                               # :200-203
                     byte = np.clip(np.floor(a * 255 + 0.5), 0, 255).astype(np.uint32)       # :312
                 verts[pos, 3] = (verts[pos, 3] & np.uint32(0xffffff00)) | byte
-            mark("host_patch")
+            s.mark("host_patch")
         return chunks, verts, sh, order, levels
-    except GsxError:
-        if leased:
-            ar.unlease("cply")
-            leased = False
-            release_arenas()    # a failed HIP call: do not keep a context in an unknown state
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-        if leased:
-            ar.unlease("cply")
-        if own and ctx is not None:
-            ctx.close()
 
 
 def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict | None" = None, listed: "dict | None" = None,
@@ -1252,73 +1266,38 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
     listed: a dict that receives the rows whose alpha byte ("alpha") or rotation word ("rotation") numpy evaluated.
     -> (out, degree): out = uint8[16 + (20 + 3 sh_dim) n], the body behind SPZ_HEADER_BYTES left for the caller's header.
 
-    Runs on the process's arena (grow-only buffers, no allocation on a repeated call) while it holds the arena's "spz" lease;
-    a second call at the same moment (another thread) takes a context and buffers of its own."""
+    One ArenaSession of the "spz" lease group."""
     lib = require_hip()
     n = len(data)
-    if data.dtype.itemsize > 512:          # only the fields this writer reads: at most 59 x 4 bytes per row
-        import numpy.lib.recfunctions as rfn
-        data = rfn.repack_fields(data[[nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields]])
-    data = np.ascontiguousarray(data)
-    ar = arena(device)
-    leased = ar.lease("spz")
-    own = not leased
-    ctx = None
-    bufs = []
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
-        if stage_ms is not None:
-            ctx.synchronize()
-            now = _time.perf_counter()
-            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
-            _t[0] = now
-
-    def alloc(nbytes, name):
-        if leased:
-            return ar.buf("spz_" + name, nbytes)
-        b = ctx.alloc(max(int(nbytes), 16))
-        bufs.append(b)
-        return b
-    try:
-        ctx = ar.context("spz") if leased else Context(device)
+    data = narrow_rows(data)
+    with ArenaSession("spz", device, stage_ms) as s:
+        ctx = s.ctx
         lay = spz_layout(data.dtype)
-        d_rows = alloc(data.nbytes + 64, "rows")        # (the kernels read up to 15 bytes past the last row)
+        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernels read up to 15 bytes past the last row)
         if n:
             upload_table(lib, ctx, d_rows.ptr, data)
-        mark("upload")
+        s.mark("upload")
         degree = sh_degree
         if callable(sh_degree):
-            word = C.c_uint64(0)
-            want = sum(1 << int(i) for i in scan_fields)
-            check(lib.gsx_spz_rest_nonzero_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, want, C.byref(word)), "gsx_spz_rest_nonzero_dev")
-            hit = [int(i) for i in scan_fields if (word.value >> int(i)) & 1]
+            word = rest_nonzero_word(lib, ctx, d_rows, lay, n, scan_fields)
+            hit = [int(i) for i in scan_fields if (word >> int(i)) & 1]
             degree = int(sh_degree(max(hit) if hit else -1))
-            mark("sh_detect")
+            s.mark("sh_detect")
         body_bytes = (20 + 3 * SPZ_SH_DIM[degree]) * n
         out = np.empty(SPZ_HEADER_BYTES + body_bytes, np.uint8)
-        toucher = prefault(out) if body_bytes >= (1 << 22) else None
-        d_body = alloc(body_bytes, "body")
-        cap = n // 64 + 4096
-        d_list, d_cnt = alloc(8 * cap, "list"), alloc(16, "count")
+        join = prefault(body_bytes >= (1 << 22), out)
+        d_body = s.buf("body", body_bytes)
 
-        def pack():
+        def pack(d_list, cap, d_cnt):
             check(lib.gsx_spz_pack_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, degree, d_body.ptr, d_list.ptr, cap, d_cnt.ptr),
                   "gsx_spz_pack_dev")
-            return int(d_cnt.download(np.uint32, 1)[0])
-        cnt = pack()
-        if cnt > cap:                      # more listed rows than room: again, with room for every one of them
-            cap = cnt
-            d_list = alloc(8 * cap, "list")
-            cnt = pack()
-        mark("pack")
-        if toucher is not None:
-            toucher.join()
+        d_list, cnt = pack_listed(s, n, pack)
+        s.mark("pack")
+        join()
         if body_bytes:
             check(lib.gsx_dev_download_staged(ctx.handle, out.ctypes.data + SPZ_HEADER_BYTES, d_body.ptr, body_bytes), "gsx_dev_download_staged")
-        lst = d_list.download(np.uint32, 2 * cnt).reshape(cnt, 2) if cnt else np.zeros((0, 2), np.uint32)
-        mark("download")
+        lst = listed_rows(d_list, cnt)
+        s.mark("download")
         a_rows = lst[lst[:, 1] == 0, 0].astype(np.int64)
         r_rows = lst[lst[:, 1] == 1, 0].astype(np.int64)
         body = out[SPZ_HEADER_BYTES:]
@@ -1328,23 +1307,10 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
             q = np.column_stack([data["rot_%d" % c][r_rows] for c in range(4)])
             spz_patch_rotations(body[16 * n:20 * n].view("<u4"), r_rows, q)
         if cnt:
-            mark("host_patch")
+            s.mark("host_patch")
         if listed is not None:
             listed["alpha"], listed["rotation"] = a_rows, r_rows
         return out, degree
-    except GsxError:
-        if leased:
-            ar.unlease("spz")
-            leased = False
-            release_arenas()
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-        if leased:
-            ar.unlease("spz")
-        if own and ctx is not None:
-            ctx.close()
 
 
 KSPLAT_HEADER_BYTES = 4096 + 1024   # file header + the one section header (ksplat.py:370-413)
@@ -1485,82 +1451,46 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
     listed: a dict that receives the rows ("rows") and buckets ("buckets") numpy evaluated, and "exp_host" (True when the numpy
     probe failed and every scale and alpha came from numpy).  -> (out, degree)
 
-    Runs on the process's arena while it holds the "ksplat" lease; a second call at the same moment (another thread) takes a
-    context and buffers of its own."""
+    One ArenaSession of the "ksplat" lease group."""
     lib = require_hip()
     n = len(data)
     exp_ok = np_exp_probe()
     src = data                               # the caller's table: numpy's host patches run on it, as the reference's expressions do
-    if data.dtype.itemsize > 512:            # only the fields this writer reads: at most 59 x 4 bytes per row
-        import numpy.lib.recfunctions as rfn
-        data = rfn.repack_fields(data[[nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields]])
-    data = np.ascontiguousarray(data)
-    ar = arena(device)
-    leased = ar.lease("ksplat")
-    own = not leased
-    ctx = None
-    bufs = []
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
-        if stage_ms is not None:
-            ctx.synchronize()
-            now = _time.perf_counter()
-            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
-            _t[0] = now
-
-    def alloc(nbytes, name):
-        if leased:
-            return ar.buf("ksplat_" + name, nbytes)
-        b = ctx.alloc(max(int(nbytes), 16))
-        bufs.append(b)
-        return b
-    try:
-        ctx = ar.context("ksplat") if leased else Context(device)
+    data = narrow_rows(data)
+    with ArenaSession("ksplat", device, stage_ms) as s:
+        ctx = s.ctx
         lay = spz_layout(data.dtype)
-        d_rows = alloc(data.nbytes + 64, "rows")        # (the kernels read up to 15 bytes past the last row)
+        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernels read up to 15 bytes past the last row)
         if n:
             upload_table(lib, ctx, d_rows.ptr, data)
-        mark("upload")
+        s.mark("upload")
         if callable(degree):
-            word = C.c_uint64(0)
-            want = sum(1 << int(i) for i in scan_fields)
-            check(lib.gsx_spz_rest_nonzero_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, want, C.byref(word)), "gsx_spz_rest_nonzero_dev")
-            degree = int(degree(word.value))
-            mark("sh_detect")
+            degree = int(degree(rest_nonzero_word(lib, ctx, d_rows, lay, n, scan_fields)))
+            s.mark("sh_detect")
         out, g = geometry(degree)
         level, sh_count, bs, nb, row_base = g["level"], g["sh_count"], g["bucket_size"], g["n_buckets"], g["row_base"]
         pay = out[KSPLAT_HEADER_BYTES:]
-        toucher = prefault(pay) if pay.nbytes >= (1 << 22) else None
-        d_pay = alloc(g["payload_bytes"] + 64, "payload")
-        cap = n // 64 + 4096
-        d_list, d_cnt = alloc(8 * cap, "list"), alloc(16, "count")
+        join = prefault(pay.nbytes >= (1 << 22), pay)
+        d_pay = s.buf("payload", g["payload_bytes"] + 64)
         centres_ptr = d_pay.ptr + len(g["head"])
 
-        def pack():
+        def pack(d_list, cap, d_cnt):
             check(lib.gsx_dev_memset(ctx.handle, d_cnt.ptr, 0, 4), "gsx_dev_memset")
             if level >= 1 and n:
                 check(lib.gsx_ksplat_centres_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, bs, centres_ptr, d_list.ptr, cap, d_cnt.ptr),
                       "gsx_ksplat_centres_dev")
-                mark("centres")
+                s.mark("centres")
             check(lib.gsx_ksplat_pack_dev(ctx.handle, d_rows.ptr, C.byref(lay), n, level, sh_count, bs if level else 1, g["sf_inv"],
                                           centres_ptr if level else None, d_pay.ptr, row_base, d_list.ptr, cap, d_cnt.ptr),
                   "gsx_ksplat_pack_dev")
-            return int(d_cnt.download(np.uint32, 1)[0])
-        cnt = pack()
-        if cnt > cap:                      # more listed entries than room: again, with room for every one of them
-            cap = cnt
-            d_list = alloc(8 * cap, "list")
-            cnt = pack()
-        mark("pack")
-        if toucher is not None:
-            toucher.join()
+        d_list, cnt = pack_listed(s, n, pack)
+        s.mark("pack")
+        join()
         if g["payload_bytes"]:
             check(lib.gsx_dev_download_staged(ctx.handle, pay.ctypes.data, d_pay.ptr, g["payload_bytes"]), "gsx_dev_download_staged")
         pay[:len(g["head"])] = np.frombuffer(g["head"], np.uint8)
-        lst = d_list.download(np.uint32, 2 * cnt).reshape(cnt, 2) if cnt else np.zeros((0, 2), np.uint32)
-        mark("download")
+        lst = listed_rows(d_list, cnt)
+        s.mark("download")
         rows = lst[lst[:, 1] == 0, 0].astype(np.int64)
         buckets = np.unique(lst[lst[:, 1] == 2, 0].astype(np.int64))
         body = pay[row_base:row_base + n * ksplat_row_dtype(level, sh_count).itemsize].view(ksplat_row_dtype(level, sh_count))
@@ -1577,23 +1507,10 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
             rows = np.unique(rows)
             body[rows] = ksplat_rows_host(src, rows, level, sh_count, cen, bs, g["py_sf_inv"])
         if cnt or not exp_ok:
-            mark("host_patch")
+            s.mark("host_patch")
         if listed is not None:
             listed["rows"], listed["buckets"], listed["exp_host"] = rows, buckets, not exp_ok
         return out, degree
-    except GsxError:
-        if leased:
-            ar.unlease("ksplat")
-            leased = False
-            release_arenas()
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-        if leased:
-            ar.unlease("ksplat")
-        if own and ctx is not None:
-            ctx.close()
 
 
 SPLAT_RECORD = np.dtype([("pos", "<f4", (3,)), ("scale", "<f4", (3,)), ("color", "u1", (4,)), ("rot", "u1", (4,))])   # splat.py:155-160
@@ -1617,101 +1534,61 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
     listed: a dict that receives "exp_host" (True when the numpy probe failed: the metric, the scales and alpha then come from
     numpy, the sort and the rest from the device).
 
-    Runs on the process's arena while it holds the "splat" lease; a second call at the same moment (another thread) takes a
-    context and buffers of its own."""
+    One ArenaSession of the "splat" lease group."""
     lib = require_hip()
     n = len(data)
     exp_ok = np_exp_probe()
     src = data
-    names = [nm for nm in SOG_FIELD_NAMES if nm in data.dtype.fields] + (["red", "green", "blue"] if rgb else [])
-    if data.dtype.itemsize > 512:            # only the fields this writer reads
-        import numpy.lib.recfunctions as rfn
-        data = rfn.repack_fields(data[names])
-    data = np.ascontiguousarray(data)
+    data = narrow_rows(data, ("red", "green", "blue") if rgb else ())
     fields = data.dtype.fields
     colour = [int(fields[c][1]) for c in ("red", "green", "blue")] if rgb else [-1, -1, -1]
-    ar = arena(device)
-    leased = ar.lease("splat")
-    own = not leased
-    ctx = None
-    bufs = []
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
-        if stage_ms is not None:
-            ctx.synchronize()
-            now = _time.perf_counter()
-            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
-            _t[0] = now
-
-    def alloc(nbytes, name):
-        if leased:
-            return ar.buf("splat_" + name, nbytes)
-        b = ctx.alloc(max(int(nbytes), 16))
-        bufs.append(b)
-        return b
-    try:
-        ctx = ar.context("splat") if leased else Context(device)
+    with ArenaSession("splat", device, stage_ms) as s:
+        ctx = s.ctx
         out = np.empty(32 * n, np.uint8)
         if n == 0:
             return out
-        toucher = prefault(out) if out.nbytes >= (1 << 22) else None
+        join = prefault(out.nbytes >= (1 << 22), out)
         lay = spz_layout(data.dtype)
-        d_rows = alloc(data.nbytes + 64, "rows")        # (the pack kernel reads up to 15 bytes past the last row)
+        d_rows = s.buf("rows", data.nbytes + 64)        # (the pack kernel reads up to 15 bytes past the last row)
         upload_table(lib, ctx, d_rows.ptr, data)
-        mark("upload")
-        d_keys, d_order = alloc(4 * n, "keys"), alloc(4 * n, "order")
-        d_recs, d_out = alloc(32 * n, "recs"), alloc(32 * n, "out")
+        s.mark("upload")
+        d_keys, d_order = s.buf("keys", 4 * n), s.buf("order", 4 * n)
+        d_recs, d_out = s.buf("recs", 32 * n), s.buf("out", 32 * n)
 
         def pack(order, keys, recs):
             check(lib.gsx_splat_pack_dev(ctx.handle, d_rows.ptr, C.byref(lay), *colour, n, order, keys, recs), "gsx_splat_pack_dev")
         if variant == "gather":
             pack(None, d_keys.ptr, None)
-            mark("keys")
+            s.mark("keys")
         else:
             pack(None, d_keys.ptr, d_recs.ptr)
-            mark("key_pack")
+            s.mark("key_pack")
         if not exp_ok:                       # another exp than numpy's: numpy's metric, keyed and sorted on the device
-            d_metric = alloc(4 * n, "metric")
+            d_metric = s.buf("metric", 4 * n)
             d_metric.upload(np.ascontiguousarray(splat_metric_host(src), np.float32))
             check(lib.gsx_splat_keys_dev(ctx.handle, d_metric.ptr, n, d_keys.ptr), "gsx_splat_keys_dev")
-            mark("host_metric")
+            s.mark("host_metric")
         check(lib.gsx_splat_order_dev(ctx.handle, d_keys.ptr, n, d_order.ptr), "gsx_splat_order_dev")
-        mark("sort")
+        s.mark("sort")
         if variant == "gather":
             pack(d_order.ptr, None, d_out.ptr)
-            mark("gather_pack")
+            s.mark("gather_pack")
         else:
             check(lib.gsx_splat_permute_dev(ctx.handle, d_recs.ptr, d_order.ptr, n, d_out.ptr), "gsx_splat_permute_dev")
-            mark("permute")
-        if toucher is not None:
-            toucher.join()
+            s.mark("permute")
+        join()
         check(lib.gsx_dev_download_staged(ctx.handle, out.ctypes.data, d_out.ptr, out.nbytes), "gsx_dev_download_staged")
-        mark("download")
+        s.mark("download")
         if not exp_ok:                       # the exp-derived bytes (scales, alpha) from numpy, in the device's order
             order = d_order.download(np.uint32, n).astype(np.int64)
             rec = out.view(SPLAT_RECORD)
             with np.errstate(all="ignore"):
                 rec["scale"] = np.column_stack([np.exp(src["scale_%d" % a][order]) for a in range(3)])
                 rec["color"][:, 3] = np.clip((1 / (1 + np.exp(-src["opacity"][order]))) * 255, 0, 255).astype(np.uint8)
-            mark("host_patch")
+            s.mark("host_patch")
         if listed is not None:
             listed["exp_host"] = not exp_ok
         return out
-    except GsxError:
-        if leased:
-            ar.unlease("splat")
-            leased = False
-            release_arenas()
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-        if leased:
-            ar.unlease("splat")
-        if own and ctx is not None:
-            ctx.close()
 
 
 _cply_tables = None
@@ -1742,8 +1619,7 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
     uploaded once, decoded by gsx_cply_unpack_dev and downloaded into a prefaulted array of `dtype` (68 + 4 n_sh bytes of
     float32 per row; formats/compressed_ply_reader.py builds it).  Rows past 256 n_chunks stay zero, as in the reference.
 
-    Runs on the process's arena while it holds the "cplyread" lease; a second call at the same moment (another thread) takes a
-    context and buffers of its own."""
+    One ArenaSession of the "cplyread" lease group."""
     lib = require_hip()
     n = int(n_vertices)
     n_dec = min(n, 256 * int(n_chunks))
@@ -1757,80 +1633,36 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
         if seg is not None:
             place[k] = total
             total += (int(seg[1]) + 16 + 15) & ~15
-    ar = arena(device)
-    leased = ar.lease("cplyread")
-    own = not leased
-    ctx = None
-    bufs = []
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
-        if stage_ms is not None:
-            ctx.synchronize()
-            now = _time.perf_counter()
-            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
-            _t[0] = now
-
-    def alloc(nbytes, name):
-        if leased:
-            return ar.buf("cplyread_" + name, nbytes)
-        b = ctx.alloc(max(int(nbytes), 16))
-        bufs.append(b)
-        return b
-    try:
-        ctx = ar.context("cplyread") if leased else Context(device)
+    with ArenaSession("cplyread", device, stage_ms) as s:
+        ctx = s.ctx
         rb = dtype.itemsize
-        toucher = prefault(out) if out.nbytes >= (1 << 22) else None
-        host = ar.pinned("cplyread_in", total)[:total] if leased else np.empty(total, np.uint8)
+        join = prefault(out.nbytes >= (1 << 22), out)
+        host = s.staging("in", total)
         with open(path, "rb") as f:
             for k, seg in parts:
                 if seg is None:
                     continue
                 f.seek(int(seg[0]))
-                view = memoryview(host[place[k]:place[k] + int(seg[1])])
-                got = 0
-                while got < len(view):
-                    r = f.readinto(view[got:])
-                    if not r:
-                        raise ValueError("%s: early end of file in element %r (%d of %d bytes)" % (path, k, got, len(view)))
-                    got += r
+                read_exact(f, host[place[k]:place[k] + int(seg[1])], path, " in element %r" % k)
         host_tab = cply_read_tables()
-        mark("file_read")
-        d_in = alloc(total, "in")
-        d_tab = alloc(host_tab.nbytes, "tables")
-        if leased:                           # page-locked already: the runtime's plain copy runs at link rate
-            check(lib.gsx_dev_upload(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload")
-        else:
-            check(lib.gsx_dev_upload_staged(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload_staged")
+        s.mark("file_read")
+        d_in = s.buf("in", total)
+        d_tab = s.buf("tables", host_tab.nbytes)
+        s.upload_staging(lib, d_in.ptr, host)
         d_tab.upload(host_tab)
-        mark("upload")
-        d_out = alloc(n_dec * rb, "out")
+        s.mark("upload")
+        d_out = s.buf("out", n_dec * rb)
         ptr = {k: d_in.ptr + place[k] for k in place}
         check(lib.gsx_cply_unpack_dev(ctx.handle, ptr["chunk"], int(n_chunks), ptr["vertex"], n, ptr.get("sh"), C.byref(layout), d_tab.ptr,
                                       d_out.ptr), "gsx_cply_unpack_dev")
-        mark("kernel")
-        if toucher is not None:
-            toucher.join()
+        s.mark("kernel")
+        join()
         flat = out.view(np.uint8)
         check(lib.gsx_dev_download_staged(ctx.handle, flat.ctypes.data, d_out.ptr, n_dec * rb), "gsx_dev_download_staged")
         if n_dec < n:
             flat[n_dec * rb:] = 0
-        mark("download")
+        s.mark("download")
         return out
-    except GsxError:
-        if leased:
-            ar.unlease("cplyread")
-            leased = False
-            release_arenas()
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-        if leased:
-            ar.unlease("cplyread")
-        if own and ctx is not None:
-            ctx.close()
 
 
 _ksplat_read_tables = None
@@ -1861,8 +1693,7 @@ def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int
     uint32 prefix sums of the partially filled buckets' lengths) and downloaded into a prefaulted array of `dtype`
     (68 + 4 n_coeffs bytes of float32 per row).
 
-    Runs on the process's arena while it holds the "ksread" lease; a second call at the same moment (another thread) takes a
-    context and buffers of its own."""
+    One ArenaSession of the "ksread" lease group."""
     lib = require_hip()
     n = int(n_rows)
     out = np.empty(n, dtype)
@@ -1874,75 +1705,31 @@ def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int
     total = int(body_bytes)
     secs = (KsplatReadSection * max(len(sections), 1))(*sections)
     prefix = np.ascontiguousarray(prefix, dtype=np.uint32)
-    ar = arena(device)
-    leased = ar.lease("ksread")
-    own = not leased
-    ctx = None
-    bufs = []
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def mark(name):   # stage clock (a synchronisation per stage) when the caller asks for it
-        if stage_ms is not None:
-            ctx.synchronize()
-            now = _time.perf_counter()
-            stage_ms[name] = round(stage_ms.get(name, 0.0) + (now - _t[0]) * 1e3, 3)
-            _t[0] = now
-
-    def alloc(nbytes, name):
-        if leased:
-            return ar.buf("ksread_" + name, nbytes)
-        b = ctx.alloc(max(int(nbytes), 16))
-        bufs.append(b)
-        return b
-    try:
-        ctx = ar.context("ksread") if leased else Context(device)
-        toucher = prefault(out) if out.nbytes >= (1 << 22) else None
-        host = ar.pinned("ksread_in", total)[:total] if leased else np.empty(total, np.uint8)
+    with ArenaSession("ksread", device, stage_ms) as s:
+        ctx = s.ctx
+        join = prefault(out.nbytes >= (1 << 22), out)
+        host = s.staging("in", total)
         with open(path, "rb") as f:
             f.seek(int(body_offset))
-            view = memoryview(host)
-            got = 0
-            while got < total:
-                r = f.readinto(view[got:])
-                if not r:
-                    raise ValueError("%s: early end of file (%d of %d payload bytes)" % (path, got, total))
-                got += r
+            read_exact(f, host, path, unit="payload bytes")
         host_tab = ksplat_read_tables()
-        mark("file_read")
-        d_in = alloc(total + 32, "in")             # the kernel's 16-byte loads reach up to 15 bytes past the last row
-        d_tab = alloc(host_tab.nbytes, "tables")
-        d_prefix = alloc(max(prefix.nbytes, 16), "prefix")
-        if leased:                                 # page-locked already: the runtime's plain copy runs at link rate
-            check(lib.gsx_dev_upload(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload")
-        else:
-            check(lib.gsx_dev_upload_staged(ctx.handle, d_in.ptr, host.ctypes.data, total), "gsx_dev_upload_staged")
+        s.mark("file_read")
+        d_in = s.buf("in", total + 32)             # the kernel's 16-byte loads reach up to 15 bytes past the last row
+        d_tab = s.buf("tables", host_tab.nbytes)
+        d_prefix = s.buf("prefix", max(prefix.nbytes, 16))
+        s.upload_staging(lib, d_in.ptr, host)
         d_tab.upload(host_tab)
         if prefix.size:
             d_prefix.upload(prefix)
-        mark("upload")
-        d_out = alloc(n * rb, "out")
+        s.mark("upload")
+        d_out = s.buf("out", n * rb)
         check(lib.gsx_ksplat_unpack_dev(ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
                                         d_tab.ptr, int(n_coeffs), d_out.ptr, n), "gsx_ksplat_unpack_dev")
-        mark("kernel")
-        if toucher is not None:
-            toucher.join()
+        s.mark("kernel")
+        join()
         check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
-        mark("download")
+        s.mark("download")
         return out
-    except GsxError:
-        if leased:
-            ar.unlease("ksread")
-            leased = False
-            release_arenas()
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-        if leased:
-            ar.unlease("ksread")
-        if own and ctx is not None:
-            ctx.close()
 
 
 class DeviceArray:
@@ -2072,7 +1859,8 @@ class DeviceArena:
     "rgb"), and every group runs on a context of its own (``context(group)``: its stream and the library's per-context work
     buffers).  ``buf()``, ``pinned()`` and ``context()`` serve a group only while it is leased (``lease`` / ``leased``): one user
     of a group at a time, so a buffer never grows -- and frees its old allocation -- under another thread that still reads it.
-    A caller that does not win its lease (another thread holds it) takes private allocations instead."""
+    A caller that does not win its lease (another thread holds it) takes private allocations instead.
+    A user whose lease lasts one call takes it through ``ArenaSession``, which does all of this for it."""
 
     def __init__(self, device: int = 0):
         self.device = int(device)
@@ -2201,6 +1989,74 @@ def release_arenas():
             if not a.closed:
                 a.release()
             del _arenas[dev]
+
+
+class ArenaSession:
+    """One call's use of a lease group: ``with ArenaSession("spz", device, stage_ms) as s:`` around the whole device part.
+
+    The call runs on the process's arena -- ``s.ctx`` is the group's context, ``s.buf("rows", n)`` the grow-only buffer
+    "spz_rows", no allocation on a repeated call -- while it holds the group's lease; a second call at the same moment (another
+    thread) takes a context and buffers of its own, freed and closed when the block ends.  ``shared=False`` never asks the arena,
+    and a caller's `ctx` is used as it is: no lease, and not closed here.
+
+    A GsxError in the block gives the lease back and THEN releases the arenas (a failed HIP call: no context in an unknown state
+    is handed on; with the lease still held release_arenas() would spare this arena); every other exit keeps the arena's
+    buffers.  Private buffers are freed before their context closes.  ``s.mark(name)`` is the stage clock (a synchronisation per
+    stage) when the caller asks for one with a `stage_ms` dict; it starts when the session is made."""
+
+    def __init__(self, group: str, device: int = 0, stage_ms: "dict | None" = None, ctx: "Context | None" = None, shared: bool = True):
+        self.group, self.device, self.stage_ms, self.ctx = group, device, stage_ms, ctx
+        self._ar = arena(device) if shared and ctx is None else None
+        self.leased = self._ar is not None and self._ar.lease(group)
+        self._own = ctx is None and not self.leased
+        self._bufs = []
+        self._t = time.perf_counter()
+
+    def __enter__(self):
+        try:
+            if self.ctx is None:
+                self.ctx = self._ar.context(self.group) if self.leased else Context(self.device)
+        except BaseException as e:      # (the lease is held already: the block's own exit paths)
+            self.__exit__(type(e), e, None)
+            raise
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        if self.leased and etype is not None and issubclass(etype, GsxError):
+            self._ar.unlease(self.group)
+            self.leased = False
+            release_arenas()
+        for b in self._bufs:
+            b.free()
+        if self.leased:
+            self._ar.unlease(self.group)
+        if self._own and self.ctx is not None:
+            self.ctx.close()
+
+    def mark(self, name: str):
+        if self.stage_ms is not None:
+            self.ctx.synchronize()
+            now = time.perf_counter()
+            self.stage_ms[name] = round(self.stage_ms.get(name, 0.0) + (now - self._t) * 1e3, 3)
+            self._t = now
+
+    def buf(self, name: str, nbytes: int) -> DeviceArray:
+        if self.leased:
+            return self._ar.buf(self.group + "_" + name, nbytes)
+        b = self.ctx.alloc(max(int(nbytes), 16))
+        self._bufs.append(b)
+        return b
+
+    def staging(self, name: str, nbytes: int) -> np.ndarray:
+        """`nbytes` of host memory to read a file into: the arena's page-locked buffer under the lease, a pageable array without"""
+        return self._ar.pinned(self.group + "_" + name, nbytes)[:nbytes] if self.leased else np.empty(nbytes, np.uint8)
+
+    def upload_staging(self, lib, dev_ptr: int, host: np.ndarray):
+        """staging() memory to the device: page-locked, the runtime's plain copy runs at link rate; pageable goes through the lanes"""
+        if self.leased:
+            check(lib.gsx_dev_upload(self.ctx.handle, dev_ptr, host.ctypes.data, host.nbytes), "gsx_dev_upload")
+        else:
+            check(lib.gsx_dev_upload_staged(self.ctx.handle, dev_ptr, host.ctypes.data, host.nbytes), "gsx_dev_upload_staged")
 
 
 class DeviceChain:

@@ -7,6 +7,7 @@ mapped): the real grow-only and lease logic, the real threaded host gathers and 
 threading.Event forces the one interleaving that hurts: thread A gathers, thread B gathers and finishes, then A reads."""
 import importlib
 import threading
+import types
 
 import numpy as np
 import pytest
@@ -350,3 +351,192 @@ def test_device_chain_that_loses_the_lease_leaves_chain_xyz_alone(fake, monkeypa
     finally:
         first.close()
     assert not L.arena(0)._leases
+
+
+# ---- ArenaSession: one call's use of a lease group (the six table readers and writers) ----------------------------------
+
+GROUPS = ("cply", "spz", "ksplat", "splat", "cplyread", "ksread")
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_session_with_the_lease_runs_on_the_arena(fake, group):
+    with L.ArenaSession(group, 0) as s:
+        ar = L.arena(0)
+        assert s.leased and ar._leases == {group} and s.ctx is ar.context(group)
+        b = s.buf("rows", 1000)
+        assert b is ar._bufs[group + "_rows"] and b.ctx is ar.context(group) and b.nbytes >= 1000
+    assert not ar._leases and not b.freed and L.arena(0) is ar
+    assert all(c.handle is not None for c in fake.made)            # the arena keeps its context
+    with L.ArenaSession(group, 0) as s:
+        assert s.buf("rows", 10) is b                              # a second call finds the buffer
+
+
+def test_session_without_the_lease_is_private_and_cleans_up(fake):
+    ar = L.arena(0)
+    assert ar.lease("spz")                                         # another user of the group, mid-call
+    made = len(fake.made)
+    with L.ArenaSession("spz", 0) as s:
+        assert not s.leased and len(fake.made) == made + 1 and s.ctx is fake.made[-1]
+        ctx, bufs = s.ctx, [s.buf("rows", 1000), s.buf("count", 0)]
+        assert bufs[0].ctx is ctx and bufs[1].nbytes == 16 and not ar._bufs
+        assert not any(b.freed for b in bufs) and ctx.handle is not None
+    assert all(b.freed for b in bufs) and ctx.handle is None
+    assert ar._leases == {"spz"} and not ar._bufs and L.arena(0) is ar
+
+
+def test_session_without_the_lease_frees_its_buffers_before_its_context(fake):
+    ar = L.arena(0)
+    assert ar.lease("ksread")
+    order = []
+    with L.ArenaSession("ksread", 0) as s:
+        b = s.buf("in", 64)
+        b.free = lambda: order.append("free")
+        s.ctx.close = lambda: order.append("close")
+    assert order == ["free", "close"]
+
+
+def test_session_gsx_error_gives_the_lease_back_and_releases_the_arena(fake):
+    with pytest.raises(L.GsxError, match="boom"):
+        with L.ArenaSession("ksplat", 0) as s:
+            ar, b = L.arena(0), s.buf("rows", 64)
+            raise L.GsxError("boom")
+    assert not ar._leases and ar.closed and b.freed and all(c.handle is None for c in fake.made)
+    assert L.arena(0) is not ar
+
+
+def test_session_gsx_error_spares_an_arena_another_group_holds(fake):
+    ar = L.arena(0)
+    assert ar.lease("chain")                                       # e.g. a DeviceChain with pending filters
+    with pytest.raises(L.GsxError):
+        with L.ArenaSession("ksplat", 0) as s:
+            b = s.buf("rows", 64)
+            raise L.GsxError("boom")
+    assert ar._leases == {"chain"} and not ar.closed and not b.freed and L.arena(0) is ar
+
+
+def test_session_gsx_error_without_the_lease_leaves_the_arena_alone(fake):
+    ar = L.arena(0)
+    assert ar.lease("splat")
+    kept = ar.buf("splat_rows", 64)
+    with pytest.raises(L.GsxError):
+        with L.ArenaSession("splat", 0) as s:
+            ctx, b = s.ctx, s.buf("rows", 64)
+            raise L.GsxError("boom")
+    assert b.freed and ctx.handle is None
+    assert ar._leases == {"splat"} and not ar.closed and not kept.freed
+
+
+def test_session_other_exception_keeps_the_arena(fake):
+    with pytest.raises(ZeroDivisionError):
+        with L.ArenaSession("cplyread", 0) as s:
+            ar, b = L.arena(0), s.buf("in", 64)
+            1 / 0
+    assert not ar._leases and not ar.closed and not b.freed and L.arena(0) is ar
+    assert ar._bufs["cplyread_in"] is b
+
+
+def test_session_gives_the_lease_back_when_its_context_cannot_be_made(fake, monkeypatch):
+    ar = L.arena(0)
+
+    def no_context(device=0, stream=None, own_stream=False):
+        raise L.GsxError("gsx_ctx_create: no device")
+    monkeypatch.setattr(L, "Context", no_context)
+    with pytest.raises(L.GsxError, match="gsx_ctx_create"):
+        with L.ArenaSession("spz", 0):
+            raise AssertionError("the block must not run")
+    assert not ar._leases and ar.closed and L.arena(0) is not ar   # a GsxError with the lease won: the arena is released too
+    assert L.arena(0).lease("ksplat")
+    with pytest.raises(L.GsxError, match="gsx_ctx_create"):        # and a private context that cannot be made has nothing to undo
+        with L.ArenaSession("ksplat", 0):
+            raise AssertionError("the block must not run")
+    assert L.arena(0)._leases == {"ksplat"}
+
+
+def test_session_on_a_callers_context_takes_no_lease_and_does_not_close_it(fake):
+    mine = fake()
+    with L.ArenaSession("cply", 0, ctx=mine, shared=False) as s:
+        assert s.ctx is mine and not s.leased
+        b = s.buf("mat", 100)
+        assert b.ctx is mine
+    assert b.freed and mine.handle is not None and fake.made == [mine] and not L._arenas
+    with pytest.raises(L.GsxError):
+        with L.ArenaSession("cply", 0, ctx=mine) as s:              # (a context decides it: shared or not, the arena is not asked)
+            raise L.GsxError("boom")
+    assert mine.handle is not None and not L._arenas
+
+
+def test_session_that_is_not_shared_never_asks_the_arena(fake):
+    with L.ArenaSession("cply", 0, shared=False) as s:             # cply_pack_table's rows that are not resident
+        assert not s.leased and s.ctx is fake.made[-1] and not L._arenas
+        ctx = s.ctx
+    assert ctx.handle is None and not L._arenas
+
+
+def test_session_stage_clock(fake, monkeypatch):
+    syncs = []
+    monkeypatch.setattr(fake, "synchronize", lambda self: syncs.append(self))
+    with L.ArenaSession("spz", 0, None) as s:
+        s.mark("a")
+        s.mark("b")
+    assert not syncs                                               # no clock asked for: no synchronisation
+    ticks = iter([10.0, 10.0012344, 10.0032344, 10.5])
+    monkeypatch.setattr(L, "time", types.SimpleNamespace(perf_counter=lambda: next(ticks)))
+    st = {}
+    with L.ArenaSession("spz", 0, st) as s:                        # the clock starts here
+        s.mark("a")
+        assert st == {"a": 1.234} and len(syncs) == 1
+        s.mark("a")
+        assert len(syncs) == 2 and syncs[0] is s.ctx
+        s.mark("b")
+    assert list(st) == ["a", "b"] and st["a"] == 3.234 and st["b"] == 496.766
+    assert all(round(v, 3) == v for v in st.values())
+
+
+def test_session_staging_is_page_locked_only_under_the_lease(fake):
+    with L.ArenaSession("ksread", 0) as s:
+        ar = L.arena(0)
+        h = s.staging("in", 1000)
+        addr, size = ar._pinned["ksread_in"]
+        assert h.dtype == np.uint8 and len(h) == 1000 and h.ctypes.data == addr and size >= 1000
+        with L.ArenaSession("ksread", 0) as t:                     # a second user at the same moment
+            p = t.staging("in", 1000)
+            assert not t.leased and p.dtype == np.uint8 and p.shape == (1000,) and p.ctypes.data != addr
+            assert list(ar._pinned) == ["ksread_in"]
+    assert not ar._leases
+
+
+def test_session_uploads_page_locked_staging_plainly_and_pageable_staging_through_the_lanes(fake):
+    calls = []
+
+    class Lib:
+        def gsx_dev_upload(self, handle, dst, src, nbytes):
+            calls.append(("plain", dst, src, nbytes))
+            return 0
+
+        def gsx_dev_upload_staged(self, handle, dst, src, nbytes):
+            calls.append(("staged", dst, src, nbytes))
+            return 0
+    with L.ArenaSession("cplyread", 0) as s, L.ArenaSession("cplyread", 0) as t:
+        hs, ht = s.staging("in", 48), t.staging("in", 32)
+        s.upload_staging(Lib(), 7, hs)
+        t.upload_staging(Lib(), 9, ht)
+    assert calls == [("plain", 7, hs.ctypes.data, 48), ("staged", 9, ht.ctypes.data, 32)]
+
+
+def test_read_exact_fills_the_view_or_names_the_early_end(tmp_path):
+    p = tmp_path / "body.bin"
+    p.write_bytes(bytes(range(100)))
+    buf = np.zeros(100, np.uint8)
+    with open(p, "rb") as f:
+        f.seek(10)
+        L.read_exact(f, buf[:90], str(p))
+        assert bytes(buf[:90]) == bytes(range(10, 100)) and f.tell() == 100
+    with open(p, "rb") as f:
+        f.seek(40)
+        with pytest.raises(ValueError) as e:
+            L.read_exact(f, buf[:90], "a%b.ply", " in element %r" % "vertex")
+        assert str(e.value) == "a%b.ply: early end of file in element 'vertex' (60 of 90 bytes)"
+    with open(p, "rb") as f:
+        with pytest.raises(ValueError) as e:
+            L.read_exact(f, np.zeros(101, np.uint8), "x.ksplat", unit="payload bytes")
+        assert str(e.value) == "x.ksplat: early end of file (100 of 101 payload bytes)"

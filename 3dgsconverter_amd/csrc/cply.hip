@@ -24,22 +24,12 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "gsx_common.h"
+#include "row_tile.h"
 #include "sog_math.h"
 
 namespace gsx {
 
 constexpr unsigned CPLY_CHUNK = 256;   // compressed_ply.py:14 CHUNK_SIZE
-
-// monotone float32 -> uint32 (atomicMin / atomicMax on the image order the floats)
-__device__ __forceinline__ unsigned f2key(float f)
-{
-    const unsigned b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k)
-{
-    return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k);
-}
 
 // ---------------------------------------------------------------- Morton order
 // One recursion level of _sort_morton_order for ALL the groups that are still being refined at once.  The M "active"
@@ -75,9 +65,9 @@ __global__ __launch_bounds__(256) void mo_bbox_kernel(const float *__restrict__ 
         const unsigned p = pos[j];
         hd = j - (p - seg[j]);
         const int64_t i = (int64_t)order[p] * stride;
-        k[0] = k[3] = f2key(x[i]);
-        k[1] = k[4] = f2key(y[i]);
-        k[2] = k[5] = f2key(z[i]);
+        k[0] = k[3] = float_key(x[i]);
+        k[1] = k[4] = float_key(y[i]);
+        k[2] = k[5] = float_key(z[i]);
     }
     const unsigned hd0 = __builtin_amdgcn_readfirstlane(hd);
     if (__all(hd == hd0 || !live) && hd0 != 0xffffffffu) {   // the whole wave is inside one group (the common case)
@@ -133,8 +123,8 @@ __device__ __forceinline__ SegBox seg_box(const unsigned *__restrict__ bb, unsig
     SegBox b;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        b.lo[a] = key2f(bb[(size_t)a * m + hd]);
-        b.len[a] = __fsub_rn(key2f(bb[(size_t)(a + 3) * m + hd]), b.lo[a]);
+        b.lo[a] = sort_unkey(bb[(size_t)a * m + hd]);
+        b.len[a] = __fsub_rn(sort_unkey(bb[(size_t)(a + 3) * m + hd]), b.lo[a]);
     }
     b.degenerate = b.len[0] == 0.0f && b.len[1] == 0.0f && b.len[2] == 0.0f;   // :265 -> the group is left as it is
     return b;
@@ -399,10 +389,7 @@ __global__ __launch_bounds__(256) void cply_pack_kernel(CplyCols c, const unsign
     if (unc_list) {   // column 9 is the opacity itself
         bool ok;
         na = cply_alpha_code(al, &ok);
-        if (!ok) {
-            const unsigned p = atomicAdd(unc_count, 1u);
-            if (p < unc_cap) unc_list[p] = make_uint2((unsigned)i, __float_as_uint(al));
-        }
+        if (!ok) list_append(unc_list, unc_cap, unc_count, (unsigned)i, __float_as_uint(al));
     } else {
         na = (unsigned)fminf(fmaxf(floorf(__fadd_rn(__fmul_rn(al, 255.0f), 0.5f)), 0.0f), 255.0f);   // :312
     }
@@ -455,9 +442,8 @@ __global__ __launch_bounds__(256) void rows_repack_kernel(const unsigned *__rest
         const int j = (int)(e - r * dst_dwords);
         unsigned v = 0u;
         if (j < row_dwords) {
-            const int64_t b = r * row_bytes + 4 * (int64_t)j;          // first source byte of this dword
-            const unsigned lo = src[b >> 2], hi = src[(b >> 2) + 1];   // (one dword past the table at most: see the header)
-            v = __builtin_amdgcn_alignbyte(hi, lo, (unsigned)(b & 3));
+            // the dword at the row's byte 4 j (reads one dword past the table at most: see the header)
+            v = ld_u32(reinterpret_cast<const unsigned char *>(src), r * row_bytes + 4 * (int64_t)j);
             const int valid = (int)min((int64_t)4, row_bytes - 4 * (int64_t)j);   // the row's last dword: the bytes behind it are the NEXT row's
             if (valid < 4) v &= (1u << (8 * valid)) - 1u;
         }

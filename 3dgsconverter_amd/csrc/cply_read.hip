@@ -21,7 +21,7 @@
 // NaN bits: x86 returns the first NaN operand, quieted, and an invalid operation (inf - inf, inf * 0) gives the negative
 // default NaN; the casts f32 <-> f64 keep the payload.  Traced through the statements above that is: a NaN max gives max's
 // bits, quieted; else a NaN min gives min's; any other NaN is 0xffc00000.  The device's own NaN bits differ, so a NaN result
-// is replaced on a cold path (cply_x86_nan).
+// is replaced on a cold path (x86_nan).
 //
 // A tile's output rows are staged in LDS and leave in 16-byte stores; its sh rows (45 bytes at degree 3, any alignment) come
 // in through LDS too (row_tile.h).  Rows past 256 x chunks are not decoded (the reference's loop never reaches them).
@@ -50,21 +50,6 @@ struct CplyReadTables {
     const float *opa, *sh;
 };
 
-// the little-endian u32 at any byte address of global memory (reads the aligned word after it too)
-__device__ __forceinline__ unsigned cply_ld_u32(const unsigned char *__restrict__ base, int64_t byte)
-{
-    const unsigned *w = reinterpret_cast<const unsigned *>(base + (byte & ~(int64_t)3));
-    return __builtin_amdgcn_alignbyte(w[1], w[0], (unsigned)(byte & 3));
-}
-
-// x86's float32 bits of a NaN result of the statements above (cold: only reached when the result is NaN)
-__device__ __noinline__ unsigned cply_x86_nan(float mn, float mx)
-{
-    if (mx != mx) return __float_as_uint(mx) | 0x00400000u;
-    if (mn != mn) return __float_as_uint(mn) | 0x00400000u;
-    return 0xffc00000u;
-}
-
 // :346-347 `(nv / t) * (v_max - v_min) + v_min` with q = nv / t, in float64
 __device__ __forceinline__ double cply_denorm(double q, float mn, float mx)
 {
@@ -75,7 +60,7 @@ __device__ __forceinline__ double cply_denorm(double q, float mn, float mx)
 __device__ __forceinline__ float cply_f32(double r, float mn, float mx)
 {
     const float o = __double2float_rn(r);
-    return o == o ? o : __uint_as_float(cply_x86_nan(mn, mx));
+    return o == o ? o : __uint_as_float(x86_nan(mx, mn));
 }
 
 // :108-110 `(cr - 0.5) / SH_C0` on the float64 colour
@@ -112,7 +97,7 @@ __global__ __launch_bounds__(256) void cply_unpack_kernel(const unsigned char *_
     if (r0 >= n) return;   // (uniform; the grid covers [0, n) exactly)
     const int cnt = (int)min((int64_t)A.tile_rows, n - r0);
     if ((int)threadIdx.x < CPLY_READ_BOUNDS)
-        bnd[threadIdx.x] = __uint_as_float(cply_ld_u32(chunks, chunk * A.chunk_stride + A.chunk_off[threadIdx.x]));
+        bnd[threadIdx.x] = __uint_as_float(ld_u32(chunks, chunk * A.chunk_stride + A.chunk_off[threadIdx.x]));
     int sh_base = 0;
     if (A.n_sh > 0) sh_base = spz_stage_tile(sh, A.sh_stride, r0, cnt, cr_lds);
     const unsigned *sh32 = reinterpret_cast<const unsigned *>(cr_lds);
@@ -120,10 +105,10 @@ __global__ __launch_bounds__(256) void cply_unpack_kernel(const unsigned char *_
     __syncthreads();
     for (int r = threadIdx.x; r < cnt; r += blockDim.x) {
         const int64_t vb = (r0 + r) * A.vertex_stride;
-        const unsigned pp = cply_ld_u32(verts, vb + A.vertex_off[0]);
-        const unsigned pr = cply_ld_u32(verts, vb + A.vertex_off[1]);
-        const unsigned ps = cply_ld_u32(verts, vb + A.vertex_off[2]);
-        const unsigned pc = cply_ld_u32(verts, vb + A.vertex_off[3]);
+        const unsigned pp = ld_u32(verts, vb + A.vertex_off[0]);
+        const unsigned pr = ld_u32(verts, vb + A.vertex_off[1]);
+        const unsigned ps = ld_u32(verts, vb + A.vertex_off[2]);
+        const unsigned pc = ld_u32(verts, vb + A.vertex_off[3]);
         unsigned *o = o32 + r * A.row_words;
         // :75-80 positions (11 / 10 / 11 bits)
         o[0] = __float_as_uint(cply_f32(cply_denorm(T.q2047[(pp >> 21) & 0x7ffu], bnd[0], bnd[3]), bnd[0], bnd[3]));
@@ -146,10 +131,7 @@ __global__ __launch_bounds__(256) void cply_unpack_kernel(const unsigned char *_
         for (int a = 0; a < 4; ++a) o[13 + a] = __float_as_uint(q[a]);
         // :122-127 sh
         const int sq = sh_base + r * A.sh_stride;
-        for (int k = 0; k < A.n_sh; ++k) {
-            const int b = sq + A.sh_off[k];
-            o[CPLY_READ_BASE + k] = __float_as_uint(T.sh[(sh32[b >> 2] >> (8 * (b & 3))) & 0xffu]);
-        }
+        for (int k = 0; k < A.n_sh; ++k) o[CPLY_READ_BASE + k] = __float_as_uint(T.sh[lds_u8(sh32, sq + A.sh_off[k])]);
     }
     __syncthreads();
     // the tile's rows are contiguous in the output and start on a 16-byte boundary (tile_rows is a multiple of 4)

@@ -27,34 +27,13 @@
 #include "gsx_common.h"
 #include "np_exp.h"
 #include "row_tile.h"
+#include "sog_math.h"
 
 namespace gsx {
 
 constexpr int KS_CT = 256;                 // rows per tile (= threads) of the centre kernel
-constexpr unsigned KS_KEY_NEG0 = 0x7fffffffu, KS_KEY_POS0 = 0x80000000u;   // ks_key(-0.0f), ks_key(+0.0f)
+constexpr unsigned KS_KEY_NEG0 = 0x7fffffffu, KS_KEY_POS0 = 0x80000000u;   // float_key(-0.0f), float_key(+0.0f)
 constexpr unsigned KS_KIND_ROW = 0u, KS_KIND_BUCKET = 2u;
-
-// float32 -> unsigned key whose unsigned order is the float order (-0 below +0; NaN is flagged apart, never keyed)
-__device__ __forceinline__ unsigned ks_key(float v)
-{
-    const unsigned u = __float_as_uint(v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float ks_unkey(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
-
-// the float32 at any byte address: the two aligned words around it (reads at most 4 bytes past the field)
-__device__ __forceinline__ float ks_ld_f32(const unsigned char *__restrict__ base, int64_t byte)
-{
-    const unsigned *w = reinterpret_cast<const unsigned *>(base + (byte & ~(int64_t)3));
-    return __uint_as_float(__builtin_amdgcn_alignbyte(w[1], w[0], (unsigned)(byte & 3)));
-}
-
-__device__ __forceinline__ void ks_list(uint2 *list, unsigned cap, unsigned *count, unsigned idx, unsigned kind)
-{
-    const unsigned k = atomicAdd(count, 1u);
-    if (k < cap) list[k] = make_uint2(idx, kind);
-}
 
 // a bucket's centre from its keys: (min + max) / 2.0 per axis in float32 (:440-444), straight into the payload
 __device__ void ks_finish_bucket(int64_t b, const unsigned mn[3], const unsigned mx[3], unsigned flag, float *centres, uint2 *list,
@@ -64,11 +43,11 @@ __device__ void ks_finish_bucket(int64_t b, const unsigned mn[3], const unsigned
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         host |= mn[a] == KS_KEY_NEG0 && mx[a] == KS_KEY_POS0;     // only zeros, both signs
-        const float c = __fdiv_rn(__fadd_rn(ks_unkey(mn[a]), ks_unkey(mx[a])), 2.0f);
+        const float c = __fdiv_rn(__fadd_rn(sort_unkey(mn[a]), sort_unkey(mx[a])), 2.0f);
         host |= c != c;                                           // -inf + inf: numpy's NaN bits are x86's
         centres[3 * b + a] = c;
     }
-    if (host) ks_list(list, cap, count, (unsigned)b, KS_KIND_BUCKET);
+    if (host) list_append(list, cap, count, (unsigned)b, KS_KIND_BUCKET);
 }
 
 __device__ __forceinline__ unsigned ks_wave_min(unsigned v)
@@ -113,13 +92,13 @@ __global__ __launch_bounds__(KS_CT) void ksplat_centre_kernel(const unsigned cha
         int64_t b = -1;
         if (t < cnt) {
             const int64_t row = t0 + t, rowb = row * rb;
-            const float v[3] = {ks_ld_f32(rows, rowb + ox), ks_ld_f32(rows, rowb + oy), ks_ld_f32(rows, rowb + oz)};
+            const float v[3] = {ld_f32(rows, rowb + ox), ld_f32(rows, rowb + oy), ld_f32(rows, rowb + oz)};
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 if (v[a] != v[a]) {
                     nan = 1u;
                 } else {
-                    kmin[a] = kmax[a] = ks_key(v[a]);
+                    kmin[a] = kmax[a] = float_key(v[a]);
                 }
             }
             b = row / B;
@@ -222,7 +201,7 @@ __global__ void ksplat_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev 
         const int r = threadIdx.x;
         if (r < cnt) {
             const int q = base + r * rb;
-            auto fld = [&](int f) { return spz_lds_f32(in32, q + off[f]); };
+            auto fld = [&](int f) { return lds_f32(in32, q + off[f]); };
             const int64_t row = t0 + r;
             unsigned char *o = img + r * bps;
             bool host = false;
@@ -296,29 +275,12 @@ __global__ void ksplat_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev 
                     o[j] = (unsigned char)ks_f32_to_u8_wrap(v);
                 }
             }
-            if (host) ks_list(list, cap, count, (unsigned)row, KS_KIND_ROW);
+            if (host) list_append(list, cap, count, (unsigned)row, KS_KIND_ROW);
         }
         __syncthreads();
         // the tile's rows -> their span of the payload: bytes up to a 16-byte boundary, 16-byte stores, the tail bytes
-        const int64_t g0 = P.row_base + t0 * bps, g1 = g0 + (int64_t)cnt * bps;
-        const int64_t h = min(g1, (g0 + 15) & ~(int64_t)15);
-        const int64_t tl = max(h, g1 & ~(int64_t)15);
-        const int nh = (int)(h - g0), nt = (int)(g1 - tl), nb = (int)((tl - h) >> 4);
-        const int t = threadIdx.x;
-        if (t < nh) payload[g0 + t] = img[t];
-        if (t < nt) payload[tl + t] = img[(int)(tl - g0) + t];
-        for (int k = t; k < nb; k += tr) {
-            const int o = nh + 16 * k;                            // byte of the image that lands on the aligned address
-            const unsigned *w32 = reinterpret_cast<const unsigned *>(img + (o & ~3));
-            const unsigned sh = (unsigned)(o & 3);
-            const unsigned a0 = w32[0], a1 = w32[1], a2 = w32[2], a3 = w32[3], a4 = w32[4];
-            uint4 v;
-            v.x = __builtin_amdgcn_alignbyte(a1, a0, sh);
-            v.y = __builtin_amdgcn_alignbyte(a2, a1, sh);
-            v.z = __builtin_amdgcn_alignbyte(a3, a2, sh);
-            v.w = __builtin_amdgcn_alignbyte(a4, a3, sh);
-            *reinterpret_cast<uint4 *>(payload + h + 16 * k) = v;
-        }
+        const int64_t g0 = P.row_base + t0 * bps;
+        store_bytes(payload, g0, g0 + (int64_t)cnt * bps, img);
     }
 }
 
@@ -332,29 +294,8 @@ __global__ void ksplat_math_kernel(const float *__restrict__ x, int64_t n, unsig
     }
 }
 
-static int ks_layout_to_dev(const gsx_spz_layout *l, int sh_count, SpzLayoutDev *out, const char *who)
-{
-    if (!l) GSX_FAIL("%s: null layout", who);
-    if (l->row_bytes < 1 || l->row_bytes > SPZ_MAX_ROW_BYTES)
-        GSX_FAIL("%s: rows of %lld bytes (1 ... %d are supported)", who, (long long)l->row_bytes, SPZ_MAX_ROW_BYTES);
-    out->row_bytes = (int)l->row_bytes;
-    for (int f = 0; f < SPZ_FIELDS; ++f) {
-        const int o = l->offset[f];
-        const bool required = f <= SPZ_F_OPACITY || f < SPZ_F_REST + sh_count;   // x .. opacity, f_rest_0 .. f_rest_{sh_count-1}
-        if (o < 0) {
-            if (required) GSX_FAIL("%s: field %d is required", who, f);
-        } else if (o + 4 > l->row_bytes) {
-            GSX_FAIL("%s: field %d at byte offset %d of a %lld-byte row", who, f, o, (long long)l->row_bytes);
-        }
-        out->off[f] = o < 0 ? -1 : o;
-    }
-    return 0;
-}
-
-static unsigned ks_blocks(gsx_ctx *c, int64_t ntiles)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)c->num_cu * 8));
-}
+// x .. opacity and f_rest_0 .. f_rest_{sh_count-1} are required
+static uint64_t ks_required(int sh_count) { return fields_below(SPZ_F_REST + sh_count); }
 
 }  // namespace gsx
 
@@ -372,7 +313,7 @@ int gsx_ksplat_centres_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layou
     if (reinterpret_cast<uintptr_t>(centres_dev) & 3) GSX_FAIL("gsx_ksplat_centres_dev: centres must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(rows_dev) & 15) GSX_FAIL("gsx_ksplat_centres_dev: rows must be 16-byte aligned");
     SpzLayoutDev L;
-    GSX_CHECK(ks_layout_to_dev(layout, 0, &L, "gsx_ksplat_centres_dev"));
+    GSX_CHECK(layout_to_dev(layout, ks_required(0), &L, "gsx_ksplat_centres_dev"));
     GSX_HIP(hipSetDevice(c->device));
     if (n == 0) return 0;
     const int64_t ntiles = (n + KS_CT - 1) / KS_CT;
@@ -380,12 +321,11 @@ int gsx_ksplat_centres_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layou
     unsigned *gmin = c->ksplat_keys.as<unsigned>(), *gmax = gmin + 3 * ntiles;
     GSX_HIP(hipMemsetAsync(gmin, 0xff, (size_t)ntiles * 3 * sizeof(unsigned), c->stream));
     GSX_HIP(hipMemsetAsync(gmax, 0, (size_t)ntiles * 4 * sizeof(unsigned), c->stream));
-    hipLaunchKernelGGL(ksplat_centre_kernel, dim3(ks_blocks(c, ntiles)), dim3(KS_CT), 0, c->stream, static_cast<const unsigned char *>(rows_dev),
+    hipLaunchKernelGGL(ksplat_centre_kernel, dim3(tile_blocks(c, n, KS_CT, 8)), dim3(KS_CT), 0, c->stream, static_cast<const unsigned char *>(rows_dev),
                        L.row_bytes, L.off[0], L.off[1], L.off[2], n, bucket_size, centres_dev, gmin, gmax, reinterpret_cast<uint2 *>(list_dev),
                        (unsigned)cap, count_dev);
     GSX_HIP(hipGetLastError());
-    const unsigned fb = (unsigned)std::min<int64_t>((ntiles + 255) / 256, (int64_t)c->num_cu * 4);
-    hipLaunchKernelGGL(ksplat_finish_kernel, dim3(std::max(1u, fb)), dim3(256), 0, c->stream, n, bucket_size, centres_dev, gmin, gmax,
+    hipLaunchKernelGGL(ksplat_finish_kernel, dim3(tile_blocks(c, ntiles, 256, 4)), dim3(256), 0, c->stream, n, bucket_size, centres_dev, gmin, gmax,
                        reinterpret_cast<uint2 *>(list_dev), (unsigned)cap, count_dev);
     GSX_HIP(hipGetLastError());
     return 0;
@@ -406,7 +346,7 @@ int gsx_ksplat_pack_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layout *
         GSX_FAIL("gsx_ksplat_pack_dev: rows and payload must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(centres_dev) & 3) GSX_FAIL("gsx_ksplat_pack_dev: centres must be 4-byte aligned");
     SpzLayoutDev L;
-    GSX_CHECK(ks_layout_to_dev(layout, sh_count, &L, "gsx_ksplat_pack_dev"));
+    GSX_CHECK(layout_to_dev(layout, ks_required(sh_count), &L, "gsx_ksplat_pack_dev"));
     GSX_HIP(hipSetDevice(c->device));
     if (n == 0) return 0;
     KsPackArgs P;
@@ -417,9 +357,8 @@ int gsx_ksplat_pack_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layout *
     P.sf = sf_inv;
     P.row_base = row_base;
     const int tr = spz_tile_rows(L.row_bytes);
-    const int64_t ntiles = (n + tr - 1) / tr;
     const size_t lds = spz_in_bytes(tr, L.row_bytes) + (size_t)tr * P.bps + 32;
-    hipLaunchKernelGGL(ksplat_pack_kernel, dim3(ks_blocks(c, ntiles)), dim3(tr), lds, c->stream, static_cast<const uint4 *>(rows_dev), L, n, P,
+    hipLaunchKernelGGL(ksplat_pack_kernel, dim3(tile_blocks(c, n, tr, 8)), dim3(tr), lds, c->stream, static_cast<const uint4 *>(rows_dev), L, n, P,
                        centres_dev, payload_dev, reinterpret_cast<uint2 *>(list_dev), (unsigned)cap, count_dev);
     GSX_HIP(hipGetLastError());
     return 0;
@@ -431,8 +370,7 @@ int gsx_ksplat_math_dev(gsx_ctx *c, const float *x_dev, int64_t n, uint32_t *exp
     if (n < 0) GSX_FAIL("gsx_ksplat_math_dev: n < 0");
     GSX_HIP(hipSetDevice(c->device));
     if (n == 0) return 0;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)c->num_cu * 16);
-    hipLaunchKernelGGL(ksplat_math_kernel, dim3(blocks), dim3(256), 0, c->stream, x_dev, n, exp_out_dev, reinterpret_cast<unsigned short *>(half_out_dev));
+    hipLaunchKernelGGL(ksplat_math_kernel, dim3(tile_blocks(c, n, 256, 16)), dim3(256), 0, c->stream, x_dev, n, exp_out_dev, reinterpret_cast<unsigned short *>(half_out_dev));
     GSX_HIP(hipGetLastError());
     GSX_HIP(hipStreamSynchronize(c->stream));
     return 0;

@@ -19,7 +19,7 @@
 // (0 * inf, inf - inf); where both operands of numpy's float32 add are NaN the reference's rows carry the second one's bits
 // (the golden cases with NaN block sizes and NaN centres pin this).  Traced through `(pos_u - sr) * sf + centre` (pos_u - sr is
 // always finite): a NaN centre gives the centre's bits, quieted; else a NaN sf gives sf's bits, quieted; else 0 * inf and
-// inf - inf give 0xffc00000.  The device's own NaN bits differ, so a NaN result is replaced on a cold path (ksr_x86_nan).
+// inf - inf give 0xffc00000.  The device's own NaN bits differ, so a NaN result is replaced on a cold path (x86_nan).
 //
 // One launch per section.  A tile's output rows are staged in LDS and leave in 16-byte stores; a tile need not start on a
 // 16-byte boundary of the output (sections of any row count follow each other), so the words before the first and after the
@@ -39,19 +39,6 @@ struct KsReadArgs {
     float sr, sf;
 };
 
-// the little-endian u32 at any byte address of global memory (reads the aligned word after it too)
-__device__ __forceinline__ unsigned ksr_ld_u32(const unsigned char *__restrict__ base, int64_t byte)
-{
-    const unsigned *w = reinterpret_cast<const unsigned *>(base + (byte & ~(int64_t)3));
-    return __builtin_amdgcn_alignbyte(w[1], w[0], (unsigned)(byte & 3));
-}
-
-// the little-endian u32 at LDS byte index q (any alignment)
-__device__ __forceinline__ unsigned ksr_lds_u32(const unsigned *lds, int q)
-{
-    return __builtin_amdgcn_alignbyte(lds[(q >> 2) + 1], lds[q >> 2], (unsigned)(q & 3));
-}
-
 // numpy's float16 -> float32: exact, and a NaN keeps its sign, its payload and its quiet bit as they are
 __device__ __forceinline__ unsigned ksr_half(unsigned h)
 {
@@ -61,20 +48,12 @@ __device__ __forceinline__ unsigned ksr_half(unsigned h)
     return __float_as_uint((float)v.f);
 }
 
-// x86's float32 bits of a NaN position (cold: only reached when the result is NaN)
-__device__ __noinline__ unsigned ksr_x86_nan(float sf, float c)
-{
-    if (c != c) return __float_as_uint(c) | 0x00400000u;
-    if (sf != sf) return __float_as_uint(sf) | 0x00400000u;
-    return 0xffc00000u;
-}
-
 // :209-210 `(pos_u - sr) * sf + centre`
 __device__ __forceinline__ unsigned ksr_position(unsigned u16, float sr, float sf, float c)
 {
     const float t2 = __fmul_rn(__fsub_rn((float)u16, sr), sf);
     const float r = __fadd_rn(t2, c);
-    return r == r ? __float_as_uint(r) : ksr_x86_nan(sf, c);
+    return r == r ? __float_as_uint(r) : x86_nan(c, sf);
 }
 
 // the first j in [lo, hi] with prefix[j] > i (hi if none: the host has checked that the lengths cover every row)
@@ -99,12 +78,7 @@ __global__ __launch_bounds__(KSR_TILE) void ksplat_unpack_kernel(const uint4 *__
     prefix += A.prefix_off;
     if (t0 >= A.n) return;   // (uniform; the grid covers [0, n) exactly)
     const int cnt = (int)min((int64_t)KSR_TILE, A.n - t0);
-    // the tile's raw bytes, from the 16-byte boundary at or below its first byte
-    const int64_t b0 = A.rows_off + t0 * A.row_bytes, b1 = b0 + (int64_t)cnt * A.row_bytes;
-    const int64_t q0 = b0 >> 4;
-    const int nq = (int)(((b1 + 15) >> 4) - q0);
-    for (int k = threadIdx.x; k < nq; k += KSR_TILE) kr_lds[k] = body[q0 + k];
-    const int in_base = (int)(b0 & 15);
+    const int in_base = spz_stage_tile(body, A.row_bytes, t0, cnt, kr_lds, A.rows_off);
     if (LV >= 1 && threadIdx.x < 2) {
         const int64_t i = threadIdx.x == 0 ? t0 : t0 + cnt - 1;
         jr[threadIdx.x] = (i < A.full_rows || A.n_partial == 0) ? 0 : ksr_search(prefix, 0, (int)A.n_partial - 1, i);
@@ -124,12 +98,12 @@ __global__ __launch_bounds__(KSR_TILE) void ksplat_unpack_kernel(const uint4 *__
         if (LV == 0) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                o[a] = ksr_lds_u32(in32, q + 4 * a);
-                o[tail + 1 + a] = ksr_lds_u32(in32, q + 12 + 4 * a);
+                o[a] = lds_u32(in32, q + 4 * a);
+                o[tail + 1 + a] = lds_u32(in32, q + 12 + 4 * a);
             }
 #pragma unroll
-            for (int a = 0; a < 4; ++a) o[tail + 4 + a] = ksr_lds_u32(in32, q + 24 + 4 * a);
-            colour = ksr_lds_u32(in32, q + 40);
+            for (int a = 0; a < 4; ++a) o[tail + 4 + a] = lds_u32(in32, q + 24 + 4 * a);
+            colour = lds_u32(in32, q + 40);
             sh_q = q + 44;
         } else {
             const int64_t i = t0 + r;
@@ -138,21 +112,21 @@ __global__ __launch_bounds__(KSR_TILE) void ksplat_unpack_kernel(const uint4 *__
             else b = (int64_t)A.n_full + (A.n_partial ? ksr_search(prefix, jr[0], jr[1], i) : 0);
             b = min(b, (int64_t)A.n_buckets - 1);
             const unsigned char *bytes = reinterpret_cast<const unsigned char *>(body);
-            const unsigned w0 = ksr_lds_u32(in32, q), w1 = ksr_lds_u32(in32, q + 4), w2 = ksr_lds_u32(in32, q + 8);
-            const unsigned w3 = ksr_lds_u32(in32, q + 12), w4 = ksr_lds_u32(in32, q + 16);
+            const unsigned w0 = lds_u32(in32, q), w1 = lds_u32(in32, q + 4), w2 = lds_u32(in32, q + 8);
+            const unsigned w3 = lds_u32(in32, q + 12), w4 = lds_u32(in32, q + 16);
             const unsigned p[3] = {w0 & 0xffffu, w0 >> 16, w1 & 0xffffu};
             const unsigned s[3] = {w1 >> 16, w2 & 0xffffu, w2 >> 16};
             const unsigned t[4] = {w3 & 0xffffu, w3 >> 16, w4 & 0xffffu, w4 >> 16};
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const float c = __uint_as_float(ksr_ld_u32(bytes, A.cen_off + 12 * b + 4 * a));
+                const float c = __uint_as_float(ld_u32(bytes, A.cen_off + 12 * b + 4 * a));
                 o[a] = ksr_position(p[a], A.sr, A.sf, c);
                 o[tail + 1 + a] = ksr_half(s[a]);
             }
 #pragma unroll
             for (int a = 0; a < 4; ++a)
                 o[tail + 4 + a] = __float_as_uint(__fmul_rn(__fdiv_rn(__fsub_rn((float)t[a], 32767.5f), 32767.5f), 1.41421356f));
-            colour = ksr_lds_u32(in32, q + 20);
+            colour = lds_u32(in32, q + 20);
             sh_q = q + 24;
         }
         o[3] = o[4] = o[5] = 0u;                                   // normals: np.zeros
@@ -162,23 +136,15 @@ __global__ __launch_bounds__(KSR_TILE) void ksplat_unpack_kernel(const uint4 *__
         o[tail] = __float_as_uint(tab[256 + (colour >> 24)]);
         for (int k = 0; k < A.sh_count; ++k) {
             unsigned v;
-            if (LV == 0) v = ksr_lds_u32(in32, sh_q + 4 * k);
-            else if (LV == 1) v = ksr_half(ksr_lds_u32(in32, sh_q + 2 * k) & 0xffffu);
-            else v = __float_as_uint(__fmul_rn((float)((int)(ksr_lds_u32(in32, sh_q + k) & 0xffu) - 128), 0.0078125f));
+            if (LV == 0) v = lds_u32(in32, sh_q + 4 * k);
+            else if (LV == 1) v = ksr_half(lds_u32(in32, sh_q + 2 * k) & 0xffffu);
+            else v = __float_as_uint(__fmul_rn((float)((int)(lds_u32(in32, sh_q + k) & 0xffu) - 128), 0.0078125f));
             o[rest + k] = v;
         }
         for (int k = A.sh_count; k < A.n_coeffs; ++k) o[rest + k] = 0u;
     }
     __syncthreads();
-    // words [gw0, gw1) of the output: whole quads from LDS quad (q - (gw0 >> 2)), the ragged ends word by word
-    const int64_t gw1 = gw0 + (int64_t)cnt * A.row_words;
-    const int64_t qa = (gw0 + 3) >> 2, qb = gw1 >> 2, qz = gw0 >> 2;
-    const uint4 *src = reinterpret_cast<const uint4 *>(o32);
-    uint4 *dst = reinterpret_cast<uint4 *>(out);
-    for (int64_t k = qa + threadIdx.x; k < qb; k += KSR_TILE) dst[k] = src[k - qz];
-    const int64_t head_end = min(qa << 2, gw1), tail_begin = max(qb << 2, head_end);
-    if (gw0 + threadIdx.x < head_end) out[gw0 + threadIdx.x] = o32[pad + threadIdx.x];
-    if (tail_begin + threadIdx.x < gw1) out[tail_begin + threadIdx.x] = o32[pad + (int)(tail_begin - gw0) + threadIdx.x];
+    store_words(out, gw0, cnt * A.row_words, o32, pad);
 }
 
 static size_t ksr_out_bytes(int row_words) { return (((size_t)KSR_TILE * row_words + 3 + 3) * 4 + 15) / 16 * 16; }

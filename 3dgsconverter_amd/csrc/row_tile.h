@@ -1,9 +1,13 @@
-// row_tile.h -- the row-tile staging shared by the writers that read a raw splat table in place (csrc/spz.hip, csrc/ksplat.hip).
+// row_tile.h -- what the format kernels share: the writers that read a raw splat table in place (csrc/spz.hip, csrc/ksplat.hip,
+// csrc/splat.hip, csrc/cply.hip) and the readers that decode a file's rows (csrc/cply_read.hip, csrc/ksplat_read.hip).
 //
 // A workgroup owns a tile of consecutive rows: the tile's raw bytes are staged in LDS with 16-byte loads (any row size up to
-// 512 bytes, fields at any byte offset: a field is assembled from two LDS words).  The layout is gsx_spz_layout's: float32
-// fields in gsx_sog_layout's order, -1 = absent.
+// 512 bytes, fields at any byte offset: a field is assembled from two LDS words), and a tile's output leaves LDS as one
+// contiguous span in 16-byte stores.  The layout is gsx_spz_layout's: float32 fields in gsx_sog_layout's order, -1 = absent.
+// The float <-> integer keys live in sog_math.h (sort_key, float_key, sort_unkey).
 #pragma once
+#include <cstddef>
+
 #include "gsx_common.h"
 
 namespace gsx {
@@ -23,28 +27,122 @@ static inline int spz_tile_rows(int row_bytes) { return row_bytes <= 256 ? 128 :
 // LDS bytes of a tile: the staged rows (16-byte aligned window, one spare quad) + the output image (+16 spare bytes)
 __host__ __device__ inline size_t spz_in_bytes(int tr, int row_bytes) { return ((size_t)tr * row_bytes + 15 + 15) / 16 * 16 + 16; }
 
-// the tile's rows [t0, t0 + cnt) -> LDS, from the 16-byte boundary at or below the first byte; -> that boundary's offset.
-// Reads at most 15 bytes past the last row (the caller's allocation has that slack).
-__device__ __forceinline__ int spz_stage_tile(const uint4 *__restrict__ rows, int row_bytes, int64_t t0, int cnt, uint4 *lds)
+// the little-endian u32 / float32 at any byte address of global memory: the two aligned words around it (reads at most 4
+// bytes past the field)
+__device__ __forceinline__ unsigned ld_u32(const unsigned char *__restrict__ base, int64_t byte)
 {
-    const int64_t b0 = t0 * row_bytes, b1 = (t0 + cnt) * row_bytes;
+    const unsigned *w = reinterpret_cast<const unsigned *>(base + (byte & ~(int64_t)3));
+    return __builtin_amdgcn_alignbyte(w[1], w[0], (unsigned)(byte & 3));
+}
+__device__ __forceinline__ float ld_f32(const unsigned char *__restrict__ base, int64_t byte) { return __uint_as_float(ld_u32(base, byte)); }
+
+// the little-endian u32 / float32 / byte at LDS byte index q (any alignment)
+__device__ __forceinline__ unsigned lds_u32(const unsigned *lds, int q)
+{
+    return __builtin_amdgcn_alignbyte(lds[(q >> 2) + 1], lds[q >> 2], (unsigned)(q & 3));
+}
+__device__ __forceinline__ float lds_f32(const unsigned *lds, int q) { return __uint_as_float(lds_u32(lds, q)); }
+__device__ __forceinline__ unsigned lds_u8(const unsigned *lds, int q) { return (lds[q >> 2] >> (8 * (q & 3))) & 0xffu; }
+
+// np.clip(t, 0, 255).astype(np.uint8): NaN stays NaN through the clip and casts to 0
+__device__ __forceinline__ unsigned spz_u8(float t)
+{
+    return t == t ? (unsigned)fminf(fmaxf(t, 0.0f), 255.0f) : 0u;
+}
+
+// x86's float32 bits of a NaN result of two operands: the first NaN operand, quieted; an invalid operation of two numbers gives
+// the negative default NaN (cold: only reached when the result is NaN, where the device's own NaN bits differ)
+__device__ __noinline__ unsigned x86_nan(float first, float second)
+{
+    if (first != first) return __float_as_uint(first) | 0x00400000u;
+    if (second != second) return __float_as_uint(second) | 0x00400000u;
+    return 0xffc00000u;
+}
+
+// hand (idx, kind) to the host: the list keeps the first `cap` entries, *count counts them all
+__device__ __forceinline__ void list_append(uint2 *list, unsigned cap, unsigned *count, unsigned idx, unsigned kind)
+{
+    const unsigned k = atomicAdd(count, 1u);
+    if (k < cap) list[k] = make_uint2(idx, kind);
+}
+
+// rows [t0, t0 + cnt) of `row_bytes` bytes, row 0 at byte `first` of `rows` -> LDS, from the 16-byte boundary at or below the
+// tile's first byte; -> that boundary's offset.  Reads at most 15 bytes past the last row (the caller's allocation has that slack).
+__device__ __forceinline__ int spz_stage_tile(const uint4 *__restrict__ rows, int row_bytes, int64_t t0, int cnt, uint4 *lds, int64_t first = 0)
+{
+    const int64_t b0 = first + t0 * row_bytes, b1 = b0 + (int64_t)cnt * row_bytes;
     const int64_t q0 = b0 >> 4, q1 = (b1 + 15) >> 4;
     const int nq = (int)(q1 - q0);
     for (int k = threadIdx.x; k < nq; k += blockDim.x) lds[k] = rows[q0 + k];
     return (int)(b0 & 15);
 }
 
-// the float32 at LDS byte index q (any alignment)
-__device__ __forceinline__ float spz_lds_f32(const unsigned *lds, int q)
+// LDS image `img` -> bytes [g0, g1) of `out` (16-byte aligned), by the whole workgroup: bytes up to a 16-byte boundary, 16-byte
+// stores assembled from the image's words (the image may start at any byte; up to 19 bytes behind it are read, never used),
+// the tail bytes
+__device__ __forceinline__ void store_bytes(unsigned char *__restrict__ out, int64_t g0, int64_t g1, const unsigned char *img)
 {
-    const unsigned lo = lds[q >> 2], hi = lds[(q >> 2) + 1];
-    return __uint_as_float(__builtin_amdgcn_alignbyte(hi, lo, (unsigned)(q & 3)));
+    const int64_t h = min(g1, (g0 + 15) & ~(int64_t)15);
+    const int64_t tl = max(h, g1 & ~(int64_t)15);
+    const int nh = (int)(h - g0), nt = (int)(g1 - tl), nb = (int)((tl - h) >> 4);
+    const int t = threadIdx.x;
+    if (t < nh) out[g0 + t] = img[t];
+    if (t < nt) out[tl + t] = img[(int)(tl - g0) + t];
+    for (int k = t; k < nb; k += blockDim.x) {
+        const int o = nh + 16 * k;                               // byte of the image that lands on the aligned address
+        const unsigned *w32 = reinterpret_cast<const unsigned *>(img + (o & ~3));
+        const unsigned sh = (unsigned)(o & 3);
+        const unsigned a0 = w32[0], a1 = w32[1], a2 = w32[2], a3 = w32[3], a4 = w32[4];
+        uint4 v;
+        v.x = __builtin_amdgcn_alignbyte(a1, a0, sh);
+        v.y = __builtin_amdgcn_alignbyte(a2, a1, sh);
+        v.z = __builtin_amdgcn_alignbyte(a3, a2, sh);
+        v.w = __builtin_amdgcn_alignbyte(a4, a3, sh);
+        *reinterpret_cast<uint4 *>(out + h + 16 * k) = v;
+    }
 }
 
-// np.clip(t, 0, 255).astype(np.uint8): NaN stays NaN through the clip and casts to 0
-__device__ __forceinline__ unsigned spz_u8(float t)
+// `words` words at o32 + pad (o32 16-byte aligned in LDS, pad = gw0 & 3) -> words [gw0, gw0 + words) of `out` (16-byte aligned),
+// by the whole workgroup: whole quads from LDS quad (q - (gw0 >> 2)), the ragged ends word by word
+__device__ __forceinline__ void store_words(unsigned *__restrict__ out, int64_t gw0, int words, const unsigned *o32, int pad)
 {
-    return t == t ? (unsigned)fminf(fmaxf(t, 0.0f), 255.0f) : 0u;
+    const int64_t gw1 = gw0 + words;
+    const int64_t qa = (gw0 + 3) >> 2, qb = gw1 >> 2, qz = gw0 >> 2;
+    const uint4 *src = reinterpret_cast<const uint4 *>(o32);
+    uint4 *dst = reinterpret_cast<uint4 *>(out);
+    for (int64_t k = qa + threadIdx.x; k < qb; k += blockDim.x) dst[k] = src[k - qz];
+    const int64_t head_end = min(qa << 2, gw1), tail_begin = max(qb << 2, head_end);
+    if (gw0 + threadIdx.x < head_end) out[gw0 + threadIdx.x] = o32[pad + threadIdx.x];
+    if (tail_begin + threadIdx.x < gw1) out[tail_begin + threadIdx.x] = o32[pad + (int)(tail_begin - gw0) + threadIdx.x];
+}
+
+// gsx_spz_layout -> SpzLayoutDev: the row size in range, every present field inside a row, bit f of `required` = field f must be
+// present.  The format's own rules follow at the caller.
+static int layout_to_dev(const gsx_spz_layout *l, uint64_t required, SpzLayoutDev *out, const char *who)
+{
+    if (!l) GSX_FAIL("%s: null layout", who);
+    if (l->row_bytes < 1 || l->row_bytes > SPZ_MAX_ROW_BYTES)
+        GSX_FAIL("%s: rows of %lld bytes (1 ... %d are supported)", who, (long long)l->row_bytes, SPZ_MAX_ROW_BYTES);
+    out->row_bytes = (int)l->row_bytes;
+    for (int f = 0; f < SPZ_FIELDS; ++f) {
+        const int o = l->offset[f];
+        if (o < 0) {
+            if ((required >> f) & 1) GSX_FAIL("%s: field %d is required", who, f);
+        } else if (o + 4 > l->row_bytes) {
+            GSX_FAIL("%s: field %d at byte offset %d of a %lld-byte row", who, f, o, (long long)l->row_bytes);
+        }
+        out->off[f] = o < 0 ? -1 : o;
+    }
+    return 0;
+}
+
+// fields [0, f)
+constexpr uint64_t fields_below(int f) { return (1ull << f) - 1; }
+
+// grid size of a grid-stride kernel: one block per `per_block` items, at most `per_cu` blocks per compute unit, at least one
+static unsigned tile_blocks(gsx_ctx *c, int64_t items, int per_block, int per_cu)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)c->num_cu * per_cu));
 }
 
 }  // namespace gsx

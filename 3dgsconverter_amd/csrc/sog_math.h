@@ -9,15 +9,20 @@
 
 namespace gsx {
 
-// float32 -> uint32 whose unsigned order is numpy's sort order: -0.0 == +0.0, every NaN last
+// float32 -> uint32 whose unsigned order is the float order: -0.0 below +0.0, a NaN by its bits (atomicMin / atomicMax on keys)
+__device__ __forceinline__ unsigned float_key(float v)
+{
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// ... whose unsigned order is numpy's sort order: -0.0 == +0.0, every NaN last
 __device__ __forceinline__ unsigned sort_key(float v)
 {
     if (v != v) return 0xffffffffu;
     if (v == 0.0f) v = 0.0f;  // -0.0 -> +0.0
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return float_key(v);
 }
-// inverse (a NaN key comes back as a NaN, -0.0 as +0.0)
+// inverse of both (a sort_key NaN comes back as a NaN, its -0.0 as +0.0)
 __device__ __host__ __forceinline__ float sort_unkey(unsigned k)
 {
     const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;

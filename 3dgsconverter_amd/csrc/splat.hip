@@ -21,26 +21,11 @@
 #include "gsx_common.h"
 #include "np_exp.h"
 #include "row_tile.h"
+#include "sog_math.h"
 
 namespace gsx {
 
 constexpr int SPLAT_REC = 32;   // bytes per record: 3 f32 position | 3 f32 scale | 4 u8 colour | 4 u8 rotation
-
-// sort key of v = -metric: ascending unsigned order is numpy's ascending float order, -0 == +0, NaN last and all equal
-__device__ __forceinline__ unsigned splat_key(float v)
-{
-    if (v != v) return 0xffffffffu;
-    unsigned u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
-// the float32 at any byte address of global memory: the two aligned words around it
-__device__ __forceinline__ float splat_ld_f32(const unsigned char *__restrict__ base, int64_t byte)
-{
-    const unsigned *w = reinterpret_cast<const unsigned *>(base + (byte & ~(int64_t)3));
-    return __uint_as_float(__builtin_amdgcn_alignbyte(w[1], w[0], (unsigned)(byte & 3)));
-}
 
 struct SplatRgb {
     int off[3];   // byte offsets of the u1 fields red, green, blue; off[0] < 0: colour from f_dc_0..2
@@ -52,7 +37,7 @@ __device__ __forceinline__ unsigned splat_metric_key(Fld fld)
 {
     const float ssum = __fadd_rn(__fadd_rn(fld(SPZ_F_SCALE), fld(SPZ_F_SCALE + 1)), fld(SPZ_F_SCALE + 2));
     const float opa = __fdiv_rn(1.0f, __fadd_rn(1.0f, np_expf(-fld(SPZ_F_OPACITY))));
-    return splat_key(-__fmul_rn(np_expf(ssum), opa));
+    return sort_key(-__fmul_rn(np_expf(ssum), opa));
 }
 
 // :104-161 -> the record's eight words.  byte(k): the k-th colour byte (red, green, blue) in the fallback of :140-143
@@ -120,8 +105,8 @@ __global__ void splat_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L
         const int r = threadIdx.x;
         if (r < cnt) {
             const int q = base + r * rb;
-            auto fld = [&](int f) { return spz_lds_f32(in32, q + off[f]); };
-            auto byte = [&](int k) { return (in32[(q + C.off[k]) >> 2] >> (8 * ((q + C.off[k]) & 3))) & 0xffu; };
+            auto fld = [&](int f) { return lds_f32(in32, q + off[f]); };
+            auto byte = [&](int k) { return lds_u8(in32, q + C.off[k]); };
             const int64_t row = t0 + r;
             keys[row] = splat_metric_key(fld);
             unsigned w[8];
@@ -141,7 +126,7 @@ __global__ __launch_bounds__(256) void splat_direct_kernel(const unsigned char *
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = order ? (int64_t)order[i] : i;
         const int64_t rowb = row * L.row_bytes;
-        auto fld = [&](int f) { return splat_ld_f32(rows, rowb + L.off[f]); };
+        auto fld = [&](int f) { return ld_f32(rows, rowb + L.off[f]); };
         auto byte = [&](int k) { return (unsigned)rows[rowb + C.off[k]]; };
         if (keys) keys[i] = splat_metric_key(fld);
         if (recs) {
@@ -156,7 +141,7 @@ __global__ __launch_bounds__(256) void splat_direct_kernel(const unsigned char *
 __global__ __launch_bounds__(256) void splat_keys_kernel(const float *__restrict__ metric, int64_t n, unsigned *__restrict__ keys)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        keys[i] = splat_key(-metric[i]);
+        keys[i] = sort_key(-metric[i]);
 }
 
 // out[i] = recs[order[i]]: two lanes per record, one 16-byte load and one 16-byte store each; the stores are contiguous
@@ -168,34 +153,17 @@ __global__ __launch_bounds__(256) void splat_permute_kernel(const uint4 *__restr
         out[j] = recs[2 * (int64_t)order[j >> 1] + (j & 1)];
 }
 
-static int splat_layout_to_dev(const gsx_spz_layout *l, const int rgb[3], SpzLayoutDev *out, SplatRgb *c, const char *who)
+// the shared checks (x .. scale_2 and opacity required, f_dc_0..2 too without colour bytes), then the colour bytes' own
+static int splat_layout(const gsx_spz_layout *l, const int rgb[3], SpzLayoutDev *out, SplatRgb *c, const char *who)
 {
-    if (!l) GSX_FAIL("%s: null layout", who);
-    if (l->row_bytes < 1 || l->row_bytes > SPZ_MAX_ROW_BYTES)
-        GSX_FAIL("%s: rows of %lld bytes (1 ... %d are supported)", who, (long long)l->row_bytes, SPZ_MAX_ROW_BYTES);
-    out->row_bytes = (int)l->row_bytes;
     const bool from_dc = rgb[0] < 0;
+    GSX_CHECK(layout_to_dev(l, fields_below(from_dc ? SPZ_F_REST : SPZ_F_DC) | 1ull << SPZ_F_OPACITY, out, who));
     if (!from_dc && (rgb[1] < 0 || rgb[2] < 0)) GSX_FAIL("%s: red, green and blue offsets go together", who);
-    for (int f = 0; f < SPZ_FIELDS; ++f) {
-        const int o = l->offset[f];
-        const bool required = f < SPZ_F_DC || f == SPZ_F_OPACITY || (from_dc && f < SPZ_F_OPACITY);
-        if (o < 0) {
-            if (required) GSX_FAIL("%s: field %d is required", who, f);
-        } else if (o + 4 > l->row_bytes) {
-            GSX_FAIL("%s: field %d at byte offset %d of a %lld-byte row", who, f, o, (long long)l->row_bytes);
-        }
-        out->off[f] = o < 0 ? -1 : o;
-    }
     for (int k = 0; k < 3; ++k) {
         if (!from_dc && rgb[k] >= l->row_bytes) GSX_FAIL("%s: colour byte %d at offset %d of a %lld-byte row", who, k, rgb[k], (long long)l->row_bytes);
         c->off[k] = from_dc ? -1 : rgb[k];
     }
     return 0;
-}
-
-static unsigned splat_blocks(gsx_ctx *c, int64_t items, int per_block, int per_cu)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)c->num_cu * per_cu));
 }
 
 }  // namespace gsx
@@ -215,15 +183,15 @@ int gsx_splat_pack_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layout *l
     const int rgb[3] = {red_off, green_off, blue_off};
     SpzLayoutDev L;
     SplatRgb C;
-    GSX_CHECK(splat_layout_to_dev(layout, rgb, &L, &C, "gsx_splat_pack_dev"));
+    GSX_CHECK(splat_layout(layout, rgb, &L, &C, "gsx_splat_pack_dev"));
     GSX_HIP(hipSetDevice(c->device));
     if (n == 0) return 0;
     if (order_dev || !recs_dev || !keys_dev) {
-        hipLaunchKernelGGL(splat_direct_kernel, dim3(splat_blocks(c, n, 256, 16)), dim3(256), 0, c->stream, static_cast<const unsigned char *>(rows_dev),
+        hipLaunchKernelGGL(splat_direct_kernel, dim3(tile_blocks(c, n, 256, 16)), dim3(256), 0, c->stream, static_cast<const unsigned char *>(rows_dev),
                            L, C, n, order_dev, keys_dev, recs_dev);
     } else {
         const int tr = spz_tile_rows(L.row_bytes);
-        hipLaunchKernelGGL(splat_pack_kernel, dim3(splat_blocks(c, n, tr, 8)), dim3(tr), spz_in_bytes(tr, L.row_bytes), c->stream,
+        hipLaunchKernelGGL(splat_pack_kernel, dim3(tile_blocks(c, n, tr, 8)), dim3(tr), spz_in_bytes(tr, L.row_bytes), c->stream,
                            static_cast<const uint4 *>(rows_dev), L, C, n, keys_dev, recs_dev);
     }
     GSX_HIP(hipGetLastError());
@@ -236,7 +204,7 @@ int gsx_splat_keys_dev(gsx_ctx *c, const float *metric_dev, int64_t n, uint32_t 
     if (n < 0) GSX_FAIL("gsx_splat_keys_dev: n < 0");
     GSX_HIP(hipSetDevice(c->device));
     if (n == 0) return 0;
-    hipLaunchKernelGGL(splat_keys_kernel, dim3(splat_blocks(c, n, 256, 16)), dim3(256), 0, c->stream, metric_dev, n, keys_dev);
+    hipLaunchKernelGGL(splat_keys_kernel, dim3(tile_blocks(c, n, 256, 16)), dim3(256), 0, c->stream, metric_dev, n, keys_dev);
     GSX_HIP(hipGetLastError());
     return 0;
 }
@@ -268,7 +236,7 @@ int gsx_splat_permute_dev(gsx_ctx *c, const uint8_t *recs_dev, const uint32_t *o
         GSX_FAIL("gsx_splat_permute_dev: records must be 16-byte aligned");
     GSX_HIP(hipSetDevice(c->device));
     if (n == 0) return 0;
-    hipLaunchKernelGGL(splat_permute_kernel, dim3(splat_blocks(c, 2 * n, 256, 16)), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(recs_dev),
+    hipLaunchKernelGGL(splat_permute_kernel, dim3(tile_blocks(c, 2 * n, 256, 16)), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(recs_dev),
                        order_dev, n, reinterpret_cast<uint4 *>(out_dev));
     GSX_HIP(hipGetLastError());
     return 0;

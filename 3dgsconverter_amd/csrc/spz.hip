@@ -111,7 +111,7 @@ __global__ void spz_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L, 
         const int r = threadIdx.x;
         if (r < cnt) {
             const int q = base + r * rb;
-            auto fld = [&](int f) { return spz_lds_f32(in32, q + off[f]); };
+            auto fld = [&](int f) { return lds_f32(in32, q + off[f]); };
             const int64_t row = t0 + r;
             // positions (:111-116): round(v * 4096) -> int32 -> the low 24 bits, little-endian
             unsigned char *p = img + 9 * r;
@@ -131,8 +131,7 @@ __global__ void spz_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L, 
                 alpha = sog_alpha_texel(oc, &ok);
                 if (!ok) {
                     alpha = 0u;
-                    const unsigned k = atomicAdd(count, 1u);
-                    if (k < cap) list[k] = make_uint2((unsigned)row, 0u);
+                    list_append(list, cap, count, (unsigned)row, 0u);
                 }
             }
             img[tr * 9 + r] = (unsigned char)alpha;
@@ -152,10 +151,7 @@ __global__ void spz_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L, 
             bool host;
             const unsigned word = spz_rot_word(fld(SPZ_F_ROT), fld(SPZ_F_ROT + 1), fld(SPZ_F_ROT + 2), fld(SPZ_F_ROT + 3), &host);
             *reinterpret_cast<unsigned *>(img + tr * 16 + 4 * r) = word;
-            if (host) {
-                const unsigned k = atomicAdd(count, 1u);
-                if (k < cap) list[k] = make_uint2((unsigned)row, 1u);
-            }
+            if (host) list_append(list, cap, count, (unsigned)row, 1u);
             // SH (:148-170): coefficient i of channel c is f_rest_{i + 15 c}; the first 9 interleaved values 5 bits, the rest 4
             unsigned char *ph = img + tr * 20 + 3 * sh_dim * r;
             for (int i = 0; i < sh_dim; ++i) {
@@ -172,26 +168,8 @@ __global__ void spz_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L, 
         for (int s = 0; s < 6; ++s) {
             const int w = width[s];
             if (w == 0) continue;
-            const int64_t g0 = (int64_t)start[s] * n + t0 * w, g1 = g0 + (int64_t)cnt * w;
-            const unsigned char *src = img + tr * start[s];
-            const int64_t h = min(g1, (g0 + 15) & ~(int64_t)15);
-            const int64_t tl = max(h, g1 & ~(int64_t)15);
-            const int nh = (int)(h - g0), nt = (int)(g1 - tl), nb = (int)((tl - h) >> 4);
-            const int t = threadIdx.x;
-            if (t < nh) out[g0 + t] = src[t];
-            if (t < nt) out[tl + t] = src[(int)(tl - g0) + t];
-            for (int k = t; k < nb; k += tr) {
-                const int o = nh + 16 * k;                        // byte of the slice that lands on the aligned address
-                const unsigned *w32 = reinterpret_cast<const unsigned *>(src + (o & ~3));
-                const unsigned sh = (unsigned)(o & 3);
-                const unsigned a0 = w32[0], a1 = w32[1], a2 = w32[2], a3 = w32[3], a4 = w32[4];
-                uint4 v;
-                v.x = __builtin_amdgcn_alignbyte(a1, a0, sh);
-                v.y = __builtin_amdgcn_alignbyte(a2, a1, sh);
-                v.z = __builtin_amdgcn_alignbyte(a3, a2, sh);
-                v.w = __builtin_amdgcn_alignbyte(a4, a3, sh);
-                *reinterpret_cast<uint4 *>(out + h + 16 * k) = v;
-            }
+            const int64_t g0 = (int64_t)start[s] * n + t0 * w;
+            store_bytes(out, g0, g0 + (int64_t)cnt * w, img + tr * start[s]);
         }
     }
 }
@@ -218,7 +196,7 @@ __global__ void spz_rest_scan_kernel(const uint4 *__restrict__ rows, SpzLayoutDe
         if ((int)threadIdx.x < cnt) {
             const int q = base + (int)threadIdx.x * rb;
             for (int i = 0; i < 45; ++i)
-                if (((want >> i) & 1ull) && !((bits >> i) & 1ull) && spz_lds_f32(in32, q + off[SPZ_F_REST + i]) != 0.0f) bits |= 1ull << i;
+                if (((want >> i) & 1ull) && !((bits >> i) & 1ull) && lds_f32(in32, q + off[SPZ_F_REST + i]) != 0.0f) bits |= 1ull << i;
         }
     }
     __syncthreads();
@@ -227,22 +205,10 @@ __global__ void spz_rest_scan_kernel(const uint4 *__restrict__ rows, SpzLayoutDe
     if (threadIdx.x == 0 && acc) atomicOr(mask, acc);
 }
 
-static int spz_layout_to_dev(const gsx_spz_layout *l, int sh_dim, SpzLayoutDev *out, const char *who)
+// the shared checks, then SPZ's own: x .. scale_2 required, f_dc_0..2 together, the SH degree's f_rest fields present
+static int spz_layout(const gsx_spz_layout *l, int sh_dim, SpzLayoutDev *out, const char *who)
 {
-    if (!l) GSX_FAIL("%s: null layout", who);
-    if (l->row_bytes < 1 || l->row_bytes > SPZ_MAX_ROW_BYTES)
-        GSX_FAIL("%s: rows of %lld bytes (1 ... %d are supported)", who, (long long)l->row_bytes, SPZ_MAX_ROW_BYTES);
-    out->row_bytes = (int)l->row_bytes;
-    for (int f = 0; f < SPZ_FIELDS; ++f) {
-        const int o = l->offset[f];
-        const bool required = f < SPZ_F_DC;   // x y z, rot_0..3, scale_0..2
-        if (o < 0) {
-            if (required) GSX_FAIL("%s: field %d is required", who, f);
-        } else if (o + 4 > l->row_bytes) {
-            GSX_FAIL("%s: field %d at byte offset %d of a %lld-byte row", who, f, o, (long long)l->row_bytes);
-        }
-        out->off[f] = o < 0 ? -1 : o;
-    }
+    GSX_CHECK(layout_to_dev(l, fields_below(SPZ_F_DC), out, who));
     if ((out->off[SPZ_F_DC] >= 0) && (out->off[SPZ_F_DC + 1] < 0 || out->off[SPZ_F_DC + 2] < 0)) GSX_FAIL("%s: f_dc_0 without f_dc_1 / f_dc_2", who);
     for (int i = 0; i < sh_dim; ++i)
         for (int c = 0; c < 3; ++c)
@@ -263,7 +229,7 @@ int gsx_spz_rest_nonzero_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_lay
     if (fields >> 45) GSX_FAIL("gsx_spz_rest_nonzero_dev: fields beyond f_rest_44");
     if (reinterpret_cast<uintptr_t>(rows_dev) & 15) GSX_FAIL("gsx_spz_rest_nonzero_dev: rows must be 16-byte aligned");
     SpzLayoutDev L;
-    GSX_CHECK(spz_layout_to_dev(layout, 0, &L, "gsx_spz_rest_nonzero_dev"));
+    GSX_CHECK(spz_layout(layout, 0, &L, "gsx_spz_rest_nonzero_dev"));
     for (int i = 0; i < 45; ++i)
         if (((fields >> i) & 1) && L.off[SPZ_F_REST + i] < 0) GSX_FAIL("gsx_spz_rest_nonzero_dev: f_rest_%d is absent", i);
     GSX_HIP(hipSetDevice(c->device));
@@ -273,9 +239,7 @@ int gsx_spz_rest_nonzero_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_lay
     unsigned long long *d_mask = c->nzmask.as<unsigned long long>();
     GSX_HIP(hipMemsetAsync(d_mask, 0, 8, c->stream));
     const int tr = spz_tile_rows(L.row_bytes);
-    const int64_t ntiles = (n + tr - 1) / tr;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)c->num_cu * 8));
-    hipLaunchKernelGGL(spz_rest_scan_kernel, dim3(blocks), dim3(tr), spz_in_bytes(tr, L.row_bytes), c->stream,
+    hipLaunchKernelGGL(spz_rest_scan_kernel, dim3(tile_blocks(c, n, tr, 8)), dim3(tr), spz_in_bytes(tr, L.row_bytes), c->stream,
                        static_cast<const uint4 *>(rows_dev), L, n, (unsigned long long)fields, d_mask);
     GSX_HIP(hipGetLastError());
     GSX_HIP(hipMemcpyAsync(mask_out, d_mask, 8, hipMemcpyDeviceToHost, c->stream));
@@ -294,15 +258,13 @@ int gsx_spz_pack_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layout *lay
         GSX_FAIL("gsx_spz_pack_dev: rows and body must be 16-byte aligned");
     const int sh_dim = spz_sh_dim(sh_degree);
     SpzLayoutDev L;
-    GSX_CHECK(spz_layout_to_dev(layout, sh_dim, &L, "gsx_spz_pack_dev"));
+    GSX_CHECK(spz_layout(layout, sh_dim, &L, "gsx_spz_pack_dev"));
     GSX_HIP(hipSetDevice(c->device));
     GSX_HIP(hipMemsetAsync(count_dev, 0, 4, c->stream));
     if (n == 0) return 0;
     const int tr = spz_tile_rows(L.row_bytes);
-    const int64_t ntiles = (n + tr - 1) / tr;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)c->num_cu * 8));
     const size_t lds = spz_in_bytes(tr, L.row_bytes) + (size_t)tr * spz_row_out_bytes(sh_dim) + 32;
-    hipLaunchKernelGGL(spz_pack_kernel, dim3(blocks), dim3(tr), lds, c->stream, static_cast<const uint4 *>(rows_dev), L, n, sh_dim,
+    hipLaunchKernelGGL(spz_pack_kernel, dim3(tile_blocks(c, n, tr, 8)), dim3(tr), lds, c->stream, static_cast<const uint4 *>(rows_dev), L, n, sh_dim,
                        body_dev, reinterpret_cast<uint2 *>(list_dev), (unsigned)cap, count_dev);
     GSX_HIP(hipGetLastError());
     return 0;

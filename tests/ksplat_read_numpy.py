@@ -250,7 +250,7 @@ def half_bits(h):
 
 
 def position_bits(u16, sr, sf, centre):
-    """`(f32(u16) - sr) * sf + centre` with the NaN bits spelled out as ksr_x86_nan does (sr, sf: np.float32)"""
+    """`(f32(u16) - sr) * sf + centre` with the NaN bits spelled out as x86_nan does (sr, sf: np.float32)"""
     with np.errstate(all="ignore"):
         t2 = (u16.astype(np.float32) - sr) * sf
         r = t2 + centre

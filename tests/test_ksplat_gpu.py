@@ -13,6 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ksplat_numpy  # noqa: E402
+import layout_refusals as refusals  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "ksplat_ref.npz")
@@ -191,3 +192,24 @@ def test_failed_probe_takes_exp_from_numpy_or_raises(gsx, writer, lib, monkeypat
     with pytest.raises(lib.GsxError, match="exp"):
         writer.encode(t, 0)
     monkeypatch.setattr(lib, "_np_exp_checked", None)
+
+
+def _ksplat_refusals():
+    R = refusals
+    centres, pack = "gsx_ksplat_centres_dev", "gsx_ksplat_pack_dev"
+    cases = []
+    for entry, args in ((centres, ()), (pack, (0,))):          # x .. opacity are required, no f_rest
+        cases += [(entry,) + c for c in R.common_cases(entry, args, R.OPACITY)]
+        cases += [(entry, "no_f_rest", R.absent(*range(R.F_REST, R.FIELDS)), args, None)]
+    for sh_count in (9, 24):                                   # ... and f_rest_0 .. f_rest_{sh_count-1}
+        cases += [(pack, "sh%d_without_f_rest_0" % sh_count, R.absent(R.F_REST), (sh_count,), pack + ": field %d is required" % R.F_REST),
+                  (pack, "sh%d_without_its_last" % sh_count, R.absent(R.F_REST + sh_count - 1), (sh_count,),
+                   pack + ": field %d is required" % (R.F_REST + sh_count - 1)),
+                  (pack, "sh%d_without_the_next" % sh_count, R.absent(*range(R.F_REST + sh_count, R.FIELDS)), (sh_count,), None)]
+    return cases
+
+
+@pytest.mark.parametrize("case", _ksplat_refusals(), ids=lambda c: c[0] + "-" + c[1])
+def test_layout_refusals(gsx, lib, case):
+    """the entry points' layout checks, message for message (all return before any launch)"""
+    refusals.check(lib, case[0], *case[2:])

@@ -13,6 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import splat_numpy  # noqa: E402
+import layout_refusals as refusals  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "splat_ref.npz")
@@ -174,3 +175,29 @@ def test_failed_probe_takes_exp_from_numpy_or_raises(gsx, writer, lib, monkeypat
     with pytest.raises(lib.GsxError, match="exp"):
         writer.encode(t)
     monkeypatch.setattr(lib, "_np_exp_checked", None)
+
+
+def _splat_refusals():
+    R = refusals
+    pack = "gsx_splat_pack_dev"
+    dc, rgb = (-1, -1, -1), (236, 237, 238)                    # colour from f_dc_0..2, or from three bytes behind the fields
+    cases = [(pack,) + c for c in R.common_cases(pack, dc, R.OPACITY)]
+    cases += [(pack, "f_dc_0_absent", R.absent(R.F_DC), dc, pack + ": field 10 is required"),
+              (pack, "f_dc_2_absent", R.absent(R.F_DC + 2), dc, pack + ": field 12 is required"),
+              (pack, "no_f_rest", R.absent(*range(R.F_REST, R.FIELDS)), dc, None),
+              (pack, "rgb_no_f_dc_no_f_rest", dict(R.absent(*range(R.F_DC, R.OPACITY), *range(R.F_REST, R.FIELDS)), row_bytes=239), rgb, None),
+              (pack, "rgb_scale_2_absent", dict(R.absent(R.SCALE_2), row_bytes=239), rgb, pack + ": field 9 is required"),
+              (pack, "rgb_opacity_absent", dict(R.absent(R.OPACITY), row_bytes=239), rgb, pack + ": field 13 is required"),
+              (pack, "rgb_field_over_the_end", dict(f10=236, row_bytes=239), rgb, pack + ": field 10 at byte offset 236 of a 239-byte row"),
+              (pack, "red_without_green", dict(row_bytes=239), (236, -1, 238), pack + ": red, green and blue offsets go together"),
+              (pack, "red_without_blue", dict(row_bytes=239), (236, 237, -1), pack + ": red, green and blue offsets go together"),
+              (pack, "green_without_red", dict(row_bytes=239), (-1, 237, 238), None),
+              (pack, "blue_at_row_bytes", dict(row_bytes=238), rgb, pack + ": colour byte 2 at offset 238 of a 238-byte row"),
+              (pack, "red_at_row_bytes", dict(row_bytes=239), (239, 237, 238), pack + ": colour byte 0 at offset 239 of a 239-byte row")]
+    return cases
+
+
+@pytest.mark.parametrize("case", _splat_refusals(), ids=lambda c: c[0] + "-" + c[1])
+def test_layout_refusals(gsx, lib, case):
+    """the entry point's layout checks, message for message (all return before any launch)"""
+    refusals.check(lib, case[0], *case[2:])

@@ -13,6 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import spz_numpy  # noqa: E402
+import layout_refusals as refusals  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "spz_ref.npz")
@@ -29,6 +30,11 @@ def gold():
 @pytest.fixture(scope="module")
 def writer():
     return importlib.import_module("3dgsconverter_amd.formats.spz_writer")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return importlib.import_module("3dgsconverter_amd._lib")
 
 
 def _table(g, spec, name):
@@ -143,3 +149,27 @@ def test_two_threads_write_different_tables_at_once(gsx, writer, tmp_path):
     for x in th:
         x.join()
     assert not errors, errors
+
+
+def _spz_refusals():
+    R = refusals
+    rest, pack = "gsx_spz_rest_nonzero_dev", "gsx_spz_pack_dev"
+    cases = []
+    for entry, args in ((rest, (0,)), (pack, (0,))):          # x .. scale_2 are required, nothing behind them
+        cases += [(entry,) + c for c in R.common_cases(entry, args, R.SCALE_2)]
+        cases += [(entry, "no_colour_no_opacity_no_sh", R.absent(*range(R.F_DC, R.FIELDS)), args, None),
+                  (entry, "f_dc_0_without_f_dc_1", R.absent(R.F_DC + 1), args, entry + ": f_dc_0 without f_dc_1 / f_dc_2"),
+                  (entry, "f_dc_0_without_f_dc_2", R.absent(R.F_DC + 2), args, entry + ": f_dc_0 without f_dc_1 / f_dc_2"),
+                  (entry, "f_dc_1_without_f_dc_0", R.absent(R.F_DC), args, None)]
+    cases += [(pack, "degree1_without_f_rest_16", R.absent(R.F_REST + 16), (1,), pack + ": f_rest_16 is absent"),
+              (pack, "degree1_without_f_rest_3", R.absent(R.F_REST + 3), (1,), None),
+              (pack, "degree3_without_f_rest_44", R.absent(R.F_REST + 44), (3,), pack + ": f_rest_44 is absent"),
+              (rest, "scan_of_absent_f_rest_5", R.absent(R.F_REST + 5), (1 << 5,), rest + ": f_rest_5 is absent"),
+              (rest, "scan_beside_absent_f_rest_5", R.absent(R.F_REST + 5), (1 << 4,), None)]
+    return cases
+
+
+@pytest.mark.parametrize("case", _spz_refusals(), ids=lambda c: c[0] + "-" + c[1])
+def test_layout_refusals(gsx, lib, case):
+    """the entry points' layout checks, message for message (all return before any launch)"""
+    refusals.check(lib, case[0], *case[2:])

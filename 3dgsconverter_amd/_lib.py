@@ -237,6 +237,7 @@ SIGNATURES = {
     "gsx_splat_permute_dev": (_I, [_P, _P, _P, _I64, _P]),
     "gsx_cply_unpack_dev": (_I, [_P, _P, _I64, _P, _I64, _P, C.POINTER(CplyReadLayout), _P, _P]),
     "gsx_ksplat_unpack_dev": (_I, [_P, _P, _I64, _I, C.POINTER(KsplatReadSection), _I, _P, _I64, _P, _I, _P, _I64]),
+    "gsx_spz_unpack_dev": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _I64]),
 }
 
 _lib = None
@@ -1725,6 +1726,89 @@ def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int
         d_out = s.buf("out", n * rb)
         check(lib.gsx_ksplat_unpack_dev(ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
                                         d_tab.ptr, int(n_coeffs), d_out.ptr, n), "gsx_ksplat_unpack_dev")
+        s.mark("kernel")
+        join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.mark("download")
+        return out
+
+
+_spz_read_tables = None
+SPZ_READ_TABLES = ("opacity", "f_dc", "rgb", "scale", "sh", "rot_legacy", "rot_v3")   # GSX_SPZ_TAB_* order (include/gsx_hip.h)
+SPZ_READ_POS_BYTES = {1: 6, 2: 9, 3: 9}   # spz.py:184, :190
+SPZ_READ_ROT_BYTES = {1: 3, 2: 3, 3: 4}   # :232, :228
+
+
+def spz_read_tables() -> dict:
+    """The SPZ reader's tables, numpy's own results for the reference's statements on every input (formats/spz.py), each with
+    the reference's expression and operand dtypes -- so the device takes no log and divides only in the positions:
+    "opacity" f4[256] :345-348 | "f_dc" f4[256] :207 | "rgb" u1[256] :214, the byte derived from that f_dc | "scale" f4[256]
+    :222 (float64 there, rounded once on assignment) | "sh" f4[256] :243 | "rot_legacy" f4[256] :256 | "rot_v3" f4[1024]
+    :274-277 (float64 there -- uint32 times a Python float -- holding a float32 value with its sign)"""
+    global _spz_read_tables
+    if _spz_read_tables is None:
+        with np.errstate(all="ignore"):
+            b = np.arange(256, dtype=np.uint8)
+            v = np.clip(b.astype(np.float32) / 255.0, 1e-7, 1.0 - 1e-7)
+            opa = np.log(v / (1.0 - v))
+            f_dc = (b.astype(np.float32) / 255.0 - 0.5) / 0.15
+            rgb = np.clip((0.5 + 0.28209479177387814 * f_dc) * 255.0, 0, 255).astype(np.uint8)
+            scale = (b / 16.0 - 10.0).astype(np.float32)
+            sh = (b.astype(np.float32) - 128.0) / 128.0
+            rot_legacy = b.astype(np.float32) / 127.5 - 1.0
+            c = np.arange(1024, dtype=np.uint32)
+            mag, neg = c & 0x1FF, (c >> 9) & 0x1
+            rot_v3 = ((mag.astype(np.float32) / 511.0) * 0.707106781186547524401 * (1.0 - 2.0 * neg)).astype(np.float32)
+        for t in (opa, f_dc, sh, rot_legacy):
+            assert t.dtype == np.float32
+        _spz_read_tables = dict(zip(SPZ_READ_TABLES, (opa, f_dc, rgb, scale, sh, rot_legacy, rot_v3)))
+    return _spz_read_tables
+
+
+def spz_read_table_words() -> np.ndarray:
+    """spz_read_tables() as the device takes them: uint32[GSX_SPZ_TAB_WORDS], the float32 bits, the colour bytes widened"""
+    t = spz_read_tables()
+    words = np.concatenate([t[k].astype(np.uint32) if t[k].dtype == np.uint8 else t[k].view(np.uint32) for k in SPZ_READ_TABLES])
+    assert words.size == 2560
+    return words
+
+
+def spz_body_bytes(version: int, degree: int, n: int) -> int:
+    """the six sections of n rows (spz.py:182-241)"""
+    return n * (SPZ_READ_POS_BYTES[version] + 1 + 3 + 3 + SPZ_READ_ROT_BYTES[version] + 3 * SPZ_SH_DIM[degree])
+
+
+def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractional_bits: int, n_rows: int, dtype: np.dtype,
+                     stage_ms: "dict | None" = None, device: int = 0, fill_stage: str = "file_read") -> np.ndarray:
+    """The SPZ reader's rows (formats/spz.py:175-251) from a file whose header the caller has parsed and checked
+    (formats/spz_reader.py): ``fill(view)`` puts the `body_bytes` bytes behind the header straight into page-locked staging
+    (it raises what the reference raises on a damaged or short file: nothing has been uploaded then), one upload, decoded by
+    gsx_spz_unpack_dev and downloaded into a prefaulted array of `dtype` (packed rows of 71 + 12 sh_dim bytes).
+
+    One ArenaSession of the "spzread" lease group."""
+    lib = require_hip()
+    n, total = int(n_rows), int(body_bytes)
+    rb = dtype.itemsize
+    if rb != 71 + 12 * SPZ_SH_DIM[degree] or total != spz_body_bytes(version, degree, n):
+        raise ValueError("spz_unpack_table: rows of %d bytes, a body of %d for version %d degree %d" % (rb, total, version, degree))
+    out = np.empty(n, dtype)
+    if n == 0:
+        return out
+    with ArenaSession("spzread", device, stage_ms) as s:
+        join = prefault(out.nbytes >= (1 << 22), out)
+        host = s.staging("in", total)
+        fill(host)
+        ctx = s.ctx
+        host_tab = spz_read_table_words()
+        s.mark(fill_stage)
+        d_in = s.buf("in", total + 32)             # the kernel's 16-byte loads reach up to 15 bytes past the last section
+        d_tab = s.buf("tables", host_tab.nbytes)
+        s.upload_staging(lib, d_in.ptr, host)
+        d_tab.upload(host_tab)
+        s.mark("upload")
+        d_out = s.buf("out", n * rb)
+        check(lib.gsx_spz_unpack_dev(ctx.handle, d_in.ptr, total, int(version), int(degree), int(fractional_bits), d_tab.ptr, d_out.ptr, n),
+              "gsx_spz_unpack_dev")
         s.mark("kernel")
         join()
         check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")

@@ -39,15 +39,6 @@ struct KsReadArgs {
     float sr, sf;
 };
 
-// numpy's float16 -> float32: exact, and a NaN keeps its sign, its payload and its quiet bit as they are
-__device__ __forceinline__ unsigned ksr_half(unsigned h)
-{
-    if ((h & 0x7c00u) == 0x7c00u && (h & 0x03ffu)) return ((h & 0x8000u) << 16) | 0x7f800000u | ((h & 0x03ffu) << 13);
-    union { unsigned short u; _Float16 f; } v;
-    v.u = (unsigned short)h;
-    return __float_as_uint((float)v.f);
-}
-
 // :209-210 `(pos_u - sr) * sf + centre`
 __device__ __forceinline__ unsigned ksr_position(unsigned u16, float sr, float sf, float c)
 {
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(KSR_TILE) void ksplat_unpack_kernel(const uint4 *__
             for (int a = 0; a < 3; ++a) {
                 const float c = __uint_as_float(ld_u32(bytes, A.cen_off + 12 * b + 4 * a));
                 o[a] = ksr_position(p[a], A.sr, A.sf, c);
-                o[tail + 1 + a] = ksr_half(s[a]);
+                o[tail + 1 + a] = half_bits(s[a]);
             }
 #pragma unroll
             for (int a = 0; a < 4; ++a)
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(KSR_TILE) void ksplat_unpack_kernel(const uint4 *__
         for (int k = 0; k < A.sh_count; ++k) {
             unsigned v;
             if (LV == 0) v = lds_u32(in32, sh_q + 4 * k);
-            else if (LV == 1) v = ksr_half(lds_u32(in32, sh_q + 2 * k) & 0xffffu);
+            else if (LV == 1) v = half_bits(lds_u32(in32, sh_q + 2 * k) & 0xffffu);
             else v = __float_as_uint(__fmul_rn((float)((int)(lds_u32(in32, sh_q + k) & 0xffu) - 128), 0.0078125f));
             o[rest + k] = v;
         }

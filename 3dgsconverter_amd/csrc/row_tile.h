@@ -44,6 +44,15 @@ __device__ __forceinline__ unsigned lds_u32(const unsigned *lds, int q)
 __device__ __forceinline__ float lds_f32(const unsigned *lds, int q) { return __uint_as_float(lds_u32(lds, q)); }
 __device__ __forceinline__ unsigned lds_u8(const unsigned *lds, int q) { return (lds[q >> 2] >> (8 * (q & 3))) & 0xffu; }
 
+// numpy's float16 -> float32: exact, and a NaN keeps its sign, its payload and its quiet bit as they are
+__device__ __forceinline__ unsigned half_bits(unsigned h)
+{
+    if ((h & 0x7c00u) == 0x7c00u && (h & 0x03ffu)) return ((h & 0x8000u) << 16) | 0x7f800000u | ((h & 0x03ffu) << 13);
+    union { unsigned short u; _Float16 f; } v;
+    v.u = (unsigned short)h;
+    return __float_as_uint((float)v.f);
+}
+
 // np.clip(t, 0, 255).astype(np.uint8): NaN stays NaN through the clip and casts to 0
 __device__ __forceinline__ unsigned spz_u8(float t)
 {

@@ -20,7 +20,7 @@ _saved = {}
 
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
-            cply_reader: bool = True, ksplat_reader: bool = True):
+            cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -39,7 +39,10 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     ksplat_reader: also rebind ``gsconverter.formats.ksplat.KSplatFormat.read`` to formats/ksplat_reader.py (header walk on the
     host, every row decoded on the GPU; the reference's rows, ``self.metadata`` and its exceptions on malformed files).  Files the
     device path does not take -- a section of SH degree above 3, thousands of section headers, rows broadcast against a single
-    bucket assignment -- go to the reference's own read.  A reference without that module is left as it is."""
+    bucket assignment -- go to the reference's own read.  A reference without that module is left as it is.
+    spz_reader: also rebind ``gsconverter.formats.spz.SpzFormat.read`` to formats/spz_reader.py (streamed inflate into page-locked
+    staging and the header on the host, every row decoded on the GPU; the reference's rows and its exceptions on malformed
+    files).  A file of SH degree above 3 goes to the reference's own read.  A reference without that module is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -125,6 +128,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.ksplat_reader import bind_read as bind_ksplat_read
             _saved.setdefault(("ksplatformat", "read"), ksmod.KSplatFormat.read)
             ksmod.KSplatFormat.read = bind_ksplat_read(_saved[("ksplatformat", "read")])
+    if spz_reader:
+        try:
+            spzmod = importlib.import_module("gsconverter.formats.spz")
+        except ImportError:
+            spzmod = None
+        if spzmod is not None and getattr(spzmod.SpzFormat, "read", None) is not None:
+            from .formats.spz_reader import bind_read as bind_spz_read
+            _saved.setdefault(("spzformat", "read"), spzmod.SpzFormat.read)
+            spzmod.SpzFormat.read = bind_spz_read(_saved[("spzformat", "read")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -140,7 +152,7 @@ def uninstall():
             setattr(importlib.import_module("gsconverter.formats.compressed_ply").CompressedPlyFormat, attr, val)
             continue
         if modname == "spzformat":
-            importlib.import_module("gsconverter.formats.spz").SpzFormat.write = val
+            setattr(importlib.import_module("gsconverter.formats.spz").SpzFormat, attr, val)
             continue
         if modname == "ksplatformat":
             setattr(importlib.import_module("gsconverter.formats.ksplat").KSplatFormat, attr, val)

@@ -759,6 +759,32 @@ int gsx_ksplat_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t body_bytes
                           int n_sections, const uint32_t *prefix_dev, int64_t n_prefix, const float *tables_dev, int n_coeffs,
                           float *out_dev, int64_t out_rows);
 
+
+/* ---- the SPZ reader (csrc/spz_read.hip) ----
+ * gsconverter/formats/spz.py:175-251 (SpzFormat._read_body) with :253-262 (_unpack_rot_legacy), :267-296 (_unpack_rot_v3) and
+ * :345-348 (_linear_u8_to_logit): the six planar sections of an inflated body -- positions (6 bytes a row at version 1, else
+ * 9), alpha (1), colour (3), scale (3), rotation (3 below version 3, else 4), sh (3 x 0/3/8/15 for degree 0..3), each
+ * following the other at any byte -- -> the reference's rows in GaussianStruct.define_dtype(has_rgb=True)'s order, x y z nx ny
+ * nz f_dc_0..2 f_rest_0.. opacity scale_0..2 rot_0..3 as float32, then red green blue as bytes, packed (71, 107, 167 or 251
+ * bytes a row), bit for bit.  The header is parsed and checked by the caller (formats/spz_reader.py).
+ * tables_dev: the host-built tables (numpy's own results), 32-bit words: float32 opacity logit of byte b [256] | float32 f_dc
+ * of byte b [256] | the red/green/blue byte the reference derives from that f_dc, as uint32 [256] | float32 scale [256] |
+ * float32 sh [256] | float32 legacy rotation component b / 127.5 - 1 [256] | float32 signed version-3 rotation component of
+ * the 10-bit code c [1024].  (Scale and sh are exact in float32 and the kernel computes them; their tables are the host's.) */
+#define GSX_SPZ_TAB_OPA 0
+#define GSX_SPZ_TAB_DC 256
+#define GSX_SPZ_TAB_RGB 512
+#define GSX_SPZ_TAB_SCALE 768
+#define GSX_SPZ_TAB_SH 1024
+#define GSX_SPZ_TAB_ROTL 1280
+#define GSX_SPZ_TAB_ROT3 1536
+#define GSX_SPZ_TAB_WORDS 2560
+/* body_dev: the inflated file from byte 16 on, 16-byte aligned and readable up to 16 bytes past body_bytes, which must hold
+ * the six sections of n rows (n < 2^32).  out_dev: n packed rows, 16-byte aligned.  version 1 ... 3, sh_degree 0 ... 3,
+ * fractional_bits 0 ... 255 (the divisor is float32(1 << fractional_bits): inf from 128 on).  One launch.  Asynchronous. */
+int gsx_spz_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t body_bytes, int version, int sh_degree, int fractional_bits,
+                       const void *tables_dev, void *out_dev, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

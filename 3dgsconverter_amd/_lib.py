@@ -162,6 +162,7 @@ SIGNATURES = {
     "gsx_mask_ge_dev": (_I, [_P, _P, _P, _I64, _D, _P]),
     "gsx_sor_knn_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _P, C.POINTER(SorInfo)]),
     "gsx_sor_knn_share_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, C.POINTER(SorInfo)]),
+    "gsx_sor_debug_brick_plan": (_I, [_P, _P, _P, _P, _I64]),
     "gsx_sor_stats_dev": (_I, [_P, _P, _I64, _D, _P]),
     "gsx_sor_mask_dev": (_I, [_P, _P, _I64, _P, _P]),
     "gsx_comm_unique_id": (_I, [_P]),
@@ -1921,6 +1922,20 @@ class Context:
                                              int(nshares), mean_out, C.byref(info) if want_info else None),
               "gsx_sor_knn_share_dev")
         return info.as_dict() if want_info else None
+
+    def debug_brick_plan(self, cap: int = 1 << 22):
+        """brick plan of this context's last grid KNN call: dict(nx, ny, nz, plan, bricks, origin (ox, oy, oz, inv_h) as
+        float32, runs = (bricks, 3) int array of (bundle, first quarter, last quarter) when the planned bricks ran)"""
+        import numpy as np
+        grid = (C.c_int32 * 8)()
+        origin = (C.c_float * 4)()
+        buf = np.zeros((cap, 2), np.uint32)
+        check(self.lib.gsx_sor_debug_brick_plan(self.handle, grid, origin, buf.ctypes.data_as(C.c_void_p), cap),
+              "gsx_sor_debug_brick_plan")
+        m = min(int(grid[4]), cap) if grid[3] else 0
+        runs = np.stack([buf[:m, 0], buf[:m, 1] & 0xffff, buf[:m, 1] >> 16], axis=1).astype(np.int64)
+        return {"nx": int(grid[0]), "ny": int(grid[1]), "nz": int(grid[2]), "plan": int(grid[3]), "bricks": int(grid[4]),
+                "origin": np.array(list(origin), np.float32), "runs": runs}
 
     def sor_stats(self, mean_dists: int, n: int, threshold_factor: float, stats_out: int):
         check(self.lib.gsx_sor_stats_dev(self.handle, mean_dists, n, float(threshold_factor), stats_out),

@@ -292,6 +292,8 @@ int gsx_ctx_set_param(gsx_ctx *c, const char *name, double value)
         c->tree_scale = value;
     } else if (!strcmp(name, "defer_words")) {
         c->defer_words = (int)value;
+    } else if (!strcmp(name, "brick_plan")) {
+        c->brick_plan = value != 0.0;
     } else if (!strcmp(name, "filter_mfma")) {
         c->filter_mfma = value != 0.0;
     } else {
@@ -380,6 +382,29 @@ int gsx_sor_knn_dev(gsx_ctx *c, const float *x, const float *y, const float *z, 
     if (algo == GSX_KNN_GRID) return launch_knn_grid(c, x, y, z, stride, n_ref, q_begin, q_count, k, mean_out, info);
     if (algo == GSX_KNN_TREE) return launch_knn_tree(c, x, y, z, stride, n_ref, q_begin, q_count, k, mean_out, nullptr, info, INT32_MAX, 0, 1, false);
     GSX_FAIL("gsx_sor_knn_dev: unknown algo %d", algo);
+}
+
+// Debug / test download of the brick plan the context's last grid KNN call ran on.  grid[8] = nx, ny, nz, plan (1: the list
+// was used), bricks, 0, 0, 0; origin[4] = ox, oy, oz, inv_h; list (nullable) receives min(bricks, cap) entries
+// {bundle = bz * ceil(ny / 2) + by, first quarter | last quarter << 16}.  Synchronises.
+int gsx_sor_debug_brick_plan(gsx_ctx *c, int32_t *grid, float *origin, uint32_t *list, int64_t cap)
+{
+    if (!c || !grid || !origin) GSX_FAIL("gsx_sor_debug_brick_plan: null argument");
+    gsx::KnnWs &w = c->ws[0];
+    if (!w.gridparams.p) GSX_FAIL("gsx_sor_debug_brick_plan: no grid KNN call has run on this context");
+    GSX_HIP(hipSetDevice(c->device));
+    gsx::GridParams h;
+    GSX_HIP(hipMemcpyAsync(&h, w.gridparams.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipStreamSynchronize(c->stream));
+    const int32_t g[8] = {h.nx, h.ny, h.nz, h.plan, h.nbricks, 0, 0, 0};
+    memcpy(grid, g, sizeof(g));
+    const float o[4] = {h.ox, h.oy, h.oz, h.inv_h};
+    memcpy(origin, o, sizeof(o));
+    if (h.plan && list && w.bricklist.p) {
+        const int64_t m = std::min<int64_t>(h.nbricks, cap);
+        if (m > 0) GSX_HIP(hipMemcpy(list, w.bricklist.p, sizeof(uint32_t) * 2 * (size_t)m, hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 
 int gsx_sor_knn_share_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n,

@@ -67,6 +67,9 @@ struct KnnWs {
     DevBuf bboxpart;    // float[7 * blocks]
     DevBuf faillist;    // u32[q_count]
     DevBuf extraitems;  // uint2[q_count/64 + 64]: (brick, first query) of every batch beyond a brick's first
+    DevBuf finestart;   // u32[4 * cap + 1]: cell_start at quarter-cell steps along x (planned bricks only)
+    DevBuf bricklist;   // uint2[n / 16 + 4096]: (bundle, first | last << 16 quarter) of every planned brick
+    DevBuf bundleoff;   // u32[2 * bundles]: planned bricks per bundle of 2x2 query rows | their exclusive scan
     // adaptive refinement (level L -> L+1)
     DevBuf deferred;    // u32[nbricks]: bricks whose neighbourhood is too populated for this level's cells
     DevBuf cellflag;    // u8[ncells]: 1 = cell belongs to the sub-cloud, 2 = ... of a deferred brick (its points are queries)
@@ -81,7 +84,7 @@ struct KnnWs {
     void release_all()
     {
         DevBuf *all[] = {&packed, &qsorted, &bucketpts, &bkcnt, &tilecnt, &tileoff, &cellstart, &qcellstart, &gridparams, &bboxpart,
-                         &faillist, &extraitems, &deferred, &cellflag, &subxyz, &submap, &submean, &subkth,
+                         &faillist, &extraitems, &finestart, &bricklist, &bundleoff, &deferred, &cellflag, &subxyz, &submap, &submean, &subkth,
                          &heavylist, &heavypart, &probe};
         for (auto b : all) b->release();
     }
@@ -181,6 +184,8 @@ struct gsx_ctx {
     int kmeans_cs = 1;   // centroid-stationary matrix-core assign for K <= 1024 (0: the streaming kernel; A/B)
     int ring_fast = 1;   // knn_ring_fast before knn_ring (0: A/B only)
     int phase2_net = 1;  // knn_brick phase 2: 1 = sorting-network block selection (TopNet), 0 = per-candidate bubble insert (A/B only)
+    int brick_plan = 1;  // knn_brick on planned bricks (runs of quarter-cell slabs holding at most 64 queries) where the call allows it: the plain
+                         // single-cloud call, k <= 16, MFMA filter + network selection (0: the fixed 2x2x2-cell bricks everywhere; A/B)
     int filter_mfma = 1; // knn_brick phase 1: 1 = bf16-split MFMA filter for batches whose mask words fit LDS, 0 = scalar-load f32 VALU filter only
 
     // SOR workspace: one KnnWs per refinement level of the KNN grid (level 0 = the whole cloud)

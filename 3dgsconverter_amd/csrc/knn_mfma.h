@@ -34,6 +34,9 @@ __device__ __forceinline__ unsigned shift_in_lt(unsigned m, float qx, float qy, 
 // <= 1e-4 even at 4 ulp each -- together < 3e-4.  MF_SLACK = 1e-3 (cell units^2, i.e. 0.05 % of the
 // radius at r ~ 1 cell) makes the filter conservative: every candidate with d2 <= tau sets its bit;
 // the few extra ones are discarded by the exact float64 phase 2 as before.
+// Planned bricks (sor_grid.hip, brick_plan_kernel) centre the frame on a run of up to 2.5 cells along x: |u_x| <= 2.25 with
+// the cell either side.  Every term above scales with |p||q| <= |u|^2, so the bound becomes 3e-4 * (2.25 / 2)^2 = 3.8e-4,
+// still well inside MF_SLACK; a longer run would have to redo this line (PLAN_MAXRUN).
 // Lane layout (measured, tools/ubench/mfma_layout.hip): A/B lane l holds row/col l&31, k =
 // 8*(l>>5)+0..7; D lane l holds col l&31, rows (r&3) + 8*(r>>2) + 4*(l>>5) for r in [0,16).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

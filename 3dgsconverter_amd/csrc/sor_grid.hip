@@ -10,7 +10,9 @@
 //   bucket_hist / bucket_offsets / bucket_scatter / bucket_sort
 //                                          two-level counting sort into float4 {x,y,z,orig}: every
 //                                          per-point atomic is an LDS atomic (see the kernels)
-//   knn_brick                              one WAVE per 2x2x2-cell brick (~56 queries)
+//   brick_plan (x2)                        plain single-cloud call, k <= 16: the bricks become runs of quarter-cell slabs along x
+//                                          holding <= 64 queries (see "brick plan" below); every other call keeps the fixed bricks
+//   knn_brick                              one WAVE per brick: 2x2x2 cells (~54 queries) or a planned run (~59)
 //   knn_ring                               expanding-ring exact fallback for the few queries
 //                                          whose (k+1)-th neighbour is farther than one cell
 //
@@ -82,6 +84,7 @@ struct GridParamArgs {   // what grid_params needs besides the partial boxes
     int cert_axis;
     float cert_lo, cert_hi;
     unsigned *cert_count;
+    int plan_req = 0, plan_cap = 0;   // planned bricks asked for (the call allows them), entries the brick list has room for
 };
 __device__ void grid_params_body(const float *part, int nparts, const GridParamArgs &a);
 
@@ -259,6 +262,10 @@ __device__ void grid_params_body(const float *part, int nparts, const GridParamA
     gp->bdx = bdx; gp->bdy = bdy; gp->bdz = bdz;
     gp->nbx = (nx + bdx - 1) / bdx; gp->nby = (ny + bdy - 1) / bdy; gp->nbz = (nz + bdz - 1) / bdz;
     gp->nbricks = bad ? 0 : gp->nbx * gp->nby * gp->nbz;
+    // planned bricks: the quarter index floor(fl(fl(x-o) * 4 inv_h)) has 4 nx values, and its rounding bound (see r_safe
+    // below) is the cell index's with dim = 4 nx -- so 4 nx <= MAX_DIM.  Larger grids keep the fixed bricks.
+    gp->plan = (a.plan_req && !bad && bdx == 2 && bdy == 2 && bdz == 2 && 4 * nx <= MAX_DIM) ? 1 : 0;
+    gp->plan_cap = a.plan_cap;
     // bricks are numbered z-major, so a contiguous share is a slab of the cloud
     gp->part_lo = (int)(((long long)gp->nbricks * share) / nshares);
     gp->part_hi = (int)(((long long)gp->nbricks * (share + 1)) / nshares);
@@ -686,28 +693,46 @@ constexpr int SORT_THREADS = GSX_SORT_THREADS;
 constexpr int SORT_PPT = GSX_SORT_PPT;                // points per thread kept in registers
 constexpr unsigned SORT_CAP = SORT_THREADS * SORT_PPT;  // buckets up to 8192 points are read ONCE
 
+// Quarter index along x: q4 >> 2 IS cell_coord(x) -- multiplying inv_h by 4 is exact in f32, so (x - o) * (4 inv_h) is exactly
+// four times the product cell_coord truncates, and floor(4t) >> 2 = floor(t) for t >= 0; the clamps agree as well.
+__device__ __forceinline__ int quarter_coord(float v, float o, float inv_h, int dim)
+{
+    int c = (int)((v - o) * (4.0f * inv_h));
+    return min(max(c, 0), 4 * dim - 1);
+}
+
+// FINE (planned bricks): the bins are the quarter-cell slabs along x, four per cell, in cell order -- the points of a cell
+// stay one contiguous range and cell_start keeps its meaning (every fourth bin start); fine_start[4 c + j] is where quarter j
+// of cell c begins.  4 x MAX_BUCKET_CELLS counters are 64 KiB of LDS: two workgroups per CU, as the registers allow anyway.
+template <bool FINE>
 __global__ __launch_bounds__(SORT_THREADS) void bucket_sort_kernel(const GridParams *__restrict__ gp,
                                                           const unsigned *__restrict__ bk_start,
                                                           const float4 *__restrict__ in, float4 *__restrict__ out,
-                                                          unsigned *__restrict__ cell_start, unsigned big_limit)
+                                                          unsigned *__restrict__ cell_start, unsigned big_limit,
+                                                          unsigned *__restrict__ fine_start)
 {
-    __shared__ unsigned cnt[MAX_BUCKET_CELLS];
+    constexpr int SUB = FINE ? 4 : 1;
+    __shared__ unsigned cnt[SUB * MAX_BUCKET_CELLS];
     __shared__ unsigned wsum[SORT_THREADS / 64];
     const GridParams g = *gp;
     const int b = blockIdx.x;
     if (g.bad_input || b >= g.bk_count) return;
-    const int cells = g.bk_cells;
+    const int ncell = g.bk_cells;
+    const int cells = SUB * ncell;   // bins of this bucket
     const unsigned s0 = bk_start[b], s1 = bk_start[b + 1];
-    if (b == g.bk_count - 1 && threadIdx.x == 0) cell_start[(size_t)g.bk_count * cells] = s1;
+    if (b == g.bk_count - 1 && threadIdx.x == 0) {
+        cell_start[(size_t)g.bk_count * ncell] = s1;
+        if (FINE) fine_start[(size_t)g.bk_count * cells] = s1;
+    }
     if (s1 - s0 > big_limit) return;  // sorted by the multi-workgroup path below
     const int by = b % g.bk_ny, bz = b / g.bk_ny;
     for (int i = threadIdx.x; i < cells; i += SORT_THREADS) cnt[i] = 0;
     __syncthreads();
     auto local_cell = [&](const float4 p) {
-        const int cx = cell_coord(p.x, g.ox, g.inv_h, g.nx);
+        const int cx = FINE ? quarter_coord(p.x, g.ox, g.inv_h, g.nx) : cell_coord(p.x, g.ox, g.inv_h, g.nx);
         const int cy = cell_coord(p.y, g.oy, g.inv_h, g.ny);
         const int cz = cell_coord(p.z, g.oz, g.inv_h, g.nz);
-        return ((cz - bz * g.bk_g) * g.bk_g + (cy - by * g.bk_g)) * g.nx + cx;
+        return ((cz - bz * g.bk_g) * g.bk_g + (cy - by * g.bk_g)) * (SUB * g.nx) + cx;
     };
     const bool fits = s1 - s0 <= SORT_CAP;  // block-uniform: the bucket's points, cells and ranks stay in registers
     float4 p[SORT_PPT];
@@ -749,8 +774,12 @@ __global__ __launch_bounds__(SORT_THREADS) void bucket_sort_kernel(const GridPar
         run += v;
     }
     __syncthreads();
-    unsigned *cs = cell_start + (size_t)b * cells;
-    for (int i = threadIdx.x; i < cells; i += SORT_THREADS) cs[i] = s0 + cnt[i];
+    unsigned *cs = cell_start + (size_t)b * ncell;
+    for (int i = threadIdx.x; i < ncell; i += SORT_THREADS) cs[i] = s0 + cnt[SUB * i];
+    if (FINE) {
+        unsigned *fs = fine_start + (size_t)b * cells;
+        for (int i = threadIdx.x; i < cells; i += SORT_THREADS) fs[i] = s0 + cnt[i];
+    }
     if (fits) {
 #pragma unroll
         for (int u = 0; u < SORT_PPT; ++u)
@@ -864,6 +893,128 @@ __global__ __launch_bounds__(256) void big_bucket_scan_kernel(const GridParams *
     }
 }
 
+// ---------------------------------------------------------------- brick plan
+// Planned bricks (the plain single-cloud call, 2x2x2-cell bricks, k <= 16): a fixed brick holds 54 +- 7.3 queries of a
+// uniform cloud, so ten of a batch's 64 lanes idle and one brick in thirteen pays a second batch for a handful of
+// queries.  A BUNDLE is the 2x2 query rows of the bricks (., by, bz); its points are ordered by quarter-cell slab along x
+// (bucket_sort<true>, fine_start).  One wave per bundle cuts the bundle's 4 nx quarter-slabs into greedy runs: a run grows
+// while it holds at most PLAN_MAXQ queries and PLAN_MAXRUN quarters; a single quarter with more queries is a run of its
+// own (knn_brick's multi-batch / extra path).  The runs of all bundles, in bundle-then-x order, are knn_brick's work items.
+// Pass 1 counts the runs of every bundle, its last workgroup scans the counts (no atomics hand out slots: the list is the
+// same for the same cloud); pass 2 cuts the same runs again and writes them.  4 nx <= MAX_DIM (grid_params), so a bundle's
+// counts fit the LDS arrays below.
+constexpr int PLAN_MAXQ = 64;
+constexpr int PLAN_MAXRUN = 10;   // quarters: 2.5 cells -- with one cell either side |u| <= 2.25 in the MFMA frame (knn_mfma.h)
+constexpr int PLAN_WAVES = 4;
+
+template <bool WRITE>
+__global__ __launch_bounds__(64 * PLAN_WAVES) void brick_plan_kernel(GridParams *__restrict__ gp, const unsigned *__restrict__ fine_start,
+                                                                     unsigned *__restrict__ bundle_cnt, unsigned *__restrict__ bundle_off,
+                                                                     uint2 *__restrict__ list)
+{
+    // Both passes are a few dependent round trips per wave (3 bundles per SIMD at 10M points), so every load of a step is
+    // independent of the others: the first version (a load pair per quarter and row inside a rolled loop, a serial walk per
+    // run start, one load after the other in the scan) took 39 + 23 us per 10M points.
+    __shared__ unsigned s_sum[PLAN_WAVES][MAX_DIM + 1];
+    __shared__ unsigned short s_nxt[PLAN_WAVES][MAX_DIM];
+    __shared__ unsigned wsum[4];
+    __shared__ unsigned s_last;
+    const GridParams g = *gp;
+    if (g.bad_input || !g.plan) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned *S = s_sum[wv];
+    unsigned short *nxt = s_nxt[wv];
+    const int nq4 = 4 * g.nx, nbund = g.nby * g.nbz;
+    const unsigned cap = (unsigned)g.plan_cap;
+    constexpr int QPL = MAX_DIM / 64 + 1;   // quarter boundaries per lane: 4 nx + 1 <= 1025
+    for (int bundle = (int)blockIdx.x * PLAN_WAVES + wv; bundle < nbund; bundle += (int)gridDim.x * PLAN_WAVES) {   // wave-uniform
+        const int bz = bundle / g.nby, by = bundle - bz * g.nby;
+        int rb[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int yy = 2 * by + (r & 1), zz = 2 * bz + (r >> 1);
+            rb[r] = yy < g.ny && zz < g.nz ? 4 * row_base(g, yy, zz) : -1;
+        }
+        // S[q] = sum over the bundle's rows of fine_start[row + q], q = 0 .. 4 nx: the queries of the quarters [a, b) are
+        // S[b] - S[a] (mod 2^32: the differences are exact)
+        unsigned v[QPL][4];
+#pragma unroll
+        for (int u = 0; u < QPL; ++u) {
+            const int q = lane + 64 * u;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[u][r] = (q <= nq4 && rb[r] >= 0) ? fine_start[rb[r] + q] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < QPL; ++u) {
+            const int q = lane + 64 * u;
+            if (q <= nq4) S[q] = v[u][0] + v[u][1] + v[u][2] + v[u][3];
+        }
+        wave_sync();
+        for (int s = lane; s < nq4; s += 64) {   // where the run that starts at quarter s ends (exclusive): S is monotone
+            const unsigned s0 = S[s];
+            int e = s + 1;
+#pragma unroll
+            for (int j = 2; j <= PLAN_MAXRUN; ++j) e += (s + j <= nq4 && S[min(s + j, nq4)] - s0 <= (unsigned)PLAN_MAXQ) ? 1 : 0;
+            nxt[s] = (unsigned short)e;
+        }
+        wave_sync();
+        if (lane == 0) {
+            const unsigned base = WRITE ? bundle_off[bundle] : 0u;
+            unsigned n = 0;
+            for (int s = 0; s < nq4; ++n) {
+                const int e = nxt[s];
+                if (WRITE && base + n < cap) list[base + n] = make_uint2((unsigned)bundle, (unsigned)s | ((unsigned)(e - 1) << 16));
+                s = e;
+            }
+            if (!WRITE) __hip_atomic_store(&bundle_cnt[bundle], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through
+        }
+        wave_sync();   // the arrays are rewritten for the wave's next bundle
+    }
+    if (WRITE) return;
+    __builtin_amdgcn_s_waitcnt(0);   // the write-through stores above have completed before the ticket
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(&gp->ticket_plan, 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!s_last) return;
+    // the last workgroup: exclusive scan of the bundles' run counts, each thread a contiguous segment (held in registers
+    // when it is short: 13 entries at 10M points)
+    constexpr int HOLD = 16;
+    const int seg = (nbund + 255) / 256;
+    const int c0 = min(nbund, (int)threadIdx.x * seg), c1 = min(nbund, c0 + seg);
+    const bool held = seg <= HOLD;   // block-uniform
+    unsigned hv[HOLD];
+    unsigned sum = 0;
+    for (int c = c0; c < c1; c += HOLD) {
+#pragma unroll
+        for (int u = 0; u < HOLD; ++u) hv[u] = c + u < c1 ? __hip_atomic_load(&bundle_cnt[c + u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+#pragma unroll
+        for (int u = 0; u < HOLD; ++u) sum += hv[u];
+    }
+    unsigned tot;
+    unsigned run = block_exclusive_scan_256(sum, &tot, wsum);
+    for (int c = c0; c < c1; c += HOLD) {
+        unsigned w[HOLD];
+#pragma unroll
+        for (int u = 0; u < HOLD; ++u)
+            w[u] = held ? hv[u] : (c + u < c1 ? __hip_atomic_load(&bundle_cnt[c + u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u);
+#pragma unroll
+        for (int u = 0; u < HOLD; ++u) {
+            if (c + u < c1) bundle_off[c + u] = run;
+            run += w[u];
+        }
+    }
+    if (threadIdx.x == 0) {
+        gp->ticket_plan = 0;
+        if (tot > cap) {
+            gp->plan = 0;   // (a cloud of long empty stretches: more runs than the list holds) -- the fixed bricks, numbered as ever
+        } else {
+            gp->nbricks = (int)tot;   // knn_brick's items are list positions now
+            gp->part_lo = 0;
+            gp->part_hi = (int)tot;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- knn_brick
 // One wave per brick.  refs/rstart: cell-sorted reference points and cell starts;
 // qpts/qstart: cell-sorted QUERY points (same arrays when every reference is a query).
@@ -908,12 +1059,19 @@ constexpr int brick_min_waves(int kcap, bool mf, bool net)
 
 // NET: phase 2 selects with TopNet<KCAP-1> (sorting-network blocks, the query excluded by index) instead
 // of the per-candidate bubble insert of TopList<KCAP>; needs KCAP-1 to be a power of two.
-template <int KCAP, bool EXTRA, bool MF, bool NET>
+// PLAN: the work items are planned bricks (brick_plan_kernel): quarter-slabs [qf, ql] of the bundle (by, bz), rows taken from
+// fine_start (passed as rstart; queries and references are the same table).  The 16 candidate rows are the quarters
+// [qf - 4, ql + 4]: |p - q| <= r_safe = h'(1 - 1e-3) is 4 - 4e-3 quarter units, and the f32 quarter index
+// floor(fl(fl(x-o) * 4 inv_h)) is monotone and off by < 4 nx * 2^-22 <= 2.5e-4 quarters (4 nx <= MAX_DIM, grid_params), so the
+// quarter indices of p and q differ by at most 4 -- the cell argument of r_safe with dim = 4 nx.  Where brick_plan withdrew
+// the plan (gp->plan == 0) the same kernel takes the fixed bricks as the aligned runs [8 bx, 8 bx + 7]: fine_start[4 c] is
+// cell_start[c], the rows are the fixed brick's.
+template <int KCAP, bool EXTRA, bool MF, bool NET, bool PLAN = false>
 __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void knn_brick_kernel(
     GridParams *__restrict__ gp, const float4 *__restrict__ refs, const unsigned *__restrict__ rstart,
     const float4 *__restrict__ qpts, const unsigned *__restrict__ qstart, int k, int q_begin,
     float *__restrict__ mean_out, unsigned *__restrict__ faillist, uint2 *__restrict__ extra,
-    unsigned *__restrict__ deferred, double *__restrict__ kth_out)
+    unsigned *__restrict__ deferred, double *__restrict__ kth_out, const uint2 *__restrict__ plist)
 {
     constexpr int WCAP = KCAP > 33 ? GSX_WCAP_BIG : (KCAP > 17 ? GSX_WCAP_MID : gsx::WCAP);
     __shared__ unsigned s_mask[BRICK_THREADS / 64][WCAP][64];
@@ -955,6 +1113,8 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
 
     WorkQueue wq;
     const int part_lo = gp->part_lo;
+    const int nq4 = 4 * nx;
+    const bool planned = PLAN && gp->plan != 0;   // kernel-uniform
     const int dw = EXTRA ? 0 : gp->defer_words;  // loaded once: gp is written by atomics, the compiler would reload it per brick
     wq_init(wq, EXTRA ? gp->extra_ctr : gp->brick_ctr, EXTRA ? (int)gp->extra_count : gp->part_hi - part_lo,
             BRICK_THREADS / 64);
@@ -967,10 +1127,29 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
             b = uniform((int)it.x);
             qb = uniform((int)it.y);
         }
-        const int bz = b / (nbx * nby);
-        const int brem = b - bz * nbx * nby;
-        const int by = brem / nbx;
-        const int bx = brem - by * nbx;
+        int bx, by, bz;
+        int qf = 0, ql = 0;   // PLAN: first and last quarter-slab of the brick
+        if constexpr (PLAN) {
+            int bundle;
+            if (planned) {
+                const uint2 e = plist[b];
+                bundle = uniform((int)e.x);
+                qf = uniform((int)(e.y & 0xffffu));
+                ql = uniform((int)(e.y >> 16));
+            } else {
+                bundle = b / nbx;
+                qf = 8 * (b - bundle * nbx);
+                ql = min(qf + 7, nq4 - 1);
+            }
+            bz = bundle / nby;
+            by = bundle - bz * nby;
+            bx = 0;
+        } else {
+            bz = b / (nbx * nby);
+            const int brem = b - bz * nbx * nby;
+            by = brem / nbx;
+            bx = brem - by * nbx;
+        }
 
         // lane r < 16: candidate row r (bdx+2 cells along x); lanes 16..19: query rows (bdx cells)
         int v_start = 0, v_len = 0;
@@ -985,12 +1164,14 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
             const int r_mod_cry = r - r_div_cry * cry;
             const int yy = isq ? by * bdy + r_mod_bdy : by * bdy - 1 + r_mod_cry;
             const int zz = isq ? bz * bdz + r_div_bdy : bz * bdz - 1 + r_div_cry;
-            const int xa = isq ? bx * bdx : max(bx * bdx - 1, 0);
-            const int xb = isq ? min(bx * bdx + bdx - 1, nx - 1) : min(bx * bdx + bdx, nx - 1);
+            // (PLAN: quarters, an index into fine_start = 4 x the row's first cell + the quarter)
+            const int xa = PLAN ? (isq ? qf : max(qf - 4, 0)) : (isq ? bx * bdx : max(bx * bdx - 1, 0));
+            const int xb = PLAN ? (isq ? ql : min(ql + 4, nq4 - 1))
+                                : (isq ? min(bx * bdx + bdx - 1, nx - 1) : min(bx * bdx + bdx, nx - 1));
             const bool valid = (isq ? (lane < 20 && r < nqrows) : r < ncrows) && yy >= 0 && yy < ny && zz >= 0 && zz < nz;
             if (valid) {
                 const unsigned *st = isq ? qstart : rstart;
-                const int row = row_base_g(yy, zz);
+                const int row = PLAN ? 4 * row_base_g(yy, zz) : row_base_g(yy, zz);
                 unsigned s = st[row + xa], e = st[row + xb + 1];
                 v_start = (int)s;
                 v_len = (int)(e - s);
@@ -1060,8 +1241,8 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 const int ulo[3] = {bx * bdx - 1, by * bdy - 1, bz * bdz - 1};
                 const int uhi[3] = {bx * bdx + bdx, by * bdy + bdy, bz * bdz + bdz};
                 const int dim[3] = {nx, ny, nz};
-                const bool boundary = ulo[0] <= 0 || ulo[1] <= 0 || ulo[2] <= 0 || uhi[0] >= nx - 1 || uhi[1] >= ny - 1 ||
-                                      uhi[2] >= nz - 1;
+                const bool boundary = (PLAN ? qf - 4 <= 0 || ql + 4 >= nq4 - 1 : ulo[0] <= 0 || uhi[0] >= nx - 1) || ulo[1] <= 0 ||
+                                      ulo[2] <= 0 || uhi[1] >= ny - 1 || uhi[2] >= nz - 1;
                 // Only for a brick's FIRST batch: the later ones scan a sub-box of the neighbourhood (below) that reaches exactly one
                 // cell beyond their queries' cells -- a radius above h' would certify against points that were never looked at.
                 // (Found by the randomised sweep, round 3: a planar cloud, k = 64, two queries at the rim wrong in ~15 % of the
@@ -1081,8 +1262,17 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
                         // faces of the searched box with cells behind them (margin as in grid_params_kernel)
+                        if (PLAN && a == 0) {
+                            // along x the searched box is the quarters [qf - 4, ql + 4]: its faces sit at (qf - 4) / 4 and
+                            // (ql + 5) / 4 cells (exact in f32).  A point left out has a quarter index <= qf - 5 or >= ql + 5, so
+                            // it lies beyond the face but for the index's rounding, 2.5e-4 quarters -- the same 2e-3 h' margin covers it
+                            const int pqf = pinned_here_s(qf), pql = pinned_here_s(ql);
+                            if (pqf - 4 > 0) rsafe = fminf(rsafe, rel[0] - (float)(pqf - 4) * 0.25f * hf - 2e-3f * hf);
+                            if (pql + 4 < nq4 - 1) rsafe = fminf(rsafe, (float)(pql + 5) * 0.25f * hf - rel[0] - 2e-3f * hf);
+                        } else {
                         if (ulo[a] > 0) rsafe = fminf(rsafe, rel[a] - (float)ulo[a] * hf - 2e-3f * hf);
                         if (uhi[a] < dim[a] - 1) rsafe = fminf(rsafe, (float)(uhi[a] + 1) * hf - rel[a] - 2e-3f * hf);
+                        }
                         // part of [q - r1, q + r1] that lies inside the grid along this axis
                         const float tl = fminf(fmaxf(rel[a], 0.0f), r1);
                         const float th = fminf(fmaxf((float)dim[a] * hf - rel[a], 0.0f), r1);
@@ -1125,12 +1315,14 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                     const int l_div_cry = cry == 4 ? (ln >> 2) : (ln * 11) >> 5;     // ln < 16
                     const int yy = by * bdy - 1 + (ln - l_div_cry * cry);
                     const int zz = bz * bdz - 1 + l_div_cry;
-                    const int xa = max(max(bx * bdx - 1, 0), lo[0] - 1);
-                    const int xb = min(min(bx * bdx + bdx, nx - 1), hi[0] + 1);
+                    // (PLAN: the brick's quarters cut to the CELLS within one of the batch's -- both are supersets of what r_safe
+                    //  needs, the quarters by the argument at the top of the kernel, the cells by r_safe's own)
+                    const int xa = PLAN ? max(max(qf - 4, 0), 4 * (lo[0] - 1)) : max(max(bx * bdx - 1, 0), lo[0] - 1);
+                    const int xb = PLAN ? min(min(ql + 4, nq4 - 1), 4 * (hi[0] + 1) + 3) : min(min(bx * bdx + bdx, nx - 1), hi[0] + 1);
                     const bool need = yy >= max(lo[1] - 1, 0) && yy <= min(hi[1] + 1, ny - 1) &&
                                       zz >= max(lo[2] - 1, 0) && zz <= min(hi[2] + 1, nz - 1) && xa <= xb;
                     if (need) {
-                        const int row = row_base_g(yy, zz);
+                        const int row = PLAN ? 4 * row_base_g(yy, zz) : row_base_g(yy, zz);
                         const unsigned s0 = rstart[row + xa], e0 = rstart[row + xb + 1];
                         rs_start = (int)s0;
                         rs_len = (int)(e0 - s0);
@@ -1270,7 +1462,9 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 // cell-unit coordinates relative to the brick centre; see the MFMA notes at the top
                 // (pinned: computed here, per batch -- nine instructions -- instead of per brick with a round trip through scratch)
                 const float hf = pinned_here((float)hp);
-                const float ccx = g_ox + ((float)(bx * bdx) + 0.5f * (float)bdx) * hf;
+                // (PLAN: the middle of the run [qf, ql + 1) quarters -- a run of at most PLAN_MAXRUN = 10 quarters and one cell
+                //  either side keep |u_x| <= 2.25, knn_mfma.h)
+                const float ccx = PLAN ? g_ox + ((float)(qf + ql + 1) * 0.125f) * hf : g_ox + ((float)(bx * bdx) + 0.5f * (float)bdx) * hf;
                 const float ccy = g_oy + ((float)(by * bdy) + 0.5f * (float)bdy) * hf;
                 const float ccz = g_oz + ((float)(bz * bdz) + 0.5f * (float)bdz) * hf;
                 const float uqx = (qx - ccx) * g_inv_h, uqy = (qy - ccy) * g_inv_h, uqz = (qz - ccz) * g_inv_h;
@@ -2191,28 +2385,31 @@ struct BrickLaunch {
     unsigned *heavylist;
     int64_t out_count;    // entries of mean_out (poisoned with NaN when the input is not finite)
     int64_t n_ref;        // reference points binned at this level (mean density for knn_ring_fast)
+    const unsigned *fstart = nullptr;   // planned bricks: fine_start and the brick list (null: the fixed bricks)
+    const uint2 *plist = nullptr;
 };
 
-template <int KCAP, bool MF, bool NET>
+template <int KCAP, bool MF, bool NET, bool PLAN = false>
 static int launch_bricks(gsx_ctx *ctx, const BrickLaunch &a)
 {
+    const unsigned *rstart = PLAN ? a.fstart : a.rstart, *qstart = PLAN ? a.fstart : a.qstart;
     // Work is assigned STATICALLY to waves, so every launched workgroup must be resident at once:
     // the grids are sized from the occupancy the built kernels actually get (a non-resident
     // workgroup would run its share only after a resident one has finished all of its own).
     static int occ_brick = 0, occ_extra = 0;
     if (!occ_brick) {
-        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_brick, knn_brick_kernel<KCAP, false, MF, NET>, BRICK_THREADS, 0));
-        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_extra, knn_brick_kernel<KCAP, true, MF, NET>, BRICK_THREADS, 0));
+        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_brick, knn_brick_kernel<KCAP, false, MF, NET, PLAN>, BRICK_THREADS, 0));
+        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_extra, knn_brick_kernel<KCAP, true, MF, NET, PLAN>, BRICK_THREADS, 0));
         occ_brick = std::max(1, std::min(occ_brick, 8));
         occ_extra = std::max(1, std::min(occ_extra, 8));
     }
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_KNN));
-    hipLaunchKernelGGL((knn_brick_kernel<KCAP, false, MF, NET>), dim3(ctx->num_cu * occ_brick), dim3(BRICK_THREADS), 0, ctx->stream,
-                       a.gp, a.refs, a.rstart, a.qpts, a.qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
-                       a.deferred, a.kth_out);
-    hipLaunchKernelGGL((knn_brick_kernel<KCAP, true, MF, NET>), dim3(ctx->num_cu * occ_extra), dim3(BRICK_THREADS), 0, ctx->stream,
-                       a.gp, a.refs, a.rstart, a.qpts, a.qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
-                       a.deferred, a.kth_out);
+    hipLaunchKernelGGL((knn_brick_kernel<KCAP, false, MF, NET, PLAN>), dim3(ctx->num_cu * occ_brick), dim3(BRICK_THREADS), 0, ctx->stream,
+                       a.gp, a.refs, rstart, a.qpts, qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
+                       a.deferred, a.kth_out, a.plist);
+    hipLaunchKernelGGL((knn_brick_kernel<KCAP, true, MF, NET, PLAN>), dim3(ctx->num_cu * occ_extra), dim3(BRICK_THREADS), 0, ctx->stream,
+                       a.gp, a.refs, rstart, a.qpts, qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
+                       a.deferred, a.kth_out, a.plist);
     GSX_HIP(hipGetLastError());
     GSX_CHECK(timing_end(ctx, GSX_T_SOR_KNN));
     return 0;
@@ -2529,6 +2726,11 @@ static int dispatch_heavy(gsx_ctx *ctx, KnnWs &w, const BrickLaunch &a, int64_t 
 static int dispatch_bricks(gsx_ctx *ctx, const BrickLaunch &a, bool mf, bool net)
 {
     const int kk = a.k + 1;
+    if (a.plist) {   // planned bricks: knn_grid_level allows them for the MFMA + network kernels of 2x2x2-cell bricks only
+        if (kk <= 9) return launch_bricks<9, true, true, true>(ctx, a);
+        if (GSX_CAP4 && kk <= 13) return launch_bricks<13, true, true, true>(ctx, a);
+        return launch_bricks<17, true, true, true>(ctx, a);
+    }
     if (net) {
 #define GSX_BRICKS(K) (mf ? launch_bricks<K, true, true>(ctx, a) : launch_bricks<K, false, true>(ctx, a))
         // (round 5: the multiples of 4 in between as well -- --sor_intensity 1 ... 10 asks for k = 10, 14, 18, 23, 27, 32, 36, 41, 45, 50
@@ -2610,7 +2812,7 @@ static int reserve_bin_tables(KnnWs &w, int64_t n)
 // hist_done: bin_hist has already run on these points.
 static int bin_points(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, const float *z, int64_t stride, int64_t first,
                       int64_t n, GridParams *gp, unsigned *start, float4 *sorted, int64_t cell_cap = 0, unsigned *cursor = nullptr,
-                      int64_t ref_only_from = INT32_MAX, bool hist_done = false)
+                      int64_t ref_only_from = INT32_MAX, bool hist_done = false, unsigned *fine = nullptr)
 {
     const bool big_path = cursor != nullptr;  // adaptive mode: oversized buckets are sorted by all workgroups
     unsigned *bk_start = w.bkcnt.as<unsigned>() + MAX_BUCKETS;
@@ -2619,8 +2821,12 @@ static int bin_points(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, co
     hipLaunchKernelGGL(bucket_scatter_kernel, dim3(std::max(BinTiles::of((int)n).ntiles, 1)), dim3(SCATTER_THREADS), 0, ctx->stream, x, y, z, stride,
                        (int)first, (int)n, gp, bk_start, w.tileoff.as<unsigned>(), tmp, (int)std::min<int64_t>(ref_only_from, INT32_MAX));
     if (big_path) GSX_HIP(hipMemsetAsync(start, 0, sizeof(unsigned) * (size_t)(cell_cap + 1), ctx->stream));  // counts of big buckets
-    hipLaunchKernelGGL(bucket_sort_kernel, dim3(MAX_BUCKETS), dim3(SORT_THREADS), 0, ctx->stream, gp, bk_start, tmp, sorted, start,
-                       big_path ? BIG_BUCKET : 0xffffffffu);
+    if (fine)
+        hipLaunchKernelGGL(bucket_sort_kernel<true>, dim3(MAX_BUCKETS), dim3(SORT_THREADS), 0, ctx->stream, gp, bk_start, tmp, sorted, start,
+                           0xffffffffu, fine);
+    else
+        hipLaunchKernelGGL(bucket_sort_kernel<false>, dim3(MAX_BUCKETS), dim3(SORT_THREADS), 0, ctx->stream, gp, bk_start, tmp, sorted, start,
+                           big_path ? BIG_BUCKET : 0xffffffffu, (unsigned *)nullptr);
     if (big_path) {
         const int chunks = div_up(n, BIG_CHUNK);
         hipLaunchKernelGGL((big_bucket_kernel<false>), dim3(chunks), dim3(256), 0, ctx->stream, gp, bk_start, (int)n, tmp, sorted,
@@ -2716,12 +2922,25 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
     GridParams *gp = w.gridparams.as<GridParams>();
     float4 *refs = w.packed.as<float4>();
     unsigned *rstart = w.cellstart.as<unsigned>();
+    // Planned bricks (brick_plan_kernel): the plain single-cloud call only -- every point a query of the one table, no share, no
+    // slab halo, no refinement level -- and the kernels they were built for: 2x2x2-cell bricks (pts_per_cell as grid_params
+    // decides), k <= 16, MFMA filter + network selection.  An adaptive call qualifies once the coarse histogram has shown that
+    // nothing will be deferred (below).  The grid's extent along x is checked on the device (grid_params).
+    const bool mfma_ok = ctx->filter_mfma != 0 && n_ref < (int64_t(1) << 28);
+    bool plan = ctx->brick_plan != 0 && level == 0 && all && !slab && !sk && nshares == 1 && !anyk && kk <= 17 && mfma_ok &&
+                ctx->phase2_net != 0 && !(pts_per_cell * 8.0 > 66.0) && h_hint == 0.0 && kth_out == nullptr;
+    const int64_t plan_cap = n_ref / 16 + 4096;
+    if (plan) {
+        GSX_CHECK(w.finestart.reserve(sizeof(unsigned) * (size_t)(4 * cap + 4)));
+        GSX_CHECK(w.bricklist.reserve(sizeof(uint2) * (size_t)plan_cap));
+        GSX_CHECK(w.bundleoff.reserve(sizeof(unsigned) * 2 * (size_t)(MAX_DIM / 2) * (MAX_DIM / 2)));
+    }
 
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_BIN));
     // (adaptive mode may still switch the deferral off below, once the histogram is known: defer_words is then cleared on the device)
     GridParamArgs gpa{(int)n_ref, pts_per_cell, (int)cap, ctx->debug_skip, share, nshares, adaptive ? ctx->defer_words : 0, parent_h, gp,
                       ctx->devflags.as<unsigned>(), h_hint, sk ? sk->cert_axis : -1, sk ? sk->cert_lo : 0.0f, sk ? sk->cert_hi : 0.0f,
-                      sk ? sk->cert_count : nullptr};
+                      sk ? sk->cert_count : nullptr, plan ? 1 : 0, (int)plan_cap};
     const bool adaptive_at_bbox = adaptive;
     if (sk && sk->box.b7)
         hipLaunchKernelGGL(grid_params_known_box_kernel, dim3(1), dim3(64), 0, ctx->stream, sk->box, w.bboxpart.as<float>(), gpa);
@@ -2771,8 +2990,22 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
         GSX_HIP(hipMemsetAsync(&gp->defer_words, 0, sizeof(int), ctx->stream));
         GSX_HIP(hipMemsetAsync(&gp->heavy_limit, 0, sizeof(int), ctx->stream));
     }
+    if (plan && adaptive) {   // bricks may be deferred to a finer level: the fixed bricks, exactly as before
+        plan = false;
+        GSX_HIP(hipMemsetAsync(&gp->plan, 0, sizeof(int), ctx->stream));
+    }
+    unsigned *fstart = plan ? w.finestart.as<unsigned>() : nullptr;
     GSX_CHECK(bin_points(ctx, w, x, y, z, stride, 0, n_ref, gp, rstart, refs, cap, adaptive ? w.qcellstart.as<unsigned>() : nullptr,
-                         slab ? ref_only_from : INT32_MAX, hist_done));
+                         slab ? ref_only_from : INT32_MAX, hist_done, fstart));
+    if (plan) {   // one wave per bundle of 2x2 query rows (grid-stride): count + scan, then write
+        unsigned *bcnt = w.bundleoff.as<unsigned>(), *boff = bcnt + (size_t)(MAX_DIM / 2) * (MAX_DIM / 2);
+        const int pblocks = ctx->num_cu * 4;
+        hipLaunchKernelGGL(brick_plan_kernel<false>, dim3(pblocks), dim3(64 * PLAN_WAVES), 0, ctx->stream, gp, fstart, bcnt, boff,
+                           w.bricklist.as<uint2>());
+        hipLaunchKernelGGL(brick_plan_kernel<true>, dim3(pblocks), dim3(64 * PLAN_WAVES), 0, ctx->stream, gp, fstart, bcnt, boff,
+                           w.bricklist.as<uint2>());
+        GSX_HIP(hipGetLastError());
+    }
     const float4 *qpts = refs;
     const unsigned *qstart = rstart;
     if (!all) {
@@ -2785,7 +3018,8 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
 
     BrickLaunch a{gp, refs, rstart, qpts, qstart, k, q_begin, mean_out, kth_out, w.faillist.as<unsigned>(),
                   w.faillist.as<unsigned>() + std::max<int64_t>(q_count, 1),
-                  w.extraitems.as<uint2>(), w.deferred.as<unsigned>(), w.heavylist.as<unsigned>(), q_count, n_ref};
+                  w.extraitems.as<uint2>(), w.deferred.as<unsigned>(), w.heavylist.as<unsigned>(), q_count, n_ref,
+                  plan ? w.finestart.as<unsigned>() : nullptr, plan ? w.bricklist.as<uint2>() : nullptr};
     if (anyk) {
         GSX_CHECK(timing_begin(ctx, GSX_T_SOR_KNN));
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((q_count + 3) / 4, (int64_t)ctx->num_cu * 2));
@@ -2813,7 +3047,7 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
     }
     // (the MFMA kernels' phase 2 addresses the sorted points with 32-bit byte offsets: 16 * n_ref < 2^32; larger clouds take the
     //  scalar filter, which is exact as well)
-    GSX_CHECK(dispatch_bricks(ctx, a, ctx->filter_mfma != 0 && n_ref < (int64_t(1) << 28), ctx->phase2_net != 0));
+    GSX_CHECK(dispatch_bricks(ctx, a, mfma_ok, ctx->phase2_net != 0));
 
     const bool trace = getenv("GSX_TRACE_LEVELS") != nullptr;
     GridParams hgp;

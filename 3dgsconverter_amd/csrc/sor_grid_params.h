@@ -42,7 +42,12 @@ struct GridParams {
     unsigned ringf_ctr[8 * 32];
     // arrival tickets of the kernels whose last workgroup finishes the job of a former one-workgroup launch
     // (bbox_partial -> grid parameters, bucket_offsets -> bucket scan); never touched by grid_params, self-resetting
-    unsigned ticket_bbox, ticket_hist;
+    unsigned ticket_bbox, ticket_hist, ticket_plan;
+    // planned bricks (brick_plan_kernel): plan != 0 -- knn_brick's work items are the entries of the brick list, runs of
+    // quarter-cell slabs of a 2x2 bundle of query rows, instead of the fixed 2x2x2-cell bricks.  Requested by the host
+    // (plan_req), granted by grid_params for grids of at most 256 cells along x (the quarter index's rounding bound) and
+    // 2x2x2 bricks, withdrawn by brick_plan when the list would not fit plan_cap entries
+    int plan, plan_cap;
     // multi-GPU slab step: the certificate of csrc/dist_slab.hip evaluated where the k-th distance is produced (instead
     // of an 8-byte array written here and read back by a kernel of its own).  cert_axis < 0: off
     int cert_axis;

@@ -110,7 +110,8 @@ int  gsx_ctx_get_timing(gsx_ctx *ctx, int slot, uint64_t *launches, double *tota
  * grid level by level instead, DESIGN.md 5.5 -- kept for A/B and used by the replicated multi-GPU shares),
  * "tree_scale" (0, default: the tree path's density probe stretches the key grid by up to 2x so that the leaves of
  * a cloud with one dominant density are cubes of ~50 points; f > 0: that factor, no probe -- A/B; results are
- * bit-identical for every value), "filter_mfma" (1 = matrix-core phase-1 filter, default), "timing_mask" (bit s set = slot
+ * bit-identical for every value), "filter_mfma" (1 = matrix-core phase-1 filter, default), "brick_plan" (1 = knn_brick on planned bricks where the call allows them, default; 0 = the fixed bricks; bit-identical
+ * either way), "timing_mask" (bit s set = slot
  * GSX_T_s records events while timing is enabled; default all -- every event pair costs stream time),
  * "tree_leaf_cap" (0, default: points per leaf of the tree path by k -- 64 up to k = 28, 96 up to 34, 128 above; 64 ... 256: that
  * capacity; results are bit-identical for every value), "tree_cand_limit" (candidates per 64 points of leaf capacity above which
@@ -245,6 +246,10 @@ int gsx_sor_knn_dev(gsx_ctx *ctx, const float *x, const float *y, const float *z
 int gsx_sor_knn_share_dev(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride,
                           int64_t n, int k, int algo, int share, int nshares, float *mean_out_dev,
                           gsx_sor_info *info /* nullable; forces a sync if given */);
+/* Debug / tests: the brick plan of the context's last grid KNN call (context parameter brick_plan).
+ * grid[8] = nx, ny, nz, plan (1: the planned bricks ran), bricks, 0, 0, 0; origin[4] = ox, oy, oz, 1/h;
+ * list (nullable, room for cap entries of two words): {bundle of 2x2 query rows, first | last << 16 quarter-cell slab}. */
+int gsx_sor_debug_brick_plan(gsx_ctx *ctx, int32_t *grid, float *origin, uint32_t *list, int64_t cap);
 /*
  * np.mean / np.std / threshold -- replaces data_processor.py:176-178 and
  * gpu_ops.py:259-261 with numpy's exact float32 arithmetic (8192-element buffered

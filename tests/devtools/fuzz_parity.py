@@ -1,7 +1,7 @@
 """Randomised parity sweep on the GPU box: gsx_sor_filter (host API, adaptive grid, MFMA filter) and the device
-API with both filters against the cKDTree restatement, over random sizes / k / cloud shapes.  Not a test
-(tests/ holds a fixed subset); prints one line per case and a summary.  usage: python tests/devtools/fuzz_parity.py [cases] [seed]"""
-import importlib, os, sys, time
+API with every combination of filter_mfma, phase2_net and brick_plan against the cKDTree restatement, over random sizes /
+k / cloud shapes.  Not a test (tests/ holds a fixed subset); prints one line per case and a summary.  usage: python tests/devtools/fuzz_parity.py [cases] [seed]"""
+import importlib, itertools, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 gsx = importlib.import_module("3dgsconverter_amd")
@@ -46,16 +46,23 @@ def main(cases=40, seed=0):
         ref = osor.sor(xyz, k, 1.0)
         res = L.sor_filter(xyz, k, 1.0, want_info=True)
         ok = np.array_equal(res["mean_dists"].view(np.uint32), ref["mean_dists"].view(np.uint32)) and np.array_equal(res["mask"], ref["mask"])
-        dev_ok = True
+        dev_ok, dev_bad = True, []
         if n >= 2048:
             cols = [np.ascontiguousarray(xyz[:, a]) for a in range(3)]
             d = [ctx.alloc(4 * n).upload(col) for col in cols]
             out = ctx.alloc(4 * n)
-            for mf in (0, 1):
+            # every form of knn_brick dispatch_bricks can select: MFMA / scalar filter, network / bubble-insert selection, planned /
+            # fixed bricks (the plan runs only with both other switches on and k <= 16; asking for it elsewhere must change nothing)
+            for mf, net, plan in itertools.product((0, 1), (0, 1), (0, 1)):
                 ctx.set_param("filter_mfma", mf)
+                ctx.set_param("phase2_net", net)
+                ctx.set_param("brick_plan", plan)
                 ctx.sor_knn(d[0].ptr, d[1].ptr, d[2].ptr, 1, n, 0, n, k, out.ptr, algo=2)
                 got = out.download(np.float32, n)
-                dev_ok &= np.array_equal(got.view(np.uint32), ref["mean_dists"].view(np.uint32))
+                same = np.array_equal(got.view(np.uint32), ref["mean_dists"].view(np.uint32))
+                if not same:
+                    dev_bad.append("mfma%d-net%d-plan%d" % (mf, net, plan))
+                dev_ok &= same
             for a in d + [out]:
                 a.free()
         tree_ok, tinfo = True, None
@@ -64,8 +71,8 @@ def main(cases=40, seed=0):
             tinfo = rt["info"]
             tree_ok = np.array_equal(rt["mean_dists"].view(np.uint32), ref["mean_dists"].view(np.uint32)) and np.array_equal(rt["mask"], ref["mask"])
         bad += not (ok and dev_ok and tree_ok)
-        print("%3d %-10s n=%7d k=%2d host=%s(algo %d) dev(mf0,mf1)=%s tree=%s deferred=%d refined=%d%s" % (
-            c, kind, n, k, "ok" if ok else "MISMATCH", res["info"]["algo"], "ok" if dev_ok else "MISMATCH", "ok" if tree_ok else "MISMATCH",
+        print("%3d %-10s n=%7d k=%2d host=%s(algo %d) dev(mfma x net x plan)=%s tree=%s deferred=%d refined=%d%s" % (
+            c, kind, n, k, "ok" if ok else "MISMATCH", res["info"]["algo"], "ok" if dev_ok else "MISMATCH " + ",".join(dev_bad), "ok" if tree_ok else "MISMATCH",
             res["info"]["n_deferred_bricks"], res["info"]["n_refined"],
             "" if tinfo is None else " leaves=%d near=%d descents=%d" % (tinfo["n_bricks"], tinfo["n_fallback"], tinfo["n_exhaustive"])), flush=True)
     ctx.close()

@@ -126,8 +126,9 @@ def sha(rows: np.ndarray) -> bytes:
     return hashlib.sha256(np.ascontiguousarray(rows).tobytes()).digest()
 
 
-def scene_file(path, n, degree, seed, chunks=None):
-    """a synthetic file of n rows: random words, random finite bounds (min <= max), `chunks` chunk rows (default ceil(n / 256))"""
+def scene_file(path, n, degree, seed, chunks=None, n_sh=None):
+    """a synthetic file of n rows: random words, random finite bounds (min <= max), `chunks` chunk rows (default ceil(n / 256));
+    the sh element has the degree's width, or `n_sh` properties (any width, 0 = no sh element) when that is given"""
     rng = np.random.default_rng(seed)
     nc = (n + 255) // 256 if chunks is None else chunks
     ch = np.zeros(nc, [(f, "<f4") for f in CHUNK_FIELDS])
@@ -141,11 +142,59 @@ def scene_file(path, n, degree, seed, chunks=None):
     for f in VERTEX_FIELDS:
         vt[f] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
     els = [("chunk", ch), ("vertex", vt)]
-    m = {0: 0, 1: 9, 2: 24, 3: 45}[degree]
+    m = {0: 0, 1: 9, 2: 24, 3: 45}[degree] if n_sh is None else n_sh
     if m:
         sh = np.zeros(n, [("f_rest_%d" % i, "u1") for i in range(m)])
         raw = rng.integers(0, 256, (n, m), dtype=np.uint8)
         sh.view(np.uint8).reshape(n, m)[:] = raw
         els.append(("sh", sh))
     write_ply(path, els)
+    return path
+
+
+ROT_EDGE = (0, 1, 511, 512, 1022, 1023)
+PATTERN_ROWS, PATTERN_SH = 4096, 45
+# odd multipliers (so i * m runs through a slot's whole range), no two alike: position y, z | scale y, x | r g b a
+PATTERN_MUL = {"pos": (5, 7), "scale": (11, 13), "colour": (1, 3, 5, 7)}
+
+
+def pattern_tables():
+    """(chunk, vertex, sh) of pattern_file: 4096 rows in 16 chunks.  Row i holds
+      position  x = i mod 2048 (bits 21-31), y = 5 i mod 1024 (bits 11-20), z = 7 i mod 2048 (bits 0-10);
+      scale     the same scheme from the other end: z = i mod 2048, y = 11 i mod 1024, x = 13 i mod 2048;
+      colour    r = i, g = 3 i, b = 5 i, alpha = 7 i, each mod 256;
+      rotation  combination i mod 864 of largest (4) x the edge codes 0, 1, 511, 512, 1022, 1023 in each 10-bit slot (6^3);
+      sh        slot k = ((2 k + 1) i + k) mod 256, k < 45;
+    every one of the 18 bounds of every chunk is a float32 of its own (min < max)."""
+    n = PATTERN_ROWS
+    i = np.arange(n, dtype=np.uint64)
+    vt = np.zeros(n, [(f, "<u4") for f in VERTEX_FIELDS])
+    a, b = PATTERN_MUL["pos"]
+    vt["packed_position"] = ((i % 2048) << 21 | (i * a % 1024) << 11 | (i * b % 2048)).astype(np.uint32)
+    a, b = PATTERN_MUL["scale"]
+    vt["packed_scale"] = ((i * b % 2048) << 21 | (i * a % 1024) << 11 | (i % 2048)).astype(np.uint32)
+    m = PATTERN_MUL["colour"]
+    vt["packed_color"] = ((i * m[0] % 256) << 24 | (i * m[1] % 256) << 16 | (i * m[2] % 256) << 8 | (i * m[3] % 256)).astype(np.uint32)
+    e = np.array(ROT_EDGE, np.uint64)
+    c = i % (4 * 6 ** 3)
+    vt["packed_rotation"] = ((c // 216) << 30 | e[c // 36 % 6] << 20 | e[c // 6 % 6] << 10 | e[c % 6]).astype(np.uint32)
+    sh = np.zeros(n, [("f_rest_%d" % k, "u1") for k in range(PATTERN_SH)])
+    for k in range(PATTERN_SH):
+        sh["f_rest_%d" % k] = ((2 * k + 1) * i + k) % 256
+    nc = n // 256
+    ch = np.zeros(nc, [(f, "<f4") for f in CHUNK_FIELDS])
+    for group in (0, 6, 12):
+        for k in range(3):
+            axis = group // 2 + k                                     # 0 .. 8
+            lo = (-8.0 + 2.0 * axis + np.arange(nc) / 16.0).astype(np.float32)   # exact in float32, as is the width
+            ch[CHUNK_FIELDS[group + k]] = lo
+            ch[CHUNK_FIELDS[group + 3 + k]] = lo + np.float32(1.0 + (4 + axis) / 256.0)
+    allb = np.stack([ch[f] for f in CHUNK_FIELDS])
+    assert len(np.unique(allb)) == allb.size and all((ch[CHUNK_FIELDS[g + k]] < ch[CHUNK_FIELDS[g + 3 + k]]).all() for g in (0, 6, 12) for k in range(3))
+    return ch, vt, sh
+
+
+def pattern_file(path):
+    ch, vt, sh = pattern_tables()
+    write_ply(path, [("chunk", ch), ("vertex", vt), ("sh", sh)])
     return path

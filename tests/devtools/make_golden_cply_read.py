@@ -1,4 +1,5 @@
-"""Build tests/golden/cply_read_ref.npz from the REFERENCE's own compressed-PLY reader (build box only: needs the reference).
+"""Build tests/golden/cply_read_ref.npz, or with --wide tests/golden/cply_read_wide_ref.npz, from the REFERENCE's own
+compressed-PLY reader (build box only: needs the reference).
 
 The reference's ``CompressedPlyFormat.read`` (formats/compressed_ply.py:14-124) runs unchanged; only ``plyfile.PlyData.read``
 (plyfile is not installed here) is replaced by a small numpy parser of the binary container.  The input files are stored whole:
@@ -6,7 +7,12 @@ files the reference's own writer made from oracle.cply scenes (its ``_write_ply_
 plyfile's layout), and synthetic files with edge words and edge bounds.  Outputs are stored whole for small cases, as sha256
 of the row bytes for larger ones.
 
-    python tests/devtools/make_golden_cply_read.py
+The wide file (wide_cases) holds sh elements of 38, 89, 192 and 256 properties -- one per tile geometry of csrc/cply_read.hip
+past the degree-3 width -- the NaN chunks of edge_bounds under a 100-property sh element, and a 257-property file that the
+reference reads and the device path refuses.  It has an rng of its own: cases() and cply_read_ref.npz are not touched by it.
+
+    python tests/devtools/make_golden_cply_read.py            # cply_read_ref.npz
+    python tests/devtools/make_golden_cply_read.py --wide     # cply_read_wide_ref.npz
 """
 import io
 import json
@@ -24,6 +30,7 @@ import cply_read_numpy as crn  # noqa: E402
 from oracle import cply as ocply, refload  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "cply_read_ref.npz")
+OUT_WIDE = os.path.join(ROOT, "tests", "golden", "cply_read_wide_ref.npz")
 WHOLE_BELOW = 40000          # row bytes up to this are stored whole
 
 
@@ -182,11 +189,49 @@ def cases(tmp):
     return out
 
 
-def main():
+# the chunk rows of edge_bounds() whose bounds reach each return of x86_nan (row_tile.h): an invalid operation of two numbers
+# (-inf .. inf gives inf * 0 where a slot holds 0, inf .. inf gives inf - inf in every row), both NaN (max's bits win), a NaN
+# max alone, a NaN min alone.  The chunk with both bounds NaN must be a whole one: there `(nv / t) * d + min` adds two NaNs,
+# and which of them numpy's vectorised add returns depends on the element's place in the array -- on the AVX-512 build host
+# the elements behind the last whole vector of 8 of an array longer than 8 take min's bits, all others max's.  A chunk of 256
+# rows has no such tail, a partial last chunk has one, and its bits are the host's, not the reference's.
+NAN_CHUNKS = [2, 3, 10, 9, 8]
+
+
+def wide_cases(tmp):
+    rng = np.random.default_rng(20261018)
+    out = []
+
+    def add(name, elements):
+        path = os.path.join(tmp, name + ".ply")
+        crn.write_ply(path, elements)
+        out.append((name, path))
+
+    def renamed(sh, names):
+        return sh.view([(f, "u1") for f in names])
+
+    # 290 rows: two chunks, the second one 34 rows, which ends inside a tile of 128, 64 or 32 rows
+    n = 256 + 34
+    add("sh38", [("chunk", chunk_table(2, rng)), ("vertex", vertex_table(n, rng)), ("sh", sh_table(n, 38, rng))])
+    add("sh89_permuted", [("chunk", chunk_table(2, rng)), ("vertex", vertex_table(n, rng)),
+                          ("sh", renamed(sh_table(n, 89, rng), ["f_rest_%d" % i for i in rng.permutation(89)]))])
+    add("sh192_other_names", [("chunk", chunk_table(2, rng)), ("vertex", vertex_table(n, rng)),
+                              ("sh", renamed(sh_table(n, 192, rng), ["coeff_%03d" % (191 - i) if i % 3 else "b%d" % i for i in range(192)]))])
+    add("sh256", [("chunk", chunk_table(2, rng)), ("vertex", vertex_table(n, rng)), ("sh", sh_table(n, 256, rng))])
+    # the NaN cold path at 64-row tiles: edge_bounds() trimmed to its NaN chunks (the 17 whole ones would take 505 KB of
+    # random bytes), the last one 70 rows, which ends inside a tile
+    n_e = 256 * (len(NAN_CHUNKS) - 1) + 70
+    add("edge_bounds_sh100", [("chunk", edge_bounds()[NAN_CHUNKS]), ("vertex", vertex_table(n_e, rng)), ("sh", sh_table(n_e, 100, rng))])
+    # one property more than the device path takes: the reference reads it
+    add("sh257_refused", [("chunk", chunk_table(1, rng)), ("vertex", vertex_table(40, rng)), ("sh", sh_table(40, 257, rng))])
+    return out
+
+
+def record(make_cases, out_path):
     import tempfile
     spec, arrays = {}, {}
     with tempfile.TemporaryDirectory() as tmp:
-        for name, path in cases(tmp):
+        for name, path in make_cases(tmp):
             with open(path, "rb") as f:
                 arrays[name + "__file"] = np.frombuffer(f.read(), np.uint8)
             rows, meta, err = reference_read(path)
@@ -209,10 +254,22 @@ def main():
     arrays["spec"] = np.frombuffer(json.dumps(spec, sort_keys=True).encode(), np.uint8)
     buf = io.BytesIO()
     np.savez_compressed(buf, **arrays)
-    with open(OUT, "wb") as f:
+    with open(out_path, "wb") as f:
         f.write(buf.getvalue())
-    print(OUT, len(buf.getvalue()), "bytes")
+    print(out_path, len(buf.getvalue()), "bytes")
+    return spec
+
+
+def main():
+    record(cases, OUT)
+
+
+def main_wide():
+    spec = record(wide_cases, OUT_WIDE)
+    assert not any("error" in r for r in spec.values()) and spec["edge_bounds_sh100"]["nan_rows"] == 1
+    assert [spec[k]["metadata"]["sh_degree"] for k in ("sh38", "sh89_permuted", "sh192_other_names", "sh256", "sh257_refused")] == [2, 3, 3, 3, 3]
+    assert os.path.getsize(OUT_WIDE) <= os.path.getsize(OUT)
 
 
 if __name__ == "__main__":
-    main()
+    main_wide() if sys.argv[1:] == ["--wide"] else main()

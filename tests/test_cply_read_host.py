@@ -1,6 +1,7 @@
 """-m "not gpu": the compressed-PLY reader's host side -- the header parser, what goes to the reference's own reader and what
-is refused, the reference's errors before any device work, the numpy restatement against the reference's rows
-(tests/golden/cply_read_ref.npz), the host tables, and the install() binding of CompressedPlyFormat.read."""
+is refused (257 sh properties and a short sh element among it), the reference's errors before any device work, the numpy
+restatement against the reference's rows (tests/golden/cply_read_ref.npz, and cply_read_wide_ref.npz for sh elements of 38 to
+257 properties), the host tables, and the install() binding of CompressedPlyFormat.read."""
 import importlib
 import json
 import os
@@ -14,11 +15,18 @@ import cply_read_numpy as crn  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "cply_read_ref.npz")
+GOLD_WIDE = os.path.join(ROOT, "tests", "golden", "cply_read_wide_ref.npz")
 
 
 @pytest.fixture(scope="module")
 def gold():
     g = np.load(GOLD)
+    return g, json.loads(bytes(g["spec"]).decode())
+
+
+@pytest.fixture(scope="module")
+def gold_wide():
+    g = np.load(GOLD_WIDE)
     return g, json.loads(bytes(g["spec"]).decode())
 
 
@@ -136,6 +144,88 @@ def test_restatement_equals_every_golden_case(gold, tmp_path):
         checked += 1
     assert checked == 14
     assert spec["edge_bounds"]["nan_rows"] == 1
+
+
+def test_restatement_equals_every_wide_golden_case(gold_wide, tmp_path):
+    g, spec = gold_wide
+    checked = 0
+    for name, rec in spec.items():
+        assert "error" not in rec, name
+        rows, meta = crn.read(_file(g, name, tmp_path))
+        assert list(rows.dtype.names) == rec["names"] and meta == rec["metadata"], name
+        assert [rows.dtype[f].str for f in rows.dtype.names] == rec["dtype"], name
+        if name + "__rows" in g:
+            assert rows.tobytes() == g[name + "__rows"].tobytes(), name
+        else:
+            assert crn.sha(rows) == g[name + "__sha256"].tobytes(), name
+        checked += 1
+    assert checked == 6
+    assert sorted(len(r["names"]) - 17 for r in spec.values()) == [38, 89, 100, 192, 256, 257]
+    assert spec["edge_bounds_sh100"]["nan_rows"] == 1 and spec["edge_bounds_sh100"]["metadata"]["chunks"] == 5
+    assert spec["sh89_permuted"]["names"][17:] != ["f_rest_%d" % i for i in range(89)]
+    assert sorted(spec["sh89_permuted"]["names"][17:]) == sorted("f_rest_%d" % i for i in range(89))
+    assert not any(n.startswith("f_rest_") for n in spec["sh192_other_names"]["names"])
+
+
+def _refused(reader, path, match):
+    """`path` is refused for `match`: UnsupportedPlyError without a fallback, the fallback's result with one"""
+    assert match in reader.parse_header(path).refusal()
+    with pytest.raises(reader.UnsupportedPlyError, match=match):
+        reader.read_compressed_ply(path)
+    assert reader.read_compressed_ply(path, fallback=lambda p: ("ref", p)) == ("ref", path)
+
+
+def test_257_sh_properties_go_to_the_reference_or_are_refused(gold_wide, reader, lib, tmp_path, monkeypatch):
+    g, spec = gold_wide
+    _no_device(monkeypatch, lib)
+    path = _file(g, "sh257_refused", tmp_path)
+    assert len(spec["sh257_refused"]["names"]) == 17 + 257
+    assert reader.parse_header(path).refusal() == "257 sh properties (the device path reads up to 256)"
+    _refused(reader, path, "257 sh properties")
+
+
+def _with_sh_rows(path, n, chunks, sh_rows):
+    ch = np.zeros(chunks, [(f, "<f4") for f in crn.CHUNK_FIELDS])
+    vt = np.zeros(n, [(f, "<u4") for f in crn.VERTEX_FIELDS])
+    crn.write_ply(path, [("chunk", ch), ("vertex", vt), ("sh", np.zeros(sh_rows, [("f_rest_%d" % i, "u1") for i in range(9)]))])
+    return path
+
+
+@pytest.mark.parametrize("n,chunks,sh_rows", [(300, 2, 299), (700, 2, 511), (300, 1, 0)])
+def test_short_sh_element_goes_to_the_reference_or_is_refused(reader, lib, tmp_path, monkeypatch, n, chunks, sh_rows):
+    """fewer sh rows than min(vertex.count, 256 x chunk.count), the rows the kernel decodes"""
+    _no_device(monkeypatch, lib)
+    path = _with_sh_rows(str(tmp_path / "s.ply"), n, chunks, sh_rows)
+    assert reader.parse_header(path).refusal() == "an sh element of %d rows for %d vertices" % (sh_rows, n)
+    _refused(reader, path, "an sh element of %d rows for %d vertices" % (sh_rows, n))
+
+
+def test_sh_element_shorter_than_the_vertices_but_not_than_the_decoded_rows_is_taken(reader, lib, tmp_path, monkeypatch):
+    path = _with_sh_rows(str(tmp_path / "s.ply"), 700, 2, 512)
+    h = reader.parse_header(path)
+    assert h.refusal() is None
+    seen = {}
+
+    def unpack(path_, segments, layout, n_chunks, n_vertices, dtype, stage_ms=None):
+        seen.update(segments=segments, n_chunks=n_chunks, n_vertices=n_vertices, n_sh=layout.n_sh)
+        return np.zeros(n_vertices, dtype)
+    monkeypatch.setattr(lib, "cply_unpack_table", unpack)
+    rows, meta = reader.read_compressed_ply(path, fallback=lambda p: pytest.fail("handed to the fallback"))
+    assert meta == {"count": 700, "sh_degree": 1, "chunks": 2} and len(rows) == 700
+    sh = h.element("sh")
+    assert seen["segments"]["sh"] == (sh.body_offset, 9 * 512) and seen["segments"]["vertex"][1] == 16 * 512
+    assert (seen["n_chunks"], seen["n_vertices"], seen["n_sh"]) == (2, 700, 9)
+
+
+def test_layout_of_a_256_property_sh_element(gold_wide, reader, tmp_path):
+    g, spec = gold_wide
+    h = reader.parse_header(_file(g, "sh256", tmp_path))
+    assert h.refusal() is None
+    lay = reader.layout_of(h)
+    assert lay.n_sh == 256 and lay.sh_stride == 256
+    assert [lay.sh_offset[i] for i in range(256)] == list(range(256))
+    assert h.element("sh").names() == spec["sh256"]["names"][17:] == ["f_rest_%d" % i for i in range(256)]
+    assert lay.chunk_stride == 72 and lay.vertex_stride == 16 and list(lay.vertex_offset) == [0, 4, 8, 12]
 
 
 def test_host_tables_are_numpys_results(lib):

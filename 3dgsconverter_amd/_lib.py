@@ -239,6 +239,7 @@ SIGNATURES = {
     "gsx_cply_unpack_dev": (_I, [_P, _P, _I64, _P, _I64, _P, C.POINTER(CplyReadLayout), _P, _P]),
     "gsx_ksplat_unpack_dev": (_I, [_P, _P, _I64, _I, C.POINTER(KsplatReadSection), _I, _P, _I64, _P, _I, _P, _I64]),
     "gsx_spz_unpack_dev": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _I64]),
+    "gsx_sog_unpack_dev": (_I, [_P, _P, _I64, C.POINTER(_I64), _I, _I64, _P, _P, _I64, _P]),
 }
 
 _lib = None
@@ -1811,6 +1812,113 @@ def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractiona
         check(lib.gsx_spz_unpack_dev(ctx.handle, d_in.ptr, total, int(version), int(degree), int(fractional_bits), d_tab.ptr, d_out.ptr, n),
               "gsx_spz_unpack_dev")
         s.mark("kernel")
+        join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.mark("download")
+        return out
+
+
+_sog_read_fixed = None
+SOG_READ_TABLES = ("scale_cb", "sh0_cb", "shn_cb", "opacity", "quat", "pos")       # GSX_SOG_TAB_* order (include/gsx_hip.h)
+SOG_READ_TEXTURES = ("means_l", "means_u", "scales", "quats", "sh0", "shN_labels", "shN_centroids")   # gsx_sog_unpack_dev's order
+SOG_COEFFS_PER_BAND = (0, 9, 24, 45)      # sog.py:170
+
+
+def sog_read_tables(mins, maxs, scale_codebook, sh0_codebook, shn_codebook=None) -> dict:
+    """The SOG reader's tables, numpy's own results for the reference's statements on every input (formats/sog.py), each with
+    the reference's expression and operand dtypes -- so the device takes no exp and no log:
+    "scale_cb", "sh0_cb", "shn_cb" f4[len] :94, :149, :205, np.array(codebook, dtype=np.float32) as long as the file's (shn_cb
+    empty without one) | "opacity" f4[256] :156-158 | "quat" f4[256] :108 | "pos" f4[3][65536] :78-86: the u16 code divided by
+    65535.0 is float64 and so is all that follows, mins and maxs being the JSON's Python numbers; rounded once to float32, as
+    the assignment into the float32 field does"""
+    global _sog_read_fixed
+    with np.errstate(all="ignore"):
+        if _sog_read_fixed is None:
+            b = np.arange(256, dtype=np.uint8)
+            alpha = np.clip(b.astype(np.float32) / 255.0, 1.0 / 255.0, 0.9999)
+            opa = -np.log((1.0 / alpha) - 1.0)
+            quat = (b.astype(np.float32) / 255.0 - 0.5) * 2.0
+            assert opa.dtype == np.float32 and quat.dtype == np.float32
+            _sog_read_fixed = (opa, quat)
+        qv = np.arange(65536, dtype=np.uint32).astype(np.uint16)
+        pos = np.empty((3, 65536), np.float32)
+        for idx in range(3):
+            norm = qv / 65535.0
+            log_val = norm * (maxs[idx] - mins[idx]) + mins[idx]
+            pos[idx] = np.sign(log_val) * (np.exp(np.abs(log_val)) - 1.0)
+        assert norm.dtype == np.float64
+    cbs = [np.array(cb if cb is not None else [], dtype=np.float32) for cb in (scale_codebook, sh0_codebook, shn_codebook)]
+    return dict(zip(SOG_READ_TABLES, (*cbs, *_sog_read_fixed, pos)))
+
+
+def sog_read_table_words(tables: dict) -> np.ndarray:
+    """sog_read_tables() as the device takes them: uint32[GSX_SOG_TAB_WORDS], the float32 bits; each codebook's first 256 entries
+    (bytes index it), a shorter one padded with zeros (the caller has checked the indices against it)"""
+    words = np.zeros(1280 + 3 * 65536, np.uint32)
+    for k, name in enumerate(SOG_READ_TABLES[:5]):
+        t = np.ascontiguousarray(tables[name], np.float32).reshape(-1)[:256]
+        words[256 * k:256 * k + len(t)] = t.view(np.uint32)
+    words[1280:] = np.ascontiguousarray(tables["pos"], np.float32).reshape(-1).view(np.uint32)
+    return words
+
+
+def sog_texel_layout(n: int, bands: int, palette: int):
+    """-> ({texture: (byte offset, bytes)}, total): where each texture's texels lie in the staging buffer, SOG_READ_TEXTURES'
+    order, each at a 16-byte boundary -- the first n RGBA texels of a per-row texture; of the centroid image the first 64 C
+    pixels of each of its ceil(palette / 64) rows of 64 * 3 C (the only ones sog.py:190-202 reads), C coefficients per channel"""
+    place, total = {}, 0
+    for name in SOG_READ_TEXTURES[:6 if bands else 5]:
+        place[name] = (total, 4 * n)
+        total += (4 * n + 15) & ~15
+    if bands:
+        c = SOG_COEFFS_PER_BAND[bands] // 3
+        nb = 4 * 64 * c * ((palette + 63) // 64)
+        place["shN_centroids"] = (total, nb)
+        total += (nb + 15) & ~15
+    return place, total
+
+
+def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, dtype: np.dtype, on_flag=None,
+                     stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+    """The SOG reader's rows (formats/sog.py:60-247) from a bundle whose meta.json the caller has parsed and checked
+    (formats/sog_reader.py): ``fill(view, place)`` decodes the textures' texels straight into page-locked staging
+    (sog_texel_layout; it raises what the reference raises on a missing or short texture: nothing has been uploaded then), one
+    upload of the staging and one of `tables` (sog_read_tables), decoded by gsx_sog_unpack_dev and downloaded into a prefaulted
+    array of `dtype` (packed rows of 68 + 4 * 9 / 24 / 45 bytes).  A label at or above `palette` makes the kernel set a flag:
+    ``on_flag(view, place)`` then raises numpy's own error from the host texels and no rows are returned.
+
+    One ArenaSession of the "sogread" lease group."""
+    lib = require_hip()
+    n, bands, palette = int(n_rows), int(bands), int(palette)
+    rb = dtype.itemsize
+    if bands not in (0, 1, 2, 3) or rb != 68 + 4 * SOG_COEFFS_PER_BAND[bands] or n < 1 or (bands and not 1 <= palette <= 65536):
+        raise ValueError("sog_unpack_table: %d rows of %d bytes, %d bands, a palette of %d" % (n, rb, bands, palette))
+    place, total = sog_texel_layout(n, bands, palette)
+    host_tab = sog_read_table_words(tables)
+    out = np.empty(n, dtype)
+    with ArenaSession("sogread", device, stage_ms) as s:
+        join = prefault(out.nbytes >= (1 << 22), out)
+        host = s.staging("in", total)
+        fill(host, place)
+        ctx = s.ctx
+        s.mark("decode")
+        d_in = s.buf("in", total + 32)             # spare bytes behind the last texel: no load reaches past the allocation
+        d_tab = s.buf("tables", host_tab.nbytes)
+        d_flag = s.buf("flag", 16)
+        s.upload_staging(lib, d_in.ptr, host)
+        d_tab.upload(host_tab)
+        check(lib.gsx_dev_memset(ctx.handle, d_flag.ptr, 0, 16), "gsx_dev_memset")
+        s.mark("upload")
+        d_out = s.buf("out", n * rb)
+        offsets = (_I64 * 7)(*[place[t][0] if t in place else -1 for t in SOG_READ_TEXTURES])
+        check(lib.gsx_sog_unpack_dev(ctx.handle, d_in.ptr, total, offsets, bands, palette, d_tab.ptr, d_out.ptr, n, d_flag.ptr),
+              "gsx_sog_unpack_dev")
+        s.mark("kernel")
+        if bands and int(d_flag.download(np.uint32, 1)[0]):
+            join()
+            if on_flag is not None:
+                on_flag(host, place)
+            raise IndexError("sog_unpack_table: a label at or above the palette's %d entries" % palette)
         join()
         check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
         s.mark("download")

@@ -20,7 +20,7 @@ _saved = {}
 
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
-            cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True):
+            cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True, sog_reader: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -42,7 +42,12 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     bucket assignment -- go to the reference's own read.  A reference without that module is left as it is.
     spz_reader: also rebind ``gsconverter.formats.spz.SpzFormat.read`` to formats/spz_reader.py (streamed inflate into page-locked
     staging and the header on the host, every row decoded on the GPU; the reference's rows and its exceptions on malformed
-    files).  A file of SH degree above 3 goes to the reference's own read.  A reference without that module is left as it is."""
+    files).  A file of SH degree above 3 goes to the reference's own read.  A reference without that module is left as it is.
+    sog_reader: also rebind ``gsconverter.formats.sog.SogFormat.read`` to formats/sog_reader.py (the bundle, meta.json and the
+    threaded WebP decode into page-locked staging on the host, every row decoded on the GPU; the reference's rows and its
+    exceptions on malformed files).  A file whose meta.json the device path does not take -- bands outside 1 ... 3, a palette
+    outside 1 ... 65 536, values of other types than the writer's -- goes to the reference's own read.  A reference without
+    that module is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -137,6 +142,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.spz_reader import bind_read as bind_spz_read
             _saved.setdefault(("spzformat", "read"), spzmod.SpzFormat.read)
             spzmod.SpzFormat.read = bind_spz_read(_saved[("spzformat", "read")])
+    if sog_reader:
+        try:
+            sogmod = importlib.import_module("gsconverter.formats.sog")
+        except ImportError:
+            sogmod = None
+        if sogmod is not None and getattr(sogmod.SogFormat, "read", None) is not None:
+            from .formats.sog_reader import bind_read as bind_sog_read
+            _saved.setdefault(("sogformat", "read"), sogmod.SogFormat.read)
+            sogmod.SogFormat.read = bind_sog_read(_saved[("sogformat", "read")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -146,7 +160,7 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
 def uninstall():
     for (modname, attr), val in list(_saved.items()):
         if modname == "sogformat":
-            importlib.import_module("gsconverter.formats.sog").SogFormat.write = val
+            setattr(importlib.import_module("gsconverter.formats.sog").SogFormat, attr, val)
             continue
         if modname == "cplyformat":
             setattr(importlib.import_module("gsconverter.formats.compressed_ply").CompressedPlyFormat, attr, val)
@@ -158,7 +172,7 @@ def uninstall():
             setattr(importlib.import_module("gsconverter.formats.ksplat").KSplatFormat, attr, val)
             continue
         if modname == "splatformat":
-            importlib.import_module("gsconverter.formats.splat").SplatFormat.write = val
+            setattr(importlib.import_module("gsconverter.formats.splat").SplatFormat, attr, val)
             continue
         if modname == "sys.modules":
             if val is None:

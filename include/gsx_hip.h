@@ -790,6 +790,32 @@ int gsx_ksplat_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t body_bytes
 int gsx_spz_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t body_bytes, int version, int sh_degree, int fractional_bits,
                        const void *tables_dev, void *out_dev, int64_t n);
 
+
+/* ---- the SOG reader (csrc/sog_read.hip) ----
+ * gsconverter/formats/sog.py:23-247 (SogFormat.read) from the textures' decoded RGBA texels: positions (:67-86), scales
+ * (:92-102), rotation (:106-142), f_dc and opacity (:147-158), the shN palette (:183-225) -> the reference's rows in
+ * GaussianStruct.define_dtype(has_scal=False, has_rgb=False)'s order, x y z nx ny nz f_dc_0..2 f_rest_0.. opacity scale_0..2
+ * rot_0..3 as float32, packed (68, 104, 164 or 248 bytes a row for 0 ... 3 bands), bit for bit.  The bundle is opened, checked
+ * and decoded to texels by the caller (formats/sog_reader.py).
+ * tables_dev: the host-built tables (numpy's own results), float32 as 32-bit words: the scales codebook [256] | the sh0
+ * codebook [256] | the shN codebook [256] | the opacity logit of alpha byte b [256] | the rotation component (b / 255 - 0.5) * 2
+ * [256] | the position of u16 code c on axis a [3][65536].  A shorter codebook is padded: the caller has checked its indices. */
+#define GSX_SOG_TAB_SCALE 0
+#define GSX_SOG_TAB_SH0 256
+#define GSX_SOG_TAB_SHN 512
+#define GSX_SOG_TAB_OPA 768
+#define GSX_SOG_TAB_QUAT 1024
+#define GSX_SOG_TAB_POS 1280
+#define GSX_SOG_TAB_WORDS (1280 + 3 * 65536)
+/* texels_dev: 16-byte aligned; offsets[7]: the byte offsets (multiples of 4) inside it of the first n RGBA texels of means_l,
+ * means_u, scales, quats, sh0 and shN_labels, and of the centroid pixels -- the first 64 C pixels of every centroid image row
+ * of 64 * 3 C, C = 3 / 8 / 15 coefficients per channel, row after row, so that pixel (label, j) is number label * C + j;
+ * palette * C of them must be there.  The last two are ignored at 0 bands.  palette 1 ... 65536: a label at or above it sets
+ * *flag_dev (which the caller has zeroed) and reads nothing; that row's f_rest are then unspecified.  out_dev: n packed rows,
+ * 16-byte aligned; n < 2^32.  One launch.  Asynchronous. */
+int gsx_sog_unpack_dev(gsx_ctx *ctx, const void *texels_dev, int64_t texels_bytes, const int64_t *offsets, int bands, int64_t palette,
+                       const void *tables_dev, void *out_dev, int64_t n, uint32_t *flag_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,8 @@ SIGNATURES = {
     "gsx_sor_knn_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _P, C.POINTER(SorInfo)]),
     "gsx_sor_knn_share_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, C.POINTER(SorInfo)]),
     "gsx_sor_debug_brick_plan": (_I, [_P, _P, _P, _P, _I64]),
+    "gsx_sor_debug_work_queue": (_I, [_P, _P, _P, _P]),
+    "gsx_sor_debug_wave_stamps": (_I, [_P, _I, _P, _I64, _P]),
     "gsx_sor_stats_dev": (_I, [_P, _P, _I64, _D, _P]),
     "gsx_sor_mask_dev": (_I, [_P, _P, _I64, _P, _P]),
     "gsx_comm_unique_id": (_I, [_P]),
@@ -2044,6 +2046,30 @@ class Context:
         runs = np.stack([buf[:m, 0], buf[:m, 1] & 0xffff, buf[:m, 1] >> 16], axis=1).astype(np.int64)
         return {"nx": int(grid[0]), "ny": int(grid[1]), "nz": int(grid[2]), "plan": int(grid[3]), "bricks": int(grid[4]),
                 "origin": np.array(list(origin), np.float32), "runs": runs}
+
+    def debug_work_queue(self):
+        """work queues of this context's last grid KNN call: dict(name -> dict(ctr = final tail counters of the eight groups,
+        items, blocks = workgroups of the launch, four waves each)) for knn_brick, knn_brick_extra, knn_ring, knn_ring_fast"""
+        import numpy as np
+        ctr = np.zeros((4, 8), np.uint32)
+        items = np.zeros(4, np.int64)
+        blocks = np.zeros(4, np.int32)
+        check(self.lib.gsx_sor_debug_work_queue(self.handle, ctr.ctypes.data_as(C.c_void_p), items.ctypes.data_as(C.c_void_p),
+                                                blocks.ctypes.data_as(C.c_void_p)), "gsx_sor_debug_work_queue")
+        names = ("knn_brick", "knn_brick_extra", "knn_ring", "knn_ring_fast")
+        return {nm: {"ctr": ctr[i].astype(np.int64), "items": int(items[i]), "blocks": int(blocks[i])} for i, nm in enumerate(names)}
+
+    def debug_wave_stamps(self, kernel: int):
+        """diagnostic builds (-DGSX_WAVE_STAMPS) only: (waves, 16) uint64 records of knn_brick (kernel 0) or knn_ring_fast
+        (kernel 1) of this context's last grid KNN call, the waves that wrote none left out (tools/wave_stamps.py)"""
+        import numpy as np
+        cap = 1 << 14
+        buf = np.zeros((cap, 16), np.uint64)
+        count = C.c_int64()
+        check(self.lib.gsx_sor_debug_wave_stamps(self.handle, int(kernel), buf.ctypes.data_as(C.c_void_p), cap, C.byref(count)),
+              "gsx_sor_debug_wave_stamps")
+        rec = buf[:min(cap, int(count.value))]
+        return rec[rec[:, 14] == 1]
 
     def sor_stats(self, mean_dists: int, n: int, threshold_factor: float, stats_out: int):
         check(self.lib.gsx_sor_stats_dev(self.handle, mean_dists, n, float(threshold_factor), stats_out),

@@ -407,6 +407,53 @@ int gsx_sor_debug_brick_plan(gsx_ctx *c, int32_t *grid, float *origin, uint32_t 
     return 0;
 }
 
+// Debug / test download of the work queues of the context's last grid KNN call (level 0), in the order knn_brick, knn_brick
+// (second batches), knn_ring, knn_ring_fast: ctr[4][8] = the final tail counters of the eight groups, items[4] = the items
+// of each queue, blocks[4] = the workgroups of each launch (four waves each).  Synchronises.
+int gsx_sor_debug_work_queue(gsx_ctx *c, uint32_t *ctr, int64_t *items, int32_t *blocks)
+{
+    if (!c || !ctr || !items || !blocks) GSX_FAIL("gsx_sor_debug_work_queue: null argument");
+    gsx::KnnWs &w = c->ws[0];
+    if (!w.gridparams.p) GSX_FAIL("gsx_sor_debug_work_queue: no grid KNN call has run on this context");
+    GSX_HIP(hipSetDevice(c->device));
+    gsx::GridParams h;
+    GSX_HIP(hipMemcpyAsync(&h, w.gridparams.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipStreamSynchronize(c->stream));
+    const unsigned *src[4] = {h.brick_ctr, h.extra_ctr, h.ring_ctr, h.ringf_ctr};
+    for (int q = 0; q < 4; ++q)
+        for (int y = 0; y < 8; ++y) ctr[q * 8 + y] = src[q][y * 32];
+    items[0] = h.part_hi - h.part_lo;
+    items[1] = h.extra_count;
+    items[2] = c->ring_fast ? h.ring2_count : h.fail_count;
+    items[3] = c->ring_fast ? h.fail_count : 0;
+    for (int q = 0; q < 4; ++q) blocks[q] = c->wq_grid[q];
+    return 0;
+}
+
+// Diagnostic builds (-DGSX_WAVE_STAMPS) only: the wave records of the context's last grid KNN call.  kernel 0 = knn_brick (first
+// launch), 1 = knn_ring_fast; out receives at most cap records of 16 words (layout: WS_WORDS in csrc/sor_grid_params.h), *count
+// the number of record slots (records of waves that did not run stay zero).  Synchronises.
+int gsx_sor_debug_wave_stamps(gsx_ctx *c, int kernel, uint64_t *out, int64_t cap, int64_t *count)
+{
+    if (!c || !out || !count || kernel < 0 || kernel > 1) GSX_FAIL("gsx_sor_debug_wave_stamps: bad arguments");
+#ifdef GSX_WAVE_STAMPS
+    gsx::KnnWs &w = c->ws[0];
+    if (!w.wavestamps.p) GSX_FAIL("gsx_sor_debug_wave_stamps: no grid KNN call has run on this context");
+    GSX_HIP(hipSetDevice(c->device));
+    GSX_HIP(hipStreamSynchronize(c->stream));
+    const int64_t slots = c->ws_cap;
+    const int64_t m = std::min<int64_t>(slots, cap);
+    if (m > 0)
+        GSX_HIP(hipMemcpy(out, (const uint64_t *)w.wavestamps.p + (size_t)kernel * slots * gsx::WS_WORDS,
+                          sizeof(uint64_t) * gsx::WS_WORDS * (size_t)m, hipMemcpyDeviceToHost));
+    *count = slots;
+    return 0;
+#else
+    (void)cap;
+    GSX_FAIL("gsx_sor_debug_wave_stamps needs a diagnostic build of the library (-DGSX_WAVE_STAMPS)");
+#endif
+}
+
 int gsx_sor_knn_share_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n,
                           int k, int algo, int share, int nshares, float *mean_out, gsx_sor_info *info)
 {

@@ -70,6 +70,7 @@ struct KnnWs {
     DevBuf finestart;   // u32[4 * cap + 1]: cell_start at quarter-cell steps along x (planned bricks only)
     DevBuf bricklist;   // uint2[n / 16 + 4096]: (bundle, first | last << 16 quarter) of every planned brick
     DevBuf bundleoff;   // u32[2 * bundles]: planned bricks per bundle of 2x2 query rows | their exclusive scan
+    DevBuf wavestamps;  // -DGSX_WAVE_STAMPS builds only: one record per wave of knn_brick and knn_ring_fast
     // adaptive refinement (level L -> L+1)
     DevBuf deferred;    // u32[nbricks]: bricks whose neighbourhood is too populated for this level's cells
     DevBuf cellflag;    // u8[ncells]: 1 = cell belongs to the sub-cloud, 2 = ... of a deferred brick (its points are queries)
@@ -84,7 +85,7 @@ struct KnnWs {
     void release_all()
     {
         DevBuf *all[] = {&packed, &qsorted, &bucketpts, &bkcnt, &tilecnt, &tileoff, &cellstart, &qcellstart, &gridparams, &bboxpart,
-                         &faillist, &extraitems, &finestart, &bricklist, &bundleoff, &deferred, &cellflag, &subxyz, &submap, &submean, &subkth,
+                         &faillist, &extraitems, &finestart, &bricklist, &bundleoff, &wavestamps, &deferred, &cellflag, &subxyz, &submap, &submean, &subkth,
                          &heavylist, &heavypart, &probe};
         for (auto b : all) b->release();
     }
@@ -186,6 +187,8 @@ struct gsx_ctx {
     int phase2_net = 1;  // knn_brick phase 2: 1 = sorting-network block selection (TopNet), 0 = per-candidate bubble insert (A/B only)
     int brick_plan = 1;  // knn_brick on planned bricks (runs of quarter-cell slabs holding at most 64 queries) where the call allows it: the plain
                          // single-cloud call, k <= 16, MFMA filter + network selection (0: the fixed 2x2x2-cell bricks everywhere; A/B)
+    int ws_cap = 0;      // -DGSX_WAVE_STAMPS builds: record slots per kernel of the last grid KNN call
+    int wq_grid[4] = {0, 0, 0, 0};   // workgroups of the last knn_brick, knn_brick (second batches), knn_ring and knn_ring_fast launches (debug)
     int filter_mfma = 1; // knn_brick phase 1: 1 = bf16-split MFMA filter for batches whose mask words fit LDS, 0 = scalar-load f32 VALU filter only
 
     // SOR workspace: one KnnWs per refinement level of the KNN grid (level 0 = the whole cloud)

@@ -85,6 +85,10 @@ struct GridParamArgs {   // what grid_params needs besides the partial boxes
     float cert_lo, cert_hi;
     unsigned *cert_count;
     int plan_req = 0, plan_cap = 0;   // planned bricks asked for (the call allows them), entries the brick list has room for
+#ifdef GSX_WAVE_STAMPS
+    unsigned long long *stamps = nullptr;
+    int stamps_cap = 0;
+#endif
 };
 __device__ void grid_params_body(const float *part, int nparts, const GridParamArgs &a);
 
@@ -299,6 +303,10 @@ __device__ void grid_params_body(const float *part, int nparts, const GridParamA
     gp->cert_lo = a.cert_lo;
     gp->cert_hi = a.cert_hi;
     gp->cert_count = a.cert_count;
+#ifdef GSX_WAVE_STAMPS
+    gp->stamps = a.stamps;
+    gp->stamps_cap = a.stamps_cap;
+#endif
     for (int i = 0; i < 8; ++i) {
         gp->brick_ctr[i * 32] = 0;
         gp->extra_ctr[i * 32] = 0;
@@ -1116,6 +1124,9 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
     const int nq4 = 4 * nx;
     const bool planned = PLAN && gp->plan != 0;   // kernel-uniform
     const int dw = EXTRA ? 0 : gp->defer_words;  // loaded once: gp is written by atomics, the compiler would reload it per brick
+#ifdef GSX_WAVE_STAMPS
+    const unsigned long long ws_t0 = ws_realtime();
+#endif
     wq_init(wq, EXTRA ? gp->extra_ctr : gp->brick_ctr, EXTRA ? (int)gp->extra_count : gp->part_hi - part_lo,
             BRICK_THREADS / 64);
     for (;;) {
@@ -1634,6 +1645,9 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
             }
         }
     }
+#ifdef GSX_WAVE_STAMPS
+    if constexpr (!EXTRA) ws_write(gp, 0, wq, ws_t0, nullptr);
+#endif
 }
 
 // ---------------------------------------------------------------- knn_ring (fallback)
@@ -2403,6 +2417,8 @@ static int launch_bricks(gsx_ctx *ctx, const BrickLaunch &a)
         occ_brick = std::max(1, std::min(occ_brick, 8));
         occ_extra = std::max(1, std::min(occ_extra, 8));
     }
+    ctx->wq_grid[0] = ctx->num_cu * occ_brick;
+    ctx->wq_grid[1] = ctx->num_cu * occ_extra;
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_KNN));
     hipLaunchKernelGGL((knn_brick_kernel<KCAP, false, MF, NET, PLAN>), dim3(ctx->num_cu * occ_brick), dim3(BRICK_THREADS), 0, ctx->stream,
                        a.gp, a.refs, rstart, a.qpts, qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
@@ -2484,6 +2500,23 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
     };
 
     WorkQueue wq;
+#ifdef GSX_WAVE_STAMPS
+    // phase sums of this wave (shader cycles): 0 row bounds, 1 candidate fetch and filter, 2 histogram and select,
+    // 3 exact rank, 4 epilogue, 5 the rest (queue, list entry, hand-over to the second list)
+    const unsigned long long ws_t0 = ws_realtime();
+    unsigned long long ws_ph[WS_PHASES] = {0, 0, 0, 0, 0, 0};
+    unsigned long long ws_last = ws_cycles();
+#define WS_MARK(i)                              \
+    do {                                        \
+        const unsigned long long t_ = ws_cycles(); \
+        ws_ph[i] += t_ - ws_last;               \
+        ws_last = t_;                           \
+    } while (0)
+#else
+#define WS_MARK(i) \
+    do {           \
+    } while (0)
+#endif
     wq_init(wq, gp->ringf_ctr, nfail, BRICK_THREADS / 64);
     // the next query's list entry and point are fetched while the current one is being worked on: the chain
     // entry -> point -> row bounds -> candidates is what a wave waits for
@@ -2513,6 +2546,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
 #pragma unroll 1
         for (int attempt = 0; attempt < 2 && !solved; ++attempt, rt = rt_max) {
             if (attempt == 1 && !(rt_first < rt_max)) break;
+            WS_MARK(5);
             const float thr = (float)(rt * rt) * (1.0f + 1e-6f);
             const float inv_thr = 1.0f / thr;
             const double rtc = rt * (double)g.inv_h;   // r_t in cell units (<= 1.9)
@@ -2550,6 +2584,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
             if (lane == 0) ro[nrows] = total;
             hist[lane] = 0;
             wave_sync();
+            WS_MARK(0);
             if (!fetched_next) {
                 qp_next = t_next >= 0 ? qpts[fq_next] : qp;   // in flight together with this query's candidates
                 fetched_next = true;
@@ -2590,6 +2625,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
                 }
             }
             wave_sync();
+            WS_MARK(1);
             if (cnt > CAND) break;      // too dense around this query: knn_ring
             if (cnt < kk) continue;     // too sparse: once more with the widest certifiable radius
             // ---- the k+1 nearest are among the candidates of the first histogram bins that hold k+1 of them (bins are
@@ -2625,6 +2661,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
                 cnt2 += (int)__builtin_popcountll(bal);
             }
             wave_sync();
+            WS_MARK(2);
             if (cnt2 > 64) break;   // a crowd of near-ties: knn_ring
             double dme = __builtin_inf();
             if (lane < cnt2) {
@@ -2641,6 +2678,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
             }
             if (lane < cnt2 && rank < kk) out[rank] = dme;
             wave_sync();
+            WS_MARK(3);
             const double kth = out[kk - 1];
             if (!(kth <= rt * rt)) continue;   // (the float32 filter admits a hair more than r_t: then r_t certifies nothing)
             for (int i = lane; i < kk; i += 64) out[i] = __dsqrt_rn(out[i]);
@@ -2652,6 +2690,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
             }
             wave_sync();
             solved = true;
+            WS_MARK(4);
         }
         if (!fetched_next) qp_next = t_next >= 0 ? qpts[fq_next] : qp;
         if (!solved) {
@@ -2661,6 +2700,11 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
         }
     }
     if (nleft) flush_left();
+#ifdef GSX_WAVE_STAMPS
+    WS_MARK(5);
+    ws_write(gp, 1, wq, ws_t0, ws_ph);
+#endif
+#undef WS_MARK
 }
 
 template <int KCAP>
@@ -2673,6 +2717,8 @@ static int launch_ring(gsx_ctx *ctx, const BrickLaunch &a)
         GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_fast, knn_ring_fast_kernel<KCAP>, BRICK_THREADS, 0));
         occ_fast = std::max(1, std::min(occ_fast, 8));
     }
+    ctx->wq_grid[2] = ctx->num_cu * occ_ring;
+    ctx->wq_grid[3] = ctx->num_cu * occ_fast;
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_FALLBACK));
     const bool fast = ctx->ring_fast;
     if (fast)
@@ -2941,6 +2987,17 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
     GridParamArgs gpa{(int)n_ref, pts_per_cell, (int)cap, ctx->debug_skip, share, nshares, adaptive ? ctx->defer_words : 0, parent_h, gp,
                       ctx->devflags.as<unsigned>(), h_hint, sk ? sk->cert_axis : -1, sk ? sk->cert_lo : 0.0f, sk ? sk->cert_hi : 0.0f,
                       sk ? sk->cert_count : nullptr, plan ? 1 : 0, (int)plan_cap};
+#ifdef GSX_WAVE_STAMPS
+    if (level == 0) {   // (a finer level would overwrite the records of the call's main launches)
+        const int ws_cap = ctx->num_cu * 8 * (BRICK_THREADS / 64);   // the launches are capped at 8 workgroups per CU
+        const size_t ws_bytes = sizeof(unsigned long long) * 2 * (size_t)ws_cap * WS_WORDS;
+        GSX_CHECK(w.wavestamps.reserve(ws_bytes));
+        GSX_HIP(hipMemsetAsync(w.wavestamps.p, 0, ws_bytes, ctx->stream));
+        gpa.stamps = w.wavestamps.as<unsigned long long>();
+        gpa.stamps_cap = ws_cap;
+        ctx->ws_cap = ws_cap;
+    }
+#endif
     const bool adaptive_at_bbox = adaptive;
     if (sk && sk->box.b7)
         hipLaunchKernelGGL(grid_params_known_box_kernel, dim3(1), dim3(64), 0, ctx->stream, sk->box, w.bboxpart.as<float>(), gpa);

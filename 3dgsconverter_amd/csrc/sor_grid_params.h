@@ -53,6 +53,12 @@ struct GridParams {
     int cert_axis;
     float cert_lo, cert_hi;      // planes between which this rank holds EVERY point of the cloud (+-inf at the cloud's ends)
     unsigned *cert_count;        // number of queries whose k-th neighbour might lie beyond them
+#ifdef GSX_WAVE_STAMPS
+    // diagnostic build only: one record of WS_WORDS 64-bit words per wave of knn_brick's first launch (records
+    // [0, stamps_cap)) and of knn_ring_fast ([stamps_cap, 2 stamps_cap)), written on exit; nothing in a kernel reads them
+    unsigned long long *stamps;
+    int stamps_cap;
+#endif
 };
 
 #ifdef __HIPCC__
@@ -88,19 +94,28 @@ struct SlabKnn {         // what launch_knn_slab's caller may add (both optional
     KnownBox box{nullptr, 0, 0.0f, 0.0f};
 };
 
-// Work distribution shared by knn_brick / knn_ring (device): static stride + a small dynamic tail.
+// Work distribution shared by knn_brick / knn_ring (device): static stride + a dynamic tail.
 // XCD y owns the contiguous item range [n*y/8, n*(y+1)/8) (its L2 then sees a compact slab of
 // the sorted array); the waves whose home is y (blockIdx % 8 -- a placement HINT only, any mapping
-// is correct) stride through the first ~85 % of that range WITHOUT atomics and pull the rest from
-// a per-XCD counter, which evens out the finish times (a static-only split ends with the
+// is correct) stride through the first WQ_STATIC_PCT % of that range WITHOUT atomics and pull the
+// rest from a per-XCD counter, which evens out the finish times (a static-only split ends with the
 // slowest wave: +10 % at 10M splats).  History: a device-wide atomic work counter saturates at
 // ~88 dequeues/us on MI355X; with 157k bricks at 10M splats the dequeues alone cost 1.0 of the
 // kernel's 3.1 ms (ablation in profiles/r01_ablate_knn_brick.log), and eight counters 128 B
 // apart did not help.  Every launched workgroup must be resident (grid sized from the occupancy
 // query), otherwise the static share of a late workgroup would start late.
+// The static share is HALF of the range, whatever the item count.  It was 85 % (70, 50 for fewer items per wave), and
+// wave stamps (tools/wave_stamps.py, profiles/wq_stamps_before.txt) showed what that cost: the VALU pipe goes to the
+// oldest wave of a SIMD first, so the youngest of knn_brick's five waves per SIMD was still in its static rounds
+// (27 items, not one from the tail) 260 us after its elders had emptied the tail and left.  Only a wave's static
+// rounds are its own; at 50 % the youngest wave's are short enough to end with the tail.
+constexpr int WQ_STATIC_PCT = 50;
 struct WorkQueue {
     unsigned *ctr;     // this XCD's tail counter
     int next, static_end, end, stride;
+#ifdef GSX_WAVE_STAMPS
+    unsigned took_static, took_tail;
+#endif
 };
 
 #ifdef __HIPCC__
@@ -110,15 +125,14 @@ __device__ __forceinline__ void wq_init(WorkQueue &q, unsigned *ctr8x32, int n, 
     const int lo = (int)(((long long)n * y) / 8), hi = (int)(((long long)n * (y + 1)) / 8);
     const int wl = (int)(blockIdx.x >> 3) * waves_per_block + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     q.stride = (((int)gridDim.x + 7 - y) / 8) * waves_per_block;  // waves whose home is y
-    // share handed out statically: 85 % when a wave gets dozens of items (the atomics cost more than the
-    // imbalance), less when it only gets a handful and one 2-batch brick too many is a 20 % longer wave
-    const int per_wave = n / max(1, (int)gridDim.x * waves_per_block);
-    const int pct = per_wave >= 16 ? 85 : (per_wave >= 6 ? 70 : 50);
-    const int rounds = (int)(((long long)(hi - lo) * pct / 100) / q.stride);  // full static rounds
+    const int rounds = (int)(((long long)(hi - lo) * WQ_STATIC_PCT / 100) / q.stride);  // full static rounds
     q.next = lo + wl;
     q.static_end = lo + rounds * q.stride;
     q.end = hi;
     q.ctr = ctr8x32 + y * 32;
+#ifdef GSX_WAVE_STAMPS
+    q.took_static = q.took_tail = 0;
+#endif
 }
 
 // next item for this wave, or -1.  Wave-uniform.
@@ -127,6 +141,9 @@ __device__ __forceinline__ int wq_next(WorkQueue &q)
     if (q.next < q.static_end) {
         const int b = q.next;
         q.next += q.stride;
+#ifdef GSX_WAVE_STAMPS
+        ++q.took_static;
+#endif
         return b;
     }
     if (q.static_end >= q.end) return -1;
@@ -134,7 +151,51 @@ __device__ __forceinline__ int wq_next(WorkQueue &q)
     if ((threadIdx.x & 63) == 0) t = (int)atomicAdd(q.ctr, 1u);
     t = __builtin_amdgcn_readfirstlane(t);
     const int b = q.static_end + t;
+#ifdef GSX_WAVE_STAMPS
+    if (b < q.end) ++q.took_tail;
+#endif
     return b < q.end ? b : -1;
+}
+#endif
+
+#if defined(__HIPCC__) && defined(GSX_WAVE_STAMPS)
+// -DGSX_WAVE_STAMPS (an experiment build like -DGSX_ABLATE, never the product library): where a wave's time goes.
+// Stamped runs compare groups and phases; their length is not a timing (the stamps cost ~10 % of the wave cycles).
+constexpr int WS_WORDS = 16;   // xcc, block, wave, start, end (100 MHz, chip-wide), items: static share, tail, 0,
+                               // six phase sums (shader cycles: knn_ring_fast only), 1 (record written), HW_ID
+constexpr int WS_PHASES = 6;
+__device__ __forceinline__ unsigned long long ws_cycles()   // shader clock of this XCD: differences only
+{
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+__device__ __forceinline__ unsigned long long ws_realtime()   // constant 100 MHz counter, the same on every XCD
+{
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+__device__ __forceinline__ void ws_write(const GridParams *gp, int kernel, const WorkQueue &q, unsigned long long t0,
+                                         const unsigned long long *phase)
+{
+    const unsigned long long t1 = ws_realtime();
+    unsigned xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+    unsigned hwid;   // wave slot [3:0], SIMD [5:4], CU [11:8], shader array [12], shader engine [15:13]
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 32)" : "=s"(hwid));
+    const int wave = (int)(threadIdx.x >> 6);
+    const int slot = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
+    if ((threadIdx.x & 63) != 0 || !gp->stamps || slot >= gp->stamps_cap) return;
+    unsigned long long *r = gp->stamps + ((size_t)kernel * gp->stamps_cap + slot) * WS_WORDS;
+    r[0] = xcc; r[1] = blockIdx.x; r[2] = (unsigned long long)wave; r[3] = t0; r[4] = t1;
+    r[5] = q.took_static; r[6] = q.took_tail; r[7] = 0;
+    for (int i = 0; i < WS_PHASES; ++i) r[8 + i] = phase ? phase[i] : 0ull;
+    r[14] = 1; r[15] = hwid;
 }
 #endif
 

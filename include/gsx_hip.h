@@ -250,6 +250,12 @@ int gsx_sor_knn_share_dev(gsx_ctx *ctx, const float *x, const float *y, const fl
  * grid[8] = nx, ny, nz, plan (1: the planned bricks ran), bricks, 0, 0, 0; origin[4] = ox, oy, oz, 1/h;
  * list (nullable, room for cap entries of two words): {bundle of 2x2 query rows, first | last << 16 quarter-cell slab}. */
 int gsx_sor_debug_brick_plan(gsx_ctx *ctx, int32_t *grid, float *origin, uint32_t *list, int64_t cap);
+/* Debug / tests: the work queues of the context's last grid KNN call, in the order knn_brick, knn_brick (second batches),
+ * knn_ring, knn_ring_fast: ctr[4][8] = final tail counters of the eight groups, items[4], blocks[4] = workgroups per launch. */
+int gsx_sor_debug_work_queue(gsx_ctx *ctx, uint32_t *ctr, int64_t *items, int32_t *blocks);
+/* Diagnostic builds (-DGSX_WAVE_STAMPS) only: per-wave records of knn_brick (kernel 0) and knn_ring_fast (kernel 1) of the
+ * context's last grid KNN call, 16 words each (csrc/sor_grid_params.h); tools/wave_stamps.py prints them. */
+int gsx_sor_debug_wave_stamps(gsx_ctx *ctx, int kernel, uint64_t *out, int64_t cap, int64_t *count);
 /*
  * np.mean / np.std / threshold -- replaces data_processor.py:176-178 and
  * gpu_ops.py:259-261 with numpy's exact float32 arithmetic (8192-element buffered

@@ -242,6 +242,9 @@ SIGNATURES = {
     "gsx_ksplat_unpack_dev": (_I, [_P, _P, _I64, _I, C.POINTER(KsplatReadSection), _I, _P, _I64, _P, _I, _P, _I64]),
     "gsx_spz_unpack_dev": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _I64]),
     "gsx_sog_unpack_dev": (_I, [_P, _P, _I64, C.POINTER(_I64), _I, _I64, _P, _P, _I64, _P]),
+    "gsx_splat_unpack_dev": (_I, [_P, _P, _I64, _P, _P]),
+    "gsx_np_log_math_dev": (_I, [_P, _P, _I64, _P]),
+    "gsx_np_logf_host": (_I, [_P, _P, _I64]),
 }
 
 _lib = None
@@ -1923,6 +1926,132 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
             raise IndexError("sog_unpack_table: a label at or above the palette's %d entries" % palette)
         join()
         check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.mark("download")
+        return out
+
+
+def np_log_host(x: np.ndarray) -> np.ndarray:
+    """csrc/np_log.h on the host (gsx_np_logf_host): the twin of the device's log"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    check(load().gsx_np_logf_host(x.ctypes.data, out.ctypes.data, x.size), "gsx_np_logf_host")
+    return out
+
+
+def np_log_probe_vector() -> np.ndarray:
+    """~64K float32 inputs: the neighbours of 1e-6f (the reader's clamp) and of every power of two, the mantissas nearest
+    sqrt(1/2) on both sides at every exponent (where the routine doubles m), denormals, +-0, +-inf, NaNs of both signs,
+    exp(uniform(-14, 6)) (the scales of real scenes) and raw bit patterns"""
+    rng = np.random.default_rng(0x6C6F67)
+    u = np.uint32
+    near = np.arange(-4, 5, dtype=np.int64)
+    clamp = int(np.float32(1e-6).view(u)) + np.arange(-64, 65, dtype=np.int64)
+    powers = ((np.arange(1, 255, dtype=np.int64) << 23)[:, None] + near).ravel()                   # 2^-126 ... 2^127
+    denormal_powers = np.unique(np.clip((1 << np.arange(23, dtype=np.int64))[:, None] + near, 0, None).ravel())
+    half_root = ((np.arange(0, 255, dtype=np.int64) << 23)[:, None] + 0x3504F3 + near).ravel()     # 0x3f3504f3 = float32(sqrt(1/2))
+    special = np.array([0, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7FFFFFFF, 0xFFFFFFFF,
+                        0x00000001, 0x007FFFFF, 0x00800000, 0x7F7FFFFF, 0x80000001, 0xBF800000, 0x3F800000], np.int64)
+    bits = np.concatenate([clamp, powers, denormal_powers, half_root, special]).astype(u).view(np.float32)
+    parts = [bits,
+             rng.integers(1, 1 << 23, 8192, dtype=np.uint64).astype(u).view(np.float32),          # denormals
+             np.exp(rng.uniform(-14.0, 6.0, 28672)).astype(np.float32),
+             rng.integers(0, 1 << 32, 20480, dtype=np.uint64).astype(u).view(np.float32)]
+    return np.concatenate(parts)
+
+
+_np_log_checked = None
+
+
+def np_log_probe() -> bool:
+    """The .splat reader stores np.log's float32 bits, so the device's log (csrc/np_log.h) must be THIS process's numpy's.  Probed
+    once per process: the host twin against np.log on np_log_probe_vector().  On a mismatch: a RuntimeWarning and False (the
+    reader then takes the three scale columns from numpy on the host, and stays exact), or under GSX_STRICT_NUMPY=1 a GsxError."""
+    global _np_log_checked
+    if _np_log_checked is not None:
+        return _np_log_checked
+    import warnings
+    x = np_log_probe_vector()
+    with np.errstate(all="ignore"):
+        want = np.log(x).view(np.uint32)
+    got = np_log_host(x).view(np.uint32)
+    bad = np.nonzero(got != want)[0]
+    _np_log_checked = not len(bad)
+    if len(bad):
+        i = int(bad[0])
+        msg = ("numpy %s's float32 log differs from the one libgsx_hip reproduces (numpy 2.x's AVX512F / AVX2 routine) on %d of %d "
+               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): the .splat reader takes the scales from numpy on the "
+               "host.  GSX_STRICT_NUMPY=1 turns this warning into an error."
+               % (np.__version__, len(bad), len(x), int(x.view(np.uint32)[i]), int(got[i]), int(want[i])))
+        if os.environ.get("GSX_STRICT_NUMPY") == "1":
+            _np_log_checked = None
+            raise GsxError(msg)
+        warnings.warn(msg, RuntimeWarning, stacklevel=2)
+    return _np_log_checked
+
+
+_splat_read_tables = None
+SPLAT_READ_TABLES = ("f_dc", "opacity")   # GSX_SPLAT_TAB_* order (include/gsx_hip.h)
+SPLAT_READ_RECORD = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("scale_0", "<f4"), ("scale_1", "<f4"), ("scale_2", "<f4"),
+                              ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("opacity", "u1"),
+                              ("rot_0", "u1"), ("rot_1", "u1"), ("rot_2", "u1"), ("rot_3", "u1")])   # splat.py:24-29
+
+
+def splat_read_tables() -> dict:
+    """The .splat reader's tables, numpy's own results for the reference's statements on every byte, each with the reference's
+    expression and operand dtypes -- so the device takes no log of them: "f_dc" f4[256] splat.py:75-77 | "opacity" f4[256]
+    :67-69 (the clip's bounds are Python floats: the chain stays float32)"""
+    global _splat_read_tables
+    if _splat_read_tables is None:
+        with np.errstate(all="ignore"):
+            b = np.arange(256, dtype=np.uint8)
+            f_dc = (b.astype(np.float32) / 255.0 - 0.5) / 0.28209479177387814
+            linear_alpha = b.astype(np.float32) / 255.0
+            linear_alpha = np.clip(linear_alpha, 1.0 / 255.0, 0.9999)
+            opa = -np.log((1.0 / linear_alpha) - 1.0)
+        assert f_dc.dtype == np.float32 and opa.dtype == np.float32
+        _splat_read_tables = dict(zip(SPLAT_READ_TABLES, (f_dc, opa)))
+    return _splat_read_tables
+
+
+def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+    """The .splat reader's rows (formats/splat.py:9-80): the first 32 `n_rows` bytes of `path` are read straight into page-locked
+    staging, uploaded once, decoded by gsx_splat_unpack_dev and downloaded into a prefaulted array of `dtype` (packed rows of 71
+    bytes; formats/splat_reader.py builds it).  When np_log_probe() fails, the three scale columns are numpy's, computed on the
+    host from the staged records.
+
+    One ArenaSession of the "splatread" lease group."""
+    lib = require_hip()
+    n = int(n_rows)
+    rb = dtype.itemsize
+    if rb != 71 or n < 1:
+        raise ValueError("splat_unpack_table: %d rows of %d bytes" % (n, rb))
+    log_ok = np_log_probe()
+    total = n * SPLAT_READ_RECORD.itemsize
+    tabs = splat_read_tables()
+    host_tab = np.concatenate([tabs[k] for k in SPLAT_READ_TABLES])
+    out = np.empty(n, dtype)
+    with ArenaSession("splatread", device, stage_ms) as s:
+        ctx = s.ctx
+        join = prefault(out.nbytes >= (1 << 22), out)
+        host = s.staging("in", total)
+        with open(path, "rb") as f:
+            read_exact(f, host, path, unit="record bytes")
+        s.mark("file_read")
+        d_in = s.buf("in", total)
+        d_tab = s.buf("tables", host_tab.nbytes)
+        s.upload_staging(lib, d_in.ptr, host)
+        d_tab.upload(host_tab)
+        s.mark("upload")
+        d_out = s.buf("out", n * rb)
+        check(lib.gsx_splat_unpack_dev(ctx.handle, d_in.ptr, n, d_tab.ptr, d_out.ptr), "gsx_splat_unpack_dev")
+        s.mark("kernel")
+        join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        if not log_ok:
+            recs = host.view(SPLAT_READ_RECORD)
+            with np.errstate(all="ignore"):
+                for f in ("scale_0", "scale_1", "scale_2"):
+                    out[f] = np.log(np.maximum(recs[f], 1e-6))                    # splat.py:43-48
         s.mark("download")
         return out
 

@@ -20,7 +20,8 @@ _saved = {}
 
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
-            cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True, sog_reader: bool = True):
+            cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True, sog_reader: bool = True,
+            splat_reader: bool = False):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -47,7 +48,12 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     threaded WebP decode into page-locked staging on the host, every row decoded on the GPU; the reference's rows and its
     exceptions on malformed files).  A file whose meta.json the device path does not take -- bands outside 1 ... 3, a palette
     outside 1 ... 65 536, values of other types than the writer's -- goes to the reference's own read.  A reference without
-    that module is left as it is."""
+    that module is left as it is.
+    splat_reader: also rebind ``gsconverter.formats.splat.SplatFormat.read`` to formats/splat_reader.py (the file's size and the
+    read into page-locked staging on the host, every row decoded on the GPU; the reference's rows and its exceptions on a
+    missing path).  Every .splat file is taken.  A reference without that module is left as it is.  Unlike the other readers
+    this one is OFF unless asked for: a plain install() has always left ``SplatFormat.read`` to the reference, callers and tests
+    rely on that, and adding a reader changes no existing behaviour."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -151,6 +157,15 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.sog_reader import bind_read as bind_sog_read
             _saved.setdefault(("sogformat", "read"), sogmod.SogFormat.read)
             sogmod.SogFormat.read = bind_sog_read(_saved[("sogformat", "read")])
+    if splat_reader:
+        try:
+            spmod = importlib.import_module("gsconverter.formats.splat")
+        except ImportError:
+            spmod = None
+        if spmod is not None and getattr(spmod.SplatFormat, "read", None) is not None:
+            from .formats.splat_reader import bind_read as bind_splat_read
+            _saved.setdefault(("splatformat", "read"), spmod.SplatFormat.read)
+            spmod.SplatFormat.read = bind_splat_read(_saved[("splatformat", "read")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops

@@ -822,6 +822,28 @@ int gsx_spz_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t body_bytes, i
 int gsx_sog_unpack_dev(gsx_ctx *ctx, const void *texels_dev, int64_t texels_bytes, const int64_t *offsets, int bands, int64_t palette,
                        const void *tables_dev, void *out_dev, int64_t n, uint32_t *flag_dev);
 
+
+/* ---- the .splat reader (csrc/splat_read.hip) ----
+ * gsconverter/formats/splat.py:9-80 (SplatFormat.read): the file's 32-byte records -- 3 f32 position, 3 f32 linear scale, 4 u8
+ * colour (r g b alpha), 4 u8 rotation -- -> the reference's rows in GaussianStruct.define_dtype(has_scal=False, has_rgb=True,
+ * sh_degree=0)'s order, x y z nx ny nz f_dc_0..2 opacity scale_0..2 rot_0..3 as float32, then red green blue as bytes, packed
+ * (71 bytes a row), bit for bit: positions moved as bits (:38-40), np.log(np.maximum(scale, 1e-6)) with numpy's own float32 log
+ * (:43-48, csrc/np_log.h), the renormalised rotation (:52-63), nx ny nz red green blue zero (:36: never assigned).
+ * tables_dev: the host-built tables (numpy's own results), float32: f_dc of colour byte b [256] (:75-77) | the opacity logit of
+ * alpha byte b [256] (:67-69). */
+#define GSX_SPLAT_TAB_DC 0
+#define GSX_SPLAT_TAB_OPA 256
+#define GSX_SPLAT_TAB_WORDS 512
+/* recs_dev: n records, 16-byte aligned (nothing behind them is read).  out_dev: n packed rows, 16-byte aligned; n < 2^32.  One
+ * launch.  Asynchronous. */
+int gsx_splat_unpack_dev(gsx_ctx *ctx, const void *recs_dev, int64_t n, const float *tables_dev, void *out_dev);
+/* splat.py:46-48 np.log: numpy's float32 log (csrc/np_log.h) of every x_dev[i], as bits.  Synchronises the context's stream
+ * (the proof of tests/devtools/check_np_log.py). */
+int gsx_np_log_math_dev(gsx_ctx *ctx, const float *x_dev, int64_t n, uint32_t *out_bits_dev);
+/* splat.py:46-48 np.log on the HOST: the twin of the device's log (csrc/np_log.h), for the reader's runtime probe against this
+ * process's numpy.  HOST pointers. */
+int gsx_np_logf_host(const float *x, float *out, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

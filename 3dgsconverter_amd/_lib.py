@@ -96,6 +96,19 @@ class CplyReadLayout(C.Structure):
                 ("vertex_offset", C.c_int32 * 4), ("n_sh", C.c_int32), ("sh_offset", C.c_int32 * CPLY_READ_MAX_SH)]
 
 
+PLY_READ_MAX_FIELDS = 128   # GSX_PLY_READ_MAX_FIELDS
+PLY_READ_MAX_STRIDE = 512   # bytes per input or output row (csrc/row_tile.h SPZ_MAX_ROW_BYTES)
+PLY_TYPE_CODES = {"i1": 0, "u1": 1, "i2": 2, "u2": 3, "i4": 4, "u4": 5, "f4": 6, "f8": 7}   # GSX_PLY_T_*: convert to float32 by value
+PLY_T_RAW = 8               # GSX_PLY_T_RAW: copy dst_bytes bytes
+
+
+class PlyReadLayout(C.Structure):
+    """gsx_ply_read_layout (include/gsx_hip.h): the 3DGS / CloudCompare PLY readers' field descriptors"""
+    _fields_ = [("in_stride", C.c_int32), ("out_stride", C.c_int32), ("n_fields", C.c_int32), ("big_endian", C.c_int32),
+                ("src_offset", C.c_int32 * PLY_READ_MAX_FIELDS), ("src_type", C.c_int32 * PLY_READ_MAX_FIELDS),
+                ("dst_offset", C.c_int32 * PLY_READ_MAX_FIELDS), ("dst_bytes", C.c_int32 * PLY_READ_MAX_FIELDS)]
+
+
 class KsplatReadSection(C.Structure):
     """gsx_ksplat_read_section (include/gsx_hip.h): one section of a .ksplat file as the reader's kernel walks it"""
     _fields_ = [("rows_offset", C.c_int64), ("centres_offset", C.c_int64), ("n_rows", C.c_int64), ("out_row", C.c_int64),
@@ -245,6 +258,8 @@ SIGNATURES = {
     "gsx_splat_unpack_dev": (_I, [_P, _P, _I64, _P, _P]),
     "gsx_np_log_math_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_np_logf_host": (_I, [_P, _P, _I64]),
+    "gsx_ply_unpack_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(PlyReadLayout), _P]),
+    "gsx_ply_unpack_host": (_I, [_P, _I64, C.POINTER(PlyReadLayout), _P]),
 }
 
 _lib = None
@@ -2054,6 +2069,56 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
                     out[f] = np.log(np.maximum(recs[f], 1e-6))                    # splat.py:43-48
         s.mark("download")
         return out
+
+
+def ply_unpack_table(path: str, body_offset: int, n_rows: int, layout: PlyReadLayout, dtype: np.dtype, stage_ms: "dict | None" = None,
+                     device: int = 0) -> np.ndarray:
+    """The 3DGS / CloudCompare PLY readers' rows (formats/ply_3dgs.py:45-58, formats/ply_cc.py:45-60): the vertex element's body
+    (`n_rows` rows of layout.in_stride bytes at byte `body_offset` of `path`) is read straight into page-locked staging, from
+    the 16-byte boundary at or below it (so row 0 sits at byte 0 ... 15 of the buffer), uploaded once, transcoded by
+    gsx_ply_unpack_dev and downloaded into a prefaulted array of `dtype` (layout.out_stride bytes per row;
+    formats/ply_reader.py builds both).  A body that ends early raises read_exact's ValueError.
+
+    One ArenaSession of the "plyread" lease group."""
+    lib = require_hip()
+    n, rb = int(n_rows), dtype.itemsize
+    if n < 1 or rb != layout.out_stride:
+        raise ValueError("ply_unpack_table: %d rows of %d bytes for a layout of %d" % (n, rb, layout.out_stride))
+    start = int(body_offset) & ~15
+    first = int(body_offset) - start
+    used = first + n * layout.in_stride
+    total = (used + 16 + 15) & ~15             # the kernel's 16-byte loads read up to 15 bytes past the last row
+    out = np.empty(n, dtype)
+    with ArenaSession("plyread", device, stage_ms) as s:
+        ctx = s.ctx
+        join = prefault(out.nbytes >= (1 << 22), out)
+        host = s.staging("in", total)
+        with open(path, "rb") as f:
+            f.seek(start)
+            read_exact(f, host[:used], path, " in element 'vertex'")
+        s.mark("file_read")
+        d_in = s.buf("in", total)
+        s.upload_staging(lib, d_in.ptr, host)
+        s.mark("upload")
+        d_out = s.buf("out", n * rb)
+        check(lib.gsx_ply_unpack_dev(ctx.handle, d_in.ptr, first, n, C.byref(layout), d_out.ptr), "gsx_ply_unpack_dev")
+        s.mark("kernel")
+        join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.mark("download")
+        return out
+
+
+def ply_unpack_host(body: np.ndarray, n_rows: int, layout: PlyReadLayout, dtype: np.dtype) -> np.ndarray:
+    """gsx_ply_unpack_host: the kernel's transcode on the host (`body`: uint8, the vertex rows from their first byte) -- the host
+    tests' model of the device and the check of a descriptor table without one"""
+    lib = load()
+    n = int(n_rows)
+    src = np.zeros(n * layout.in_stride + 4, np.uint8)
+    src[:n * layout.in_stride] = body[:n * layout.in_stride]
+    out = np.empty(n, dtype)
+    check(lib.gsx_ply_unpack_host(src.ctypes.data, n, C.byref(layout), out.ctypes.data), "gsx_ply_unpack_host")
+    return out
 
 
 class DeviceArray:

@@ -21,7 +21,7 @@ _saved = {}
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
             cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True, sog_reader: bool = True,
-            splat_reader: bool = False):
+            splat_reader: bool = False, ply_reader: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -53,7 +53,13 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     read into page-locked staging on the host, every row decoded on the GPU; the reference's rows and its exceptions on a
     missing path).  Every .splat file is taken.  A reference without that module is left as it is.  Unlike the other readers
     this one is OFF unless asked for: a plain install() has always left ``SplatFormat.read`` to the reference, callers and tests
-    rely on that, and adding a reader changes no existing behaviour."""
+    rely on that, and adding a reader changes no existing behaviour.
+    ply_reader: also rebind ``gsconverter.formats.ply_3dgs.Ply3DGSFormat.read`` and ``gsconverter.formats.ply_cc.PlyCCFormat.read``
+    to formats/ply_reader.py (header, name mapping and the non-vertex elements on the host, the row transcode on the GPU, no
+    plyfile; the reference's rows and ``self.extra_elements``).  Files the device path does not take -- ascii bodies, list
+    properties, a duplicated vertex property, colours that are not uchar, big-endian files with extra fields, rows over 512
+    bytes or 128 fields -- go to the reference's own read when plyfile is there.  A reference without those modules is left as
+    it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -166,6 +172,17 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             from .formats.splat_reader import bind_read as bind_splat_read
             _saved.setdefault(("splatformat", "read"), spmod.SplatFormat.read)
             spmod.SplatFormat.read = bind_splat_read(_saved[("splatformat", "read")])
+    if ply_reader:
+        from .formats import ply_reader as plyr
+        for key, modname, cls, bind in (("ply3dgsformat", "gsconverter.formats.ply_3dgs", "Ply3DGSFormat", plyr.bind_read_3dgs),
+                                        ("plyccformat", "gsconverter.formats.ply_cc", "PlyCCFormat", plyr.bind_read_cc)):
+            try:
+                plymod = importlib.import_module(modname)
+            except ImportError:
+                plymod = None
+            if plymod is not None and getattr(getattr(plymod, cls, None), "read", None) is not None:
+                _saved.setdefault((key, "read"), getattr(plymod, cls).read)
+                getattr(plymod, cls).read = bind(_saved[(key, "read")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -188,6 +205,12 @@ def uninstall():
             continue
         if modname == "splatformat":
             setattr(importlib.import_module("gsconverter.formats.splat").SplatFormat, attr, val)
+            continue
+        if modname == "ply3dgsformat":
+            setattr(importlib.import_module("gsconverter.formats.ply_3dgs").Ply3DGSFormat, attr, val)
+            continue
+        if modname == "plyccformat":
+            setattr(importlib.import_module("gsconverter.formats.ply_cc").PlyCCFormat, attr, val)
             continue
         if modname == "sys.modules":
             if val is None:

@@ -844,6 +844,46 @@ int gsx_np_log_math_dev(gsx_ctx *ctx, const float *x_dev, int64_t n, uint32_t *o
  * process's numpy.  HOST pointers. */
 int gsx_np_logf_host(const float *x, float *out, int64_t n);
 
+
+/* ---- the 3DGS / CloudCompare PLY readers (csrc/ply_read.hip) ----
+ * gsconverter/formats/ply_3dgs.py:8-60 (Ply3DGSFormat.read) and gsconverter/formats/ply_cc.py:8-62 (PlyCCFormat.read): the
+ * zeroed table of :45 and the mapping loop of ply_3dgs.py:48-58 / ply_cc.py:48-60 (`converted_data[target] = vertices[source]`,
+ * numpy's cast by value) as one pass over the vertex element's rows -> the reference's packed rows, bit for bit.  Which source
+ * a target takes is decided on the host (formats/ply_reader.py); a field is described by
+ *   src_offset   byte offset inside an input row, -1 = no source: the field stays zero
+ *   src_type     GSX_PLY_T_I1 ... GSX_PLY_T_F8: convert that PLY scalar to float32 by value (dst_bytes 4; f4 moves its bits, f8
+ *                rounds as x86 does, NaN payload kept and quieted); GSX_PLY_T_RAW: copy dst_bytes bytes as they are
+ *   dst_offset   byte offset inside an output row
+ *   dst_bytes    1, 2, 4 or 8
+ * The output fields must tile the output row.  big_endian: every converted field is byte-swapped as it is read (a raw copy of
+ * more than one byte is then refused). */
+#define GSX_PLY_READ_MAX_FIELDS 128
+#define GSX_PLY_T_I1 0
+#define GSX_PLY_T_U1 1
+#define GSX_PLY_T_I2 2
+#define GSX_PLY_T_U2 3
+#define GSX_PLY_T_I4 4
+#define GSX_PLY_T_U4 5
+#define GSX_PLY_T_F4 6
+#define GSX_PLY_T_F8 7
+#define GSX_PLY_T_RAW 8
+typedef struct gsx_ply_read_layout {
+    int32_t in_stride;                  /* bytes per row of the file's vertex element, 1 ... 512 */
+    int32_t out_stride;                 /* bytes per output row, 1 ... 512 */
+    int32_t n_fields;                   /* output fields, 1 ... GSX_PLY_READ_MAX_FIELDS */
+    int32_t big_endian;                 /* 0 or 1 */
+    int32_t src_offset[GSX_PLY_READ_MAX_FIELDS];
+    int32_t src_type[GSX_PLY_READ_MAX_FIELDS];
+    int32_t dst_offset[GSX_PLY_READ_MAX_FIELDS];
+    int32_t dst_bytes[GSX_PLY_READ_MAX_FIELDS];
+} gsx_ply_read_layout;
+/* body_dev: 16-byte aligned, row 0 at its byte first_byte (0 ... 15), readable up to 16 bytes past the last row.  out_dev: n
+ * rows of out_stride bytes, 16-byte aligned.  One launch.  Asynchronous. */
+int gsx_ply_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t first_byte, int64_t n, const gsx_ply_read_layout *layout, void *out_dev);
+/* the same transcode on the HOST, field by field with the kernel's own conversion code (the host tests hold it against numpy).
+ * HOST pointers; body readable up to 4 bytes past the last row. */
+int gsx_ply_unpack_host(const void *body, int64_t n, const gsx_ply_read_layout *layout, void *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSX_LIB_PATH") or os.path.join(_HERE, "libgsx_hip.so")
 
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_TREE = 0, 1, 2, 3
+PROBE_ROOT_DIST2, PROBE_ROOT_DSQRT = 0, 1                                    # gsx_knn_probe_root_dev modes
+PROBE_MEAN_NET, PROBE_MEAN_LIST, PROBE_MEAN_LE128, PROBE_MEAN_NP = 0, 1, 2, 3   # gsx_knn_probe_mean_dev forms
 T_SOR_KNN, T_SOR_BIN, T_SOR_FALLBACK, T_SOR_STATS, T_DENSITY, T_KMEANS_ASSIGN, T_KMEANS_UPDATE, T_QUANTIZE = range(8)
 T_SLAB_PREP, T_SLAB_ROWS, T_SLAB_MEANS, T_SLAB_COLL = range(8, 12)   # multi-GPU slab step (round 5)
 
@@ -178,6 +180,8 @@ SIGNATURES = {
     "gsx_sor_debug_brick_plan": (_I, [_P, _P, _P, _P, _I64]),
     "gsx_sor_debug_work_queue": (_I, [_P, _P, _P, _P]),
     "gsx_sor_debug_wave_stamps": (_I, [_P, _I, _P, _I64, _P]),
+    "gsx_knn_probe_root_dev": (_I, [_P, _P, _I64, _I, _P]),
+    "gsx_knn_probe_mean_dev": (_I, [_P, _P, _I64, _I64, _I, _I, _I, _P]),
     "gsx_sor_stats_dev": (_I, [_P, _P, _I64, _D, _P]),
     "gsx_sor_mask_dev": (_I, [_P, _P, _I64, _P, _P]),
     "gsx_comm_unique_id": (_I, [_P]),
@@ -2264,6 +2268,16 @@ class Context:
               "gsx_sor_debug_wave_stamps")
         rec = buf[:min(cap, int(count.value))]
         return rec[rec[:, 14] == 1]
+
+    def knn_probe_root(self, values: int, n: int, mode: int, out: int):
+        """debug / tests: out[i] = float64 root of values[i] (device pointers); mode 0 sqrt_rn_dist2, 1 __dsqrt_rn"""
+        check(self.lib.gsx_knn_probe_root_dev(self.handle, values, int(n), int(mode), out), "gsx_knn_probe_root_dev")
+
+    def knn_probe_mean(self, d2: int, m: int, stride: int, k: int, form: int, cap: int, out: int):
+        """debug / tests: float32 row means of m rows of ascending float64 squared distances (device pointers) through one
+        form of the KNN epilogue: PROBE_MEAN_NET / LIST (cap = list length / capacity), LE128, NP (include/gsx_hip.h)"""
+        check(self.lib.gsx_knn_probe_mean_dev(self.handle, d2, int(m), int(stride), int(k), int(form), int(cap), out),
+              "gsx_knn_probe_mean_dev")
 
     def sor_stats(self, mean_dists: int, n: int, threshold_factor: float, stats_out: int):
         check(self.lib.gsx_sor_stats_dev(self.handle, mean_dists, n, float(threshold_factor), stats_out),

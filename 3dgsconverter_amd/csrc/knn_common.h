@@ -201,7 +201,8 @@ struct TopNet {
 // scaling (inputs below 2^-767 are scaled by 2^256: squared differences of float32 coordinates are 0 or >= 2^-298)
 // and without the class test for 0 / inf: the seed is taken of max(x, 1e-300), so x = 0 (duplicate points) runs
 // through as g = 0 * y = 0 and every correction term stays 0.  Same instruction sequence otherwise, hence the same
-// bits (the GPU suite compares 10M mean distances with cKDTree's).  11 instead of ~18 instructions per root.
+// bits: tests/test_knn_epilogue_gpu.py compares it with np.sqrt on 4.3M inputs of that domain -- every binade, and the doubles whose
+// root lies within 2^-42 ulp of a tie, the only ones on which the second correction shows.  11 instead of ~18 instructions per root.
 __device__ __forceinline__ double sqrt_rn_dist2(double x)
 {
     double xs;
@@ -216,6 +217,12 @@ __device__ __forceinline__ double sqrt_rn_dist2(double x)
     g = __builtin_fma(d, h, g);
     d = __builtin_fma(-g, g, x);
     return __builtin_fma(d, h, g);
+}
+
+// the last line of every epilogue: the f64 sum of the k roots -> (float)(sum / k), an IEEE f64 divide and one rounding to f32
+__device__ __forceinline__ float mean_finish(double sum, int k)
+{
+    return __double2float_rn(__ddiv_rn(sum, (double)k));
 }
 
 // epilogue for TopNet: entries 0..k-1 are the neighbours (the query was never inserted)
@@ -254,7 +261,7 @@ __device__ __forceinline__ float mean_from_net(const TopNet<L> &lst, int k)
         for (int j = 8; j < L; ++j)
             if (j >= nfull && j < k) res = __dadd_rn(res, b[j]);
     }
-    return __double2float_rn(__ddiv_rn(res, (double)k));
+    return mean_finish(res, k);
 }
 
 // numpy pairwise sum of n <= 128 doubles read through a functor (loops_utils.h.src);
@@ -283,6 +290,20 @@ __device__ __forceinline__ double pairwise_sum_le128(F at, int n)
                            __dadd_rn(__dadd_rn(r4, r5), __dadd_rn(r6, r7)));
     for (; i < n; ++i) res = __dadd_rn(res, at(i));
     return res;
+}
+
+// numpy's pairwise_sum for any n (DEPTH halvings unrolled): above 128 the left half is n/2 rounded down to a multiple of 8
+template <int DEPTH, class F>
+__device__ double pairwise_sum_np(F at, int lo, int n)
+{
+    if constexpr (DEPTH == 0) {
+        return pairwise_sum_le128([&](int i) { return at(lo + i); }, n);
+    } else {
+        if (n <= 128) return pairwise_sum_le128([&](int i) { return at(lo + i); }, n);
+        int n2 = n / 2;
+        n2 -= n2 % 8;
+        return __dadd_rn(pairwise_sum_np<DEPTH - 1>(at, lo, n2), pairwise_sum_np<DEPTH - 1>(at, lo + n2, n - n2));
+    }
 }
 
 // Epilogue: list -> (float) mean of sqrt(entries 1..k) in numpy's pairwise order (entry 0 is the
@@ -314,7 +335,7 @@ __device__ __forceinline__ float mean_from_list(const TopList<KCAP> &lst, int k)
         for (int j = 8; j < KCAP - 1; ++j)
             if (j >= nfull && j < k) res = __dadd_rn(res, b[j]);
     }
-    return __double2float_rn(__ddiv_rn(res, (double)k));
+    return mean_finish(res, k);
 }
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }

@@ -1817,7 +1817,7 @@ __global__ __launch_bounds__(BRICK_THREADS) void knn_ring_kernel(
                 if (lane == 0) {
                     if (covers && !(kth <= rH * rH)) atomicAdd(&gp->exhaustive_count, 1u);
                     double sum = pairwise_sum_le128([&](int i) { return out[1 + i]; }, k);
-                    mean_out[(int)__float_as_uint(qp.w) - q_begin] = __double2float_rn(__ddiv_rn(sum, (double)k));
+                    mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_finish(sum, k);
                     kth_emit(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth, qp.x, qp.y, qp.z);
                 }
                 wave_sync();
@@ -1841,19 +1841,6 @@ __global__ __launch_bounds__(BRICK_THREADS) void knn_ring_kernel(
 // elements, halves rounded down to a multiple of 8 above).  k + 1 <= 2048.  Slow (9 distance evaluations per candidate)
 // and rare: nothing in the CLI's documented flags reaches it (--sor_intensity maps to k <= 50).
 constexpr int ANYK_MAX = 2048;
-
-template <int DEPTH, class F>
-__device__ double pairwise_sum_np(F at, int lo, int n)   // numpy's pairwise_sum for any n (DEPTH halvings unrolled)
-{
-    if constexpr (DEPTH == 0) {
-        return pairwise_sum_le128([&](int i) { return at(lo + i); }, n);
-    } else {
-        if (n <= 128) return pairwise_sum_le128([&](int i) { return at(lo + i); }, n);
-        int n2 = n / 2;
-        n2 -= n2 % 8;
-        return __dadd_rn(pairwise_sum_np<DEPTH - 1>(at, lo, n2), pairwise_sum_np<DEPTH - 1>(at, lo + n2, n - n2));
-    }
-}
 
 __global__ __launch_bounds__(BRICK_THREADS) void knn_anyk_kernel(GridParams *__restrict__ gp, const float4 *__restrict__ refs,
                                                                  const unsigned *__restrict__ rstart, const float4 *__restrict__ qpts,
@@ -1989,7 +1976,7 @@ __global__ __launch_bounds__(BRICK_THREADS) void knn_anyk_kernel(GridParams *__r
             wave_sync();
             if (lane == 0) {
                 const double sum = pairwise_sum_np<5>([&](int i) { return sel[1 + i]; }, 0, k);   // entry 0 is the query itself
-                mean_out[(int)__float_as_uint(qp.w) - q_begin] = __double2float_rn(__ddiv_rn(sum, (double)k));
+                mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_finish(sum, k);
                 kth_emit(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth, qp.x, qp.y, qp.z);   // (slab mode: the certificate is counted here)
                 if (covers && !(kth <= rH * rH)) atomicAdd(&gp->exhaustive_count, 1u);
             }
@@ -2109,7 +2096,7 @@ __global__ __launch_bounds__(BRICK_THREADS) void knn_heavy_merge_kernel(GridPara
         const float4 qp = qpts[heavylist[first + qi]];
         atomicAdd(&gp->exhaustive_count, 1u);
         double sum = pairwise_sum_le128([&](int i) { return out[1 + i]; }, k);
-        mean_out[(int)__float_as_uint(qp.w) - q_begin] = __double2float_rn(__ddiv_rn(sum, (double)k));
+        mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_finish(sum, k);
         kth_emit(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth, qp.x, qp.y, qp.z);   // (slab mode: the certificate is counted here)
     }
 }
@@ -2685,7 +2672,7 @@ __global__ __launch_bounds__(BRICK_THREADS, KCAP <= 33 ? RINGF_WAVES : 3) void k
             wave_sync();
             if (lane == 0) {   // out[0] = the query itself
                 double sum = pairwise_sum_le128([&](int i) { return out[1 + i]; }, k);
-                mean_out[(int)__float_as_uint(qp.w) - q_begin] = __double2float_rn(__ddiv_rn(sum, (double)k));
+                mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_finish(sum, k);
                 kth_emit(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth, qp.x, qp.y, qp.z);
             }
             wave_sync();

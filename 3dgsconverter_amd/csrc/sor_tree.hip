@@ -1225,7 +1225,7 @@ __global__ __launch_bounds__(TREE_THREADS, 6) void knn_tree_near_kernel(
         if (lane == 0) {
             const int qorig = (int)(self_w & 0x7fffffffu) - q_begin;
             const double sum = pairwise_sum_le128([&](int i) { return out[i]; }, k);
-            mean_out[qorig] = __double2float_rn(__ddiv_rn(sum, (double)k));
+            mean_out[qorig] = mean_finish(sum, k);
             if (kth_out) kth_out[qorig] = kth2;
         }
         wave_sync();
@@ -1540,7 +1540,7 @@ __global__ __launch_bounds__(TREE_THREADS, 3) void knn_tree_query_kernel(
                     if (lane == 0) {
                         const int qorig = (int)(self_w & 0x7fffffffu) - q_begin;
                         const double sum = pairwise_sum_le128([&](int i) { return out[i]; }, k);
-                        mean_out[qorig] = __double2float_rn(__ddiv_rn(sum, (double)k));
+                        mean_out[qorig] = mean_finish(sum, k);
                         if (kth_out) kth_out[qorig] = kth2;
                     }
                     wave_sync();
@@ -1556,7 +1556,7 @@ __global__ __launch_bounds__(TREE_THREADS, 3) void knn_tree_query_kernel(
                 if (lane == 0) {
                     const int qorig = (int)(self_w & 0x7fffffffu) - q_begin;
                     const double sum = pairwise_sum_le128([&](int i) { return out[i]; }, k);
-                    mean_out[qorig] = __double2float_rn(__ddiv_rn(sum, (double)k));
+                    mean_out[qorig] = mean_finish(sum, k);
                     if (kth_out) kth_out[qorig] = kv;
 #ifdef GSX_TREE_PROFILE
                     const unsigned long long dt = wall_clock64() - t_begin;

@@ -256,6 +256,25 @@ int gsx_sor_debug_work_queue(gsx_ctx *ctx, uint32_t *ctr, int64_t *items, int32_
 /* Diagnostic builds (-DGSX_WAVE_STAMPS) only: per-wave records of knn_brick (kernel 0) and knn_ring_fast (kernel 1) of the
  * context's last grid KNN call, 16 words each (csrc/sor_grid_params.h); tools/wave_stamps.py prints them. */
 int gsx_sor_debug_wave_stamps(gsx_ctx *ctx, int kernel, uint64_t *out, int64_t cap, int64_t *count);
+/* Debug / tests: the device functions beneath every mean distance (csrc/knn_common.h), called on the caller's inputs by
+ * csrc/knn_probe.hip -- the same inline functions the KNN kernels call, not copies (tests/test_knn_epilogue_gpu.py).
+ * Root: out[i] = the float64 square root of in[i] as knn_brick's and knn_anyk's epilogues take it (sqrt_rn_dist2; defined
+ * for 0 and [2^-298, 2^260), what a squared distance of float32 coordinates can be) or as every other epilogue and the
+ * SPZ / compressed-PLY readers take it (__dsqrt_rn). */
+enum { GSX_PROBE_ROOT_DIST2 = 0, GSX_PROBE_ROOT_DSQRT = 1 };
+int gsx_knn_probe_root_dev(gsx_ctx *ctx, const double *in_dev, int64_t n, int mode, double *out_dev);
+/* Mean: d2_dev holds m rows of `stride` >= k ascending squared distances of a query's neighbours (the query itself is not
+ * in the row); out_dev[r] = (float)(sum of the roots of row r's first k entries / k), summed the way `form` does:
+ *   NET    mean_from_net<cap>: cap = a list length of knn_brick / knn_leaf (8, 12, 16, ... 56, 64), k <= cap; row entries
+ *          k .. cap-1 are loaded into the list as the further neighbours they are in the kernels (+inf past the row);
+ *   LIST   mean_from_list<cap>: cap = a capacity of knn_brick's bubble-insert variant / knn_brute (9, 17, 26, 33, 51, 65),
+ *          k <= cap - 1; entry 0 of the list is the query (squared distance 0);
+ *   LE128  __dsqrt_rn of an LDS list, then pairwise_sum_le128 by one lane (knn_ring, knn_ring_fast, the tree's fallbacks), k <= 128;
+ *   NP     sqrt_rn_dist2 of an LDS list, then pairwise_sum_np<5> (knn_anyk), k <= 1000;  cap is ignored by LE128 and NP.
+ * A form or capacity that no kernel instantiates is refused. */
+enum { GSX_PROBE_MEAN_NET = 0, GSX_PROBE_MEAN_LIST = 1, GSX_PROBE_MEAN_LE128 = 2, GSX_PROBE_MEAN_NP = 3 };
+int gsx_knn_probe_mean_dev(gsx_ctx *ctx, const double *d2_dev, int64_t m, int64_t stride, int k, int form, int cap,
+                           float *out_dev);
 /*
  * np.mean / np.std / threshold -- replaces data_processor.py:176-178 and
  * gpu_ops.py:259-261 with numpy's exact float32 arithmetic (8192-element buffered

@@ -111,6 +111,17 @@ class PlyReadLayout(C.Structure):
                 ("dst_offset", C.c_int32 * PLY_READ_MAX_FIELDS), ("dst_bytes", C.c_int32 * PLY_READ_MAX_FIELDS)]
 
 
+PLY_WRITE_MAX_RUNS = 128    # GSX_PLY_WRITE_MAX_RUNS
+PLY_WRITE_MAX_STRIDE = 512  # bytes per row of the table or of the file (csrc/row_tile.h SPZ_MAX_ROW_BYTES)
+
+
+class PlyWriteLayout(C.Structure):
+    """gsx_ply_write_layout (include/gsx_hip.h): the 3DGS / CloudCompare PLY writers' run table"""
+    _fields_ = [("in_stride", C.c_int32), ("out_stride", C.c_int32), ("n_runs", C.c_int32), ("reserved", C.c_int32),
+                ("src_offset", C.c_int32 * PLY_WRITE_MAX_RUNS), ("dst_offset", C.c_int32 * PLY_WRITE_MAX_RUNS),
+                ("bytes", C.c_int32 * PLY_WRITE_MAX_RUNS)]
+
+
 class KsplatReadSection(C.Structure):
     """gsx_ksplat_read_section (include/gsx_hip.h): one section of a .ksplat file as the reader's kernel walks it"""
     _fields_ = [("rows_offset", C.c_int64), ("centres_offset", C.c_int64), ("n_rows", C.c_int64), ("out_row", C.c_int64),
@@ -264,6 +275,9 @@ SIGNATURES = {
     "gsx_np_logf_host": (_I, [_P, _P, _I64]),
     "gsx_ply_unpack_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(PlyReadLayout), _P]),
     "gsx_ply_unpack_host": (_I, [_P, _I64, C.POINTER(PlyReadLayout), _P]),
+    "gsx_ply_pack_dev": (_I, [_P, _P, _I64, C.POINTER(PlyWriteLayout), _P]),
+    "gsx_ply_pack_host": (_I, [_P, _I64, C.POINTER(PlyWriteLayout), _P]),
+    "gsx_ply_rest_nonzero_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(C.c_int32), C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -2122,6 +2136,67 @@ def ply_unpack_host(body: np.ndarray, n_rows: int, layout: PlyReadLayout, dtype:
     src[:n * layout.in_stride] = body[:n * layout.in_stride]
     out = np.empty(n, dtype)
     check(lib.gsx_ply_unpack_host(src.ctypes.data, n, C.byref(layout), out.ctypes.data), "gsx_ply_unpack_host")
+    return out
+
+
+def ply_pack_table(data: np.ndarray, plan_of, scan=None, stage_ms: "dict | None" = None, device: int = 0):
+    """The 3DGS / CloudCompare PLY writers' vertex rows from a whole table (formats/ply_3dgs.py:70-109, formats/ply_cc.py:70-116):
+    the raw rows are uploaded ONCE through the staging lanes, the crop scan reads its fields straight out of them, the plan is
+    made from its answer, gsx_ply_pack_dev moves whole rows, and the file's rows come back through the staging lanes into the
+    buffer the file is written from.
+
+    data: 1-D C-contiguous structured table of n >= 1 rows of up to 512 bytes.  scan: None, or (offsets, present_mask) of the
+    little-endian float32 f_rest_* fields for gsx_ply_rest_nonzero_dev; plan_of(last_idx) -- the highest scanned index holding a
+    value != 0, -1 for none, None without a scan -- -> the plan (formats/ply_writer.py: WritePlan).
+    -> (plan, rows): rows = uint8[n * plan.out_stride], or None when the plan is refused or its rows are the table's already
+    (nothing is packed or downloaded then).
+
+    One ArenaSession of the "plyw" lease group."""
+    lib = require_hip()
+    n = len(data)
+    if n < 1 or not data.flags.c_contiguous or data.dtype.itemsize > PLY_WRITE_MAX_STRIDE:
+        raise ValueError("ply_pack_table: %d rows of %d bytes (C-contiguous rows of up to %d)" % (n, data.dtype.itemsize, PLY_WRITE_MAX_STRIDE))
+    with ArenaSession("plyw", device, stage_ms) as s:
+        ctx = s.ctx
+        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernels read up to 15 bytes past the last row)
+        upload_table(lib, ctx, d_rows.ptr, data)
+        s.mark("upload")
+        last_idx = None
+        if scan is not None:
+            offsets, present = scan
+            word = C.c_uint64(0)
+            check(lib.gsx_ply_rest_nonzero_dev(ctx.handle, d_rows.ptr, data.dtype.itemsize, n, (C.c_int32 * 45)(*[int(o) for o in offsets]),
+                                               int(present), C.byref(word)), "gsx_ply_rest_nonzero_dev")
+            last_idx = word.value.bit_length() - 1
+            s.mark("sh_detect")
+        plan = plan_of(last_idx)
+        s.mark("plan")
+        if plan.refusal is not None or plan.identity:
+            return plan, None
+        lay = plan.layout()
+        if lay.in_stride != data.dtype.itemsize:
+            raise ValueError("ply_pack_table: a layout for rows of %d bytes, a table of %d" % (lay.in_stride, data.dtype.itemsize))
+        nbytes = n * lay.out_stride
+        out = np.empty(nbytes, np.uint8)
+        join = prefault(nbytes >= (1 << 22), out)
+        d_out = s.buf("out", nbytes)
+        check(lib.gsx_ply_pack_dev(ctx.handle, d_rows.ptr, n, C.byref(lay), d_out.ptr), "gsx_ply_pack_dev")
+        s.mark("pack")
+        join()
+        check(lib.gsx_dev_download_staged(ctx.handle, out.ctypes.data, d_out.ptr, nbytes), "gsx_dev_download_staged")
+        s.mark("download")
+        return plan, out
+
+
+def ply_pack_host(data: np.ndarray, layout: PlyWriteLayout) -> np.ndarray:
+    """gsx_ply_pack_host: the kernel's run code on the host (`data`: a 1-D C-contiguous table of layout.in_stride bytes a row) ->
+    uint8[n * layout.out_stride] -- the host tests' model of the device and the check of a run table without one"""
+    lib = load()
+    n = len(data)
+    if not data.flags.c_contiguous or data.dtype.itemsize != layout.in_stride:
+        raise ValueError("ply_pack_host: C-contiguous rows of %d bytes" % layout.in_stride)
+    out = np.empty(n * layout.out_stride, np.uint8)
+    check(lib.gsx_ply_pack_host(data.ctypes.data, n, C.byref(layout), out.ctypes.data), "gsx_ply_pack_host")
     return out
 
 

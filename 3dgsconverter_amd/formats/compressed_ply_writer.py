@@ -23,6 +23,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils import debug_print
+from .ply_container import write_ply as _write_ply   # :385-390 without plyfile (shared with formats/ply_writer.py)
 
 CHUNK_SIZE = 256   # :12
 
@@ -85,22 +86,6 @@ def encode(data: np.ndarray, order=None):
     return chunk_data, vertex_data, sh_data, order
 
 
-_PLY_TYPES = {"f4": "float", "u4": "uint", "u1": "uchar"}
-
-
-def _write_ply(path, elements):
-    """binary little-endian PLY with the given (name, structured array) elements -- the layout plyfile produces for
-    ``PlyData(elements, text=False, byte_order='<')`` (:385-390)"""
-    with open(path, "wb") as f:
-        head = ["ply", "format binary_little_endian 1.0"]
-        for name, arr in elements:
-            head.append(f"element {name} {len(arr)}")
-            for field in arr.dtype.names:
-                head.append(f"property {_PLY_TYPES[arr.dtype[field].str[1:]]} {field}")
-        head.append("end_header")
-        f.write(("\n".join(head) + "\n").encode("ascii"))
-        for _, arr in elements:
-            f.write(np.ascontiguousarray(arr).astype(arr.dtype.newbyteorder("<"), copy=False).tobytes())
 
 
 def write_compressed_ply(data: np.ndarray, path: str, **kwargs) -> None:

@@ -21,7 +21,7 @@ _saved = {}
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
             cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True, sog_reader: bool = True,
-            splat_reader: bool = False, ply_reader: bool = True):
+            splat_reader: bool = False, ply_reader: bool = True, ply_writer: bool = True):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -59,7 +59,12 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     plyfile; the reference's rows and ``self.extra_elements``).  Files the device path does not take -- ascii bodies, list
     properties, a duplicated vertex property, colours that are not uchar, big-endian files with extra fields, rows over 512
     bytes or 128 fields -- go to the reference's own read when plyfile is there.  A reference without those modules is left as
-    it is."""
+    it is.
+    ply_writer: also rebind ``gsconverter.formats.ply_3dgs.Ply3DGSFormat.write`` and ``gsconverter.formats.ply_cc.PlyCCFormat.write``
+    to formats/ply_writer.py (the output layout and the container on the host, the crop_sh scan and the row pack on the GPU, no
+    plyfile; the reference's file byte for byte, `crop_sh` and `extra_elements` honoured).  Tables the device path does not take
+    -- a field that is no PLY scalar, a big-endian field, rows over 512 bytes, more than 128 runs -- go to the reference's own
+    write when plyfile is there.  A reference without those modules, or whose classes have no `write`, is left as it is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -183,6 +188,17 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             if plymod is not None and getattr(getattr(plymod, cls, None), "read", None) is not None:
                 _saved.setdefault((key, "read"), getattr(plymod, cls).read)
                 getattr(plymod, cls).read = bind(_saved[(key, "read")])
+    if ply_writer:
+        from .formats import ply_writer as plyw
+        for key, modname, cls, bind in (("ply3dgsformat", "gsconverter.formats.ply_3dgs", "Ply3DGSFormat", plyw.bind_write_3dgs),
+                                        ("plyccformat", "gsconverter.formats.ply_cc", "PlyCCFormat", plyw.bind_write_cc)):
+            try:
+                plymod = importlib.import_module(modname)
+            except ImportError:
+                plymod = None
+            if plymod is not None and getattr(getattr(plymod, cls, None), "write", None) is not None:
+                _saved.setdefault((key, "write"), getattr(plymod, cls).write)
+                getattr(plymod, cls).write = bind(_saved[(key, "write")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops

@@ -903,6 +903,41 @@ int gsx_ply_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t first_byte, i
  * HOST pointers; body readable up to 4 bytes past the last row. */
 int gsx_ply_unpack_host(const void *body, int64_t n, const gsx_ply_read_layout *layout, void *out);
 
+
+/* ---- the 3DGS / CloudCompare PLY writers (csrc/ply_write.hip) ----
+ * gsconverter/formats/ply_3dgs.py:62-121 (Ply3DGSFormat.write) and gsconverter/formats/ply_cc.py:64-132 (PlyCCFormat.write): the
+ * zeroed table of ply_3dgs.py:104 / ply_cc.py:112 and the copy loop of ply_3dgs.py:107-109 / ply_cc.py:115-116
+ * (`output_data[name] = data[name]`, never a cast: the file keeps the table's types) as one pass over the table's rows -> the
+ * rows of the file's vertex element, byte for byte.  Which fields the file holds and in what order is decided on the host
+ * (formats/ply_writer.py), which merges fields adjacent in the table and in the file into runs:
+ *   src_offset   byte offset inside a row of the table, -1 = no source: the run is zero (a padded nx ny nz or f_rest_*)
+ *   dst_offset   byte offset inside a row of the file
+ *   bytes        1 ... 512
+ * The runs must tile the output row. */
+#define GSX_PLY_WRITE_MAX_RUNS 128
+typedef struct gsx_ply_write_layout {
+    int32_t in_stride;                  /* bytes per row of the table (its itemsize: holes included), 1 ... 512 */
+    int32_t out_stride;                 /* bytes per row of the file, 1 ... 512 */
+    int32_t n_runs;                     /* 1 ... GSX_PLY_WRITE_MAX_RUNS */
+    int32_t reserved;
+    int32_t src_offset[GSX_PLY_WRITE_MAX_RUNS];
+    int32_t dst_offset[GSX_PLY_WRITE_MAX_RUNS];
+    int32_t bytes[GSX_PLY_WRITE_MAX_RUNS];
+} gsx_ply_write_layout;
+/* ply_3dgs.py:104-109 / ply_cc.py:112-116.  rows_dev: n rows of in_stride bytes, 16-byte aligned, readable up to 16 bytes past
+ * the last row.  out_dev: n rows of out_stride bytes, 16-byte aligned.  One launch.  Asynchronous. */
+int gsx_ply_pack_dev(gsx_ctx *ctx, const void *rows_dev, int64_t n, const gsx_ply_write_layout *layout, void *out_dev);
+/* the same pack on the HOST, tile by tile and unit by unit with the kernel's own run code (the host tests hold it against
+ * numpy).  HOST pointers; nothing outside the rows is read. */
+int gsx_ply_pack_host(const void *rows, int64_t n, const gsx_ply_write_layout *layout, void *out);
+/* ply_3dgs.py:70-76 `np.any(data[f'f_rest_{i}'] != 0)` / ply_cc.py:70-76 `np.any(data[f'f_rest_{i}'])`, the loop behind crop_sh:
+ * bit i of *mask_out (HOST word) is set iff some row holds a little-endian float32 != 0 at byte offsets[i] (NaN and denormals
+ * count, -0.0 does not), for the i whose bit is set in present_mask -- the result word of gsx_spz_rest_nonzero_dev, for a table
+ * that need not hold the fields gsx_spz_layout requires.  offsets: 45 HOST values, read where present.  rows_dev as above; rows
+ * of 1 ... 512 bytes.  One pass over the rows for every field at once.  Synchronises the context's stream. */
+int gsx_ply_rest_nonzero_dev(gsx_ctx *ctx, const void *rows_dev, int64_t stride, int64_t n, const int32_t *offsets, uint64_t present_mask,
+                             uint64_t *mask_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -369,11 +369,11 @@ static int kmeans1d_dev(gsx_ctx *c, const float *vals, int64_t n, int k, int ite
     float *xs = reinterpret_cast<float *>(take(un));
     double *p1 = reinterpret_cast<double *>(take(dn)), *p2 = reinterpret_cast<double *>(take(dn));
     double *tiles = reinterpret_cast<double *>(take(sizeof(double) * 2 * (size_t)(ntiles + 2)));
-    unsigned *flags = reinterpret_cast<unsigned *>(take(64));     // [0]: non-finite input, [8]: k1_lloyd's arrival ticket
-    double *inertia = reinterpret_cast<double *>(take(64));
+    unsigned *flags = reinterpret_cast<unsigned *>(take(128));    // [0]: non-finite input, [8]: k1_lloyd's arrival ticket
+    double *inertia = reinterpret_cast<double *>(flags + 16);     // [3]; a start that does not run leaves its slot 0.0
     float *cent_tmp = reinterpret_cast<float *>(take(sizeof(float) * 2 * K1_MAXK));
     void *temp = take(temp_bytes);
-    GSX_HIP(hipMemsetAsync(flags, 0, 64, c->stream));
+    GSX_HIP(hipMemsetAsync(flags, 0, 128, c->stream));
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n, 1024), (int64_t)c->num_cu * 8));
     hipLaunchKernelGGL(k1_keys_kernel, dim3(blocks), dim3(256), 0, c->stream, vals, n, ka, flags);
     GSX_HIP(rocprim::radix_sort_keys(temp, temp_bytes, ka, kb, (size_t)n, 0, 32, c->stream));

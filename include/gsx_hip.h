@@ -470,7 +470,9 @@ int gsx_quantize_sorted_codebook(const float *vals, int64_t n, const float *code
  */
 int gsx_kmeans1d(const float *vals, int64_t n, int k, int iters, float *centroids_out, int32_t *labels_out,
                  double *inertia3_out);
-/* start_mask: bit 0 = uniform-bin start, bit 1 = equal-count-bin start (0 = both); inertia3_host is a HOST array */
+/* start_mask: bit 0 = uniform-bin start, bit 1 = equal-count-bin start (0 = both); inertia3_host is a HOST array.
+ * The slot of a start that start_mask leaves out is 0.0 (cleared on every call); with both starts the first wins unless
+ * the second's inertia is strictly smaller. */
 int gsx_kmeans1d_dev(gsx_ctx *ctx, const float *vals_dev, int64_t n, int k, int iters, int start_mask,
                      float *centroids_dev, int32_t *labels_dev, double *inertia3_host);
 

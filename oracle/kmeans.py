@@ -263,3 +263,175 @@ def kmeans_pp_restated(data: np.ndarray, k: int, uniforms: np.ndarray, n_local_t
         idx.append(int(cand[b]))
         mind = np.minimum(mind, dist[b])
     return np.asarray(idx)
+
+
+# ---- exact-sum checkers of csrc/kmeans1d.hip and csrc/kmeans_pp.hip ---------------------------------------------------
+# The device sums in another order than numpy.  On inputs whose every partial sum is exact the order cannot matter, and the
+# device must equal these float64 restatements on every bit (tests/test_kmeans_exact_gpu.py; what the builders promise is
+# asserted without a GPU in tests/test_kmeans1d_oracle.py).
+class K1Sorted:
+    """sorted values with their float64 prefix sums: the state csrc/kmeans1d.hip builds before its Lloyd steps"""
+
+    def __init__(self, xs_sorted: np.ndarray):
+        self.xs = np.ascontiguousarray(xs_sorted, dtype=np.float32).reshape(-1)
+        assert np.all(self.xs[1:] >= self.xs[:-1]), "values must be sorted"
+        self.n = len(self.xs)
+        self.x64 = self.xs.astype(np.float64)
+        self.p1 = np.concatenate([[0.0], np.cumsum(self.x64)])
+        self.p2 = np.concatenate([[0.0], np.cumsum(self.x64 * self.x64)])
+
+    def bounds(self, c: np.ndarray) -> np.ndarray:
+        """run boundaries b[0..k] of centroids c: run j = xs[b[j]:b[j+1]], a value on a midpoint goes to the lower run"""
+        mid = (c[:-1].astype(np.float64) + c[1:].astype(np.float64)) * 0.5
+        b = np.concatenate([[0], np.searchsorted(self.x64, mid, side="right"), [self.n]])
+        return np.maximum.accumulate(b)
+
+    def step(self, c: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
+        """one Lloyd step: float32(s1 / cnt) per run, an empty run keeps its centroid"""
+        b = self.bounds(c) if b is None else b
+        cnt = np.diff(b)
+        s1 = self.p1[b[1:]] - self.p1[b[:-1]]
+        return np.where(cnt > 0, s1 / np.maximum(cnt, 1), c).astype(np.float32)
+
+    def inertia_terms(self, c: np.ndarray, b: np.ndarray | None = None):
+        """per run: the device's S2 - 2 c S1 + cnt c^2 (0 for an empty run), and the magnitude S2 + 2 |c S1| + cnt c^2
+        its rounding error is proportional to"""
+        b = self.bounds(c) if b is None else b
+        cnt = np.diff(b)
+        s1 = self.p1[b[1:]] - self.p1[b[:-1]]
+        s2 = self.p2[b[1:]] - self.p2[b[:-1]]
+        cd = c.astype(np.float64)
+        terms = np.where(cnt > 0, s2 - 2.0 * cd * s1 + cnt * cd * cd, 0.0)
+        mags = np.where(cnt > 0, s2 + 2.0 * np.abs(cd * s1) + cnt * cd * cd, 0.0)
+        return terms, mags
+
+
+def kmeans1d_lloyd_from(xs_sorted, start_f32: np.ndarray, iters: int):
+    """exactly ``iters`` Lloyd steps of csrc/kmeans1d.hip from a given float32 start (the loop of kmeans1d_sorted: midpoints
+    in float64, searchsorted(side="right"), an empty run keeps its centroid, float32(s1 / cnt)).  xs_sorted: sorted float32
+    values or a K1Sorted.  -> (centroids f32[k], boundaries i64[k + 1], inertia by the device's S2 - 2 c S1 + cnt c^2)"""
+    s = xs_sorted if isinstance(xs_sorted, K1Sorted) else K1Sorted(xs_sorted)
+    c = np.ascontiguousarray(start_f32, dtype=np.float32).reshape(-1).copy()
+    for _ in range(int(iters)):
+        c = s.step(c)
+    b = s.bounds(c)
+    return c, b, float(s.inertia_terms(c, b)[0].sum())
+
+
+def kmeans1d_steps_until_fixed(xs_sorted, start_f32: np.ndarray, cap: int = 1000) -> int:
+    """the first T at which a Lloyd step no longer moves a run boundary (so step T + 1 reproduces the centroids of step T:
+    where the device leaves its loop early); ``cap`` if there is none below it"""
+    s = xs_sorted if isinstance(xs_sorted, K1Sorted) else K1Sorted(xs_sorted)
+    c = np.ascontiguousarray(start_f32, dtype=np.float32).reshape(-1).copy()
+    prev = None
+    for t in range(cap):
+        b = s.bounds(c)
+        if prev is not None and np.array_equal(b, prev):
+            return t
+        prev = b
+        c = s.step(c, b)
+    return cap
+
+
+class KmeansPPStepper:
+    """kmeans_pp_restated one centroid at a time, with its state in the open (mind, cumsum, total, and after each step the
+    candidates and their potentials), so that a test can choose a uniform that depends on that state -- a target exactly on
+    a cumulative sum, two trials on one row.  Same arithmetic as kmeans_pp_restated: the same picks bit for bit."""
+
+    def __init__(self, data: np.ndarray, n_local_trials: int):
+        self.x = np.asarray(data, dtype=np.float64)
+        self.n = len(self.x)
+        self.L = int(n_local_trials)
+        self.idx: list[int] = []
+        self.mind = None
+        self.cand = None
+        self.pots = None
+
+    def _dist(self, row: int) -> np.ndarray:
+        return ((self.x - self.x[row]) ** 2).sum(1)
+
+    def first(self, u0: float) -> int:
+        assert not self.idx
+        self.idx.append(min(int(float(u0) * self.n), self.n - 1))
+        self.mind = self._dist(self.idx[0])
+        return self.idx[0]
+
+    @property
+    def cumsum(self) -> np.ndarray:
+        return np.cumsum(self.mind)
+
+    @property
+    def total(self) -> float:
+        return float(self.cumsum[-1])
+
+    def candidates(self, ut: np.ndarray) -> np.ndarray:
+        ut = np.asarray(ut, dtype=np.float64)
+        assert ut.shape == (self.L,)
+        cs = self.cumsum
+        if not cs[-1] > 0:
+            return np.minimum((ut * self.n).astype(np.int64), self.n - 1)
+        return np.minimum(np.searchsorted(cs, ut * cs[-1], side="right"), self.n - 1)
+
+    def step(self, ut: np.ndarray) -> int:
+        self.cand = self.candidates(ut)
+        dist = np.stack([self._dist(int(c)) for c in self.cand])
+        self.pots = np.minimum(self.mind[None, :], dist).sum(1)
+        b = int(np.argmin(self.pots))
+        self.idx.append(int(self.cand[b]))
+        self.mind = np.minimum(self.mind, dist[b])
+        return self.idx[-1]
+
+    def run(self, k: int, uniforms: np.ndarray) -> np.ndarray:
+        u = np.asarray(uniforms, dtype=np.float64)
+        assert u.shape == (1 + (k - 1) * self.L,)
+        self.first(u[0])
+        for t in range(1, k):
+            self.step(u[1 + (t - 1) * self.L: 1 + t * self.L])
+        return np.asarray(self.idx)
+
+
+EXACT_1D_SHIFT = 10      # values are multiples of 2^-10 ...
+EXACT_1D_LIMIT = 1 << 15  # ... below 2^5 in magnitude ...
+EXACT_1D_MAXN = 1 << 20   # ... and at most 2^20 of them
+
+
+def exact_values_1d(m: np.ndarray, negative_zero: bool = False) -> np.ndarray:
+    """float32 values m * 2^-10 for integers |m| < 2^15, at most 2^20 of them: any sum of them is an integer below 2^35
+    times 2^-10, any sum of their squares an integer below 2^50 times 2^-20 -- both fit 53 bits, so float64 sums of them
+    are exact in ANY order.  Asserted in integer arithmetic.  negative_zero: the zeros are written as -0.0."""
+    m = np.asarray(m)
+    assert m.dtype.kind == "i" and m.ndim == 1 and 1 <= len(m) <= EXACT_1D_MAXN
+    m = m.astype(np.int64)
+    assert np.abs(m).max() < EXACT_1D_LIMIT
+    assert int(np.abs(m).sum()) < 1 << 53 and int((m * m).sum()) < 1 << 53
+    x = (m.astype(np.float64) * 2.0 ** -EXACT_1D_SHIFT).astype(np.float32)
+    x64 = x.astype(np.float64)
+    assert np.array_equal(x64 * 2.0 ** EXACT_1D_SHIFT, m.astype(np.float64))
+    assert np.array_equal((np.cumsum(x64) * 2.0 ** EXACT_1D_SHIFT).astype(np.int64), np.cumsum(m))
+    assert np.array_equal(np.cumsum(x64) * 2.0 ** EXACT_1D_SHIFT, np.cumsum(m).astype(np.float64))
+    assert np.array_equal(np.cumsum(x64 * x64) * 4.0 ** EXACT_1D_SHIFT, np.cumsum(m * m).astype(np.float64))
+    assert np.array_equal((np.cumsum(x64 * x64) * 4.0 ** EXACT_1D_SHIFT).astype(np.int64), np.cumsum(m * m))
+    if negative_zero:
+        x[m == 0] = np.float32(-0.0)
+    return x
+
+
+EXACT_PP_COORD = 15
+EXACT_PP_MAXD = 1024
+EXACT_PP_MAXN = 5000
+
+
+def exact_rows_pp(rows: np.ndarray) -> np.ndarray:
+    """float32 rows with integer coordinates in [-15, 15], d <= 1024, n <= 5000: a squared distance is a sum of d squares of
+    integers up to 30, every partial sum of it at most 900 d < 2^24 and so exact in float32 whatever the order or the
+    contraction; a sum of n of them is below 2^24 * 5000 < 2^53 and exact in float64.  Asserted on the integers."""
+    r = np.asarray(rows)
+    assert r.dtype.kind == "i" and r.ndim == 2
+    n, d = r.shape
+    assert 1 <= n <= EXACT_PP_MAXN and 1 <= d <= EXACT_PP_MAXD
+    r = r.astype(np.int64)
+    assert np.abs(r).max() <= EXACT_PP_COORD
+    assert d * (2 * EXACT_PP_COORD) ** 2 < 1 << 24 and n * d * (2 * EXACT_PP_COORD) ** 2 < 1 << 53
+    x = r.astype(np.float32)
+    assert np.array_equal(x.astype(np.int64), r)
+    return x

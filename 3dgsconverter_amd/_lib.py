@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import os
 import threading
 import time
@@ -1098,6 +1099,19 @@ def prefault(large: bool, *arrays):
     return th.join
 
 
+def stage_in(s: "ArenaSession", out: np.ndarray, nbytes: int, fill, stage: str):
+    """A table reader's host half, all of it before any device work: prefault `out` when it is at least 4 MiB, take the
+    session's staging buffer "in" of `nbytes`, let ``fill(host)`` put the file's bytes there and mark `stage`.  What `fill`
+    raises leaves the block as it is: no device buffer has been asked for by then, nothing uploaded or launched.  A function of
+    the session and no method of it, because the SPZ and SOG host tests run it on a stand-in session that has staging() and
+    nothing else.  -> (host, join); ArenaSession.upload_in and .download_rows are the device half"""
+    join = prefault(out.nbytes >= (1 << 22), out)
+    host = s.staging("in", nbytes)
+    fill(host)
+    s.mark(stage)
+    return host, join
+
+
 def file_backed(a) -> bool:
     """is this array a view of a memory-mapped FILE (np.memmap, np.frombuffer over an mmap)?  Pinning such pages in place would
     either fail (read-only mapping) or, for a copy-on-write mapping, make the kernel copy every page first"""
@@ -1166,6 +1180,13 @@ def read_exact(f, view, path: str, where: str = "", unit: str = "bytes"):
         if not r:
             raise ValueError("%s: early end of file%s (%d of %d %s)" % (path, where, got, len(view), unit))
         got += r
+
+
+def read_file(path: str, offset: int, view, where: str = "", unit: str = "bytes"):
+    """read_exact() from byte `offset` of the file `path`"""
+    with open(path, "rb") as f:
+        f.seek(int(offset))
+        read_exact(f, view, path, where, unit)
 
 
 def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = None, ctx: "Context | None" = None, stage_ms: "dict | None" = None):
@@ -1448,34 +1469,41 @@ def np_exp_probe_vector() -> np.ndarray:
 
 
 _np_exp_checked = None
+NP_PROBE_FALLBACK = {"exp": "the .ksplat and .splat writers take every exp-derived value from numpy on the host",
+                     "log": "the .splat reader takes the scales from numpy on the host"}
+
+
+def np_probe(name: str) -> bool:
+    """np_exp_probe and np_log_probe, `name` = "exp" / "log": numpy's float32 function against its host twin np_<name>_host on
+    np_<name>_probe_vector(), once per process (the verdict: _np_<name>_checked).  On a mismatch, with the first differing
+    input: a RuntimeWarning and False, or under GSX_STRICT_NUMPY=1 a GsxError and the verdict forgotten.  The twin, the vector
+    and the verdict are looked up by name at the call: the tests replace them in this module."""
+    g, slot = globals(), "_np_%s_checked" % name
+    if g[slot] is not None:
+        return g[slot]
+    import warnings
+    x = g["np_%s_probe_vector" % name]()
+    with np.errstate(all="ignore"):
+        want = getattr(np, name)(x).view(np.uint32)
+    got = g["np_%s_host" % name](x).view(np.uint32)
+    bad = np.nonzero(got != want)[0]
+    if len(bad):
+        i = int(bad[0])
+        msg = ("numpy %s's float32 %s differs from the one libgsx_hip reproduces (numpy 2.x's AVX512F / AVX2 routine) on %d of %d "
+               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): %s.  GSX_STRICT_NUMPY=1 turns this warning into an error."
+               % (np.__version__, name, len(bad), len(x), int(x.view(np.uint32)[i]), int(got[i]), int(want[i]), NP_PROBE_FALLBACK[name]))
+        if os.environ.get("GSX_STRICT_NUMPY") == "1":
+            raise GsxError(msg)
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+    g[slot] = not len(bad)
+    return g[slot]
 
 
 def np_exp_probe() -> bool:
-    """The .ksplat and .splat writers store np.exp's float32 bits, so the device's exp (csrc/np_exp.h) must be THIS process's numpy's.  Probed
-    once per process: the host twin against np.exp on np_exp_probe_vector().  On a mismatch: a RuntimeWarning and False (the
-    writer then takes every exp-derived result -- scales, alpha -- from numpy on the host, and stays exact), or under
-    GSX_STRICT_NUMPY=1 a GsxError."""
-    global _np_exp_checked
-    if _np_exp_checked is not None:
-        return _np_exp_checked
-    import warnings
-    x = np_exp_probe_vector()
-    with np.errstate(all="ignore"):
-        want = np.exp(x).view(np.uint32)
-    got = np_exp_host(x).view(np.uint32)
-    bad = np.nonzero(got != want)[0]
-    _np_exp_checked = not len(bad)
-    if len(bad):
-        i = int(bad[0])
-        msg = ("numpy %s's float32 exp differs from the one libgsx_hip reproduces (numpy 2.x's AVX512F / AVX2 routine) on %d of %d "
-               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): the .ksplat and .splat writers take every exp-derived "
-               "value from numpy on the host.  GSX_STRICT_NUMPY=1 turns this warning into an error."
-               % (np.__version__, len(bad), len(x), int(x.view(np.uint32)[i]), int(got[i]), int(want[i])))
-        if os.environ.get("GSX_STRICT_NUMPY") == "1":
-            _np_exp_checked = None
-            raise GsxError(msg)
-        warnings.warn(msg, RuntimeWarning, stacklevel=2)
-    return _np_exp_checked
+    """The .ksplat and .splat writers store np.exp's float32 bits, so the device's exp (csrc/np_exp.h) must be THIS process's
+    numpy's: np_probe("exp").  False: the writer takes every exp-derived result -- scales, alpha -- from numpy on the host, and
+    stays exact."""
+    return np_probe("exp")
 
 
 def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms: "dict | None" = None, listed: "dict | None" = None,
@@ -1632,25 +1660,21 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
         return out
 
 
-_cply_tables = None
-
-
+@functools.cache
 def cply_read_tables() -> np.ndarray:
     """The compressed-PLY reader's quotient tables (GSX_CPLY_TAB_*), each entry numpy's own result for the reference's statement
     on that input -- so the device divides only in the colour's `/ SH_C0` and takes no log.  -> uint8[GSX_CPLY_TAB_BYTES]"""
-    global _cply_tables
-    if _cply_tables is None:
-        with np.errstate(all="ignore"):
-            q2047 = np.arange(2048, dtype=np.uint32) / 2047                                     # compressed_ply.py:346
-            q1023 = np.arange(1024, dtype=np.uint32) / 1023
-            q255 = np.arange(256, dtype=np.uint32) / 255.0                                      # :359
-            dq = (np.arange(1024, dtype=np.uint32) / 1023.0 - 0.5) / 0.7071067811865476        # :370-371
-            a = np.clip(np.arange(256, dtype=np.uint32) / 255.0, 1e-6, 1.0 - 1e-6)             # :361, :118-119
-            opa = np.log(a / (1.0 - a)).astype(np.float32)
-            sh = ((np.arange(256, dtype=np.uint8) / 256.0 - 0.5) * 8.0).astype(np.float32)     # :126
-        _cply_tables = np.concatenate([np.concatenate([q2047, q1023, q255, dq]).view(np.uint8), opa.view(np.uint8), sh.view(np.uint8)])
-        assert _cply_tables.nbytes == 8 * 4352 + 4 * 512
-    return _cply_tables
+    with np.errstate(all="ignore"):
+        q2047 = np.arange(2048, dtype=np.uint32) / 2047                                     # compressed_ply.py:346
+        q1023 = np.arange(1024, dtype=np.uint32) / 1023
+        q255 = np.arange(256, dtype=np.uint32) / 255.0                                      # :359
+        dq = (np.arange(1024, dtype=np.uint32) / 1023.0 - 0.5) / 0.7071067811865476        # :370-371
+        a = np.clip(np.arange(256, dtype=np.uint32) / 255.0, 1e-6, 1.0 - 1e-6)             # :361, :118-119
+        opa = np.log(a / (1.0 - a)).astype(np.float32)
+        sh = ((np.arange(256, dtype=np.uint8) / 256.0 - 0.5) * 8.0).astype(np.float32)     # :126
+    tables = np.concatenate([np.concatenate([q2047, q1023, q255, dq]).view(np.uint8), opa.view(np.uint8), sh.view(np.uint8)])
+    assert tables.nbytes == 8 * 4352 + 4 * 512
+    return tables
 
 
 def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunks: int, n_vertices: int, dtype: np.dtype,
@@ -1668,62 +1692,46 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
     if n_dec == 0:
         out.view(np.uint8)[:] = 0
         return out
-    parts = [(k, segments.get(k)) for k in ("chunk", "vertex", "sh")]
     place, total = {}, 0
-    for k, seg in parts:                     # each body at a 16-byte boundary of one staging buffer, 16 spare bytes after it
-        if seg is not None:
+    for k in ("chunk", "vertex", "sh"):      # each body at a 16-byte boundary of one staging buffer, 16 spare bytes after it
+        if segments.get(k) is not None:
             place[k] = total
-            total += (int(seg[1]) + 16 + 15) & ~15
-    with ArenaSession("cplyread", device, stage_ms) as s:
-        ctx = s.ctx
-        rb = dtype.itemsize
-        join = prefault(out.nbytes >= (1 << 22), out)
-        host = s.staging("in", total)
+            total += (int(segments[k][1]) + 16 + 15) & ~15
+    rb = dtype.itemsize
+
+    def fill(host):
         with open(path, "rb") as f:
-            for k, seg in parts:
-                if seg is None:
-                    continue
-                f.seek(int(seg[0]))
-                read_exact(f, host[place[k]:place[k] + int(seg[1])], path, " in element %r" % k)
-        host_tab = cply_read_tables()
-        s.mark("file_read")
-        d_in = s.buf("in", total)
-        d_tab = s.buf("tables", host_tab.nbytes)
-        s.upload_staging(lib, d_in.ptr, host)
-        d_tab.upload(host_tab)
+            for k, at in place.items():
+                f.seek(int(segments[k][0]))
+                read_exact(f, host[at:at + int(segments[k][1])], path, " in element %r" % k)
+    with ArenaSession("cplyread", device, stage_ms) as s:
+        host, join = stage_in(s, out, total, fill, "file_read")
+        d_in, d_tab = s.upload_in(lib, host, total, cply_read_tables())
         s.mark("upload")
         d_out = s.buf("out", n_dec * rb)
         ptr = {k: d_in.ptr + place[k] for k in place}
-        check(lib.gsx_cply_unpack_dev(ctx.handle, ptr["chunk"], int(n_chunks), ptr["vertex"], n, ptr.get("sh"), C.byref(layout), d_tab.ptr,
+        check(lib.gsx_cply_unpack_dev(s.ctx.handle, ptr["chunk"], int(n_chunks), ptr["vertex"], n, ptr.get("sh"), C.byref(layout), d_tab.ptr,
                                       d_out.ptr), "gsx_cply_unpack_dev")
         s.mark("kernel")
-        join()
-        flat = out.view(np.uint8)
-        check(lib.gsx_dev_download_staged(ctx.handle, flat.ctypes.data, d_out.ptr, n_dec * rb), "gsx_dev_download_staged")
-        if n_dec < n:
-            flat[n_dec * rb:] = 0
+        s.download_rows(lib, out, d_out, n_dec * rb, join)
+        out.view(np.uint8)[n_dec * rb:] = 0        # rows past 256 n_chunks
         s.mark("download")
         return out
 
 
-_ksplat_read_tables = None
-
-
+@functools.cache
 def ksplat_read_tables() -> np.ndarray:
     """The .ksplat reader's colour tables, numpy's own results for the reference's statements on every byte: float32
     (b / 255.0 - 0.5) / SH_C0 [256] (formats/ksplat.py:230-233) | log(a / (1 - a)), a = clip(b / 255.0, 1e-7, 1 - 1e-7) [256]
     (:24-27) -- so the device takes no log.  -> float32[512]"""
-    global _ksplat_read_tables
-    if _ksplat_read_tables is None:
-        with np.errstate(all="ignore"):
-            b = np.arange(256, dtype=np.uint8)
-            rgba_f = b.astype(np.float32) / 255.0
-            f_dc = (rgba_f - 0.5) / 0.28209479177387814
-            alpha = np.clip(b.astype(np.float32) / 255.0, 1e-7, 1.0 - 1e-7)
-            opa = np.log(alpha / (1.0 - alpha))
-        assert f_dc.dtype == np.float32 and opa.dtype == np.float32
-        _ksplat_read_tables = np.concatenate([f_dc, opa])
-    return _ksplat_read_tables
+    with np.errstate(all="ignore"):
+        b = np.arange(256, dtype=np.uint8)
+        rgba_f = b.astype(np.float32) / 255.0
+        f_dc = (rgba_f - 0.5) / 0.28209479177387814
+        alpha = np.clip(b.astype(np.float32) / 255.0, 1e-7, 1.0 - 1e-7)
+        opa = np.log(alpha / (1.0 - alpha))
+    assert f_dc.dtype == np.float32 and opa.dtype == np.float32
+    return np.concatenate([f_dc, opa])
 
 
 def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int, sections, prefix: np.ndarray, n_coeffs: int,
@@ -1747,62 +1755,48 @@ def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int
     secs = (KsplatReadSection * max(len(sections), 1))(*sections)
     prefix = np.ascontiguousarray(prefix, dtype=np.uint32)
     with ArenaSession("ksread", device, stage_ms) as s:
-        ctx = s.ctx
-        join = prefault(out.nbytes >= (1 << 22), out)
-        host = s.staging("in", total)
-        with open(path, "rb") as f:
-            f.seek(int(body_offset))
-            read_exact(f, host, path, unit="payload bytes")
-        host_tab = ksplat_read_tables()
-        s.mark("file_read")
-        d_in = s.buf("in", total + 32)             # the kernel's 16-byte loads reach up to 15 bytes past the last row
-        d_tab = s.buf("tables", host_tab.nbytes)
+        host, join = stage_in(s, out, total, lambda view: read_file(path, body_offset, view, unit="payload bytes"), "file_read")
+        d_in, d_tab = s.upload_in(lib, host, total + 32, ksplat_read_tables())   # 16-byte loads reach up to 15 bytes past the last row
         d_prefix = s.buf("prefix", max(prefix.nbytes, 16))
-        s.upload_staging(lib, d_in.ptr, host)
-        d_tab.upload(host_tab)
         if prefix.size:
             d_prefix.upload(prefix)
         s.mark("upload")
         d_out = s.buf("out", n * rb)
-        check(lib.gsx_ksplat_unpack_dev(ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
+        check(lib.gsx_ksplat_unpack_dev(s.ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
                                         d_tab.ptr, int(n_coeffs), d_out.ptr, n), "gsx_ksplat_unpack_dev")
         s.mark("kernel")
-        join()
-        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
 
 
-_spz_read_tables = None
 SPZ_READ_TABLES = ("opacity", "f_dc", "rgb", "scale", "sh", "rot_legacy", "rot_v3")   # GSX_SPZ_TAB_* order (include/gsx_hip.h)
 SPZ_READ_POS_BYTES = {1: 6, 2: 9, 3: 9}   # spz.py:184, :190
 SPZ_READ_ROT_BYTES = {1: 3, 2: 3, 3: 4}   # :232, :228
 
 
+@functools.cache
 def spz_read_tables() -> dict:
     """The SPZ reader's tables, numpy's own results for the reference's statements on every input (formats/spz.py), each with
     the reference's expression and operand dtypes -- so the device takes no log and divides only in the positions:
     "opacity" f4[256] :345-348 | "f_dc" f4[256] :207 | "rgb" u1[256] :214, the byte derived from that f_dc | "scale" f4[256]
     :222 (float64 there, rounded once on assignment) | "sh" f4[256] :243 | "rot_legacy" f4[256] :256 | "rot_v3" f4[1024]
     :274-277 (float64 there -- uint32 times a Python float -- holding a float32 value with its sign)"""
-    global _spz_read_tables
-    if _spz_read_tables is None:
-        with np.errstate(all="ignore"):
-            b = np.arange(256, dtype=np.uint8)
-            v = np.clip(b.astype(np.float32) / 255.0, 1e-7, 1.0 - 1e-7)
-            opa = np.log(v / (1.0 - v))
-            f_dc = (b.astype(np.float32) / 255.0 - 0.5) / 0.15
-            rgb = np.clip((0.5 + 0.28209479177387814 * f_dc) * 255.0, 0, 255).astype(np.uint8)
-            scale = (b / 16.0 - 10.0).astype(np.float32)
-            sh = (b.astype(np.float32) - 128.0) / 128.0
-            rot_legacy = b.astype(np.float32) / 127.5 - 1.0
-            c = np.arange(1024, dtype=np.uint32)
-            mag, neg = c & 0x1FF, (c >> 9) & 0x1
-            rot_v3 = ((mag.astype(np.float32) / 511.0) * 0.707106781186547524401 * (1.0 - 2.0 * neg)).astype(np.float32)
-        for t in (opa, f_dc, sh, rot_legacy):
-            assert t.dtype == np.float32
-        _spz_read_tables = dict(zip(SPZ_READ_TABLES, (opa, f_dc, rgb, scale, sh, rot_legacy, rot_v3)))
-    return _spz_read_tables
+    with np.errstate(all="ignore"):
+        b = np.arange(256, dtype=np.uint8)
+        v = np.clip(b.astype(np.float32) / 255.0, 1e-7, 1.0 - 1e-7)
+        opa = np.log(v / (1.0 - v))
+        f_dc = (b.astype(np.float32) / 255.0 - 0.5) / 0.15
+        rgb = np.clip((0.5 + 0.28209479177387814 * f_dc) * 255.0, 0, 255).astype(np.uint8)
+        scale = (b / 16.0 - 10.0).astype(np.float32)
+        sh = (b.astype(np.float32) - 128.0) / 128.0
+        rot_legacy = b.astype(np.float32) / 127.5 - 1.0
+        c = np.arange(1024, dtype=np.uint32)
+        mag, neg = c & 0x1FF, (c >> 9) & 0x1
+        rot_v3 = ((mag.astype(np.float32) / 511.0) * 0.707106781186547524401 * (1.0 - 2.0 * neg)).astype(np.float32)
+    for t in (opa, f_dc, sh, rot_legacy):
+        assert t.dtype == np.float32
+    return dict(zip(SPZ_READ_TABLES, (opa, f_dc, rgb, scale, sh, rot_legacy, rot_v3)))
 
 
 def spz_read_table_words() -> np.ndarray:
@@ -1834,32 +1828,35 @@ def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractiona
     out = np.empty(n, dtype)
     if n == 0:
         return out
+    host_tab = spz_read_table_words()
     with ArenaSession("spzread", device, stage_ms) as s:
-        join = prefault(out.nbytes >= (1 << 22), out)
-        host = s.staging("in", total)
-        fill(host)
-        ctx = s.ctx
-        host_tab = spz_read_table_words()
-        s.mark(fill_stage)
-        d_in = s.buf("in", total + 32)             # the kernel's 16-byte loads reach up to 15 bytes past the last section
-        d_tab = s.buf("tables", host_tab.nbytes)
-        s.upload_staging(lib, d_in.ptr, host)
-        d_tab.upload(host_tab)
+        host, join = stage_in(s, out, total, fill, fill_stage)
+        d_in, d_tab = s.upload_in(lib, host, total + 32, host_tab)   # 16-byte loads reach up to 15 bytes past the last section
         s.mark("upload")
         d_out = s.buf("out", n * rb)
-        check(lib.gsx_spz_unpack_dev(ctx.handle, d_in.ptr, total, int(version), int(degree), int(fractional_bits), d_tab.ptr, d_out.ptr, n),
+        check(lib.gsx_spz_unpack_dev(s.ctx.handle, d_in.ptr, total, int(version), int(degree), int(fractional_bits), d_tab.ptr, d_out.ptr, n),
               "gsx_spz_unpack_dev")
         s.mark("kernel")
-        join()
-        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
 
 
-_sog_read_fixed = None
 SOG_READ_TABLES = ("scale_cb", "sh0_cb", "shn_cb", "opacity", "quat", "pos")       # GSX_SOG_TAB_* order (include/gsx_hip.h)
 SOG_READ_TEXTURES = ("means_l", "means_u", "scales", "quats", "sh0", "shN_labels", "shN_centroids")   # gsx_sog_unpack_dev's order
 SOG_COEFFS_PER_BAND = (0, 9, 24, 45)      # sog.py:170
+
+
+@functools.cache
+def sog_read_fixed_tables():
+    """sog_read_tables' "opacity" and "quat": the two that depend on no file"""
+    with np.errstate(all="ignore"):
+        b = np.arange(256, dtype=np.uint8)
+        alpha = np.clip(b.astype(np.float32) / 255.0, 1.0 / 255.0, 0.9999)
+        opa = -np.log((1.0 / alpha) - 1.0)
+        quat = (b.astype(np.float32) / 255.0 - 0.5) * 2.0
+    assert opa.dtype == np.float32 and quat.dtype == np.float32
+    return opa, quat
 
 
 def sog_read_tables(mins, maxs, scale_codebook, sh0_codebook, shn_codebook=None) -> dict:
@@ -1869,15 +1866,7 @@ def sog_read_tables(mins, maxs, scale_codebook, sh0_codebook, shn_codebook=None)
     empty without one) | "opacity" f4[256] :156-158 | "quat" f4[256] :108 | "pos" f4[3][65536] :78-86: the u16 code divided by
     65535.0 is float64 and so is all that follows, mins and maxs being the JSON's Python numbers; rounded once to float32, as
     the assignment into the float32 field does"""
-    global _sog_read_fixed
     with np.errstate(all="ignore"):
-        if _sog_read_fixed is None:
-            b = np.arange(256, dtype=np.uint8)
-            alpha = np.clip(b.astype(np.float32) / 255.0, 1.0 / 255.0, 0.9999)
-            opa = -np.log((1.0 / alpha) - 1.0)
-            quat = (b.astype(np.float32) / 255.0 - 0.5) * 2.0
-            assert opa.dtype == np.float32 and quat.dtype == np.float32
-            _sog_read_fixed = (opa, quat)
         qv = np.arange(65536, dtype=np.uint32).astype(np.uint16)
         pos = np.empty((3, 65536), np.float32)
         for idx in range(3):
@@ -1886,7 +1875,7 @@ def sog_read_tables(mins, maxs, scale_codebook, sh0_codebook, shn_codebook=None)
             pos[idx] = np.sign(log_val) * (np.exp(np.abs(log_val)) - 1.0)
         assert norm.dtype == np.float64
     cbs = [np.array(cb if cb is not None else [], dtype=np.float32) for cb in (scale_codebook, sh0_codebook, shn_codebook)]
-    return dict(zip(SOG_READ_TABLES, (*cbs, *_sog_read_fixed, pos)))
+    return dict(zip(SOG_READ_TABLES, (*cbs, *sog_read_fixed_tables(), pos)))
 
 
 def sog_read_table_words(tables: dict) -> np.ndarray:
@@ -1935,21 +1924,14 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
     host_tab = sog_read_table_words(tables)
     out = np.empty(n, dtype)
     with ArenaSession("sogread", device, stage_ms) as s:
-        join = prefault(out.nbytes >= (1 << 22), out)
-        host = s.staging("in", total)
-        fill(host, place)
-        ctx = s.ctx
-        s.mark("decode")
-        d_in = s.buf("in", total + 32)             # spare bytes behind the last texel: no load reaches past the allocation
-        d_tab = s.buf("tables", host_tab.nbytes)
+        host, join = stage_in(s, out, total, lambda view: fill(view, place), "decode")
+        d_in, d_tab = s.upload_in(lib, host, total + 32, host_tab)   # spare bytes behind the last texel: no load reaches past the allocation
         d_flag = s.buf("flag", 16)
-        s.upload_staging(lib, d_in.ptr, host)
-        d_tab.upload(host_tab)
-        check(lib.gsx_dev_memset(ctx.handle, d_flag.ptr, 0, 16), "gsx_dev_memset")
+        check(lib.gsx_dev_memset(s.ctx.handle, d_flag.ptr, 0, 16), "gsx_dev_memset")
         s.mark("upload")
         d_out = s.buf("out", n * rb)
         offsets = (_I64 * 7)(*[place[t][0] if t in place else -1 for t in SOG_READ_TEXTURES])
-        check(lib.gsx_sog_unpack_dev(ctx.handle, d_in.ptr, total, offsets, bands, palette, d_tab.ptr, d_out.ptr, n, d_flag.ptr),
+        check(lib.gsx_sog_unpack_dev(s.ctx.handle, d_in.ptr, total, offsets, bands, palette, d_tab.ptr, d_out.ptr, n, d_flag.ptr),
               "gsx_sog_unpack_dev")
         s.mark("kernel")
         if bands and int(d_flag.download(np.uint32, 1)[0]):
@@ -1957,8 +1939,7 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
             if on_flag is not None:
                 on_flag(host, place)
             raise IndexError("sog_unpack_table: a label at or above the palette's %d entries" % palette)
-        join()
-        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
 
@@ -1999,51 +1980,28 @@ def np_log_probe() -> bool:
     """The .splat reader stores np.log's float32 bits, so the device's log (csrc/np_log.h) must be THIS process's numpy's.  Probed
     once per process: the host twin against np.log on np_log_probe_vector().  On a mismatch: a RuntimeWarning and False (the
     reader then takes the three scale columns from numpy on the host, and stays exact), or under GSX_STRICT_NUMPY=1 a GsxError."""
-    global _np_log_checked
-    if _np_log_checked is not None:
-        return _np_log_checked
-    import warnings
-    x = np_log_probe_vector()
-    with np.errstate(all="ignore"):
-        want = np.log(x).view(np.uint32)
-    got = np_log_host(x).view(np.uint32)
-    bad = np.nonzero(got != want)[0]
-    _np_log_checked = not len(bad)
-    if len(bad):
-        i = int(bad[0])
-        msg = ("numpy %s's float32 log differs from the one libgsx_hip reproduces (numpy 2.x's AVX512F / AVX2 routine) on %d of %d "
-               "probe inputs (first: x=0x%08x -> device 0x%08x, numpy 0x%08x): the .splat reader takes the scales from numpy on the "
-               "host.  GSX_STRICT_NUMPY=1 turns this warning into an error."
-               % (np.__version__, len(bad), len(x), int(x.view(np.uint32)[i]), int(got[i]), int(want[i])))
-        if os.environ.get("GSX_STRICT_NUMPY") == "1":
-            _np_log_checked = None
-            raise GsxError(msg)
-        warnings.warn(msg, RuntimeWarning, stacklevel=2)
-    return _np_log_checked
+    return np_probe("log")
 
 
-_splat_read_tables = None
 SPLAT_READ_TABLES = ("f_dc", "opacity")   # GSX_SPLAT_TAB_* order (include/gsx_hip.h)
 SPLAT_READ_RECORD = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("scale_0", "<f4"), ("scale_1", "<f4"), ("scale_2", "<f4"),
                               ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("opacity", "u1"),
                               ("rot_0", "u1"), ("rot_1", "u1"), ("rot_2", "u1"), ("rot_3", "u1")])   # splat.py:24-29
 
 
+@functools.cache
 def splat_read_tables() -> dict:
     """The .splat reader's tables, numpy's own results for the reference's statements on every byte, each with the reference's
     expression and operand dtypes -- so the device takes no log of them: "f_dc" f4[256] splat.py:75-77 | "opacity" f4[256]
     :67-69 (the clip's bounds are Python floats: the chain stays float32)"""
-    global _splat_read_tables
-    if _splat_read_tables is None:
-        with np.errstate(all="ignore"):
-            b = np.arange(256, dtype=np.uint8)
-            f_dc = (b.astype(np.float32) / 255.0 - 0.5) / 0.28209479177387814
-            linear_alpha = b.astype(np.float32) / 255.0
-            linear_alpha = np.clip(linear_alpha, 1.0 / 255.0, 0.9999)
-            opa = -np.log((1.0 / linear_alpha) - 1.0)
-        assert f_dc.dtype == np.float32 and opa.dtype == np.float32
-        _splat_read_tables = dict(zip(SPLAT_READ_TABLES, (f_dc, opa)))
-    return _splat_read_tables
+    with np.errstate(all="ignore"):
+        b = np.arange(256, dtype=np.uint8)
+        f_dc = (b.astype(np.float32) / 255.0 - 0.5) / 0.28209479177387814
+        linear_alpha = b.astype(np.float32) / 255.0
+        linear_alpha = np.clip(linear_alpha, 1.0 / 255.0, 0.9999)
+        opa = -np.log((1.0 / linear_alpha) - 1.0)
+    assert f_dc.dtype == np.float32 and opa.dtype == np.float32
+    return dict(zip(SPLAT_READ_TABLES, (f_dc, opa)))
 
 
 def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
@@ -2064,22 +2022,13 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
     host_tab = np.concatenate([tabs[k] for k in SPLAT_READ_TABLES])
     out = np.empty(n, dtype)
     with ArenaSession("splatread", device, stage_ms) as s:
-        ctx = s.ctx
-        join = prefault(out.nbytes >= (1 << 22), out)
-        host = s.staging("in", total)
-        with open(path, "rb") as f:
-            read_exact(f, host, path, unit="record bytes")
-        s.mark("file_read")
-        d_in = s.buf("in", total)
-        d_tab = s.buf("tables", host_tab.nbytes)
-        s.upload_staging(lib, d_in.ptr, host)
-        d_tab.upload(host_tab)
+        host, join = stage_in(s, out, total, lambda view: read_file(path, 0, view, unit="record bytes"), "file_read")
+        d_in, d_tab = s.upload_in(lib, host, total, host_tab)
         s.mark("upload")
         d_out = s.buf("out", n * rb)
-        check(lib.gsx_splat_unpack_dev(ctx.handle, d_in.ptr, n, d_tab.ptr, d_out.ptr), "gsx_splat_unpack_dev")
+        check(lib.gsx_splat_unpack_dev(s.ctx.handle, d_in.ptr, n, d_tab.ptr, d_out.ptr), "gsx_splat_unpack_dev")
         s.mark("kernel")
-        join()
-        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.download_rows(lib, out, d_out, n * rb, join)
         if not log_ok:
             recs = host.view(SPLAT_READ_RECORD)
             with np.errstate(all="ignore"):
@@ -2108,21 +2057,13 @@ def ply_unpack_table(path: str, body_offset: int, n_rows: int, layout: PlyReadLa
     total = (used + 16 + 15) & ~15             # the kernel's 16-byte loads read up to 15 bytes past the last row
     out = np.empty(n, dtype)
     with ArenaSession("plyread", device, stage_ms) as s:
-        ctx = s.ctx
-        join = prefault(out.nbytes >= (1 << 22), out)
-        host = s.staging("in", total)
-        with open(path, "rb") as f:
-            f.seek(start)
-            read_exact(f, host[:used], path, " in element 'vertex'")
-        s.mark("file_read")
-        d_in = s.buf("in", total)
-        s.upload_staging(lib, d_in.ptr, host)
+        host, join = stage_in(s, out, total, lambda view: read_file(path, start, view[:used], " in element 'vertex'"), "file_read")
+        d_in, _ = s.upload_in(lib, host, total)
         s.mark("upload")
         d_out = s.buf("out", n * rb)
-        check(lib.gsx_ply_unpack_dev(ctx.handle, d_in.ptr, first, n, C.byref(layout), d_out.ptr), "gsx_ply_unpack_dev")
+        check(lib.gsx_ply_unpack_dev(s.ctx.handle, d_in.ptr, first, n, C.byref(layout), d_out.ptr), "gsx_ply_unpack_dev")
         s.mark("kernel")
-        join()
-        check(lib.gsx_dev_download_staged(ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, n * rb), "gsx_dev_download_staged")
+        s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
 
@@ -2182,8 +2123,7 @@ def ply_pack_table(data: np.ndarray, plan_of, scan=None, stage_ms: "dict | None"
         d_out = s.buf("out", nbytes)
         check(lib.gsx_ply_pack_dev(ctx.handle, d_rows.ptr, n, C.byref(lay), d_out.ptr), "gsx_ply_pack_dev")
         s.mark("pack")
-        join()
-        check(lib.gsx_dev_download_staged(ctx.handle, out.ctypes.data, d_out.ptr, nbytes), "gsx_dev_download_staged")
+        s.download_rows(lib, out, d_out, nbytes, join)
         s.mark("download")
         return plan, out
 
@@ -2518,7 +2458,11 @@ class ArenaSession:
     A GsxError in the block gives the lease back and THEN releases the arenas (a failed HIP call: no context in an unknown state
     is handed on; with the lease still held release_arenas() would spare this arena); every other exit keeps the arena's
     buffers.  Private buffers are freed before their context closes.  ``s.mark(name)`` is the stage clock (a synchronisation per
-    stage) when the caller asks for one with a `stage_ms` dict; it starts when the session is made."""
+    stage) when the caller asks for one with a `stage_ms` dict; it starts when the session is made.
+
+    The six table readers share one sequence: stage_in() -- staging, the caller's fill, the fill stage's mark, all on the host --
+    then ``s.upload_in``, the caller's own uploads and mark("upload"), its launch and mark("kernel"), ``s.download_rows`` and
+    mark("download")."""
 
     def __init__(self, group: str, device: int = 0, stage_ms: "dict | None" = None, ctx: "Context | None" = None, shared: bool = True):
         self.group, self.device, self.stage_ms, self.ctx = group, device, stage_ms, ctx
@@ -2573,6 +2517,23 @@ class ArenaSession:
             check(lib.gsx_dev_upload(self.ctx.handle, dev_ptr, host.ctypes.data, host.nbytes), "gsx_dev_upload")
         else:
             check(lib.gsx_dev_upload_staged(self.ctx.handle, dev_ptr, host.ctypes.data, host.nbytes), "gsx_dev_upload_staged")
+
+    def upload_in(self, lib, host: np.ndarray, dev_bytes: int, tables: "np.ndarray | None" = None):
+        """a reader's uploads after stage_in(): the staging `host` into the buffer "in" of `dev_bytes` (the caller's size: what its
+        kernel's 16-byte loads may reach behind the last row), `tables` into the buffer "tables".  No mark: the caller adds its
+        own uploads and marks "upload".  -> (d_in, d_tables or None)"""
+        d_in = self.buf("in", dev_bytes)
+        d_tab = self.buf("tables", tables.nbytes) if tables is not None else None
+        self.upload_staging(lib, d_in.ptr, host)
+        if d_tab is not None:
+            d_tab.upload(tables)
+        return d_in, d_tab
+
+    def download_rows(self, lib, out: np.ndarray, d_out: DeviceArray, nbytes: int, join):
+        """the last step of a reader and of the PLY writer: the prefault joined, then the first `nbytes` of `d_out` through the
+        staging lanes into the first `nbytes` of `out`"""
+        join()
+        check(lib.gsx_dev_download_staged(self.ctx.handle, out.view(np.uint8).ctypes.data, d_out.ptr, nbytes), "gsx_dev_download_staged")
 
 
 class DeviceChain:

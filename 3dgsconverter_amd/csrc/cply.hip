@@ -567,16 +567,11 @@ int gsx_fields_nonzero_dev(gsx_ctx *c, const float *first_field_dev, int64_t row
     GSX_HIP(hipSetDevice(c->device));
     *mask_out = 0;
     if (n == 0 || m == 0) return 0;
-    GSX_CHECK(c->nzmask.reserve(16));
-    unsigned long long *d_mask = c->nzmask.as<unsigned long long>();
-    GSX_HIP(hipMemsetAsync(d_mask, 0, 8, c->stream));
     const int64_t groups = div_up(n, (int64_t)8);
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(div_up(groups, (int64_t)4), (int64_t)c->num_cu * 16));
-    hipLaunchKernelGGL(fields_nonzero_kernel, dim3(blocks), dim3(256), 0, c->stream, first_field_dev, row_stride, n, m, d_mask);
-    GSX_HIP(hipGetLastError());
-    GSX_HIP(hipMemcpyAsync(mask_out, d_mask, 8, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return nzmask_word(c, mask_out, [&](unsigned long long *d_mask) {
+        hipLaunchKernelGGL(fields_nonzero_kernel, dim3(blocks), dim3(256), 0, c->stream, first_field_dev, row_stride, n, m, d_mask);
+    });
 }
 
 }  // extern "C"

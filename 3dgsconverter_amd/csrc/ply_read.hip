@@ -29,13 +29,10 @@
 namespace gsx {
 
 constexpr int PLYR_MAX_FIELDS = GSX_PLY_READ_MAX_FIELDS;
-constexpr int PLYR_NO_SRC = 0x3ff;            // descriptor: no source, the field stays zero
-constexpr size_t PLYR_MAX_LDS = 2 * 32768 + 256;
-constexpr int PLYR_THREADS = 256;             // lanes per workgroup: four waves share a tile of 128 or 64 rows
 
 struct PlyReadArgs {
     int in_stride, out_stride, n_fields, big_endian, in_quads, tile_rows;
-    unsigned desc[PLYR_MAX_FIELDS];           // src offset (10 bits, PLYR_NO_SRC = none) | type << 10 | dst offset << 14 | dst bytes << 24
+    unsigned desc[PLYR_MAX_FIELDS];           // src offset (10 bits, PLY_NO_SRC = none) | type << 10 | dst offset << 14 | dst bytes << 24
 };
 
 __host__ __device__ inline unsigned ply_swap32(unsigned w) { return (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24); }
@@ -103,8 +100,8 @@ struct PlyLdsWord {
     __device__ __forceinline__ unsigned operator()(int q) const { return lds_u32(lds, q); }
 };
 
-// one workgroup of PLYR_THREADS lanes per tile of A.tile_rows rows; rows [0, n), row 0 at byte `first` of `body`
-__global__ __launch_bounds__(PLYR_THREADS) void ply_unpack_kernel(const uint4 *__restrict__ body, int64_t first, int64_t n, PlyReadArgs A,
+// one workgroup of PLY_THREADS lanes per tile of A.tile_rows rows; rows [0, n), row 0 at byte `first` of `body`
+__global__ __launch_bounds__(PLY_THREADS) void ply_unpack_kernel(const uint4 *__restrict__ body, int64_t first, int64_t n, PlyReadArgs A,
                                                          unsigned char *__restrict__ out)
 {
     extern __shared__ uint4 pr_lds[];
@@ -119,13 +116,13 @@ __global__ __launch_bounds__(PLYR_THREADS) void ply_unpack_kernel(const uint4 *_
     const unsigned nf = (unsigned)A.n_fields;
     const unsigned pairs = (unsigned)cnt * nf;
     const bool be = A.big_endian != 0;
-    for (unsigned p = threadIdx.x; p < pairs; p += PLYR_THREADS) {
+    for (unsigned p = threadIdx.x; p < pairs; p += PLY_THREADS) {
         const unsigned r = p / nf, f = p - r * nf;
         const unsigned d = A.desc[f];
         const unsigned so = d & 0x3ffu, type = (d >> 10) & 15u, nb = d >> 24;
         const unsigned o = r * (unsigned)A.out_stride + ((d >> 14) & 0x3ffu);
         unsigned w0 = 0u, w1 = 0u;
-        if (so != (unsigned)PLYR_NO_SRC) ply_field(word, base + (int)(r * (unsigned)A.in_stride + so), type, nb, be, w0, w1);
+        if (so != (unsigned)PLY_NO_SRC) ply_field(word, base + (int)(r * (unsigned)A.in_stride + so), type, nb, be, w0, w1);
         if (nb == 4 && (o & 3u) == 0u) {
             *reinterpret_cast<unsigned *>(img + o) = w0;
         } else {
@@ -144,8 +141,7 @@ static int ply_type_bytes(int type) { return type <= GSX_PLY_T_U1 ? 1 : type <= 
 static int ply_layout_to_args(const gsx_ply_read_layout *l, PlyReadArgs *A, const char *who)
 {
     if (!l) GSX_FAIL("%s: null layout", who);
-    if (l->in_stride < 1 || l->in_stride > SPZ_MAX_ROW_BYTES || l->out_stride < 1 || l->out_stride > SPZ_MAX_ROW_BYTES)
-        GSX_FAIL("%s: row strides in %d, out %d (1 ... %d are supported)", who, l->in_stride, l->out_stride, SPZ_MAX_ROW_BYTES);
+    GSX_CHECK(ply_strides(l->in_stride, l->out_stride, who));
     if (l->n_fields < 1 || l->n_fields > PLYR_MAX_FIELDS) GSX_FAIL("%s: %d fields (1 ... %d are supported)", who, l->n_fields, PLYR_MAX_FIELDS);
     if (l->big_endian != 0 && l->big_endian != 1) GSX_FAIL("%s: big_endian %d", who, l->big_endian);
     unsigned char covered[SPZ_MAX_ROW_BYTES] = {0};
@@ -158,21 +154,12 @@ static int ply_layout_to_args(const gsx_ply_read_layout *l, PlyReadArgs *A, cons
         if (type == GSX_PLY_T_RAW && nb > 1 && l->big_endian && so >= 0) GSX_FAIL("%s: field %d is a byte copy of %d bytes from a big-endian body", who, f, nb);
         const int sb = type == GSX_PLY_T_RAW ? nb : ply_type_bytes(type);
         if (so < -1 || (so >= 0 && so + sb > l->in_stride)) GSX_FAIL("%s: field %d reads %d bytes at offset %d of a %d-byte row", who, f, sb, so, l->in_stride);
-        for (int i = 0; i < nb; ++i) {
-            if (covered[dof + i]) GSX_FAIL("%s: field %d overlaps another at output byte %d", who, f, dof + i);
-            covered[dof + i] = 1;
-        }
-        A->desc[f] = (unsigned)(so < 0 ? PLYR_NO_SRC : so) | ((unsigned)type << 10) | ((unsigned)dof << 14) | ((unsigned)nb << 24);
+        GSX_CHECK(ply_cover(covered, dof, nb, "field", f, who));
+        A->desc[f] = (unsigned)(so < 0 ? PLY_NO_SRC : so) | ((unsigned)type << 10) | ((unsigned)dof << 14) | ((unsigned)nb << 24);
     }
-    for (int i = 0; i < l->out_stride; ++i)
-        if (!covered[i]) GSX_FAIL("%s: output byte %d belongs to no field", who, i);
-    for (int f = l->n_fields; f < PLYR_MAX_FIELDS; ++f) A->desc[f] = 0u;
-    A->in_stride = l->in_stride;
-    A->out_stride = l->out_stride;
     A->n_fields = l->n_fields;
     A->big_endian = l->big_endian;
-    A->in_quads = A->tile_rows = 0;
-    return 0;
+    return ply_args_finish(covered, "field", A->desc, l->n_fields, l->in_stride, l->out_stride, A, who);
 }
 
 struct PlyHostWord {
@@ -193,24 +180,11 @@ int gsx_ply_unpack_dev(gsx_ctx *c, const void *body_dev, int64_t first_byte, int
     GSX_CHECK(ply_layout_to_args(layout, &A, "gsx_ply_unpack_dev"));
     if (n < 0 || first_byte < 0 || first_byte > 15) GSX_FAIL("gsx_ply_unpack_dev: n >= 0 and 0 <= first_byte <= 15");
     if (n == 0) return 0;
-    if (!body_dev || !out_dev) GSX_FAIL("gsx_ply_unpack_dev: null argument");
-    if ((reinterpret_cast<uintptr_t>(body_dev) & 15) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
-        GSX_FAIL("gsx_ply_unpack_dev: body and output must be 16-byte aligned");
-    const int tr = spz_tile_rows(std::max(A.in_stride, A.out_stride));
-    const int64_t tiles = (n + tr - 1) / tr;
-    if (tiles >= (1LL << 31)) GSX_FAIL("gsx_ply_unpack_dev: too many rows");
-    const size_t in_bytes = spz_in_bytes(tr, A.in_stride);
-    const size_t lds = in_bytes + ((size_t)tr * A.out_stride + 32 + 15) / 16 * 16;   // + what store_bytes reads behind the image
-    A.in_quads = (int)(in_bytes / 16);
-    A.tile_rows = tr;
-    if (lds > PLYR_MAX_LDS) GSX_FAIL("gsx_ply_unpack_dev: a tile of %zu LDS bytes", lds);
-    GSX_HIP(hipSetDevice(c->device));
-    if (lds > 65536)   // two staged tiles of up to 32 KiB each: past the default limit of dynamic LDS, within the 160 KiB of a CU
-        GSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ply_unpack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLYR_MAX_LDS));
-    hipLaunchKernelGGL(ply_unpack_kernel, dim3((unsigned)tiles), dim3(PLYR_THREADS), lds, c->stream, static_cast<const uint4 *>(body_dev), first_byte, n, A,
-                       static_cast<unsigned char *>(out_dev));
-    GSX_HIP(hipGetLastError());
-    return 0;
+    return ply_launch(c, reinterpret_cast<const void *>(ply_unpack_kernel), A, n, body_dev, "body", out_dev, "gsx_ply_unpack_dev",
+                      [&](unsigned tiles, size_t lds) {
+                          hipLaunchKernelGGL(ply_unpack_kernel, dim3(tiles), dim3(PLY_THREADS), lds, c->stream, static_cast<const uint4 *>(body_dev),
+                                             first_byte, n, A, static_cast<unsigned char *>(out_dev));
+                      });
 }
 
 int gsx_ply_unpack_host(const void *body, int64_t n, const gsx_ply_read_layout *layout, void *out)
@@ -226,7 +200,7 @@ int gsx_ply_unpack_host(const void *body, int64_t n, const gsx_ply_read_layout *
             const unsigned so = d & 0x3ffu, nb = d >> 24;
             unsigned w0 = 0u, w1 = 0u;
             // (rows are walked one at a time from their own base: q stays below 2^31 for any n)
-            if (so != (unsigned)PLYR_NO_SRC) {
+            if (so != (unsigned)PLY_NO_SRC) {
                 const PlyHostWord row{word.rows + r * A.in_stride};
                 ply_field(row, (int)so, (d >> 10) & 15u, nb, A.big_endian != 0, w0, w1);
             }

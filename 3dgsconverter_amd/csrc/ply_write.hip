@@ -23,17 +23,15 @@
 // and still move as dwords.
 #include "gsx_common.h"
 #include "row_tile.h"
+#include "rest_scan.h"
 
 namespace gsx {
 
 constexpr int PLYW_MAX_RUNS = GSX_PLY_WRITE_MAX_RUNS;
-constexpr int PLYW_NO_SRC = 0x3ff;            // descriptor: no source, the run is zero
-constexpr size_t PLYW_MAX_LDS = 2 * 32768 + 256;
-constexpr int PLYW_THREADS = 256;             // lanes per workgroup: four waves share a tile of 128 or 64 rows
 
 struct PlyWriteArgs {
     int in_stride, out_stride, n_runs, in_quads, tile_rows;
-    unsigned run[PLYW_MAX_RUNS];              // src offset (10 bits, PLYW_NO_SRC = none) | dst offset << 10 | (bytes - 1) << 20
+    unsigned run[PLYW_MAX_RUNS];              // src offset (10 bits, PLY_NO_SRC = none) | dst offset << 10 | (bytes - 1) << 20
 };
 
 // the units of a run of nb bytes: unit 0 = the bytes outside the destination's aligned dwords, units 1 ... nb / 4 = those dwords
@@ -70,8 +68,8 @@ struct PlyLdsDst {
     __device__ __forceinline__ void word(int o, unsigned v) const { *reinterpret_cast<unsigned *>(img + o) = v; }
 };
 
-// one workgroup of PLYW_THREADS lanes per tile of A.tile_rows rows; rows [0, n)
-__global__ __launch_bounds__(PLYW_THREADS) void ply_pack_kernel(const uint4 *__restrict__ rows, int64_t n, PlyWriteArgs A, unsigned char *__restrict__ out)
+// one workgroup of PLY_THREADS lanes per tile of A.tile_rows rows; rows [0, n)
+__global__ __launch_bounds__(PLY_THREADS) void ply_pack_kernel(const uint4 *__restrict__ rows, int64_t n, PlyWriteArgs A, unsigned char *__restrict__ out)
 {
     extern __shared__ uint4 pw_lds[];
     const int tr = A.tile_rows;
@@ -86,9 +84,9 @@ __global__ __launch_bounds__(PLYW_THREADS) void ply_pack_kernel(const uint4 *__r
     for (int k = 0; k < A.n_runs; ++k) {
         const unsigned d = A.run[k];
         const int so = (int)(d & 0x3ffu), dof = (int)((d >> 10) & 0x3ffu), nb = (int)(d >> 20) + 1;
-        const bool fill = so == PLYW_NO_SRC;
+        const bool fill = so == PLY_NO_SRC;
         const unsigned units = (unsigned)ply_run_units(nb), items = (unsigned)cnt * units;
-        for (unsigned p = threadIdx.x; p < items; p += PLYW_THREADS) {
+        for (unsigned p = threadIdx.x; p < items; p += PLY_THREADS) {
             const unsigned r = p / units, u = p - r * units;
             ply_run_unit(src, dst, fill, base + (int)r * A.in_stride + so, (int)r * A.out_stride + dof, nb, (int)u);
         }
@@ -98,69 +96,23 @@ __global__ __launch_bounds__(PLYW_THREADS) void ply_pack_kernel(const uint4 *__r
     store_bytes(out, g0, g0 + (int64_t)cnt * A.out_stride, img);
 }
 
-// ply_3dgs.py:74 / ply_cc.py:74: bit i of *mask = some row holds f_rest_i != 0 (NaN and denormals count, -0.0 does not: the
-// test is on the bits, whatever the denormal mode), for the fields in `want`; off[i] = byte offset of f_rest_i inside a row
-struct PlyRestOffsets {
-    int off[45];
-};
-
-__global__ void ply_rest_scan_kernel(const uint4 *__restrict__ rows, int rb, int64_t n, PlyRestOffsets O, unsigned long long want,
-                                     unsigned long long *__restrict__ mask)
-{
-    extern __shared__ uint4 pw_lds[];
-    __shared__ unsigned long long acc;
-    __shared__ int off[45];                                       // (dynamic indices: LDS, not SGPRs)
-    if ((int)threadIdx.x < 45) off[threadIdx.x] = O.off[threadIdx.x];
-    const int tr = blockDim.x;
-    const unsigned *in32 = reinterpret_cast<const unsigned *>(pw_lds);
-    if (threadIdx.x == 0) acc = 0ull;
-    unsigned long long bits = 0ull;
-    const int64_t ntiles = (n + tr - 1) / tr;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t t0 = tile * tr;
-        const int cnt = (int)min((int64_t)tr, n - t0);
-        __syncthreads();
-        const int base = spz_stage_tile(rows, rb, t0, cnt, pw_lds);
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const int q = base + (int)threadIdx.x * rb;
-            for (int i = 0; i < 45; ++i)
-                if (((want >> i) & 1ull) && !((bits >> i) & 1ull) && (lds_u32(in32, q + off[i]) & 0x7fffffffu) != 0u) bits |= 1ull << i;
-        }
-    }
-    __syncthreads();
-    if (bits) atomicOr(&acc, bits);
-    __syncthreads();
-    if (threadIdx.x == 0 && acc) atomicOr(mask, acc);
-}
-
 // gsx_ply_write_layout -> PlyWriteArgs: strides and counts in range, every source inside an input row, the runs tile the output
 // row (every byte written exactly once: nothing of the LDS image leaves unwritten)
 static int ply_write_layout_to_args(const gsx_ply_write_layout *l, PlyWriteArgs *A, const char *who)
 {
     if (!l) GSX_FAIL("%s: null layout", who);
-    if (l->in_stride < 1 || l->in_stride > SPZ_MAX_ROW_BYTES || l->out_stride < 1 || l->out_stride > SPZ_MAX_ROW_BYTES)
-        GSX_FAIL("%s: row strides in %d, out %d (1 ... %d are supported)", who, l->in_stride, l->out_stride, SPZ_MAX_ROW_BYTES);
+    GSX_CHECK(ply_strides(l->in_stride, l->out_stride, who));
     if (l->n_runs < 1 || l->n_runs > PLYW_MAX_RUNS) GSX_FAIL("%s: %d runs (1 ... %d are supported)", who, l->n_runs, PLYW_MAX_RUNS);
     unsigned char covered[SPZ_MAX_ROW_BYTES] = {0};
     for (int k = 0; k < l->n_runs; ++k) {
         const int so = l->src_offset[k], dof = l->dst_offset[k], nb = l->bytes[k];
         if (nb < 1 || dof < 0 || dof + nb > l->out_stride) GSX_FAIL("%s: run %d of %d bytes at byte offset %d of a %d-byte output row", who, k, nb, dof, l->out_stride);
         if (so < -1 || (so >= 0 && so + nb > l->in_stride)) GSX_FAIL("%s: run %d reads %d bytes at offset %d of a %d-byte row", who, k, nb, so, l->in_stride);
-        for (int i = 0; i < nb; ++i) {
-            if (covered[dof + i]) GSX_FAIL("%s: run %d overlaps another at output byte %d", who, k, dof + i);
-            covered[dof + i] = 1;
-        }
-        A->run[k] = (unsigned)(so < 0 ? PLYW_NO_SRC : so) | ((unsigned)dof << 10) | ((unsigned)(nb - 1) << 20);
+        GSX_CHECK(ply_cover(covered, dof, nb, "run", k, who));
+        A->run[k] = (unsigned)(so < 0 ? PLY_NO_SRC : so) | ((unsigned)dof << 10) | ((unsigned)(nb - 1) << 20);
     }
-    for (int i = 0; i < l->out_stride; ++i)
-        if (!covered[i]) GSX_FAIL("%s: output byte %d belongs to no run", who, i);
-    for (int k = l->n_runs; k < PLYW_MAX_RUNS; ++k) A->run[k] = 0u;
-    A->in_stride = l->in_stride;
-    A->out_stride = l->out_stride;
     A->n_runs = l->n_runs;
-    A->in_quads = A->tile_rows = 0;
-    return 0;
+    return ply_args_finish(covered, "run", A->run, l->n_runs, l->in_stride, l->out_stride, A, who);
 }
 
 struct PlyHostSrc {
@@ -194,24 +146,11 @@ int gsx_ply_pack_dev(gsx_ctx *c, const void *rows_dev, int64_t n, const gsx_ply_
     GSX_CHECK(ply_write_layout_to_args(layout, &A, "gsx_ply_pack_dev"));
     if (n < 0) GSX_FAIL("gsx_ply_pack_dev: n >= 0");
     if (n == 0) return 0;
-    if (!rows_dev || !out_dev) GSX_FAIL("gsx_ply_pack_dev: null argument");
-    if ((reinterpret_cast<uintptr_t>(rows_dev) & 15) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
-        GSX_FAIL("gsx_ply_pack_dev: rows and output must be 16-byte aligned");
-    const int tr = spz_tile_rows(std::max(A.in_stride, A.out_stride));
-    const int64_t tiles = (n + tr - 1) / tr;
-    if (tiles >= (1LL << 31)) GSX_FAIL("gsx_ply_pack_dev: too many rows");
-    const size_t in_bytes = spz_in_bytes(tr, A.in_stride);
-    const size_t lds = in_bytes + ((size_t)tr * A.out_stride + 32 + 15) / 16 * 16;   // + what store_bytes reads behind the image
-    A.in_quads = (int)(in_bytes / 16);
-    A.tile_rows = tr;
-    if (lds > PLYW_MAX_LDS) GSX_FAIL("gsx_ply_pack_dev: a tile of %zu LDS bytes", lds);
-    GSX_HIP(hipSetDevice(c->device));
-    if (lds > 65536)   // two staged tiles of up to 32 KiB each: past the default limit of dynamic LDS, within the 160 KiB of a CU
-        GSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ply_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLYW_MAX_LDS));
-    hipLaunchKernelGGL(ply_pack_kernel, dim3((unsigned)tiles), dim3(PLYW_THREADS), lds, c->stream, static_cast<const uint4 *>(rows_dev), n, A,
-                       static_cast<unsigned char *>(out_dev));
-    GSX_HIP(hipGetLastError());
-    return 0;
+    return ply_launch(c, reinterpret_cast<const void *>(ply_pack_kernel), A, n, rows_dev, "rows", out_dev, "gsx_ply_pack_dev",
+                      [&](unsigned tiles, size_t lds) {
+                          hipLaunchKernelGGL(ply_pack_kernel, dim3(tiles), dim3(PLY_THREADS), lds, c->stream, static_cast<const uint4 *>(rows_dev), n, A,
+                                             static_cast<unsigned char *>(out_dev));
+                      });
 }
 
 int gsx_ply_pack_host(const void *rows, int64_t n, const gsx_ply_write_layout *layout, void *out)
@@ -230,7 +169,7 @@ int gsx_ply_pack_host(const void *rows, int64_t n, const gsx_ply_write_layout *l
             const int so = (int)(d & 0x3ffu), dof = (int)((d >> 10) & 0x3ffu), nb = (int)(d >> 20) + 1;
             const int units = ply_run_units(nb);
             for (int p = 0; p < cnt * units; ++p)
-                ply_run_unit(src, dst, so == PLYW_NO_SRC, (p / units) * A.in_stride + so, (p / units) * A.out_stride + dof, nb, p % units);
+                ply_run_unit(src, dst, so == PLY_NO_SRC, (p / units) * A.in_stride + so, (p / units) * A.out_stride + dof, nb, p % units);
         }
     }
     return 0;
@@ -244,7 +183,7 @@ int gsx_ply_rest_nonzero_dev(gsx_ctx *c, const void *rows_dev, int64_t stride, i
     if (present_mask >> 45) GSX_FAIL("gsx_ply_rest_nonzero_dev: fields beyond f_rest_44");
     if (stride < 1 || stride > SPZ_MAX_ROW_BYTES) GSX_FAIL("gsx_ply_rest_nonzero_dev: rows of %lld bytes (1 ... %d are supported)", (long long)stride, SPZ_MAX_ROW_BYTES);
     if (reinterpret_cast<uintptr_t>(rows_dev) & 15) GSX_FAIL("gsx_ply_rest_nonzero_dev: rows must be 16-byte aligned");
-    PlyRestOffsets O;
+    RestOffsets O;
     for (int i = 0; i < 45; ++i) {
         const bool on = (present_mask >> i) & 1;
         if (on && (offsets[i] < 0 || offsets[i] + 4 > stride)) GSX_FAIL("gsx_ply_rest_nonzero_dev: f_rest_%d at byte offset %d of a %lld-byte row", i, offsets[i], (long long)stride);
@@ -253,16 +192,7 @@ int gsx_ply_rest_nonzero_dev(gsx_ctx *c, const void *rows_dev, int64_t stride, i
     GSX_HIP(hipSetDevice(c->device));
     *mask_out = 0;
     if (n == 0 || present_mask == 0) return 0;
-    GSX_CHECK(c->nzmask.reserve(16));
-    unsigned long long *d_mask = c->nzmask.as<unsigned long long>();
-    GSX_HIP(hipMemsetAsync(d_mask, 0, 8, c->stream));
-    const int tr = spz_tile_rows((int)stride);
-    hipLaunchKernelGGL(ply_rest_scan_kernel, dim3(tile_blocks(c, n, tr, 8)), dim3(tr), spz_in_bytes(tr, (int)stride), c->stream,
-                       static_cast<const uint4 *>(rows_dev), (int)stride, n, O, (unsigned long long)present_mask, d_mask);
-    GSX_HIP(hipGetLastError());
-    GSX_HIP(hipMemcpyAsync(mask_out, d_mask, 8, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return rest_scan(c, rows_dev, (int)stride, n, O, present_mask, mask_out);
 }
 
 }  // extern "C"

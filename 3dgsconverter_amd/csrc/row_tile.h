@@ -1,5 +1,7 @@
 // row_tile.h -- what the format kernels share: the writers that read a raw splat table in place (csrc/spz.hip, csrc/ksplat.hip,
-// csrc/splat.hip, csrc/cply.hip) and the readers that decode a file's rows (csrc/cply_read.hip, csrc/ksplat_read.hip).
+// csrc/splat.hip, csrc/cply.hip, csrc/ply_write.hip) and the readers that decode a file's rows (csrc/cply_read.hip,
+// csrc/ksplat_read.hip, csrc/spz_read.hip, csrc/sog_read.hip, csrc/splat_read.hip, csrc/ply_read.hip).  The f_rest scan of the
+// SPZ, .ksplat and PLY writers has a header of its own beside this one (rest_scan.h).
 //
 // A workgroup owns a tile of consecutive rows: the tile's raw bytes are staged in LDS with 16-byte loads (any row size up to
 // 512 bytes, fields at any byte offset: a field is assembled from two LDS words), and a tile's output leaves LDS as one
@@ -152,6 +154,85 @@ constexpr uint64_t fields_below(int f) { return (1ull << f) - 1; }
 static unsigned tile_blocks(gsx_ctx *c, int64_t items, int per_block, int per_cu)
 {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)c->num_cu * per_cu));
+}
+
+// a scan kernel's one 64-bit result word -> *mask_out: the context's nzmask word zeroed, launch(d_mask) on the context's stream,
+// the word copied out, the stream joined
+template <class Launch>
+static int nzmask_word(gsx_ctx *c, uint64_t *mask_out, Launch launch)
+{
+    GSX_CHECK(c->nzmask.reserve(16));
+    unsigned long long *d_mask = c->nzmask.as<unsigned long long>();
+    GSX_HIP(hipMemsetAsync(d_mask, 0, 8, c->stream));
+    launch(d_mask);
+    GSX_HIP(hipGetLastError());
+    GSX_HIP(hipMemcpyAsync(mask_out, d_mask, 8, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- what the PLY reader's and the PLY writer's transcodes share (csrc/ply_read.hip, csrc/ply_write.hip): a workgroup of
+// PLY_THREADS lanes per tile, the staged input and an image of the output tile both in LDS, a descriptor word per field / run
+
+constexpr int PLY_NO_SRC = 0x3ff;             // descriptor: no source, the bytes stay zero
+constexpr size_t PLY_MAX_LDS = 2 * 32768 + 256;
+constexpr int PLY_THREADS = 256;              // lanes per workgroup: four waves share a tile of 128 or 64 rows
+
+static int ply_strides(int in_stride, int out_stride, const char *who)
+{
+    if (in_stride < 1 || in_stride > SPZ_MAX_ROW_BYTES || out_stride < 1 || out_stride > SPZ_MAX_ROW_BYTES)
+        GSX_FAIL("%s: row strides in %d, out %d (1 ... %d are supported)", who, in_stride, out_stride, SPZ_MAX_ROW_BYTES);
+    return 0;
+}
+
+// output bytes [dof, dof + nb) are those of `noun` k ("field" / "run"): none of them may be another's
+static int ply_cover(unsigned char *covered, int dof, int nb, const char *noun, int k, const char *who)
+{
+    for (int i = 0; i < nb; ++i) {
+        if (covered[dof + i]) GSX_FAIL("%s: %s %d overlaps another at output byte %d", who, noun, k, dof + i);
+        covered[dof + i] = 1;
+    }
+    return 0;
+}
+
+// every output byte written exactly once (nothing of the LDS image leaves unwritten), the descriptors from `used` on zeroed, the
+// strides taken over; in_quads and tile_rows are ply_launch's
+template <class Args, int N>
+static int ply_args_finish(const unsigned char *covered, const char *noun, unsigned (&desc)[N], int used, int in_stride, int out_stride,
+                           Args *A, const char *who)
+{
+    for (int i = 0; i < out_stride; ++i)
+        if (!covered[i]) GSX_FAIL("%s: output byte %d belongs to no %s", who, i, noun);
+    for (int k = used; k < N; ++k) desc[k] = 0u;
+    A->in_stride = in_stride;
+    A->out_stride = out_stride;
+    A->in_quads = A->tile_rows = 0;
+    return 0;
+}
+
+// n >= 1 rows through `kernel`, one workgroup per tile: the pointers checked (`in_name`: what the input is called), the tile of
+// the larger stride, its LDS (A.in_quads and A.tile_rows are set here), launch(tiles, lds_bytes)
+template <class Args, class Launch>
+static int ply_launch(gsx_ctx *c, const void *kernel, Args &A, int64_t n, const void *in_dev, const char *in_name, const void *out_dev,
+                      const char *who, Launch launch)
+{
+    if (!in_dev || !out_dev) GSX_FAIL("%s: null argument", who);
+    if ((reinterpret_cast<uintptr_t>(in_dev) & 15) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        GSX_FAIL("%s: %s and output must be 16-byte aligned", who, in_name);
+    const int tr = spz_tile_rows(std::max(A.in_stride, A.out_stride));
+    const int64_t tiles = (n + tr - 1) / tr;
+    if (tiles >= (1LL << 31)) GSX_FAIL("%s: too many rows", who);
+    const size_t in_bytes = spz_in_bytes(tr, A.in_stride);
+    const size_t lds = in_bytes + ((size_t)tr * A.out_stride + 32 + 15) / 16 * 16;   // + what store_bytes reads behind the image
+    A.in_quads = (int)(in_bytes / 16);
+    A.tile_rows = tr;
+    if (lds > PLY_MAX_LDS) GSX_FAIL("%s: a tile of %zu LDS bytes", who, lds);
+    GSX_HIP(hipSetDevice(c->device));
+    if (lds > 65536)   // two staged tiles of up to 32 KiB each: past the default limit of dynamic LDS, within the 160 KiB of a CU
+        GSX_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLY_MAX_LDS));
+    launch((unsigned)tiles, lds);
+    GSX_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace gsx

@@ -1,7 +1,7 @@
 // spz.hip -- numeric core of the SPZ v3 writer: the whole packed body of a `.spz` file from the raw rows of a splat table.
 //
 // Replaces, in gsconverter/formats/spz.py:
-//   write, SH detection      :60-77    `np.any(data[f] != 0)` per strided f_rest column   -> spz_rest_scan_kernel
+//   write, SH detection      :60-77    `np.any(data[f] != 0)` per strided f_rest column   -> rest_scan_kernel (rest_scan.h)
 //   _pack_v3                 :111-170  positions, alpha, colours, scales, SH              -> spz_pack_kernel
 //   _pack_rot_v3             :298-343  smallest-three quaternion words (a per-splat loop) -> spz_pack_kernel
 //
@@ -21,6 +21,7 @@
 #include "gsx_common.h"
 #include "sog_math.h"
 #include "row_tile.h"
+#include "rest_scan.h"
 
 namespace gsx {
 
@@ -174,37 +175,6 @@ __global__ void spz_pack_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L, 
     }
 }
 
-// spz.py:60-77: bit i of *mask = some row holds f_rest_i != 0 (NaN counts, -0.0 does not), for the fields in `want`
-__global__ void spz_rest_scan_kernel(const uint4 *__restrict__ rows, SpzLayoutDev L, int64_t n, unsigned long long want,
-                                     unsigned long long *__restrict__ mask)
-{
-    extern __shared__ uint4 spz_lds[];
-    __shared__ unsigned long long acc;
-    __shared__ int off[SPZ_FIELDS];
-    if ((int)threadIdx.x < SPZ_FIELDS) off[threadIdx.x] = L.off[threadIdx.x];
-    const int tr = blockDim.x, rb = L.row_bytes;
-    const unsigned *in32 = reinterpret_cast<const unsigned *>(spz_lds);
-    if (threadIdx.x == 0) acc = 0ull;
-    unsigned long long bits = 0ull;
-    const int64_t ntiles = (n + tr - 1) / tr;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t t0 = tile * tr;
-        const int cnt = (int)min((int64_t)tr, n - t0);
-        __syncthreads();
-        const int base = spz_stage_tile(rows, rb, t0, cnt, spz_lds);
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const int q = base + (int)threadIdx.x * rb;
-            for (int i = 0; i < 45; ++i)
-                if (((want >> i) & 1ull) && !((bits >> i) & 1ull) && lds_f32(in32, q + off[SPZ_F_REST + i]) != 0.0f) bits |= 1ull << i;
-        }
-    }
-    __syncthreads();
-    if (bits) atomicOr(&acc, bits);
-    __syncthreads();
-    if (threadIdx.x == 0 && acc) atomicOr(mask, acc);
-}
-
 // the shared checks, then SPZ's own: x .. scale_2 required, f_dc_0..2 together, the SH degree's f_rest fields present
 static int spz_layout(const gsx_spz_layout *l, int sh_dim, SpzLayoutDev *out, const char *who)
 {
@@ -230,21 +200,15 @@ int gsx_spz_rest_nonzero_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_lay
     if (reinterpret_cast<uintptr_t>(rows_dev) & 15) GSX_FAIL("gsx_spz_rest_nonzero_dev: rows must be 16-byte aligned");
     SpzLayoutDev L;
     GSX_CHECK(spz_layout(layout, 0, &L, "gsx_spz_rest_nonzero_dev"));
-    for (int i = 0; i < 45; ++i)
+    RestOffsets O;
+    for (int i = 0; i < 45; ++i) {
         if (((fields >> i) & 1) && L.off[SPZ_F_REST + i] < 0) GSX_FAIL("gsx_spz_rest_nonzero_dev: f_rest_%d is absent", i);
+        O.off[i] = L.off[SPZ_F_REST + i];
+    }
     GSX_HIP(hipSetDevice(c->device));
     *mask_out = 0;
     if (n == 0 || fields == 0) return 0;
-    GSX_CHECK(c->nzmask.reserve(16));
-    unsigned long long *d_mask = c->nzmask.as<unsigned long long>();
-    GSX_HIP(hipMemsetAsync(d_mask, 0, 8, c->stream));
-    const int tr = spz_tile_rows(L.row_bytes);
-    hipLaunchKernelGGL(spz_rest_scan_kernel, dim3(tile_blocks(c, n, tr, 8)), dim3(tr), spz_in_bytes(tr, L.row_bytes), c->stream,
-                       static_cast<const uint4 *>(rows_dev), L, n, (unsigned long long)fields, d_mask);
-    GSX_HIP(hipGetLastError());
-    GSX_HIP(hipMemcpyAsync(mask_out, d_mask, 8, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return rest_scan(c, rows_dev, L.row_bytes, n, O, fields, mask_out);
 }
 
 int gsx_spz_pack_dev(gsx_ctx *c, const void *rows_dev, const gsx_spz_layout *layout, int64_t n, int sh_degree, uint8_t *body_dev,

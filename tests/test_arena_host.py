@@ -5,6 +5,7 @@ of its name before the first "_") and is only served while that group is leased,
 device calls are stubbed and only the allocator is faked (numpy memory; a "freed" block is poisoned with NaN bytes but stays
 mapped): the real grow-only and lease logic, the real threaded host gathers and the real DataProcessor / DeviceChain code run.
 threading.Event forces the one interleaving that hurts: thread A gathers, thread B gathers and finishes, then A reads."""
+import ctypes
 import importlib
 import threading
 import types
@@ -521,6 +522,166 @@ def test_session_uploads_page_locked_staging_plainly_and_pageable_staging_throug
         s.upload_staging(Lib(), 7, hs)
         t.upload_staging(Lib(), 9, ht)
     assert calls == [("plain", 7, hs.ctypes.data, 48), ("staged", 9, ht.ctypes.data, 32)]
+
+
+# ---- the six table readers: one sequence (stage_in, ArenaSession.upload_in, .download_rows) -----------------------------
+
+class _ReaderLib:
+    """every gsx_* entry point a reader calls is recorded and answers 0; the staged download fills its destination with 0xAB"""
+
+    def __init__(self, events):
+        self.events = events
+
+    def __getattr__(self, name):
+        def call(*args):
+            self.events.append(name)
+            if name == "gsx_dev_download_staged":
+                ctypes.memset(args[1], 0xAB, args[3])
+            return 0
+        return call
+
+
+@pytest.fixture
+def reader(fake, monkeypatch):
+    """-> the list of events of one reader call: "staging", "fill" (the caller's fill, or read_exact), then the device work --
+    "alloc" / "upload" / "download" of a device buffer and the name of every entry point"""
+    events = []
+
+    class Array(_StubArray):
+        def upload(self, arr):
+            events.append("upload")
+            return super().upload(arr)
+
+        def download(self, dtype, count):
+            events.append("download")
+            return np.zeros(count, dtype)
+
+    def alloc(self, nbytes):
+        events.append("alloc")
+        return Array(self, nbytes)
+
+    def staging(self, name, nbytes, real=L.ArenaSession.staging):
+        events.append("staging")
+        return real(self, name, nbytes)
+
+    def read_exact(f, view, *a, real=L.read_exact, **k):
+        events.append("fill")
+        return real(f, view, *a, **k)
+    monkeypatch.setattr(fake, "alloc", alloc)
+    monkeypatch.setattr(L.ArenaSession, "staging", staging)
+    monkeypatch.setattr(L, "read_exact", read_exact)
+    monkeypatch.setattr(L, "require_hip", lambda: _ReaderLib(events))
+    monkeypatch.setattr(L, "_np_log_checked", True)
+    return events
+
+
+def _rows_dtype(itemsize):
+    return np.dtype([("b", "u1", (itemsize,))])
+
+
+def _file(tmp_path, nbytes):
+    p = tmp_path / "body.bin"
+    p.write_bytes(bytes(nbytes))
+    return str(p)
+
+
+class _Damaged(Exception):
+    pass
+
+
+def _fill(events, good):
+    def fill(view, place=None):
+        events.append("fill")
+        if not good:
+            raise _Damaged("the stream ends early")
+        view[:] = 1
+    return fill
+
+
+SOG_PLACE_BYTES = 6 * 32 + 768      # n = 5, one band, a palette of 1: six textures of 20 -> 32 bytes, one centroid row of 4 * 64 * 3
+
+
+def _read_cply(tmp_path, events, good, st):
+    seg = {"chunk": (0, 72), "vertex": (72, 16 * 300), "sh": None}
+    return L.cply_unpack_table(_file(tmp_path, 72 + 16 * 300 - (0 if good else 1)), seg, L.CplyReadLayout(), 1, 300, _rows_dtype(68), st)
+
+
+def _read_ksplat(tmp_path, events, good, st):
+    return L.ksplat_unpack_table(_file(tmp_path, 108 if good else 107), 8, 100, 0, [L.KsplatReadSection()], np.arange(2), 0, 3, _rows_dtype(68), st)
+
+
+def _read_spz(tmp_path, events, good, st):
+    return L.spz_unpack_table(_fill(events, good), 95, 2, 0, 12, 5, _rows_dtype(71), st, fill_stage="gunzip")
+
+
+def _read_sog(tmp_path, events, good, st):
+    tables = dict(zip(L.SOG_READ_TABLES, [np.zeros(256, np.float32)] * 5 + [np.zeros((3, 65536), np.float32)]))
+    return L.sog_unpack_table(_fill(events, good), 5, 1, 1, tables, _rows_dtype(104), stage_ms=st)
+
+
+def _read_splat(tmp_path, events, good, st):
+    return L.splat_unpack_table(_file(tmp_path, 128 if good else 127), 4, _rows_dtype(71), st)
+
+
+def _read_ply(tmp_path, events, good, st):
+    lay = L.PlyReadLayout(in_stride=20, out_stride=12)
+    return L.ply_unpack_table(_file(tmp_path, 21 + 60 - (0 if good else 1)), 21, 3, lay, _rows_dtype(12), st)
+
+
+# group -> (the call, the stage clock's keys, the arena's buffers in the order they are asked for: (name, bytes), what a short file raises)
+READERS = {
+    "cplyread": (_read_cply, ["file_read", "upload", "kernel", "download"],
+                 [("in", 96 + 4816), ("tables", 8 * 4352 + 4 * 512), ("out", 256 * 68)], ValueError),
+    "ksread": (_read_ksplat, ["file_read", "upload", "kernel", "download"],
+               [("in", 100 + 32), ("tables", 4 * 512), ("prefix", 16), ("out", 3 * 68)], ValueError),
+    "spzread": (_read_spz, ["gunzip", "upload", "kernel", "download"],
+                [("in", 95 + 32), ("tables", 4 * 2560), ("out", 5 * 71)], _Damaged),
+    "sogread": (_read_sog, ["decode", "upload", "kernel", "download"],
+                [("in", SOG_PLACE_BYTES + 32), ("tables", 4 * (1280 + 3 * 65536)), ("flag", 16), ("out", 5 * 104)], _Damaged),
+    "splatread": (_read_splat, ["file_read", "upload", "kernel", "download"],
+                  [("in", 4 * 32), ("tables", 4 * 512), ("out", 4 * 71)], ValueError),
+    "plyread": (_read_ply, ["file_read", "upload", "kernel", "download"],
+                [("in", 96), ("out", 3 * 12)], ValueError),       # 5 bytes before row 0, 60 of rows, 16 spare: 81 -> 96
+}
+
+
+@pytest.mark.parametrize("group", list(READERS))
+def test_reader_stages_and_fills_before_any_device_work(reader, tmp_path, group):
+    call, stages, bufs, _ = READERS[group]
+    st = {}
+    rows = call(tmp_path, reader, True, st)
+    assert reader[0] == "staging" and reader[1] == "fill", reader
+    first = [e for e in reader if e not in ("staging", "fill")][0]
+    assert first == "alloc" and reader.index("alloc") > max(i for i, e in enumerate(reader) if e == "fill"), reader
+    entry = {"cplyread": "gsx_cply_unpack_dev", "ksread": "gsx_ksplat_unpack_dev", "spzread": "gsx_spz_unpack_dev",
+             "sogread": "gsx_sog_unpack_dev", "splatread": "gsx_splat_unpack_dev", "plyread": "gsx_ply_unpack_dev"}[group]
+    assert reader.count(entry) == 1 and reader.count("gsx_dev_download_staged") == 1 and reader[-1] == "gsx_dev_download_staged"
+    assert reader.index("gsx_dev_upload") < reader.index(entry) < reader.index("gsx_dev_download_staged")
+    assert list(st) == stages
+    ar = L.arena(0)
+    assert [(name, b.nbytes - 256) for name, b in ar._bufs.items()] == [(group + "_" + name, size) for name, size in bufs]
+    staged = {"cplyread": 96 + 4816, "ksread": 100, "spzread": 95, "sogread": SOG_PLACE_BYTES, "splatread": 4 * 32, "plyread": 96}[group]
+    assert list(ar._pinned) == [group + "_in"] and ar._pinned[group + "_in"][1] == staged
+    assert not ar._leases and not ar.closed
+    flat = rows.view(np.uint8).reshape(len(rows), -1)
+    n_dec = 256 if group == "cplyread" else len(rows)
+    assert np.all(flat[:n_dec] == 0xAB) and not flat[n_dec:].any()       # the download's bytes; compressed PLY: zero past 256 n_chunks
+    assert len(rows) == {"cplyread": 300, "ksread": 3, "spzread": 5, "sogread": 5, "splatread": 4, "plyread": 3}[group]
+
+
+@pytest.mark.parametrize("group", list(READERS))
+def test_reader_whose_fill_raises_has_done_no_device_work(reader, tmp_path, group):
+    call, _, _, error = READERS[group]
+    st = {}
+    with pytest.raises(error) as e:
+        call(tmp_path, reader, False, st)
+    assert "early" in str(e.value)                                       # read_exact's message, or the fill's own: unchanged
+    assert set(reader) == {"staging", "fill"} and reader[0] == "staging", reader
+    ar = L.arena(0)
+    assert not ar._leases and not ar.closed and not ar._bufs and list(ar._pinned) == [group + "_in"]
+    assert not st                                                        # not even the fill stage's mark
+    with L.ArenaSession(group, 0) as s:                                  # the lease is there for the next call
+        assert s.leased
 
 
 def test_read_exact_fills_the_view_or_names_the_early_end(tmp_path):

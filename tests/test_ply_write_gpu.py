@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ply_read_numpy as pn  # noqa: E402
 import ply_write_numpy as pw  # noqa: E402
+import rest_scan_cases as rsc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "ply_write_ref.npz")
@@ -96,6 +97,27 @@ def test_crop_scan_finds_the_references_last_idx(cases, written):
             on_device = len(c.table) > 0 and name not in HOST_SCAN and any(f.startswith("f_rest_") for f in c.table.dtype.names)
             assert "sh_detect" in st and ("upload" in st) >= on_device, (name, d, st)
     assert seen >= {-1, 0, 5, 8, 9, 23, 24, 44}
+
+
+@pytest.mark.parametrize("row_bytes,n", rsc.CASES)
+def test_rest_scan_is_numpys_any_nonzero_at_the_edge_values(lib, writer, row_bytes, n):
+    """gsx_ply_rest_nonzero_dev on rows of 248 bytes (tiles of 128) and of 261 (tiles of 64, every field at an odd offset), one
+    row, one full tile and one row more: -0.0 in the last row sets no bit; the smallest denormal of either sign, a NaN and 1.0
+    set exactly their field's bit; the fields that are not asked for hold 1.0 and never show"""
+    import ctypes as C
+    t = rsc.table(row_bytes, n)
+    offsets = (C.c_int32 * 45)(*[t.dtype.fields[f][1] for f in rsc.REST])
+    ctx = lib.Context(0)
+    d_rows = ctx.alloc(t.nbytes + 64)
+    try:
+        for i, want, word in rsc.plantings(t):
+            d_rows.upload(t)
+            got = C.c_uint64(0)
+            lib.check(ctx.lib.gsx_ply_rest_nonzero_dev(ctx.handle, d_rows.ptr, row_bytes, n, offsets, want, C.byref(got)), "gsx_ply_rest_nonzero_dev")
+            assert got.value == word, "f_rest_%d: got %#x, numpy %#x" % (i, got.value, word)
+    finally:
+        d_rows.free()
+        ctx.close()
 
 
 def test_written_files_read_back_the_tables_standard_fields(cases, written, lib):

@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import spz_numpy  # noqa: E402
 import layout_refusals as refusals  # noqa: E402
+import rest_scan_cases as rsc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "spz_ref.npz")
@@ -173,3 +174,22 @@ def _spz_refusals():
 def test_layout_refusals(gsx, lib, case):
     """the entry points' layout checks, message for message (all return before any launch)"""
     refusals.check(lib, case[0], *case[2:])
+
+
+@pytest.mark.parametrize("row_bytes,n", rsc.CASES)
+def test_rest_scan_is_numpys_any_nonzero_at_the_edge_values(gsx, lib, row_bytes, n):
+    """gsx_spz_rest_nonzero_dev on rows of 248 bytes (tiles of 128) and of 261 (tiles of 64, every field at an odd offset), one
+    row, one full tile and one row more: -0.0 in the last row sets no bit; the smallest denormal of either sign, a NaN and 1.0
+    set exactly their field's bit; the fields that are not asked for hold 1.0 and never show"""
+    t = rsc.table(row_bytes, n)
+    lay = lib.spz_layout(t.dtype)
+    ctx = lib.Context(0)
+    d_rows = ctx.alloc(t.nbytes + 64)
+    try:
+        for i, want, word in rsc.plantings(t):
+            d_rows.upload(t)
+            got = lib.rest_nonzero_word(ctx.lib, ctx, d_rows, lay, n, rsc.ASKED)
+            assert got == word, "f_rest_%d: got %#x, numpy %#x" % (i, got, word)
+    finally:
+        d_rows.free()
+        ctx.close()

@@ -123,6 +123,28 @@ class PlyWriteLayout(C.Structure):
                 ("bytes", C.c_int32 * PLY_WRITE_MAX_RUNS)]
 
 
+PARQUET_MAX_FIELDS = 128    # GSX_PARQUET_MAX_FIELDS
+PARQUET_MAX_STRIDE = 512    # bytes per row of the table (csrc/row_tile.h SPZ_MAX_ROW_BYTES)
+PARQUET_TYPE_CODES = dict(PLY_TYPE_CODES, i8=9, u8=10, f2=11)   # + GSX_PARQUET_T_I8 / _U8 / _F2: convert to float32 by value
+PARQUET_TYPE_BYTES = {0: 1, 1: 1, 2: 2, 3: 2, 4: 4, 5: 4, 6: 4, 7: 8, 9: 8, 10: 8, 11: 2}
+
+
+class ParquetRowsLayout(C.Structure):
+    """gsx_parquet_rows_layout (include/gsx_hip.h): the Parquet reader's field descriptors"""
+    _fields_ = [("out_stride", C.c_int32), ("n_fields", C.c_int32),
+                ("src_type", C.c_int32 * PARQUET_MAX_FIELDS), ("dst_offset", C.c_int32 * PARQUET_MAX_FIELDS),
+                ("dst_bytes", C.c_int32 * PARQUET_MAX_FIELDS), ("col_offset", C.c_int64 * PARQUET_MAX_FIELDS),
+                ("valid_offset", C.c_int64 * PARQUET_MAX_FIELDS)]
+
+
+class ParquetColumnsLayout(C.Structure):
+    """gsx_parquet_columns_layout (include/gsx_hip.h): the Parquet writer's field descriptors"""
+    _fields_ = [("in_stride", C.c_int32), ("n_fields", C.c_int32),
+                ("src_offset", C.c_int32 * PARQUET_MAX_FIELDS), ("bytes", C.c_int32 * PARQUET_MAX_FIELDS),
+                ("kind", C.c_int32 * PARQUET_MAX_FIELDS), ("col_offset", C.c_int64 * PARQUET_MAX_FIELDS),
+                ("valid_offset", C.c_int64 * PARQUET_MAX_FIELDS)]
+
+
 class KsplatReadSection(C.Structure):
     """gsx_ksplat_read_section (include/gsx_hip.h): one section of a .ksplat file as the reader's kernel walks it"""
     _fields_ = [("rows_offset", C.c_int64), ("centres_offset", C.c_int64), ("n_rows", C.c_int64), ("out_row", C.c_int64),
@@ -279,6 +301,10 @@ SIGNATURES = {
     "gsx_ply_pack_dev": (_I, [_P, _P, _I64, C.POINTER(PlyWriteLayout), _P]),
     "gsx_ply_pack_host": (_I, [_P, _I64, C.POINTER(PlyWriteLayout), _P]),
     "gsx_ply_rest_nonzero_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(C.c_int32), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsx_parquet_rows_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(ParquetRowsLayout), _P]),
+    "gsx_parquet_rows_host": (_I, [_P, _I64, _I64, C.POINTER(ParquetRowsLayout), _P]),
+    "gsx_parquet_columns_dev": (_I, [_P, _P, _I64, C.POINTER(ParquetColumnsLayout), _P, _I64, _P]),
+    "gsx_parquet_columns_host": (_I, [_P, _I64, C.POINTER(ParquetColumnsLayout), _P, _I64, _P]),
 }
 
 _lib = None
@@ -2138,6 +2164,198 @@ def ply_pack_host(data: np.ndarray, layout: PlyWriteLayout) -> np.ndarray:
     out = np.empty(n * layout.out_stride, np.uint8)
     check(lib.gsx_ply_pack_host(data.ctypes.data, n, C.byref(layout), out.ctypes.data), "gsx_ply_pack_host")
     return out
+
+
+def parquet_chunk_bits(validity, bit_offset: int, length: int) -> np.ndarray:
+    """bits [bit_offset, bit_offset + length) of an Arrow validity bitmap (LSB first; None: every row is valid) -> bool[length]"""
+    if validity is None:
+        return np.ones(length, bool)
+    v = np.frombuffer(validity, np.uint8)
+    if (bit_offset + length + 7) >> 3 > len(v):
+        raise ValueError("parquet: a validity bitmap of %d bytes for bits %d ... %d" % (len(v), bit_offset, bit_offset + length))
+    bits = np.unpackbits(v[bit_offset >> 3:(bit_offset + length + 7) >> 3], bitorder="little")
+    return bits[bit_offset & 7:(bit_offset & 7) + length].astype(bool)
+
+
+def parquet_rows_plan(columns, n_rows: int, fields, out_stride: int):
+    """Where the Parquet reader's columns lie in the one buffer its kernel reads.
+
+    columns: per column a list of chunks (values, validity bytes or None, bit offset, length) -- `values` a 1-D array of the
+    column's type whose first `length` elements are the chunk's (the caller has applied the chunk's offset to it), `validity`
+    the chunk's Arrow bitmap as it lies in memory, its bit `bit offset` the chunk's first row; any bit offset, any length, the
+    lengths of a column adding up to n_rows.  fields: per output field (column index or None, type code, destination offset,
+    destination bytes).  A column's chunks are laid end to end from a 64-byte boundary; a column any of whose chunks has a
+    bitmap gets ONE bitmap of (n + 63) / 64 * 8 bytes with bit r = row r, re-packed here.
+    -> (ParquetRowsLayout, buffer bytes, [(byte offset, uint8 array)]: what to copy where)"""
+    n = int(n_rows)
+    if len(fields) < 1 or len(fields) > PARQUET_MAX_FIELDS:
+        raise ValueError("parquet_rows_plan: %d fields (1 ... %d)" % (len(fields), PARQUET_MAX_FIELDS))
+    lay = ParquetRowsLayout()
+    lay.out_stride, lay.n_fields = int(out_stride), len(fields)
+    placed, parts, total = {}, [], 0
+    for k, (ci, code, dof, nb) in enumerate(fields):
+        lay.src_type[k], lay.dst_offset[k], lay.dst_bytes[k] = int(code), int(dof), int(nb)
+        lay.col_offset[k] = lay.valid_offset[k] = -1
+        if ci is None:
+            continue
+        size = int(nb) if code == PLY_T_RAW else PARQUET_TYPE_BYTES[int(code)]
+        if ci not in placed:
+            chunks = columns[ci]
+            if sum(int(c[3]) for c in chunks) != n:
+                raise ValueError("parquet_rows_plan: column %d has %d rows in its chunks, the table %d" % (ci, sum(int(c[3]) for c in chunks), n))
+            off, pos = total, 0
+            total = (total + n * size + 63) & ~63
+            for values, _, _, length in chunks:
+                values = np.asarray(values)
+                if values.dtype.itemsize != size or values.ndim != 1 or len(values) < length:
+                    raise ValueError("parquet_rows_plan: column %d holds %s[%d], field %d reads %d values of %d bytes" % (ci, values.dtype, len(values), k, length, size))
+                if length:
+                    parts.append((off + pos * size, np.ascontiguousarray(values[:length]).view(np.uint8)))
+                pos += int(length)
+            voff = -1
+            if n and any(c[1] is not None for c in chunks):
+                bits = np.concatenate([parquet_chunk_bits(v, int(bo), int(ln)) for _, v, bo, ln in chunks])
+                bitmap = np.zeros((n + 63) // 64 * 8, np.uint8)
+                packed = np.packbits(bits, bitorder="little")
+                bitmap[:len(packed)] = packed
+                voff = total
+                total = (total + len(bitmap) + 63) & ~63
+                parts.append((voff, bitmap))
+            placed[ci] = (off, voff, size)
+        off, voff, have = placed[ci]
+        if have != size:
+            raise ValueError("parquet_rows_plan: column %d is read with %d and %d bytes a value" % (ci, have, size))
+        lay.col_offset[k] = off
+        lay.valid_offset[k] = -1 if code == PLY_T_RAW else voff
+        if code == PLY_T_RAW and voff >= 0:
+            raise ValueError("parquet_rows_plan: field %d is a byte copy of a column with a validity bitmap" % k)
+    return lay, total + 64, parts
+
+
+def _parquet_fill(parts):
+    def fill(host):
+        for off, a in parts:
+            host[off:off + a.nbytes] = a
+    return fill
+
+
+def parquet_rows_table(columns, n_rows: int, fields, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+    """The Parquet reader's rows (formats/parquet.py:51-55): Arrow's column chunks are laid end to end in page-locked staging
+    (parquet_rows_plan: the one host copy a pageable upload makes anyway), uploaded once, transposed and cast by
+    gsx_parquet_rows_dev and downloaded into a prefaulted array of `dtype`.  n_rows = 0 -> the empty array, no launch.
+
+    One ArenaSession of the "pqread" lease group.  Stage clocks: gather, upload, kernel, download."""
+    lib = require_hip()
+    dtype = np.dtype(dtype)
+    n, rb = int(n_rows), dtype.itemsize
+    lay, total, parts = parquet_rows_plan(columns, n, fields, rb)
+    if n == 0:
+        return np.zeros(0, dtype)
+    out = np.empty(n, dtype)
+    with ArenaSession("pqread", device, stage_ms) as s:
+        host, join = stage_in(s, out, total, _parquet_fill(parts), "gather")
+        d_in, _ = s.upload_in(lib, host, total)
+        s.mark("upload")
+        d_out = s.buf("out", n * rb)
+        check(lib.gsx_parquet_rows_dev(s.ctx.handle, d_in.ptr, total, n, C.byref(lay), d_out.ptr), "gsx_parquet_rows_dev")
+        s.mark("kernel")
+        s.download_rows(lib, out, d_out, n * rb, join)
+        s.mark("download")
+        return out
+
+
+def parquet_rows_host(columns, n_rows: int, fields, dtype: np.dtype) -> np.ndarray:
+    """gsx_parquet_rows_host: the kernel's casts on the host, from the same buffer -- the host tests' model of the device"""
+    lib = load()
+    dtype = np.dtype(dtype)
+    n = int(n_rows)
+    lay, total, parts = parquet_rows_plan(columns, n, fields, dtype.itemsize)
+    buf = np.zeros(total, np.uint8)
+    _parquet_fill(parts)(buf)
+    out = np.zeros(n, dtype)
+    check(lib.gsx_parquet_rows_host(buf.ctypes.data, total, n, C.byref(lay), out.ctypes.data), "gsx_parquet_rows_host")
+    return out
+
+
+def parquet_columns_plan(in_stride: int, n_rows: int, fields):
+    """fields: per output column (source byte offset, bytes, kind) -- kind 0: a bit copy alone, 1: float32, 2: float64 (a validity
+    bitmap and a null count with it).  -> (ParquetColumnsLayout, buffer bytes, [(column offset, bitmap offset or -1)])"""
+    n = int(n_rows)
+    if len(fields) < 1 or len(fields) > PARQUET_MAX_FIELDS:
+        raise ValueError("parquet_columns_plan: %d fields (1 ... %d)" % (len(fields), PARQUET_MAX_FIELDS))
+    lay = ParquetColumnsLayout()
+    lay.in_stride, lay.n_fields = int(in_stride), len(fields)
+    total, places = 0, []
+    for k, (so, nb, kind) in enumerate(fields):
+        lay.src_offset[k], lay.bytes[k], lay.kind[k] = int(so), int(nb), int(kind)
+        lay.col_offset[k] = total
+        total = (total + n * int(nb) + 63) & ~63
+        lay.valid_offset[k] = -1
+        if kind:
+            lay.valid_offset[k] = total
+            total = (total + (n + 63) // 64 * 8 + 63) & ~63
+        places.append((lay.col_offset[k], lay.valid_offset[k]))
+    return lay, total + 64, places
+
+
+def _parquet_column_views(host, n, fields, places, counts):
+    cols, bitmaps, nulls = [], [], []
+    for (so, nb, kind), (co, vo) in zip(fields, places):
+        cols.append(host[co:co + n * nb])
+        bitmaps.append(host[vo:vo + (n + 7) // 8] if kind else None)
+        nulls.append(int(counts[len(nulls)]) if kind else 0)
+    return cols, bitmaps, nulls
+
+
+def parquet_columns_table(data: np.ndarray, fields, stage_ms: "dict | None" = None, device: int = 0, consume=None):
+    """The Parquet writer's columns from a whole table (formats/parquet.py:94-108 and pa.Table.from_pandas behind :111): the raw
+    rows are uploaded ONCE, gsx_parquet_columns_dev writes every field as a contiguous column, with the Arrow validity bitmap
+    and the null count of every float column, and all of it comes back into page-locked staging in one copy.
+
+    data: 1-D C-contiguous structured table of n >= 1 rows of up to 512 bytes.  fields: parquet_columns_plan's.
+    -> (columns, bitmaps, null counts): per field uint8[n * bytes], uint8[(n + 7) // 8] or None (kind 0), int.  They are views
+    of the session's staging, good while the session lasts: `consume(columns, bitmaps, null_counts)` runs inside it and its
+    result is returned; without one they are copied.
+
+    One ArenaSession of the "pqw" lease group.  Stage clocks: upload, kernel, download (and what `consume` marks itself)."""
+    lib = require_hip()
+    n = len(data)
+    if n < 1 or not data.flags.c_contiguous or data.dtype.itemsize > PARQUET_MAX_STRIDE:
+        raise ValueError("parquet_columns_table: %d rows of %d bytes (C-contiguous rows of up to %d)" % (n, data.dtype.itemsize, PARQUET_MAX_STRIDE))
+    fields = [(int(so), int(nb), int(kind)) for so, nb, kind in fields]
+    lay, total, places = parquet_columns_plan(data.dtype.itemsize, n, fields)
+    with ArenaSession("pqw", device, stage_ms) as s:
+        ctx = s.ctx
+        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernel's 16-byte loads read up to 15 bytes past the last row)
+        upload_table(lib, ctx, d_rows.ptr, data)
+        s.mark("upload")
+        d_out, d_cnt = s.buf("out", total), s.buf("count", 8 * PARQUET_MAX_FIELDS)
+        check(lib.gsx_parquet_columns_dev(ctx.handle, d_rows.ptr, n, C.byref(lay), d_out.ptr, total, d_cnt.ptr), "gsx_parquet_columns_dev")
+        s.mark("kernel")
+        host = s.staging("out", total)
+        if s.leased:                                    # page-locked: the runtime's plain copy runs at link rate
+            check(lib.gsx_dev_download(ctx.handle, host.ctypes.data, d_out.ptr, total), "gsx_dev_download")
+        else:
+            check(lib.gsx_dev_download_staged(ctx.handle, host.ctypes.data, d_out.ptr, total), "gsx_dev_download_staged")
+        counts = d_cnt.download(np.uint64, PARQUET_MAX_FIELDS)
+        s.mark("download")
+        cols, bitmaps, nulls = _parquet_column_views(host, n, fields, places, counts)
+        if consume is not None:
+            return consume(cols, bitmaps, nulls)
+        return [c.copy() for c in cols], [None if b is None else b.copy() for b in bitmaps], nulls
+
+
+def parquet_columns_host(data: np.ndarray, fields):
+    """gsx_parquet_columns_host: the kernel's split on the host -> (columns, bitmaps, null counts) as parquet_columns_table"""
+    lib = load()
+    n = len(data)
+    data = np.ascontiguousarray(data)
+    fields = [(int(so), int(nb), int(kind)) for so, nb, kind in fields]
+    lay, total, places = parquet_columns_plan(data.dtype.itemsize, n, fields)
+    host = np.zeros(total, np.uint8)
+    counts = np.zeros(PARQUET_MAX_FIELDS, np.uint64)
+    check(lib.gsx_parquet_columns_host(data.ctypes.data, n, C.byref(lay), host.ctypes.data, total, counts.ctypes.data), "gsx_parquet_columns_host")
+    return _parquet_column_views(host, n, fields, places, counts)
 
 
 class DeviceArray:

@@ -37,15 +37,7 @@ struct PlyReadArgs {
 
 __host__ __device__ inline unsigned ply_swap32(unsigned w) { return (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24); }
 
-// float64 bits -> float32 bits: the plain cast.  On the host it is x86's cvtsd2ss, which numpy's cast runs; on the device it is
-// v_cvt_f32_f64, which gives the same bits for every pattern tried (round to nearest even, overflow to +-inf, subnormal results
-// kept, a NaN's sign and top payload bits kept, a signalling NaN quieted: DESIGN.md section 6j)
-__host__ __device__ inline unsigned ply_f64_to_f32(unsigned lo, unsigned hi)
-{
-    const unsigned long long b = ((unsigned long long)hi << 32) | lo;
-    const float f = (float)__builtin_bit_cast(double, b);
-    return __builtin_bit_cast(unsigned, f);
-}
+// (ply_f64_to_f32, the float64 -> float32 cast, lives in row_tile.h: the Parquet reader casts with it too)
 
 // the output bytes of one field, as up to two little-endian words: W(q) is the little-endian u32 at byte q of the staged rows
 template <class W>

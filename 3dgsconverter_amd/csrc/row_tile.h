@@ -46,13 +46,25 @@ __device__ __forceinline__ unsigned lds_u32(const unsigned *lds, int q)
 __device__ __forceinline__ float lds_f32(const unsigned *lds, int q) { return __uint_as_float(lds_u32(lds, q)); }
 __device__ __forceinline__ unsigned lds_u8(const unsigned *lds, int q) { return (lds[q >> 2] >> (8 * (q & 3))) & 0xffu; }
 
-// numpy's float16 -> float32: exact, and a NaN keeps its sign, its payload and its quiet bit as they are
-__device__ __forceinline__ unsigned half_bits(unsigned h)
+// numpy's float16 -> float32: exact, and a NaN keeps its sign, its payload and its quiet bit as they are (host and device: the
+// host twins of the readers run it too)
+__host__ __device__ __forceinline__ unsigned half_bits(unsigned h)
 {
     if ((h & 0x7c00u) == 0x7c00u && (h & 0x03ffu)) return ((h & 0x8000u) << 16) | 0x7f800000u | ((h & 0x03ffu) << 13);
     union { unsigned short u; _Float16 f; } v;
     v.u = (unsigned short)h;
-    return __float_as_uint((float)v.f);
+    const float f = (float)v.f;
+    return __builtin_bit_cast(unsigned, f);
+}
+
+// float64 bits -> float32 bits: the plain cast.  On the host it is x86's cvtsd2ss, which numpy's cast runs; on the device it is
+// v_cvt_f32_f64, which gives the same bits for every pattern tried (round to nearest even, overflow to +-inf, subnormal results
+// kept, a NaN's sign and top payload bits kept, a signalling NaN quieted: DESIGN.md section 6j)
+__host__ __device__ inline unsigned ply_f64_to_f32(unsigned lo, unsigned hi)
+{
+    const unsigned long long b = ((unsigned long long)hi << 32) | lo;
+    const float f = (float)__builtin_bit_cast(double, b);
+    return __builtin_bit_cast(unsigned, f);
 }
 
 // np.clip(t, 0, 255).astype(np.uint8): NaN stays NaN through the clip and casts to 0

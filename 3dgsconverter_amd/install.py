@@ -21,7 +21,8 @@ _saved = {}
 
 def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: bool = True, splat_writer: bool = True,
             cply_reader: bool = True, ksplat_reader: bool = True, spz_reader: bool = True, sog_reader: bool = True,
-            splat_reader: bool = False, ply_reader: bool = True, ply_writer: bool = True):
+            splat_reader: bool = False, ply_reader: bool = True, ply_writer: bool = True, parquet_reader: bool = False,
+            parquet_writer: bool = False):
     """sog_writer: also rebind ``gsconverter.formats.sog.SogFormat.write`` to formats/sog_writer.py:write_sog (spatial
     sort, quaternion packing, codebook quantiser and SH palette on the GPU; identical bytes where the reference is
     deterministic) and ``gsconverter.formats.compressed_ply.CompressedPlyFormat.write`` to
@@ -64,7 +65,18 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
     to formats/ply_writer.py (the output layout and the container on the host, the crop_sh scan and the row pack on the GPU, no
     plyfile; the reference's file byte for byte, `crop_sh` and `extra_elements` honoured).  Tables the device path does not take
     -- a field that is no PLY scalar, a big-endian field, rows over 512 bytes, more than 128 runs -- go to the reference's own
-    write when plyfile is there.  A reference without those modules, or whose classes have no `write`, is left as it is."""
+    write when plyfile is there.  A reference without those modules, or whose classes have no `write`, is left as it is.
+    parquet_reader: also rebind ``gsconverter.formats.parquet.ParquetFormat.read`` to formats/parquet_reader.py (pyarrow's decode
+    of the columns the rows use on the host, the columns -> rows transpose with numpy's casts and the validity bitmaps on the
+    GPU; the reference's rows).  Files the device path does not take -- two columns on one output name, a needed column of
+    another type than the integers and floats, a needed integer column with nulls, a stored index column -- go to the
+    reference's own read.  OFF unless asked for, like splat_reader and for its reason: a plain install() has always left
+    ``ParquetFormat`` to the reference, callers and tests on machines without a GPU rely on that.
+    parquet_writer: also rebind ``gsconverter.formats.parquet.ParquetFormat.write`` to formats/parquet_writer.py (the rows ->
+    columns transpose, the validity bitmaps and the null counts on the GPU, pyarrow's own write_table behind them; the
+    reference's file byte for byte under the same pyarrow and pandas).  Tables the device path does not take -- a field that is
+    none of f4, f8 and the integers, two fields on one column name, rows over 512 bytes or 128 fields -- go to the reference's
+    own write.  OFF unless asked for, as parquet_reader is."""
     from . import processing
     from .processing import gpu_ops
     # the orchestrator ignores the filters' return values (converter.py:196-236), so ITS name gets the lazy class (coordinates
@@ -199,6 +211,19 @@ def install(sog_writer: bool = True, spz_writer: bool = True, ksplat_writer: boo
             if plymod is not None and getattr(getattr(plymod, cls, None), "write", None) is not None:
                 _saved.setdefault((key, "write"), getattr(plymod, cls).write)
                 getattr(plymod, cls).write = bind(_saved[(key, "write")])
+    if parquet_reader or parquet_writer:
+        try:
+            pqmod = importlib.import_module("gsconverter.formats.parquet")
+        except ImportError:
+            pqmod = None
+        if pqmod is not None and parquet_reader and getattr(pqmod.ParquetFormat, "read", None) is not None:
+            from .formats.parquet_reader import bind_read as bind_parquet_read
+            _saved.setdefault(("parquetformat", "read"), pqmod.ParquetFormat.read)
+            pqmod.ParquetFormat.read = bind_parquet_read(_saved[("parquetformat", "read")])
+        if pqmod is not None and parquet_writer and getattr(pqmod.ParquetFormat, "write", None) is not None:
+            from .formats.parquet_writer import bind_write as bind_parquet_write
+            _saved.setdefault(("parquetformat", "write"), pqmod.ParquetFormat.write)
+            pqmod.ParquetFormat.write = bind_parquet_write(_saved[("parquetformat", "write")])
     _saved.setdefault(("sys.modules", "gsconverter.processing.gpu_ops"),
                       sys.modules.get("gsconverter.processing.gpu_ops"))
     sys.modules["gsconverter.processing.gpu_ops"] = gpu_ops
@@ -227,6 +252,9 @@ def uninstall():
             continue
         if modname == "plyccformat":
             setattr(importlib.import_module("gsconverter.formats.ply_cc").PlyCCFormat, attr, val)
+            continue
+        if modname == "parquetformat":
+            setattr(importlib.import_module("gsconverter.formats.parquet").ParquetFormat, attr, val)
             continue
         if modname == "sys.modules":
             if val is None:

@@ -940,6 +940,65 @@ int gsx_ply_pack_host(const void *rows, int64_t n, const gsx_ply_write_layout *l
 int gsx_ply_rest_nonzero_dev(gsx_ctx *ctx, const void *rows_dev, int64_t stride, int64_t n, const int32_t *offsets, uint64_t present_mask,
                              uint64_t *mask_out);
 
+
+/* ---- the Parquet reader and writer (csrc/parquet.hip) ----
+ * gsconverter/formats/parquet.py (ParquetFormat).  pyarrow keeps the file's pages, snappy, dictionaries and Thrift on both sides;
+ * the device does the transposes between Arrow's columns and the table's rows, with the casts and the validity bitmaps. */
+#define GSX_PARQUET_MAX_FIELDS 128
+/* source types of the reader beyond GSX_PLY_T_I1 ... GSX_PLY_T_F8 (and GSX_PLY_T_RAW = 8: copy dst_bytes bytes) */
+#define GSX_PARQUET_T_I8 9
+#define GSX_PARQUET_T_U8 10
+#define GSX_PARQUET_T_F2 11
+/* The reader, parquet.py:51-55: the loop `converted_data[name] = df_renamed[name].values` (one strided, casting column copy per
+ * output field) with the null -> NaN pass pandas runs ahead of it, as one pass.  Per output field:
+ *   col_offset    byte offset of the source column's n values inside cols_dev (a multiple of 16), -1 = none: the field is zero
+ *   valid_offset  byte offset of its Arrow validity bitmap there (bit r = row r, LSB first, (n + 63) / 64 * 8 bytes, a multiple
+ *                 of 8), -1 = every row is valid.  A row whose bit is cleared reads 0x7fc00000 whatever its value slot holds
+ *                 (0x7fffe000 from a float16 column: to_pandas' half NaN 0x7fff, cast).
+ *                 Converted fields only.
+ *   src_type      GSX_PLY_T_I1 ... GSX_PLY_T_F8, GSX_PARQUET_T_I8 / _U8 / _F2: numpy's cast of that type to float32, bit for bit
+ *                 (dst_bytes 4); GSX_PLY_T_RAW: a copy of dst_bytes bytes (1, 2, 4 or 8: red green blue from a uint8 column)
+ *   dst_offset, dst_bytes   where the field lies in an output row.  The fields must tile the output row. */
+typedef struct gsx_parquet_rows_layout {
+    int32_t out_stride;                 /* bytes per output row, 1 ... 512 */
+    int32_t n_fields;                   /* output fields, 1 ... GSX_PARQUET_MAX_FIELDS */
+    int32_t src_type[GSX_PARQUET_MAX_FIELDS];
+    int32_t dst_offset[GSX_PARQUET_MAX_FIELDS];
+    int32_t dst_bytes[GSX_PARQUET_MAX_FIELDS];
+    int64_t col_offset[GSX_PARQUET_MAX_FIELDS];
+    int64_t valid_offset[GSX_PARQUET_MAX_FIELDS];
+} gsx_parquet_rows_layout;
+/* cols_dev: cols_bytes bytes, 16-byte aligned; every column and bitmap is checked to lie inside it.  out_dev: n rows of
+ * out_stride bytes, 16-byte aligned.  One launch.  Asynchronous. */
+int gsx_parquet_rows_dev(gsx_ctx *ctx, const void *cols_dev, int64_t cols_bytes, int64_t n, const gsx_parquet_rows_layout *layout, void *out_dev);
+/* the same on the HOST with the kernel's own cast code (the host tests hold it against numpy).  HOST pointers. */
+int gsx_parquet_rows_host(const void *cols, int64_t cols_bytes, int64_t n, const gsx_parquet_rows_layout *layout, void *out);
+/* The writer, parquet.py:94-108: `pd.DataFrame(data)`, the rename and the reorder -- a strided copy of every field into a column
+ * of its own -- and the NaN scan `pa.Table.from_pandas` runs over every float column for its validity bitmap and null count, as
+ * one pass over the rows.  Per field (= output column):
+ *   src_offset, bytes   where the field lies in a row of the table; 1, 2, 4 or 8 bytes, any byte offset.  A bit copy.
+ *   kind          0: no bitmap; 1: float32, 2: float64 -- bit r of the bitmap is !isnan(row r)
+ *   col_offset    byte offset of the column's n values inside out_dev (a multiple of 16)
+ *   valid_offset  byte offset of the bitmap there (kind 1, 2; a multiple of 8): (n + 63) / 64 * 8 bytes, every one of them
+ *                 written, LSB first, the bits past n zero */
+typedef struct gsx_parquet_columns_layout {
+    int32_t in_stride;                  /* bytes per row of the table (its itemsize: holes included), 1 ... 512 */
+    int32_t n_fields;                   /* 1 ... GSX_PARQUET_MAX_FIELDS */
+    int32_t src_offset[GSX_PARQUET_MAX_FIELDS];
+    int32_t bytes[GSX_PARQUET_MAX_FIELDS];
+    int32_t kind[GSX_PARQUET_MAX_FIELDS];
+    int64_t col_offset[GSX_PARQUET_MAX_FIELDS];
+    int64_t valid_offset[GSX_PARQUET_MAX_FIELDS];
+} gsx_parquet_columns_layout;
+/* rows_dev: n rows of in_stride bytes, 16-byte aligned, readable up to 16 bytes past the last row.  out_dev: out_bytes bytes,
+ * 16-byte aligned; every column and bitmap is checked to lie inside it.  null_counts_dev: GSX_PARQUET_MAX_FIELDS device words,
+ * zeroed here; word f receives the NaN count of field f (kind 1, 2).  One launch.  Asynchronous. */
+int gsx_parquet_columns_dev(gsx_ctx *ctx, const void *rows_dev, int64_t n, const gsx_parquet_columns_layout *layout, void *out_dev,
+                            int64_t out_bytes, uint64_t *null_counts_dev);
+/* the same on the HOST (the host tests hold it against numpy).  HOST pointers; nothing outside the rows is read. */
+int gsx_parquet_columns_host(const void *rows, int64_t n, const gsx_parquet_columns_layout *layout, void *out, int64_t out_bytes,
+                             uint64_t *null_counts);
+
 #ifdef __cplusplus
 }
 #endif

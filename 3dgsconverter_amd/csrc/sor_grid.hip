@@ -1481,6 +1481,10 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 const float uqx = (qx - ccx) * g_inv_h, uqy = (qy - ccy) * g_inv_h, uqz = (qz - ccz) * g_inv_h;
                 const float nq2 = __builtin_fmaf(uqz, uqz, __builtin_fmaf(uqy, uqy, uqx * uqx));
                 const bool upper = lane >= 32;
+                // what the word loop multiplies and fills in per word, held in vector registers for the batch: as scalars the
+                // allocator parked 1/h in a lane of a spill register and fetched it back (v_readlane) for every word
+                const float inv_h_v = pinned_here(g_inv_h);
+                const unsigned kconst = mf_candidate_const(upper);
                 // (tau * inv_h) * inv_h: no overflow for tiny cells; dead lanes (tau = -1) never pass
                 const float s_q = tau >= 0.0f ? nq2 - ((tau * g_inv_h) * g_inv_h * (1.0f + 1e-6f) + MF_SLACK) : 1.0e30f;
                 bf16x8 opa, opb;
@@ -1521,38 +1525,53 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                     o.off = off;
                     return o;
                 };
-                const int my_cand = mf_cand_of_row(lane & 31);
+                // (from a lane id made here, per batch: computed from the kernel's it is hoisted to the entry and, with the loop's
+                //  registers taken, parked in scratch and reloaded per batch)
+                const int my_cand = mf_cand_of_row(fresh_lane_id() & 31);
+                const int my_cand16 = my_cand << 4;
                 auto fetch = [&](const Word &w) __attribute__((always_inline)) {
                     const int c = w.c1 + w.c2;
                     if (c == 0) return make_float4(0.f, 0.f, 0.f, 0.f);
-                    const int t = min(my_cand, c - 1);  // slots past the end repeat the last candidate (masked out below)
-                    const int idx = t < w.c1 ? w.b1 + t : w.b2 + (t - w.c1);
-                    if constexpr (NET) return *(const float4 *)((const char *)refs + ((unsigned)idx << 4));  // (as phase 2)
-                    else return refs[idx];
+                    if constexpr (NET) {
+                        // a 32-bit byte offset (as phase 2), built in bytes from the start: slots past the end repeat the last
+                        // candidate (masked out below), the second segment is one conditional add of a wave-uniform delta
+                        // (the sum with the delta is pinned: left alone, the select is moved in front of the adds, where it
+                        //  chooses between two scalars and costs two v_mov on top)
+                        const int t16 = min(my_cand16, (c - 1) << 4);
+                        const unsigned off1 = (unsigned)t16 + ((unsigned)w.b1 << 4);
+                        const unsigned off2 = (unsigned)pinned_here((int)(off1 + ((unsigned)(w.b2 - w.c1 - w.b1) << 4)));
+                        return *(const float4 *)((const char *)refs + (t16 >= (w.c1 << 4) ? off2 : off1));
+                    } else {
+                        const int t = min(my_cand, c - 1);
+                        const int idx = t < w.c1 ? w.b1 + t : w.b2 + (t - w.c1);
+                        return refs[idx];
+                    }
                 };
+                // The word metadata phase 2 reads (first candidate; candidates of the first segment, offset of the second) is
+                // collected in lane widx of three registers and stored once after the loop: no per-word stores by lane 0
+                unsigned meta_b1 = 0, meta_c1 = 0, meta_d = 0;
                 auto process = [&](const Word &w_cur, const float4 &p_cur) __attribute__((always_inline)) {
-                    const bf16x8 cand = mf_candidate_operand((p_cur.x - ccx) * g_inv_h, (p_cur.y - ccy) * g_inv_h,
-                                                             (p_cur.z - ccz) * g_inv_h, upper);
+                    const bf16x8 cand = mf_candidate_operand((p_cur.x - ccx) * inv_h_v, (p_cur.y - ccy) * inv_h_v,
+                                                             (p_cur.z - ccz) * inv_h_v, kconst);
                     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     // lane l: tile a = rows-set (l>>5) of query l&31, tile b = of query 32 + (l&31)
                     const unsigned ma = mf_sign_bits(__builtin_amdgcn_mfma_f32_32x32x16_bf16(cand, opa, zero, 0, 0, 0));
                     const unsigned mb = mf_sign_bits(__builtin_amdgcn_mfma_f32_32x32x16_bf16(cand, opb, zero, 0, 0, 0));
                     auto sw = __builtin_amdgcn_permlane32_swap(ma, mb, false, false);
-                    // now sw[0] = rows-set 0, sw[1] = rows-set 1 of THIS lane's query; drop the bits of
-                    // the clamped duplicates past the end of a partial word
-                    const unsigned m = ((sw[0] << 16) | (sw[1] & 0xffffu)) & (0xffffffffu << (32 - (w_cur.c1 + w_cur.c2)));
+                    // now sw[0] = rows-set 0, sw[1] = rows-set 1 of THIS lane's query (16 bits each: mf_sign_bits starts
+                    // from 0); drop the bits of the clamped duplicates past the end of a partial word
+                    const unsigned m = ((sw[0] << 16) | sw[1]) & (0xffffffffu << (32 - (w_cur.c1 + w_cur.c2)));
                     if (dbg & 64) atomicAdd(&gp->exhaustive_count, (unsigned)__builtin_popcount(m));  // profiling: candidates passed
                     mask[widx][lane] = m;
-                    if (lane == 0) {
-                        wbase[widx] = (unsigned)w_cur.b1;
-                        wseg[widx] = make_uint2((unsigned)w_cur.c1, (unsigned)(w_cur.b2 - w_cur.c1));
-                    }
-                    nzw |= (m != 0 ? 1u : 0u) << widx;
+                    write_lane3(meta_b1, meta_c1, meta_d, w_cur.b1, w_cur.c1, w_cur.b2 - w_cur.c1, widx);
+                    nzw |= nonzero01(m) << widx;
                     ++widx;
                 };
 #if GSX_BRICK_UNROLL3
-                // the three-deep word pipeline with ROTATING names instead of register moves (the ISA of the rolled loop spends
-                // ~10 of its 105 VALU instructions per word on v_mov rotations of the two prefetched points and words)
+                // the three-deep word pipeline with ROTATING names instead of register moves (the rolled loop spends 4 of its 79
+                // vector instructions per word on moves of the two prefetched points; unrolled the count is 78.3 per word at
+                // three times the code -- not the default.  Names alternating over two words, or one point in flight loaded in
+                // place, make the compiler wait for the newest load in the middle of a word: tools/asm_count.py)
                 Word w0 = next_word(0, 0);
                 Word w1 = next_word(w0.r, w0.off), w2;
                 float4 p0 = fetch(w0), p1 = fetch(w1), p2;
@@ -1584,6 +1603,14 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                     p_n1 = p_n2;
                 }
 #endif
+                // (drain()'s wave_sync orders these stores before phase 2 reads them)
+                {
+                    const int ln = fresh_lane_id();  // (not the kernel's lane id: that one is live, or spilled, across everything)
+                    if (ln < widx) {
+                        wbase[ln] = meta_b1;
+                        wseg[ln] = make_uint2(meta_c1, meta_d);
+                    }
+                }
                 lst.init();
                 }
             }

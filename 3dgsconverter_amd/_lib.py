@@ -63,6 +63,19 @@ class SlabPlan(C.Structure):
         return out
 
 
+class RefineSizingIn(C.Structure):
+    """gsx_refine_sizing_in (include/gsx_hip.h)"""
+    _fields_ = [("qb_lo", C.c_float * 3), ("qb_hi", C.c_float * 3), ("sub_queries", C.c_uint32), ("n_sub", C.c_uint32),
+                ("pts_per_cell", C.c_double), ("parent_h", C.c_float), ("adaptive", C.c_int32), ("hist", C.c_uint32 * 32),
+                ("bin_vol", C.c_double)]
+
+
+class RefineSizingOut(C.Structure):
+    """gsx_refine_sizing_out (include/gsx_hip.h)"""
+    _fields_ = [("nd3", C.c_int32), ("probe_g", C.c_int32), ("h_est", C.c_double), ("margin", C.c_double), ("cert", C.c_double),
+                ("clip_lo", C.c_float * 3), ("clip_hi", C.c_float * 3), ("r_cert", C.c_float), ("h_hint", C.c_double)]
+
+
 class SlabStep(C.Structure):
     """gsx_slab_step_t (include/gsx_hip.h)"""
     _fields_ = [("status", C.c_int32), ("plan", SlabPlan), ("mask_dev", C.c_void_p), ("mean_dists_dev", C.c_void_p),
@@ -214,6 +227,9 @@ SIGNATURES = {
     "gsx_sor_debug_brick_plan": (_I, [_P, _P, _P, _P, _I64]),
     "gsx_sor_debug_work_queue": (_I, [_P, _P, _P, _P]),
     "gsx_sor_debug_wave_stamps": (_I, [_P, _I, _P, _I64, _P]),
+    "gsx_sor_debug_points_per_cell": (_D, [_I, _I64, _I]),
+    "gsx_sor_debug_group_bricks": (_I, [_P, _I64, _I, _I, _I, _P, C.POINTER(C.c_int32)]),
+    "gsx_sor_debug_refine_sizing": (_I, [C.POINTER(RefineSizingIn), C.POINTER(RefineSizingOut)]),
     "gsx_knn_probe_root_dev": (_I, [_P, _P, _I64, _I, _P]),
     "gsx_knn_probe_mean_dev": (_I, [_P, _P, _I64, _I64, _I, _I, _I, _P]),
     "gsx_sor_stats_dev": (_I, [_P, _P, _I64, _D, _P]),
@@ -1461,6 +1477,31 @@ def ksplat_centres_host(data: np.ndarray, bucket_size: int) -> np.ndarray:
             v = data[a]
             cols.append((np.minimum.reduceat(v, idx) + np.maximum.reduceat(v, idx)) / 2.0)
     return np.column_stack(cols).astype(np.float32)
+
+
+def grid_points_per_cell(k: int, n: int, tuned: bool) -> float:
+    """csrc/grid_policy.h: grid_pts_per_cell (tuned) or grid_pts_per_cell_base; no GPU needed"""
+    return float(load().gsx_sor_debug_points_per_cell(int(k), int(n), int(bool(tuned))))
+
+
+def grid_group_bricks(bricks, nbx: int, nby: int, nbz: int):
+    """csrc/grid_policy.h: group_deferred_bricks -> (the list rewritten group by group, the groups' sizes); no GPU needed"""
+    b = np.array(bricks, dtype=np.uint32)
+    sizes = np.zeros(8, np.uint32)
+    ng = C.c_int32()
+    check(load().gsx_sor_debug_group_bricks(b.ctypes.data, b.size, int(nbx), int(nby), int(nbz), sizes.ctypes.data, C.byref(ng)),
+          "gsx_sor_debug_group_bricks")
+    return b, [int(v) for v in sizes[:ng.value]]
+
+
+def grid_refine_sizing(qb_lo, qb_hi, sub_queries: int, n_sub: int, pts_per_cell: float, parent_h: float, adaptive: int, hist,
+                       bin_vol: float) -> RefineSizingOut:
+    """csrc/grid_policy.h: refine_clip + refine_probe_edge for one group of deferred bricks; no GPU needed"""
+    a = RefineSizingIn((C.c_float * 3)(*qb_lo), (C.c_float * 3)(*qb_hi), int(sub_queries), int(n_sub), float(pts_per_cell),
+                       float(parent_h), int(adaptive), (C.c_uint32 * 32)(*[int(v) for v in hist]), float(bin_vol))
+    out = RefineSizingOut()
+    check(load().gsx_sor_debug_refine_sizing(C.byref(a), C.byref(out)), "gsx_sor_debug_refine_sizing")
+    return out
 
 
 def np_exp_host(x: np.ndarray) -> np.ndarray:

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <mutex>
 
+#include "grid_policy.h"
 #include "gsx_common.h"
 #include "sor_grid_params.h"
 
@@ -452,6 +453,35 @@ int gsx_sor_debug_wave_stamps(gsx_ctx *c, int kernel, uint64_t *out, int64_t cap
     (void)cap;
     GSX_FAIL("gsx_sor_debug_wave_stamps needs a diagnostic build of the library (-DGSX_WAVE_STAMPS)");
 #endif
+}
+
+// Tests: the host-side decisions of the grid (grid_policy.h), the very functions knn_grid_level calls.  No device is touched.
+double gsx_sor_debug_points_per_cell(int k, int64_t n, int tuned)
+{
+    return tuned ? gsx::grid_pts_per_cell(k, n) : gsx::grid_pts_per_cell_base(k, n);
+}
+
+int gsx_sor_debug_group_bricks(uint32_t *bricks, int64_t count, int nbx, int nby, int nbz, uint32_t *group_sizes, int32_t *n_groups)
+{
+    if (!bricks || !group_sizes || !n_groups || count < 0 || count > UINT32_MAX || nbx < 1 || nby < 1 || nbz < 1)
+        GSX_FAIL("gsx_sor_debug_group_bricks: bad arguments");
+    for (int64_t i = 0; i < count; ++i)
+        if ((uint64_t)bricks[i] >= (uint64_t)nbx * nby * nbz) GSX_FAIL("gsx_sor_debug_group_bricks: brick %u outside the grid", bricks[i]);
+    const std::vector<unsigned> sizes = gsx::group_deferred_bricks(bricks, (unsigned)count, nbx, nby, nbz);
+    for (int g = 0; g < gsx::GRID_MAX_GROUPS; ++g) group_sizes[g] = g < (int)sizes.size() ? sizes[g] : 0u;
+    *n_groups = (int32_t)sizes.size();
+    return 0;
+}
+
+int gsx_sor_debug_refine_sizing(const gsx_refine_sizing_in *in, gsx_refine_sizing_out *out)
+{
+    if (!in || !out) GSX_FAIL("gsx_sor_debug_refine_sizing: null argument");
+    const gsx::RefineClip r = gsx::refine_clip(in->qb_lo, in->qb_hi, in->sub_queries, in->pts_per_cell, in->parent_h, in->adaptive);
+    *out = gsx_refine_sizing_out{r.nd3, r.probe_g, r.h_est, r.M, r.cert, {r.lo[0], r.lo[1], r.lo[2]}, {r.hi[0], r.hi[1], r.hi[2]}, r.r_cert,
+                                 r.probe_g ? gsx::refine_probe_edge(in->hist, in->bin_vol, in->qb_lo, in->qb_hi, r.r_cert, in->n_sub,
+                                                                    r.h_est, in->pts_per_cell)
+                                           : 0.0};
+    return 0;
 }
 
 int gsx_sor_knn_share_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n,

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "grid_policy.h"
 #include "gsx_common.h"
 #include "sor_grid_params.h"
 
@@ -275,17 +276,6 @@ __global__ __launch_bounds__(256) void slab_pack_pieces_kernel(const float *__re
 
 int launch_sor_mask(gsx_ctx *ctx, const float *md, int64_t n, const float *thr_dev, uint8_t *mask);
 
-// cell population of the KNN grid for n reference points (the rule of knn_grid_level in sor_grid.hip; Python restates
-// it as dist_slab.pts_per_cell)
-static double slab_pts_per_cell(int k, int64_t n)
-{
-    double m = std::max(2.0, 0.47 * (double)(k + 1));
-    const double fill = n >= 4000000 ? 54.0 : 58.0;
-    for (int cells = 8; cells >= 1; cells /= 2)
-        if (m * cells > fill && m * cells <= 66.0) m = fill / cells;
-    return m;
-}
-
 int launch_knn_slab(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride, int64_t n_own,
                     int64_t n_halo, int k, float *mean_out, double *kth_out, const SlabKnn *sk = nullptr);
 int launch_sor_piece_sums(gsx_ctx *ctx, const float *a, int64_t n, const float *mean_dev, float *piece_out);
@@ -510,7 +500,9 @@ int gsx_slab_plan(const uint32_t *words, int world, int rank, int64_t n_local, i
             vol *= (double)ext[a];
             ++nd;
         }
-    const double per = nd ? vol * slab_pts_per_cell(k, n_total / G) / (double)n_total : 0.0;
+    // (the BASE rule of grid_policy.h, grid_pts_per_cell_base, which Python restates as dist_slab.pts_per_cell -- not the grid's
+    //  own tuned rule, which has smaller cells for k = 17...20, 26...31 and 35...62: the halo width stays what it was)
+    const double per = nd ? vol * grid_pts_per_cell_base(k, n_total / G) / (double)n_total : 0.0;
     const double h_est = nd ? std::pow(per, 1.0 / (double)nd) : 0.0;
     const double bw = hi > lo ? ((double)hi - (double)lo) / SLAB_BINS : 0.0;
     const int halo_bins = bw > 0.0 ? (int)std::ceil(halo_cells * h_est / bw) + 1 : SLAB_BINS;

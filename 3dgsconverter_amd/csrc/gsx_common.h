@@ -164,7 +164,7 @@ struct gsx_ctx {
     void *comm = nullptr;  // gsx_comm (RCCL communicator, dist_slab.hip) or null
 
     // tunables
-    double grid_points_per_cell = 0.0;  // 0 = auto: 0.47 * (k + 1), see launch_knn_grid
+    double grid_points_per_cell = 0.0;  // 0 = auto: grid_policy.h, grid_pts_per_cell
     int64_t brute_below = 2048;
     int debug_skip = 0;  // profiling ablations of knn_brick (never set by the product path)
     int adaptive = 0;    // 1: bricks too populated for the grid are re-run on a finer grid (one host sync per call)

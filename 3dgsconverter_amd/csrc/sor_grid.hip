@@ -40,6 +40,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "grid_policy.h"
 #include "gsx_common.h"
 #include "knn_common.h"
 #include "knn_mfma.h"
@@ -49,8 +50,7 @@ namespace gsx {
 
 
 constexpr int MAX_DIM = 1024;       // cells per axis (keeps the cell-index rounding bound, see r_safe)
-constexpr int MAX_BUCKETS = 4096;         // LDS histogram bins of the coarse pass
-constexpr int MAX_BUCKET_CELLS = 4096;    // LDS counters of the fine pass (16 KiB)
+// (MAX_BUCKETS and MAX_BUCKET_CELLS, the two-level sort's limits: grid_policy.h, where they also bound a level's cells)
 #ifndef GSX_BUCKET_POINTS
 #define GSX_BUCKET_POINTS 4096
 #endif
@@ -2842,8 +2842,6 @@ int launch_knn_tree(gsx_ctx *ctx, const float *x, const float *y, const float *z
                     int64_t q_count, int k, float *mean_out, double *kth_out, gsx_sor_info *info, int64_t ref_only_from, int share,
                     int nshares, bool guard);
 
-int64_t grid_cell_cap(int64_t n_ref) { return std::max<int64_t>(n_ref / 2, 64) + 64; }
-
 // The coarse histogram of (x,y,z)[first, first+n): per-tile bucket counts, their per-bucket scans and bk_start.
 static int bin_hist(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, const float *z, int64_t stride, int64_t first,
                     int64_t n, GridParams *gp)
@@ -2899,63 +2897,56 @@ static int bin_points(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, co
     return 0;
 }
 
-// candidate words of a brick's neighbourhood above which it is deferred (a uniform cloud has ~15)
+// ---------------------------------------------------------------- one level of the grid: knn_grid_level and its stages
+// The decisions (points per cell, cell budget, histogram verdict, planned bricks, grouping, refinement sizing) live in
+// grid_policy.h; the stages below are the launches, copies and synchronisations around them, in stream order.
+struct GridLevel {
+    // the call
+    gsx_ctx *ctx;
+    int level;
+    KnnWs &w;
+    const float *x, *y, *z;
+    int64_t stride, n_ref, q_begin, q_count;
+    int k;
+    float *mean_out;
+    double *kth_out;
+    gsx_sor_info *info;
+    int share, nshares;
+    float parent_h;
+    int64_t ref_only_from;
+    double h_hint;
+    const SlabKnn *sk;
+    bool anyk;       // k > 64: the list-free exact path (knn_anyk_kernel) instead of knn_brick + ring kernels
+    bool slab;       // slab mode (multi-GPU): every point is binned once, the halo [ref_only_from, n_ref) is flagged reference-only
+    bool all;        // every reference point is a query
+    bool adaptive;   // bricks may still be deferred to a finer level (the histogram stage can switch it off)
+    bool trace;      // GSX_TRACE_LEVELS
+    int64_t cap;     // cells the grid may have
+    double pts_per_cell;
+    // what the stages leave for one another
+    int bbox_blocks = 0;
+    bool mfma_ok = false, plan = false, adaptive_at_bbox = false, tree_ok = false, hist_done = false, have_hgp = false;
+    int64_t plan_cap = 0;
+    GridParams *gp = nullptr;
+    float4 *refs = nullptr;
+    const float4 *qpts = nullptr;
+    unsigned *rstart = nullptr;
+    const unsigned *qstart = nullptr;
+    GridParams hgp;   // the grid parameters and counters as the host read them after knn_brick (have_hgp)
+};
 
+// (a refinement round calls the next level)
 static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *y, const float *z, int64_t stride,
                           int64_t n_ref, int64_t q_begin, int64_t q_count, int k, float *mean_out, double *kth_out,
                           gsx_sor_info *info, int share, int nshares, bool adaptive, float parent_h,
-                          int64_t ref_only_from = INT32_MAX, double h_hint = 0.0, const SlabKnn *sk = nullptr)
+                          int64_t ref_only_from = INT32_MAX, double h_hint = 0.0, const SlabKnn *sk = nullptr);
+
+static int level_reserve(GridLevel &L)
 {
-    KnnWs &w = ctx->ws[level];
-    if (level == 0) ctx->last_knn_algo = GSX_KNN_GRID;
-    w.refined_total = 0;
-    const int kk = k + 1;
-    const bool anyk = kk > 65;   // k > 64: the list-free exact path (knn_anyk_kernel) instead of knn_brick + ring kernels
-    if (kk > ANYK_MAX) GSX_FAIL("sor: k=%d not supported (k must be <= %d)", k, ANYK_MAX - 1);
-    // cells the grid may have.  Level 0: about one cell per two points (more would be empty cells to walk).  A refinement
-    // level sized by the density probe covers a box that is mostly EMPTY by construction (a blob's tails, the few floaters
-    // around a scene), so it gets room for 4 cells per point, within what the two-level sort can address.
-    const int64_t cap = h_hint > 0.0 ? std::min<int64_t>(std::max<int64_t>(4 * n_ref, 64), (int64_t)MAX_BUCKETS * MAX_BUCKET_CELLS - 64) + 64
-                                     : grid_cell_cap(n_ref);
-    // slab mode (multi-GPU): every point is binned once, the halo [ref_only_from, n_ref) is flagged reference-only
-    const bool slab = ref_only_from < n_ref;
-    if (anyk && (nshares > 1 || slab)) GSX_FAIL("sor: k=%d > 64 is served by the single-GPU path only", k);
-    if (anyk) adaptive = false;
-    const bool all = (q_begin == 0 && q_count == n_ref) || slab;
-    // (a share of the bricks -- the replicated multi-GPU exchange -- refines the deferred bricks of ITS share only)
-    adaptive = adaptive && all && !slab && level + 1 < KNN_MAX_LEVELS;
-    const int bbox_blocks = std::min(grid_blocks(ctx, n_ref, 8), ctx->num_cu * 4);
-    // cell edge h is also the guaranteed search radius: the expected number of points within h is
-    // 4.19 * m, and a query falls back to knn_ring when fewer than k+1 are.  m = 0.47 (k+1) puts
-    // ~2 (k+1) points inside h (measured optimum at k = 8, 16, 25, 32: profiles/r01_sweep_m.log).
-    // A brick's population cells*m should stay <= ~58 so that its queries fit ONE 64-lane batch
-    // (at 64 on average 47 % of the bricks need a second one): k = 16 -> m = 7.25, not 8.
-    double pts_per_cell = ctx->grid_points_per_cell;
-    if (!(pts_per_cell > 0.0)) {
-        pts_per_cell = std::max(2.0, 0.47 * (double)(k + 1));
-        // a brick's queries must fit ONE 64-lane batch with a margin.  Fewer points per cell = fewer candidates per
-        // query in knn_brick but more queries for the ring kernels, which are cheap per query once tens of thousands
-        // of them keep every wave busy and latency-bound below that (profiles/r02_variants.txt: 10M k=16 is fastest at
-        // 54 / 8 cells, 1M at 58 / 8, 50M k=32 at 52-54 / 4)
-        const double fill = n_ref >= 4000000 ? 54.0 : 58.0;
-        for (int cells = 8; cells >= 1; cells /= 2)
-            if (pts_per_cell * cells > fill && pts_per_cell * cells <= 66.0) pts_per_cell = fill / cells;
-        // k = 17 ... 20 (round 4; the reference CLI's --sor_intensity 3 is k = 18): 0.47 (k + 1) points per cell would
-        // halve the brick to 2x2x1 cells -- 36 of 64 lanes busy, 12x instead of 8x its points as candidates.  Smaller cells
-        // keep the 2x2x2 brick full at the price of ring queries (10M uniform, step ms: k = 18 3.16 -> 2.60 with 175 k ring
-        // queries, k = 20 3.17 -> 2.90 with 186 k; from k = 23 on the ring queries cost more than the full lanes save)
-        if (k >= 17 && k <= 20) pts_per_cell = std::min(pts_per_cell, fill / 8.0 + 0.375 * (double)std::max(0, k - 18));
-        // ... and k = 35 ... 52 (--sor_intensity 7 ... 10: k = 36, 41, 45, 50) keeps 2x2x1 bricks instead of 2x1x1 (10M uniform, step ms:
-        // k = 36 6.28 -> 4.52, k = 41 6.10 -> 5.02, k = 45 7.26 -> 5.73, k = 48 7.50 -> 6.3, k = 50 10.3 -> 8.3; k >= 56: the ring
-        // queries win -- profiles/r04_variants.txt)
-        if (k >= 26 && k <= 31) pts_per_cell = std::min(pts_per_cell, 12.0 * fill / 54.0);   // (k = 27: 3.49 -> 3.36, k = 30: 3.58 -> 3.42)
-        if (k >= 35 && k <= 43) pts_per_cell = std::min(pts_per_cell, (k <= 38 ? 13.5 : 14.5) * fill / 54.0);
-        // Round 5: with 32 parked words (1024 candidates) for the lists of more than 32 entries the cells of k >= 44 can be larger
-        // again -- fewer ring queries (k = 50 at 15 points per cell: 595 k of them, 2.5 of 7.6 ms).  10M uniform, step ms, best of
-        // a sweep 15 ... 26 (profiles/r05_variants.txt): k = 45 5.67 -> 5.41 (16), 47 6.01 -> 5.58 (16), 50 7.60 -> 6.37 (22), 52 8.86 ->
-        // 6.14 (22), 55 7.17 -> 6.81 (22), 57 7.87 -> 7.22 (22), 60 7.87 -> 7.34 (24); k >= 63: 0.47 (k + 1) as before
-        if (k >= 44 && k <= 62) pts_per_cell = std::min(pts_per_cell, k <= 49 ? 16.0 : (k <= 58 ? 22.0 : 24.0));
-    }
+    gsx_ctx *ctx = L.ctx;
+    KnnWs &w = L.w;
+    const int64_t n_ref = L.n_ref, q_count = L.q_count, cap = L.cap;
+    L.bbox_blocks = std::min(grid_blocks(ctx, n_ref, 8), ctx->num_cu * 4);
     GSX_CHECK(w.packed.reserve(sizeof(float4) * (size_t)n_ref));
     GSX_CHECK(w.bucketpts.reserve(sizeof(float4) * (size_t)n_ref));
     GSX_CHECK(w.cellstart.reserve(sizeof(unsigned) * (size_t)(cap + 1)));
@@ -2968,41 +2959,47 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
         GSX_CHECK(w.gridparams.reserve(sizeof(GridParams)));
         GSX_HIP(hipMemsetAsync(w.gridparams.p, 0, sizeof(GridParams), ctx->stream));
     }
-    GSX_CHECK(w.bboxpart.reserve(sizeof(float) * 7 * (size_t)bbox_blocks));
+    GSX_CHECK(w.bboxpart.reserve(sizeof(float) * 7 * (size_t)L.bbox_blocks));
     GSX_CHECK(w.faillist.reserve(sizeof(unsigned) * 2 * (size_t)std::max<int64_t>(q_count, 1)));   // fail list | knn_ring_fast's leftovers
-    GSX_CHECK(w.extraitems.reserve(sizeof(uint2) * (size_t)(std::max(q_count, slab ? n_ref : q_count) / 64 + 64)));
-    if (adaptive) {
+    GSX_CHECK(w.extraitems.reserve(sizeof(uint2) * (size_t)(std::max(q_count, L.slab ? n_ref : q_count) / 64 + 64)));
+    if (L.adaptive) {
         GSX_CHECK(w.deferred.reserve(sizeof(unsigned) * (size_t)(cap + 64)));  // nbricks <= ncells <= cap
         GSX_CHECK(w.heavylist.reserve(sizeof(unsigned) * (size_t)std::max<int64_t>(q_count, 1)));
     }
-    if (!all) {
+    if (!L.all) {
         GSX_CHECK(w.qsorted.reserve(sizeof(float4) * (size_t)q_count));
         GSX_CHECK(w.qcellstart.reserve(sizeof(unsigned) * (size_t)(cap + 1)));
     }
-    GridParams *gp = w.gridparams.as<GridParams>();
-    float4 *refs = w.packed.as<float4>();
-    unsigned *rstart = w.cellstart.as<unsigned>();
-    // Planned bricks (brick_plan_kernel): the plain single-cloud call only -- every point a query of the one table, no share, no
-    // slab halo, no refinement level -- and the kernels they were built for: 2x2x2-cell bricks (pts_per_cell as grid_params
-    // decides), k <= 16, MFMA filter + network selection.  An adaptive call qualifies once the coarse histogram has shown that
-    // nothing will be deferred (below).  The grid's extent along x is checked on the device (grid_params).
-    const bool mfma_ok = ctx->filter_mfma != 0 && n_ref < (int64_t(1) << 28);
-    bool plan = ctx->brick_plan != 0 && level == 0 && all && !slab && !sk && nshares == 1 && !anyk && kk <= 17 && mfma_ok &&
-                ctx->phase2_net != 0 && !(pts_per_cell * 8.0 > 66.0) && h_hint == 0.0 && kth_out == nullptr;
-    const int64_t plan_cap = n_ref / 16 + 4096;
-    if (plan) {
+    L.gp = w.gridparams.as<GridParams>();
+    L.refs = w.packed.as<float4>();
+    L.rstart = w.cellstart.as<unsigned>();
+    // (the MFMA kernels' phase 2 addresses the sorted points with 32-bit byte offsets: 16 * n_ref < 2^32; larger clouds take the
+    //  scalar filter, which is exact as well)
+    L.mfma_ok = ctx->filter_mfma != 0 && n_ref < (int64_t(1) << 28);
+    L.plan = grid_plan_eligible({ctx->brick_plan != 0, L.level, L.all, L.slab, L.sk != nullptr, L.nshares, L.k, L.mfma_ok,
+                                 ctx->phase2_net != 0, L.pts_per_cell, L.h_hint, L.kth_out != nullptr});
+    L.plan_cap = n_ref / 16 + 4096;
+    if (L.plan) {
         GSX_CHECK(w.finestart.reserve(sizeof(unsigned) * (size_t)(4 * cap + 4)));
-        GSX_CHECK(w.bricklist.reserve(sizeof(uint2) * (size_t)plan_cap));
+        GSX_CHECK(w.bricklist.reserve(sizeof(uint2) * (size_t)L.plan_cap));
         GSX_CHECK(w.bundleoff.reserve(sizeof(unsigned) * 2 * (size_t)(MAX_DIM / 2) * (MAX_DIM / 2)));
     }
+    return 0;
+}
 
+// the bounding box and, in its last workgroup, the grid parameters; opens the level's first GSX_T_SOR_BIN interval
+static int level_grid_params(GridLevel &L)
+{
+    gsx_ctx *ctx = L.ctx;
+    KnnWs &w = L.w;
+    const SlabKnn *sk = L.sk;
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_BIN));
     // (adaptive mode may still switch the deferral off below, once the histogram is known: defer_words is then cleared on the device)
-    GridParamArgs gpa{(int)n_ref, pts_per_cell, (int)cap, ctx->debug_skip, share, nshares, adaptive ? ctx->defer_words : 0, parent_h, gp,
-                      ctx->devflags.as<unsigned>(), h_hint, sk ? sk->cert_axis : -1, sk ? sk->cert_lo : 0.0f, sk ? sk->cert_hi : 0.0f,
-                      sk ? sk->cert_count : nullptr, plan ? 1 : 0, (int)plan_cap};
+    GridParamArgs gpa{(int)L.n_ref, L.pts_per_cell, (int)L.cap, ctx->debug_skip, L.share, L.nshares, L.adaptive ? ctx->defer_words : 0,
+                      L.parent_h, L.gp, ctx->devflags.as<unsigned>(), L.h_hint, sk ? sk->cert_axis : -1, sk ? sk->cert_lo : 0.0f,
+                      sk ? sk->cert_hi : 0.0f, sk ? sk->cert_count : nullptr, L.plan ? 1 : 0, (int)L.plan_cap};
 #ifdef GSX_WAVE_STAMPS
-    if (level == 0) {   // (a finer level would overwrite the records of the call's main launches)
+    if (L.level == 0) {   // (a finer level would overwrite the records of the call's main launches)
         const int ws_cap = ctx->num_cu * 8 * (BRICK_THREADS / 64);   // the launches are capped at 8 workgroups per CU
         const size_t ws_bytes = sizeof(unsigned long long) * 2 * (size_t)ws_cap * WS_WORDS;
         GSX_CHECK(w.wavestamps.reserve(ws_bytes));
@@ -3012,63 +3009,70 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
         ctx->ws_cap = ws_cap;
     }
 #endif
-    const bool adaptive_at_bbox = adaptive;
+    L.adaptive_at_bbox = L.adaptive;
     if (sk && sk->box.b7)
         hipLaunchKernelGGL(grid_params_known_box_kernel, dim3(1), dim3(64), 0, ctx->stream, sk->box, w.bboxpart.as<float>(), gpa);
     else
-        hipLaunchKernelGGL(bbox_partial_kernel, dim3(bbox_blocks), dim3(256), 0, ctx->stream, x, y, z, stride, (int)n_ref,
+        hipLaunchKernelGGL(bbox_partial_kernel, dim3(L.bbox_blocks), dim3(256), 0, ctx->stream, L.x, L.y, L.z, L.stride, (int)L.n_ref,
                            w.bboxpart.as<float>(), gpa);   // its last workgroup computes the grid parameters
     GSX_HIP(hipGetLastError());
-    if (adaptive) GSX_CHECK(w.qcellstart.reserve(sizeof(unsigned) * (size_t)(cap + 1)));  // free in this mode: the cursors
-    // Adaptive mode, first decision: can ONE grid resolve this cloud at all?  The coarse histogram of the two-level sort (one
-    // bucket = a column of cells sized for ~4096 points of a uniform cloud) says so after 0.1 ms: a cloud whose fullest bucket
-    // holds several times the average (a scene inside a box inflated by floaters: 2400x; Gaussian blobs: 30x+) goes to the
-    // Morton-tree path (sor_tree.hip) at once -- no cell size fits it, and refining level by level costs a host round trip
-    // and a re-binning per level (clustered 1M: 16.5 ms against 1.3 ms).
-    // (slab mode -- one rank's slab + halo of the multi-GPU exchange -- never refines, but an uneven slab still goes to the tree:
-    //  the grid would search its dense cells quadratically)
-    bool tree_ok = (adaptive || (slab && ctx->adaptive)) && ctx->tree && level == 0 && kk <= 65 && n_ref > k;
-    bool hist_done = false;
-    if (tree_ok) {
-        GSX_CHECK(bin_hist(ctx, w, x, y, z, stride, 0, n_ref, gp));
-        static thread_local std::vector<unsigned> starts(MAX_BUCKETS + 1);
-        GSX_HIP(hipMemcpyAsync(starts.data(), w.bkcnt.as<unsigned>() + MAX_BUCKETS, sizeof(unsigned) * (MAX_BUCKETS + 1), hipMemcpyDeviceToHost, ctx->stream));
-        GSX_HIP(hipStreamSynchronize(ctx->stream));
-        unsigned mx = 0, nonzero = 0;
-        for (int b = 0; b < MAX_BUCKETS; ++b) {
-            const unsigned c = starts[b + 1] >= starts[b] ? starts[b + 1] - starts[b] : 0u;   // (entries past the last bucket repeat the total)
-            mx = std::max(mx, c);
-            nonzero += c > 0;
+    if (L.adaptive) GSX_CHECK(w.qcellstart.reserve(sizeof(unsigned) * (size_t)(L.cap + 1)));  // free in this mode: the cursors
+    return 0;
+}
+
+// Adaptive mode, first decision (grid_policy.h: grid_hist_verdict): an uneven cloud goes to the Morton tree, *done = it took
+// the call; an even one will defer nothing.  The one host synchronisation of an adaptive call on an even cloud is here.
+// (slab mode -- one rank's slab + halo of the multi-GPU exchange -- never refines, but an uneven slab still goes to the tree:
+//  the grid would search its dense cells quadratically)
+static int level_histogram(GridLevel &L, bool *done)
+{
+    gsx_ctx *ctx = L.ctx;
+    KnnWs &w = L.w;
+    L.tree_ok = (L.adaptive || (L.slab && ctx->adaptive)) && ctx->tree && L.level == 0 && L.k + 1 <= 65 && L.n_ref > L.k;
+    if (!L.tree_ok) return 0;
+    GSX_CHECK(bin_hist(ctx, w, L.x, L.y, L.z, L.stride, 0, L.n_ref, L.gp));
+    static thread_local std::vector<unsigned> starts(MAX_BUCKETS + 1);
+    GSX_HIP(hipMemcpyAsync(starts.data(), w.bkcnt.as<unsigned>() + MAX_BUCKETS, sizeof(unsigned) * (MAX_BUCKETS + 1), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    const HistVerdict v = grid_hist_verdict(starts.data(), L.n_ref, L.nshares);
+    L.hist_done = true;
+    if (v.to_tree) {
+        GSX_CHECK(timing_end(ctx, GSX_T_SOR_BIN));
+        if (L.trace)
+            fprintf(stderr, "[gsx] level 0: fullest bucket %u of %lld points in %u buckets -> tree path\n", v.fullest, (long long)L.n_ref, v.nonzero);
+        const int rc = launch_knn_tree(ctx, L.x, L.y, L.z, L.stride, L.n_ref, L.q_begin, L.q_count, L.k, L.mean_out, L.kth_out, L.info,
+                                       L.slab ? L.ref_only_from : INT32_MAX, L.share, L.nshares, true);
+        if (rc != GSX_TREE_UNSUITABLE) {
+            *done = true;
+            return rc;
         }
-        hist_done = true;
-        if (nonzero > 0 && (double)mx > 3.0 * (double)n_ref / (double)nonzero) {
-            GSX_CHECK(timing_end(ctx, GSX_T_SOR_BIN));
-            if (getenv("GSX_TRACE_LEVELS"))
-                fprintf(stderr, "[gsx] level 0: fullest bucket %u of %lld points in %u buckets -> tree path\n", mx, (long long)n_ref, nonzero);
-            const int rc = launch_knn_tree(ctx, x, y, z, stride, n_ref, q_begin, q_count, k, mean_out, kth_out, info,
-                                           slab ? ref_only_from : INT32_MAX, share, nshares, true);
-            if (rc != GSX_TREE_UNSUITABLE) return rc;
-            // (tens of thousands of points inside one cell of the tree's finest resolution: the refinement below re-scales)
-            tree_ok = false;
-            ctx->last_knn_algo = GSX_KNN_GRID;
-            GSX_CHECK(timing_begin(ctx, GSX_T_SOR_BIN));
-        }
-        // an even histogram (fullest bucket within 1.5x of the average): no brick can be far over-full, so none is deferred and
-        // the host does not have to look at the counters again -- the call costs ONE synchronisation, as before the probe existed
-        if (nonzero > 0 && (double)mx <= 1.5 * (double)n_ref / (double)nonzero && nshares == 1) adaptive = false;
+        // (tens of thousands of points inside one cell of the tree's finest resolution: the refinement below re-scales)
+        L.tree_ok = false;
+        ctx->last_knn_algo = GSX_KNN_GRID;
+        GSX_CHECK(timing_begin(ctx, GSX_T_SOR_BIN));
     }
-    if (adaptive_at_bbox && !adaptive) {   // the grid parameters were written with deferral on
+    if (v.no_deferral) L.adaptive = false;
+    return 0;
+}
+
+// the two-level sort of the references (and of the queries of a partial call), the brick plan; closes GSX_T_SOR_BIN
+static int level_bin(GridLevel &L)
+{
+    gsx_ctx *ctx = L.ctx;
+    KnnWs &w = L.w;
+    GridParams *gp = L.gp;
+    if (L.adaptive_at_bbox && !L.adaptive) {   // the grid parameters were written with deferral on
         GSX_HIP(hipMemsetAsync(&gp->defer_words, 0, sizeof(int), ctx->stream));
         GSX_HIP(hipMemsetAsync(&gp->heavy_limit, 0, sizeof(int), ctx->stream));
     }
-    if (plan && adaptive) {   // bricks may be deferred to a finer level: the fixed bricks, exactly as before
-        plan = false;
+    if (L.plan && L.adaptive) {   // bricks may be deferred to a finer level: the fixed bricks, exactly as before
+        L.plan = false;
         GSX_HIP(hipMemsetAsync(&gp->plan, 0, sizeof(int), ctx->stream));
     }
-    unsigned *fstart = plan ? w.finestart.as<unsigned>() : nullptr;
-    GSX_CHECK(bin_points(ctx, w, x, y, z, stride, 0, n_ref, gp, rstart, refs, cap, adaptive ? w.qcellstart.as<unsigned>() : nullptr,
-                         slab ? ref_only_from : INT32_MAX, hist_done, fstart));
-    if (plan) {   // one wave per bundle of 2x2 query rows (grid-stride): count + scan, then write
+    unsigned *fstart = L.plan ? w.finestart.as<unsigned>() : nullptr;
+    GSX_CHECK(bin_points(ctx, w, L.x, L.y, L.z, L.stride, 0, L.n_ref, gp, L.rstart, L.refs, L.cap,
+                         L.adaptive ? w.qcellstart.as<unsigned>() : nullptr, L.slab ? L.ref_only_from : INT32_MAX, L.hist_done, fstart));
+    if (L.plan) {   // one wave per bundle of 2x2 query rows (grid-stride): count + scan, then write
         unsigned *bcnt = w.bundleoff.as<unsigned>(), *boff = bcnt + (size_t)(MAX_DIM / 2) * (MAX_DIM / 2);
         const int pblocks = ctx->num_cu * 4;
         hipLaunchKernelGGL(brick_plan_kernel<false>, dim3(pblocks), dim3(64 * PLAN_WAVES), 0, ctx->stream, gp, fstart, bcnt, boff,
@@ -3077,309 +3081,249 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
                            w.bricklist.as<uint2>());
         GSX_HIP(hipGetLastError());
     }
-    const float4 *qpts = refs;
-    const unsigned *qstart = rstart;
-    if (!all) {
-        GSX_CHECK(bin_points(ctx, w, x, y, z, stride, q_begin, q_count, gp, w.qcellstart.as<unsigned>(),
+    L.qpts = L.refs;
+    L.qstart = L.rstart;
+    if (!L.all) {
+        GSX_CHECK(bin_points(ctx, w, L.x, L.y, L.z, L.stride, L.q_begin, L.q_count, gp, w.qcellstart.as<unsigned>(),
                              w.qsorted.as<float4>()));
-        qpts = w.qsorted.as<float4>();
-        qstart = w.qcellstart.as<unsigned>();
+        L.qpts = w.qsorted.as<float4>();
+        L.qstart = w.qcellstart.as<unsigned>();
     }
     GSX_CHECK(timing_end(ctx, GSX_T_SOR_BIN));
+    return 0;
+}
 
-    BrickLaunch a{gp, refs, rstart, qpts, qstart, k, q_begin, mean_out, kth_out, w.faillist.as<unsigned>(),
-                  w.faillist.as<unsigned>() + std::max<int64_t>(q_count, 1),
-                  w.extraitems.as<uint2>(), w.deferred.as<unsigned>(), w.heavylist.as<unsigned>(), q_count, n_ref,
-                  plan ? w.finestart.as<unsigned>() : nullptr, plan ? w.bricklist.as<uint2>() : nullptr};
-    if (anyk) {
-        GSX_CHECK(timing_begin(ctx, GSX_T_SOR_KNN));
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((q_count + 3) / 4, (int64_t)ctx->num_cu * 2));
-        hipLaunchKernelGGL(knn_anyk_kernel, dim3(blocks), dim3(BRICK_THREADS), 0, ctx->stream, gp, refs, rstart, qpts, (int)q_count, k,
-                           (int)q_begin, mean_out, kth_out);
+static int level_anyk(GridLevel &L)
+{
+    gsx_ctx *ctx = L.ctx;
+    GSX_CHECK(timing_begin(ctx, GSX_T_SOR_KNN));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((L.q_count + 3) / 4, (int64_t)ctx->num_cu * 2));
+    hipLaunchKernelGGL(knn_anyk_kernel, dim3(blocks), dim3(BRICK_THREADS), 0, ctx->stream, L.gp, L.refs, L.rstart, L.qpts, (int)L.q_count,
+                       L.k, (int)L.q_begin, L.mean_out, L.kth_out);
+    GSX_HIP(hipGetLastError());
+    GSX_CHECK(timing_end(ctx, GSX_T_SOR_KNN));
+    return 0;
+}
+
+// One refinement round: the sub-cloud around one group of deferred bricks gets a grid of its own (level + 1) and its answers
+// are merged back.  Two host synchronisations: the queries' box (the clip needs it), then the gathered count with the probe.
+static int refine_group(GridLevel &L, const BrickLaunch &a, const unsigned *g_list, unsigned g_count)
+{
+    gsx_ctx *ctx = L.ctx;
+    KnnWs &w = L.w;
+    GridParams *gp = L.gp;
+    const int64_t n_ref = L.n_ref;
+    uint8_t *flag = w.cellflag.as<uint8_t>();
+    float *sub = w.subxyz.as<float>();
+    unsigned *sub_orig = w.submap.as<unsigned>(), *sub_sorted = sub_orig + n_ref;
+    GSX_CHECK(timing_begin(ctx, GSX_T_SOR_BIN));
+    GSX_HIP(hipMemsetAsync(flag, 0, (size_t)L.hgp.ncells, ctx->stream));
+    hipLaunchKernelGGL(reset_refine_kernel, dim3(1), dim3(1), 0, ctx->stream, gp);
+    hipLaunchKernelGGL(mark_cells_kernel, dim3(g_count), dim3(64), 0, ctx->stream, gp, g_list, g_count, flag, 0);
+    hipLaunchKernelGGL(mark_cells_kernel, dim3(g_count), dim3(64), 0, ctx->stream, gp, g_list, g_count, flag, 1);
+    hipLaunchKernelGGL(query_bbox_kernel, dim3(std::min(div_up(n_ref, 256), ctx->num_cu * 4)), dim3(256), 0, ctx->stream, gp,
+                       L.refs, (int)n_ref, flag);
+    GSX_HIP(hipGetLastError());
+    GridParams hq;
+    GSX_HIP(hipMemcpyAsync(&hq, gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    const RefineClip rc = refine_clip(hq.qb_lo, hq.qb_hi, hq.sub_queries, L.pts_per_cell, L.hgp.h, ctx->adaptive);
+    const ClipBox clip{{rc.lo[0], rc.lo[1], rc.lo[2]}, {rc.hi[0], rc.hi[1], rc.hi[2]}, rc.r_cert};
+    if (L.trace)
+        fprintf(stderr, "[gsx] level %d: group of %u bricks, %u deferred queries in [%g,%g]x[%g,%g]x[%g,%g], clip margin %g\n", L.level, g_count,
+                hq.sub_queries, hq.qb_lo[0], hq.qb_hi[0], hq.qb_lo[1], hq.qb_hi[1], hq.qb_lo[2], hq.qb_hi[2], (double)clip.r_cert);
+    hipLaunchKernelGGL(gather_sub_kernel, dim3(div_up(n_ref, GATHER_CHUNK)), dim3(256), 0, ctx->stream, gp, L.refs, (int)n_ref,
+                       flag, clip, sub, sub_orig, sub_sorted);
+    GSX_HIP(hipGetLastError());
+    // density probe of the gathered points (see probe_count_kernel): rides on the synchronisation that reads n_sub
+    double bin_vol = 0.0;
+    unsigned hist_h[32] = {0};
+    if (rc.probe_g) {
+        const int G = rc.probe_g;
+        GSX_CHECK(w.probe.reserve(sizeof(unsigned) * ((size_t)G * G * G + 32)));
+        unsigned *counts = w.probe.as<unsigned>(), *probe_hist = counts + (size_t)G * G * G;
+        GSX_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned) * ((size_t)G * G * G + 32), ctx->stream));
+        ProbeBox pb{};
+        pb.g = G;
+        bin_vol = 1.0;
+        for (int ax = 0; ax < 3; ++ax) {
+            const double e = (double)hq.qb_hi[ax] - (double)hq.qb_lo[ax];
+            pb.lo[ax] = hq.qb_lo[ax];
+            pb.inv[ax] = (float)((double)G / e);
+            bin_vol *= e / (double)G;
+        }
+        const int pblocks = std::min(div_up(n_ref, 1024), ctx->num_cu * 4);
+        hipLaunchKernelGGL(probe_count_kernel, dim3(pblocks), dim3(256), 0, ctx->stream, sub, (int)n_ref, &gp->sub_count, pb, counts);
+        hipLaunchKernelGGL(probe_hist_kernel, dim3(pblocks), dim3(256), 0, ctx->stream, sub, (int)n_ref, &gp->sub_count, pb, counts,
+                           probe_hist);
         GSX_HIP(hipGetLastError());
-        GSX_CHECK(timing_end(ctx, GSX_T_SOR_KNN));
-        if (info) {
-            GridParams h2;
-            GSX_HIP(hipMemcpyAsync(&h2, gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
-            GSX_HIP(hipStreamSynchronize(ctx->stream));
-            info->algo = GSX_KNN_GRID;
-            info->grid_dim[0] = h2.nx;
-            info->grid_dim[1] = h2.ny;
-            info->grid_dim[2] = h2.nz;
-            info->cell_size = h2.h;
-            info->n_cells = (int64_t)h2.nx * h2.ny * h2.nz;
-            info->n_bricks = 0;
-            info->n_fallback = q_count;
-            info->n_exhaustive = h2.exhaustive_count;
-            info->n_deferred_bricks = 0;
-            info->n_refined = 0;
-        }
-        return 0;
+        GSX_HIP(hipMemcpyAsync(hist_h, probe_hist, sizeof(hist_h), hipMemcpyDeviceToHost, ctx->stream));
     }
-    // (the MFMA kernels' phase 2 addresses the sorted points with 32-bit byte offsets: 16 * n_ref < 2^32; larger clouds take the
-    //  scalar filter, which is exact as well)
-    GSX_CHECK(dispatch_bricks(ctx, a, mfma_ok, ctx->phase2_net != 0));
+    unsigned n_sub = 0;
+    GSX_HIP(hipMemcpyAsync(&n_sub, &gp->sub_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    GSX_CHECK(timing_end(ctx, GSX_T_SOR_BIN));
+    const double h_hint_sub =
+        rc.probe_g ? refine_probe_edge(hist_h, bin_vol, hq.qb_lo, hq.qb_hi, clip.r_cert, n_sub, rc.h_est, L.pts_per_cell) : 0.0;
+    if (L.trace) fprintf(stderr, "[gsx] level %d: sub-cloud %u points, probed cell edge %g\n", L.level, n_sub, h_hint_sub);
+    if (n_sub == 0) GSX_FAIL("sor: refinement gathered no points for %u deferred bricks", g_count);
+    GSX_CHECK(w.submean.reserve(sizeof(float) * (size_t)n_sub));
+    GSX_CHECK(w.subkth.reserve(sizeof(double) * (size_t)n_sub));
+    GSX_CHECK(knn_grid_level(ctx, L.level + 1, sub, sub + n_ref, sub + 2 * n_ref, 1, (int64_t)n_sub, 0, (int64_t)n_sub, L.k,
+                             w.submean.as<float>(), w.subkth.as<double>(), nullptr, 0, 1, true, L.hgp.h, INT32_MAX, h_hint_sub, nullptr));
+    hipLaunchKernelGGL(merge_sub_kernel, dim3(div_up((int64_t)n_sub, 256)), dim3(256), 0, ctx->stream, gp, sub, (int)n_ref,
+                       sub_orig, sub_sorted, w.submean.as<float>(), w.subkth.as<double>(), (int)L.q_begin, clip.r_cert,
+                       L.mean_out, L.kth_out, a.faillist);
+    GSX_HIP(hipGetLastError());
+    w.refined_total += n_sub;
+    return 0;
+}
 
-    const bool trace = getenv("GSX_TRACE_LEVELS") != nullptr;
-    GridParams hgp;
-    bool have_hgp = false;
-    if (adaptive) {
-        // the only host decision of the pipeline: did any brick ask for a finer grid?
-        GSX_HIP(hipMemcpyAsync(&hgp, gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
-        GSX_HIP(hipStreamSynchronize(ctx->stream));
-        have_hgp = true;
-        if (getenv("GSX_TRACE_LEVELS"))
-            fprintf(stderr, "[gsx] level %d: n=%lld h=%.5g dims=%dx%dx%d bricks=%d defer_words=%d deferred=%u extra=%u fail=%u\n", level,
-                    (long long)n_ref, hgp.h, hgp.nx, hgp.ny, hgp.nz, hgp.nbricks, hgp.defer_words, hgp.deferred_count,
-                    hgp.extra_count, hgp.fail_count);
-        if (hgp.deferred_count > 0 && !hgp.bad_input && tree_ok && nshares == 1) {   // (a share sees only ITS bricks: the ranks of a
-                                                                                    // replicated exchange could decide differently)
-            // second decision: the histogram looked even, yet some bricks hold far more than their cells were sized for
-            // (density varying inside the buckets).  The tree path takes the whole cloud over; this level's work is lost.
-            if (getenv("GSX_TRACE_LEVELS")) fprintf(stderr, "[gsx] level 0: %u deferred bricks -> tree path\n", hgp.deferred_count);
-            const int rc = launch_knn_tree(ctx, x, y, z, stride, n_ref, q_begin, q_count, k, mean_out, kth_out, info, INT32_MAX, 0, 1, true);
-            if (rc != GSX_TREE_UNSUITABLE) return rc;
-            ctx->last_knn_algo = GSX_KNN_GRID;
+// After knn_brick in adaptive mode: read the counters; deferred bricks go to the tree (*done = it took the call) or, group by
+// group, to a finer grid.
+static int level_refine(GridLevel &L, const BrickLaunch &a, bool *done)
+{
+    gsx_ctx *ctx = L.ctx;
+    KnnWs &w = L.w;
+    GridParams &hgp = L.hgp;
+    // the only host decision of the pipeline: did any brick ask for a finer grid?
+    GSX_HIP(hipMemcpyAsync(&hgp, L.gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    L.have_hgp = true;
+    if (L.trace)
+        fprintf(stderr, "[gsx] level %d: n=%lld h=%.5g dims=%dx%dx%d bricks=%d defer_words=%d deferred=%u extra=%u fail=%u\n", L.level,
+                (long long)L.n_ref, hgp.h, hgp.nx, hgp.ny, hgp.nz, hgp.nbricks, hgp.defer_words, hgp.deferred_count,
+                hgp.extra_count, hgp.fail_count);
+    if (!(hgp.deferred_count > 0 && !hgp.bad_input)) return 0;
+    if (L.tree_ok && L.nshares == 1) {   // (a share sees only ITS bricks: the ranks of a replicated exchange could decide differently)
+        // second decision: the histogram looked even, yet some bricks hold far more than their cells were sized for
+        // (density varying inside the buckets).  The tree path takes the whole cloud over; this level's work is lost.
+        if (L.trace) fprintf(stderr, "[gsx] level 0: %u deferred bricks -> tree path\n", hgp.deferred_count);
+        const int rc = launch_knn_tree(ctx, L.x, L.y, L.z, L.stride, L.n_ref, L.q_begin, L.q_count, L.k, L.mean_out, L.kth_out, L.info,
+                                       INT32_MAX, 0, 1, true);
+        if (rc != GSX_TREE_UNSUITABLE) {
+            *done = true;
+            return rc;
         }
-        if (hgp.deferred_count > 0 && !hgp.bad_input) {
-            const unsigned nd = hgp.deferred_count;
-            GSX_CHECK(w.cellflag.reserve((size_t)hgp.ncells + 64));
-            GSX_CHECK(w.subxyz.reserve(sizeof(float) * 3 * (size_t)n_ref));
-            GSX_CHECK(w.submap.reserve(sizeof(unsigned) * 2 * (size_t)n_ref));
-            uint8_t *flag = w.cellflag.as<uint8_t>();
-            float *sub = w.subxyz.as<float>();
-            unsigned *sub_orig = w.submap.as<unsigned>(), *sub_sorted = sub_orig + n_ref;
-            // Deferred bricks that are far apart belong to different clusters with different densities:
-            // each connected group (bricks within 2 of each other, i.e. overlapping neighbourhoods)
-            // gets its own sub-cloud, hence its own bounding box and cell size.  At most 8 groups
-            // (the smallest ones are merged into the last).
-            std::vector<unsigned> dl(nd);
-            GSX_HIP(hipMemcpyAsync(dl.data(), a.deferred, sizeof(unsigned) * nd, hipMemcpyDeviceToHost, ctx->stream));
-            GSX_HIP(hipStreamSynchronize(ctx->stream));
-            std::vector<std::vector<unsigned>> groups;
-            {
-                std::unordered_map<unsigned, int> where;  // brick id -> index in dl
-                for (unsigned i = 0; i < nd; ++i) where[dl[i]] = (int)i;
-                std::vector<int> comp(nd, -1);
-                const int nbx = hgp.nbx, nby = hgp.nby, nbz = hgp.nbz;
-                for (unsigned s0i = 0; s0i < nd; ++s0i) {
-                    if (comp[s0i] >= 0) continue;
-                    const int c = (int)groups.size();
-                    groups.emplace_back();
-                    std::vector<unsigned> stack{s0i};
-                    comp[s0i] = c;
-                    while (!stack.empty()) {
-                        const unsigned i = stack.back();
-                        stack.pop_back();
-                        groups[c].push_back(dl[i]);
-                        const int b = (int)dl[i];
-                        const int bz = b / (nbx * nby), by = (b - bz * nbx * nby) / nbx, bx = b - bz * nbx * nby - by * nbx;
-                        for (int dz = -2; dz <= 2; ++dz)
-                            for (int dy = -2; dy <= 2; ++dy)
-                                for (int dx = -2; dx <= 2; ++dx) {
-                                    const int x2 = bx + dx, y2 = by + dy, z2 = bz + dz;
-                                    if (x2 < 0 || y2 < 0 || z2 < 0 || x2 >= nbx || y2 >= nby || z2 >= nbz) continue;
-                                    auto it = where.find((unsigned)((z2 * nby + y2) * nbx + x2));
-                                    if (it != where.end() && comp[it->second] < 0) {
-                                        comp[it->second] = c;
-                                        stack.push_back((unsigned)it->second);
-                                    }
-                                }
-                    }
-                }
-                std::sort(groups.begin(), groups.end(), [](const auto &l, const auto &r) { return l.size() > r.size(); });
-                while (groups.size() > 8) {
-                    groups[7].insert(groups[7].end(), groups.back().begin(), groups.back().end());
-                    groups.pop_back();
-                }
-                unsigned o = 0;
-                for (auto &g : groups) {
-                    std::copy(g.begin(), g.end(), dl.begin() + o);
-                    o += (unsigned)g.size();
-                }
-                if (groups.size() > 1) {  // one group: the device list is already it
-                    GSX_HIP(hipMemcpyAsync(a.deferred, dl.data(), sizeof(unsigned) * nd, hipMemcpyHostToDevice, ctx->stream));
-                    GSX_HIP(hipStreamSynchronize(ctx->stream));  // dl is a local
-                }
-            }
-            unsigned g_first = 0;
-            for (const auto &grp : groups) {
-            const unsigned g_count = (unsigned)grp.size();
-            const unsigned *g_list = a.deferred + g_first;
-            g_first += g_count;
-            GSX_CHECK(timing_begin(ctx, GSX_T_SOR_BIN));
-            GSX_HIP(hipMemsetAsync(flag, 0, (size_t)hgp.ncells, ctx->stream));
-            hipLaunchKernelGGL(reset_refine_kernel, dim3(1), dim3(1), 0, ctx->stream, gp);
-            hipLaunchKernelGGL(mark_cells_kernel, dim3(g_count), dim3(64), 0, ctx->stream, gp, g_list, g_count, flag, 0);
-            hipLaunchKernelGGL(mark_cells_kernel, dim3(g_count), dim3(64), 0, ctx->stream, gp, g_list, g_count, flag, 1);
-            hipLaunchKernelGGL(query_bbox_kernel, dim3(std::min(div_up(n_ref, 256), ctx->num_cu * 4)), dim3(256), 0, ctx->stream, gp,
-                               refs, (int)n_ref, flag);
-            GSX_HIP(hipGetLastError());
-            // The neighbourhood cells reach up to two of THIS level's cells beyond the queries; a stray
-            // far point among them (the very outliers that inflated the bounding box) would inflate the
-            // finer grid again.  Reference points farther than M from the queries' box are left out, and
-            // the finer level's answers are accepted only up to M: M = 4 x the cell edge the finer grid
-            // will get, i.e. ~5x its typical (k+1)-th neighbour distance.
-            ClipBox clip{};
-            unsigned hq_sub_queries = 0;
-            int hq_nd3 = 0;
-            double h_est = 0.0;   // cell edge the finer level would get from the box volume of the group's queries
-            float hq_lo[3] = {0, 0, 0}, hq_hi[3] = {0, 0, 0};
-            {
-                GridParams hq;
-                GSX_HIP(hipMemcpyAsync(&hq, gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
-                GSX_HIP(hipStreamSynchronize(ctx->stream));
-                double vol = 1.0, amax = 0.0;
-                int nd3 = 0;
-                for (int ax = 0; ax < 3; ++ax) {
-                    const double e = (double)hq.qb_hi[ax] - (double)hq.qb_lo[ax];
-                    if (e > 0.0) { vol *= e; ++nd3; }
-                    amax = std::max({amax, std::fabs((double)hq.qb_lo[ax]), std::fabs((double)hq.qb_hi[ax])});
-                }
-                hq_sub_queries = hq.sub_queries;
-                hq_nd3 = nd3;
-                for (int ax = 0; ax < 3; ++ax) {
-                    hq_lo[ax] = hq.qb_lo[ax];
-                    hq_hi[ax] = hq.qb_hi[ax];
-                }
-                const double per = hq.sub_queries > 0 ? vol * pts_per_cell / (double)hq.sub_queries : 0.0;
-                h_est = nd3 == 3 ? std::cbrt(per) : (nd3 == 2 ? std::sqrt(per) : (nd3 == 1 ? per : 0.0));
-                const double M = std::max(4.0 * h_est, 0.01 * (double)hgp.h);
-                const double cert = M * (1.0 - 1e-3) - 4e-7 * amax;  // f32 rounding of lo - M / hi + M
-                if (ctx->adaptive == 1 && hq.sub_queries > 0 && M < 2.0 * (double)hgp.h && cert > 0.0) {
-                    for (int ax = 0; ax < 3; ++ax) {
-                        clip.lo[ax] = std::nextafterf((float)((double)hq.qb_lo[ax] - M), -__builtin_inff());
-                        clip.hi[ax] = std::nextafterf((float)((double)hq.qb_hi[ax] + M), __builtin_inff());
-                    }
-                    clip.r_cert = (float)cert;
-                }
-                if (getenv("GSX_TRACE_LEVELS"))
-                    fprintf(stderr, "[gsx] level %d: group of %u bricks, %u deferred queries in [%g,%g]x[%g,%g]x[%g,%g], clip margin %g\n", level, g_count,
-                            hq.sub_queries, hq.qb_lo[0], hq.qb_hi[0], hq.qb_lo[1], hq.qb_hi[1], hq.qb_lo[2], hq.qb_hi[2],
-                            (double)clip.r_cert);
-            }
-            hipLaunchKernelGGL(gather_sub_kernel, dim3(div_up(n_ref, GATHER_CHUNK)), dim3(256), 0, ctx->stream, gp, refs, (int)n_ref,
-                               flag, clip, sub, sub_orig, sub_sorted);
-            GSX_HIP(hipGetLastError());
-            // density probe of the gathered points (see probe_count_kernel): rides on the synchronisation that reads n_sub
-            ProbeBox pb{};
-            double bin_vol = 0.0;
-            unsigned hist_h[32] = {0};
-            unsigned *probe_hist = nullptr;
-            if (ctx->adaptive == 1 && hq_sub_queries > 0 && hq_nd3 == 3) {
-                int G = (int)std::lround(std::cbrt((double)hq_sub_queries / 32.0));
-                G = std::max(8, std::min(64, G));
-                GSX_CHECK(w.probe.reserve(sizeof(unsigned) * ((size_t)G * G * G + 32)));
-                unsigned *counts = w.probe.as<unsigned>();
-                probe_hist = counts + (size_t)G * G * G;
-                GSX_HIP(hipMemsetAsync(counts, 0, sizeof(unsigned) * ((size_t)G * G * G + 32), ctx->stream));
-                pb.g = G;
-                bin_vol = 1.0;
-                for (int ax = 0; ax < 3; ++ax) {
-                    const double e = (double)hq_hi[ax] - (double)hq_lo[ax];
-                    pb.lo[ax] = hq_lo[ax];
-                    pb.inv[ax] = (float)((double)G / e);
-                    bin_vol *= e / (double)G;
-                }
-                const int pblocks = std::min(div_up(n_ref, 1024), ctx->num_cu * 4);
-                hipLaunchKernelGGL(probe_count_kernel, dim3(pblocks), dim3(256), 0, ctx->stream, sub, (int)n_ref, &gp->sub_count, pb, counts);
-                hipLaunchKernelGGL(probe_hist_kernel, dim3(pblocks), dim3(256), 0, ctx->stream, sub, (int)n_ref, &gp->sub_count, pb, counts,
-                                   probe_hist);
-                GSX_HIP(hipGetLastError());
-                GSX_HIP(hipMemcpyAsync(hist_h, probe_hist, sizeof(hist_h), hipMemcpyDeviceToHost, ctx->stream));
-            }
-            unsigned n_sub = 0;
-            GSX_HIP(hipMemcpyAsync(&n_sub, &gp->sub_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-            GSX_HIP(hipStreamSynchronize(ctx->stream));
-            GSX_CHECK(timing_end(ctx, GSX_T_SOR_BIN));
-            double h_hint_sub = 0.0;
-            constexpr double probe_q = 0.85, probe_shrink = 0.7;   // measured: quantiles 0.5 / 0.7 / 0.85 on four clouds
-            if (probe_hist) {
-                unsigned long long tot = 0, run = 0;
-                for (int b = 0; b < 32; ++b) tot += hist_h[b];
-                int bq = -1;
-                for (int b = 0; b < 32 && tot; ++b) {
-                    run += hist_h[b];
-                    if ((double)run >= probe_q * (double)tot) {
-                        bq = b;
-                        break;
-                    }
-                }
-                if (bq >= 0 && bin_vol > 0.0) {
-                    // 85 % of the points sit in probe bins of at most ~1.5 * 2^bq points: cells sized for THAT density are
-                    // over-full only for the densest 15 % (a Gaussian's core is 1.4x denser than its 85 % level: no second
-                    // refinement), under-full for the tails, whose queries go to the ring kernels
-                    const double rho = 1.5 * std::ldexp(1.0, bq) / bin_vol;
-                    h_hint_sub = std::cbrt(pts_per_cell / rho);
-                    // a grid of that edge over the group's box must fit the cell budget, otherwise the edge would be stretched
-                    // to something in between and every brick of a uniform region would be over-full: keep the old sizing then
-                    double cells = 1.0;
-                    for (int ax = 0; ax < 3; ++ax) cells *= std::floor(((double)hq_hi[ax] - (double)hq_lo[ax] + 2.0 * (double)clip.r_cert) / h_hint_sub) + 1.0;
-                    const double budget = (double)std::min<int64_t>(4 * (int64_t)n_sub, (int64_t)MAX_BUCKETS * MAX_BUCKET_CELLS - 64);
-                    if (!(cells <= 0.8 * budget)) h_hint_sub = 0.0;
-                    // a near-uniform group (the probed edge within 30 % of the box-volume edge) keeps the box-volume edge: the
-                    // population per cell is tuned to a few per cent there (0.92x the edge = 13x the ring queries, measured)
-                    if (h_hint_sub > probe_shrink * h_est) h_hint_sub = 0.0;
-                }
-            }
-            if (getenv("GSX_TRACE_LEVELS")) fprintf(stderr, "[gsx] level %d: sub-cloud %u points, probed cell edge %g\n", level, n_sub, h_hint_sub);
-            if (n_sub == 0) GSX_FAIL("sor: refinement gathered no points for %u deferred bricks", g_count);
-            GSX_CHECK(w.submean.reserve(sizeof(float) * (size_t)n_sub));
-            GSX_CHECK(w.subkth.reserve(sizeof(double) * (size_t)n_sub));
-            GSX_CHECK(knn_grid_level(ctx, level + 1, sub, sub + n_ref, sub + 2 * n_ref, 1, (int64_t)n_sub, 0, (int64_t)n_sub, k,
-                                     w.submean.as<float>(), w.subkth.as<double>(), nullptr, 0, 1, true, hgp.h, INT32_MAX, h_hint_sub));
-            hipLaunchKernelGGL(merge_sub_kernel, dim3(div_up((int64_t)n_sub, 256)), dim3(256), 0, ctx->stream, gp, sub, (int)n_ref,
-                               sub_orig, sub_sorted, w.submean.as<float>(), w.subkth.as<double>(), (int)q_begin, clip.r_cert,
-                               mean_out, kth_out, a.faillist);
-            GSX_HIP(hipGetLastError());
-            w.refined_total += n_sub;
-            }
-        }
+        ctx->last_knn_algo = GSX_KNN_GRID;
     }
+    const unsigned nd = hgp.deferred_count;
+    GSX_CHECK(w.cellflag.reserve((size_t)hgp.ncells + 64));
+    GSX_CHECK(w.subxyz.reserve(sizeof(float) * 3 * (size_t)L.n_ref));
+    GSX_CHECK(w.submap.reserve(sizeof(unsigned) * 2 * (size_t)L.n_ref));
+    std::vector<unsigned> dl(nd);
+    GSX_HIP(hipMemcpyAsync(dl.data(), a.deferred, sizeof(unsigned) * nd, hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    const std::vector<unsigned> groups = group_deferred_bricks(dl.data(), nd, hgp.nbx, hgp.nby, hgp.nbz);
+    if (groups.size() > 1) {  // one group: the device list is already it
+        GSX_HIP(hipMemcpyAsync(a.deferred, dl.data(), sizeof(unsigned) * nd, hipMemcpyHostToDevice, ctx->stream));
+        GSX_HIP(hipStreamSynchronize(ctx->stream));  // dl is a local
+    }
+    unsigned g_first = 0;
+    for (const unsigned g_count : groups) {
+        GSX_CHECK(refine_group(L, a, a.deferred + g_first, g_count));
+        g_first += g_count;
+    }
+    return 0;
+}
+
+static int level_ring_heavy(GridLevel &L, const BrickLaunch &a)
+{
+    gsx_ctx *ctx = L.ctx;
+    GridParams *gp = L.gp;
     std::chrono::steady_clock::time_point t_ring0;
-    if (trace) {
+    if (L.trace) {
         GSX_HIP(hipStreamSynchronize(ctx->stream));
         t_ring0 = std::chrono::steady_clock::now();
     }
     // a ring can only meet a huge cell if some brick was too populated for this level, i.e. deferred;
     // otherwise knn_ring keeps every query (no hand-over list, no second host sync)
-    const bool heavy_possible = adaptive && have_hgp && hgp.deferred_count > 0;
-    if (adaptive && !heavy_possible) GSX_HIP(hipMemsetAsync(&gp->heavy_limit, 0, sizeof(int), ctx->stream));
+    const bool heavy_possible = L.adaptive && L.have_hgp && L.hgp.deferred_count > 0;
+    if (L.adaptive && !heavy_possible) GSX_HIP(hipMemsetAsync(&gp->heavy_limit, 0, sizeof(int), ctx->stream));
     GSX_CHECK(dispatch_ring(ctx, a));
     if (heavy_possible) {
         unsigned nheavy = 0;
         GSX_HIP(hipMemcpyAsync(&nheavy, &gp->heavy_count, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
         GSX_HIP(hipStreamSynchronize(ctx->stream));
-        if (trace) fprintf(stderr, "[gsx] level %d: %u ring queries handed to knn_heavy\n", level, nheavy);
-        if (nheavy > 0) GSX_CHECK(dispatch_heavy(ctx, w, a, n_ref, nheavy));
+        if (L.trace) fprintf(stderr, "[gsx] level %d: %u ring queries handed to knn_heavy\n", L.level, nheavy);
+        if (nheavy > 0) GSX_CHECK(dispatch_heavy(ctx, L.w, a, L.n_ref, nheavy));
     }
-    if (trace) {
+    if (L.trace) {
         GSX_HIP(hipStreamSynchronize(ctx->stream));
         GridParams h3;
         GSX_HIP(hipMemcpy(&h3, gp, sizeof(GridParams), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[gsx] level %d: knn_ring %.3f ms for %u queries (%u exhaustive)\n", level,
+        fprintf(stderr, "[gsx] level %d: knn_ring %.3f ms for %u queries (%u exhaustive)\n", L.level,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ring0).count(), h3.fail_count,
                 h3.exhaustive_count);
     }
-
-    if (info) {
-        GridParams h2;
-        GSX_HIP(hipMemcpyAsync(&h2, gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
-        GSX_HIP(hipStreamSynchronize(ctx->stream));
-        if (h2.bad_input) return gsx_ctx_check(ctx);  // reports (and clears) the device flag
-        info->algo = GSX_KNN_GRID;
-        info->grid_dim[0] = h2.nx; info->grid_dim[1] = h2.ny; info->grid_dim[2] = h2.nz;
-        info->cell_size = h2.h;
-        info->n_cells = h2.ncells;
-        info->n_bricks = h2.nbricks;
-        info->n_fallback = h2.fail_count;
-        info->n_exhaustive = h2.exhaustive_count;
-        info->n_deferred_bricks = h2.deferred_count;
-        info->n_refined = (int64_t)w.refined_total;
-    } else if (have_hgp && hgp.bad_input && level == 0) {
-        return gsx_ctx_check(ctx);
-    }
     return 0;
+}
+
+// What the call reports (one more synchronisation, only when the caller asks).  The any-k path has no bricks and no ring:
+// every query is a "fallback" there, its cells are the unpadded nx ny nz, and it leaves bad input to the caller's check.
+static int level_info(GridLevel &L)
+{
+    gsx_ctx *ctx = L.ctx;
+    gsx_sor_info *info = L.info;
+    if (!info) return !L.anyk && L.have_hgp && L.hgp.bad_input && L.level == 0 ? gsx_ctx_check(ctx) : 0;
+    GridParams h2;
+    GSX_HIP(hipMemcpyAsync(&h2, L.gp, sizeof(GridParams), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    if (!L.anyk && h2.bad_input) return gsx_ctx_check(ctx);  // reports (and clears) the device flag
+    info->algo = GSX_KNN_GRID;
+    info->grid_dim[0] = h2.nx;
+    info->grid_dim[1] = h2.ny;
+    info->grid_dim[2] = h2.nz;
+    info->cell_size = h2.h;
+    info->n_cells = L.anyk ? (int64_t)h2.nx * h2.ny * h2.nz : (int64_t)h2.ncells;
+    info->n_bricks = L.anyk ? 0 : h2.nbricks;
+    info->n_fallback = L.anyk ? L.q_count : (int64_t)h2.fail_count;
+    info->n_exhaustive = h2.exhaustive_count;
+    info->n_deferred_bricks = L.anyk ? 0 : h2.deferred_count;
+    info->n_refined = L.anyk ? 0 : (int64_t)L.w.refined_total;
+    return 0;
+}
+
+static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *y, const float *z, int64_t stride,
+                          int64_t n_ref, int64_t q_begin, int64_t q_count, int k, float *mean_out, double *kth_out,
+                          gsx_sor_info *info, int share, int nshares, bool adaptive, float parent_h,
+                          int64_t ref_only_from, double h_hint, const SlabKnn *sk)
+{
+    KnnWs &w = ctx->ws[level];
+    if (level == 0) ctx->last_knn_algo = GSX_KNN_GRID;
+    w.refined_total = 0;
+    const bool anyk = k + 1 > 65;
+    if (k + 1 > ANYK_MAX) GSX_FAIL("sor: k=%d not supported (k must be <= %d)", k, ANYK_MAX - 1);
+    const bool slab = ref_only_from < n_ref;
+    if (anyk && (nshares > 1 || slab)) GSX_FAIL("sor: k=%d > 64 is served by the single-GPU path only", k);
+    const bool all = (q_begin == 0 && q_count == n_ref) || slab;
+    // (a share of the bricks -- the replicated multi-GPU exchange -- refines the deferred bricks of ITS share only)
+    adaptive = adaptive && !anyk && all && !slab && level + 1 < KNN_MAX_LEVELS;
+    GridLevel L{ctx, level, w, x, y, z, stride, n_ref, q_begin, q_count, k, mean_out, kth_out, info, share, nshares, parent_h,
+                ref_only_from, h_hint, sk, anyk, slab, all, adaptive, getenv("GSX_TRACE_LEVELS") != nullptr,
+                h_hint > 0.0 ? grid_refine_cell_cap(n_ref) : grid_cell_cap(n_ref),
+                ctx->grid_points_per_cell > 0.0 ? ctx->grid_points_per_cell : grid_pts_per_cell(k, n_ref)};
+    GSX_CHECK(level_reserve(L));
+    GSX_CHECK(level_grid_params(L));
+    bool done = false;
+    int rc = level_histogram(L, &done);
+    if (rc != 0 || done) return rc;
+    GSX_CHECK(level_bin(L));
+    BrickLaunch a{L.gp, L.refs, L.rstart, L.qpts, L.qstart, k, q_begin, mean_out, kth_out, w.faillist.as<unsigned>(),
+                  w.faillist.as<unsigned>() + std::max<int64_t>(q_count, 1),
+                  w.extraitems.as<uint2>(), w.deferred.as<unsigned>(), w.heavylist.as<unsigned>(), q_count, n_ref,
+                  L.plan ? w.finestart.as<unsigned>() : nullptr, L.plan ? w.bricklist.as<uint2>() : nullptr};
+    if (anyk) {
+        GSX_CHECK(level_anyk(L));
+        return level_info(L);
+    }
+    GSX_CHECK(dispatch_bricks(ctx, a, L.mfma_ok, ctx->phase2_net != 0));
+    if (L.adaptive) {
+        rc = level_refine(L, a, &done);
+        if (rc != 0 || done) return rc;
+    }
+    GSX_CHECK(level_ring_heavy(L, a));
+    return level_info(L);
 }
 
 int launch_knn_grid(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride, int64_t n_ref,

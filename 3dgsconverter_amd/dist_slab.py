@@ -315,7 +315,8 @@ class HipSlabBackend:
 
 # ------------------------------------------------------------------------------------------ the step
 def pts_per_cell(k: int, n: int = 0) -> float:
-    """the KNN grid's cell population for n reference points (csrc/sor_grid.hip: knn_grid_level)"""
+    """cells' population the slab plan estimates its halo width with: csrc/grid_policy.h, grid_pts_per_cell_base.  The KNN
+    grid's own rule (grid_pts_per_cell) adds caps for k = 17...20, 26...31 and 35...62 and is NOT this one."""
     m = max(2.0, 0.47 * (k + 1))
     fill = 54.0 if n >= 4_000_000 else 58.0
     for cells in (8, 4, 2, 1):

@@ -256,6 +256,31 @@ int gsx_sor_debug_work_queue(gsx_ctx *ctx, uint32_t *ctr, int64_t *items, int32_
 /* Diagnostic builds (-DGSX_WAVE_STAMPS) only: per-wave records of knn_brick (kernel 0) and knn_ring_fast (kernel 1) of the
  * context's last grid KNN call, 16 words each (csrc/sor_grid_params.h); tools/wave_stamps.py prints them. */
 int gsx_sor_debug_wave_stamps(gsx_ctx *ctx, int kernel, uint64_t *out, int64_t cap, int64_t *count);
+/* Tests: the grid's host-side decisions (csrc/grid_policy.h), callable without a GPU (tests/test_grid_policy_host.py).
+ * Points per cell for k neighbours and n reference points: tuned = 0 the base rule (what the slab plan estimates its halo
+ * with), 1 the rule the grid uses when the context's grid_points_per_cell is 0. */
+double gsx_sor_debug_points_per_cell(int k, int64_t n, int tuned);
+/* The deferred bricks `bricks[count]` (ids (bz * nby + by) * nbx + bx) rewritten group by group, largest group first;
+ * group_sizes[8] and *n_groups receive the groups. */
+int gsx_sor_debug_group_bricks(uint32_t *bricks, int64_t count, int nbx, int nby, int nbz, uint32_t *group_sizes, int32_t *n_groups);
+/* Sizing of one refinement round: the clip around the group's queries, the density probe's grid and the cell edge its histogram
+ * suggests (0 = the box-volume edge h_est stays). */
+typedef struct gsx_refine_sizing_in {
+    float    qb_lo[3], qb_hi[3];     /* box of the group's queries                                              */
+    uint32_t sub_queries, n_sub;     /* queries in the box; points gathered around them                          */
+    double   pts_per_cell;
+    float    parent_h;               /* cell edge of the level that deferred the bricks                          */
+    int32_t  adaptive;               /* the context's adaptive mode: 1 clips and probes                          */
+    uint32_t hist[32];               /* the probe's point-weighted histogram of log2(points per bin)             */
+    double   bin_vol;                /* volume of one probe bin                                                  */
+} gsx_refine_sizing_in;
+typedef struct gsx_refine_sizing_out {
+    int32_t nd3, probe_g;            /* axes with an extent; probe bins per axis (0: no probe)                   */
+    double  h_est, margin, cert;
+    float   clip_lo[3], clip_hi[3], r_cert;   /* r_cert = 0: no clipping                                         */
+    double  h_hint;                  /* 0 when probe_g is 0: the histogram is not looked at                      */
+} gsx_refine_sizing_out;
+int gsx_sor_debug_refine_sizing(const gsx_refine_sizing_in *in, gsx_refine_sizing_out *out);
 /* Debug / tests: the device functions beneath every mean distance (csrc/knn_common.h), called on the caller's inputs by
  * csrc/knn_probe.hip -- the same inline functions the KNN kernels call, not copies (tests/test_knn_epilogue_gpu.py).
  * Root: out[i] = the float64 square root of in[i] as knn_brick's and knn_anyk's epilogues take it (sqrt_rn_dist2; defined

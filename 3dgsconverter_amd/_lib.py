@@ -173,6 +173,7 @@ class SogScan(C.Structure):
 
 
 DENSITY_OK, DENSITY_EMPTY, DENSITY_HOST = range(3)
+DENSITY_STAGES = ("table", "init", "hook", "flatten", "reduce", "membership")   # GSX_DENSITY_STAGES
 SLAB_OK, SLAB_EMPTY, SLAB_NONFINITE, SLAB_SMALL_SHARD, SLAB_NO_STRUCTURE = range(5)
 COMM_F32_MAX, COMM_F32_SUM, COMM_I64_SUM, COMM_F64_MAX, COMM_I64_MIN = range(5)
 
@@ -290,6 +291,10 @@ SIGNATURES = {
     "gsx_density_voxels_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _I64, _I64, C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "gsx_density_mask_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _P, _I64, _P]),
     "gsx_density_filter_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _I64, _I, _P, _P, C.POINTER(DensityInfo)]),
+    "gsx_density_filter_large_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _I64, _I, _P, _P, C.POINTER(DensityInfo)]),
+    "gsx_voxel_clusters": (_I, [_P, _I64, _I, _P, C.POINTER(DensityInfo)]),
+    "gsx_voxel_clusters_dev": (_I, [_P, _P, _I64, _I, _P, C.POINTER(DensityInfo)]),
+    "gsx_density_stage_clocks": (_I, [_P, C.POINTER(_D)]),
     "gsx_density_hist_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _I64, C.POINTER(_I64), _P, _P]),
     "gsx_density_merge_dev": (_I, [_P, _P, _P, _I64, _I64, _I64, C.POINTER(_I64), C.POINTER(_I64), _P, _P]),
     "gsx_kmeans_lloyd_dev": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P]),
@@ -809,6 +814,20 @@ def density_mask(xyz, voxel_size: float, kept_keys: np.ndarray) -> np.ndarray:
           "gsx_density_mask")
     del keep
     return mask.view(np.bool_)
+
+
+def voxel_clusters(keys, keep_multicluster: bool):
+    """6-connected clusters of distinct absolute voxel keys and the keep rule (C ABI gsx_voxel_clusters)
+    -> dict(status, keep bool[M] in input order, kept_clusters, largest); status DENSITY_HOST: a tie for the largest cluster
+    without keep_multicluster -- ``keep`` decides nothing, take the host steps (processing/clusters.py)"""
+    lib = require_hip()
+    kk = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1, 3)
+    keep = np.zeros(len(kk), dtype=np.uint8)
+    info = DensityInfo()
+    check(lib.gsx_voxel_clusters(kk.ctypes.data, len(kk), 1 if keep_multicluster else 0, keep.ctypes.data, C.byref(info)),
+          "gsx_voxel_clusters")
+    return {"status": int(info.status), "keep": keep.view(np.bool_), "kept_clusters": int(info.kept_clusters),
+            "largest": int(info.largest)}
 
 
 def kmeans_lloyd(data: np.ndarray, init_centroids: np.ndarray, max_iter: int):
@@ -2487,6 +2506,12 @@ class Context:
         check(self.lib.gsx_ctx_get_timing(self.handle, int(slot), C.byref(n), C.byref(ms)), "gsx_ctx_get_timing")
         return int(n.value), float(ms.value)
 
+    def density_stage_clocks(self):
+        """stage clocks (ms) of this context's last density_filter_large / voxel_clusters call while timing was on"""
+        ms = (C.c_double * len(DENSITY_STAGES))()
+        check(self.lib.gsx_density_stage_clocks(self.handle, ms), "gsx_density_stage_clocks")
+        return dict(zip(DENSITY_STAGES, (float(v) for v in ms)))
+
     def alloc(self, nbytes: int) -> DeviceArray:
         return DeviceArray(self, nbytes)
 
@@ -2931,7 +2956,17 @@ class DeviceChain:
 
     def density_filter(self, voxel_size: float, min_points: int, keep_multicluster: bool):
         """the whole density filter on the device (gsx_density_filter_dev) -> dict(status, n_unique, kept_clusters, largest,
-        left: rows after the compaction) ; status DENSITY_HOST: nothing was applied, take the host path"""
+        left: rows after the compaction) ; status DENSITY_HOST (more than 1024 dense voxels, or a tie for the largest cluster):
+        nothing was applied, take density_filter_large"""
+        return self._density_filter("gsx_density_filter_dev", voxel_size, min_points, keep_multicluster)
+
+    def density_filter_large(self, voxel_size: float, min_points: int, keep_multicluster: bool):
+        """density_filter for any number of dense voxels (gsx_density_filter_large_dev: union-find over the voxel table), the same
+        dict; status DENSITY_HOST only for a tie for the largest cluster without keep_multicluster: nothing was applied, take the
+        host path"""
+        return self._density_filter("gsx_density_filter_large_dev", voxel_size, min_points, keep_multicluster)
+
+    def _density_filter(self, entry: str, voxel_size: float, min_points: int, keep_multicluster: bool):
         if self._box is None:     # box of the rows as they are now: a superset of whatever survives later filters
             lo, hi = self._bbox_dev()
             self._box = np.array(list(lo) + list(hi), dtype=np.float32)
@@ -2939,9 +2974,8 @@ class DeviceChain:
                 self._pristine_box = self._box
         info = DensityInfo()
         x, y, z, st = self._xyz()
-        check(self.ctx.lib.gsx_density_filter_dev(self.ctx.handle, x, y, z, st, self.n, float(voxel_size), int(min_points),
-                                                  1 if keep_multicluster else 0, self._box.ctypes.data, self.mask.ptr, C.byref(info)),
-              "gsx_density_filter_dev")
+        check(getattr(self.ctx.lib, entry)(self.ctx.handle, x, y, z, st, self.n, float(voxel_size), int(min_points),
+                                           1 if keep_multicluster else 0, self._box.ctypes.data, self.mask.ptr, C.byref(info)), entry)
         out = {"status": int(info.status), "n_unique": int(info.n_unique), "kept_clusters": int(info.kept_clusters),
                "largest": int(info.largest), "left": None}
         if info.status == DENSITY_OK:

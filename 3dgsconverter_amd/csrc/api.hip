@@ -96,6 +96,9 @@ int density_hist_dev(gsx_ctx *, const float *, const float *, const float *, int
 int density_merge_dev(gsx_ctx *, const int64_t *, const int64_t *, int64_t, int64_t, int64_t, int64_t *, int64_t *, int64_t *, int64_t *);
 int density_filter_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, int64_t, int, const float *,
                        uint8_t *, gsx_density_info *);
+int density_filter_large_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, int64_t, int, const float *,
+                             uint8_t *, gsx_density_info *);
+int voxel_clusters_dev(gsx_ctx *, const int64_t *, int64_t, int, uint8_t *, gsx_density_info *);
 int density_mask_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, const int64_t *,
                      int64_t, uint8_t *);
 int kmeans_lloyd_dev(gsx_ctx *, const float *, int64_t, int, int, int, float *, int32_t *);
@@ -654,6 +657,43 @@ int gsx_density_filter_dev(gsx_ctx *c, const float *x, const float *y, const flo
     if (n <= 0) GSX_FAIL("gsx_density_filter_dev: empty cloud");
     GSX_HIP(hipSetDevice(c->device));
     return density_filter_dev(c, x, y, z, stride, n, voxel_size, min_points, keep_multicluster, box6, mask_out_dev, info);
+}
+
+int gsx_density_filter_large_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n, double voxel_size,
+                                 int64_t min_points, int keep_multicluster, const float *box6, uint8_t *mask_out_dev, gsx_density_info *info)
+{
+    if (!c || !x || !y || !z || !mask_out_dev || !info) GSX_FAIL("gsx_density_filter_large_dev: null argument");
+    if (n <= 0) GSX_FAIL("gsx_density_filter_large_dev: empty cloud");
+    GSX_HIP(hipSetDevice(c->device));
+    return density_filter_large_dev(c, x, y, z, stride, n, voxel_size, min_points, keep_multicluster, box6, mask_out_dev, info);
+}
+
+int gsx_voxel_clusters_dev(gsx_ctx *c, const int64_t *keys3, int64_t m, int keep_multicluster, uint8_t *keep_out, gsx_density_info *info)
+{
+    if (!c || !info || m < 0 || (m > 0 && (!keys3 || !keep_out))) GSX_FAIL("gsx_voxel_clusters_dev: null argument");
+    if (m > (1ll << 30)) GSX_FAIL("gsx_voxel_clusters_dev: too many keys for the voxel table");
+    if (m == 0) {
+        *info = gsx_density_info{};
+        info->status = GSX_DENSITY_EMPTY;
+        return 0;
+    }
+    GSX_HIP(hipSetDevice(c->device));
+    return voxel_clusters_dev(c, keys3, m, keep_multicluster, keep_out, info);
+}
+
+int gsx_voxel_clusters(const int64_t *keys3, int64_t m, int keep_multicluster, uint8_t *keep_out, gsx_density_info *info)
+{
+    std::lock_guard<std::mutex> lk(g_host_mu);
+    gsx_ctx *c;
+    GSX_CHECK(host_ctx(&c));
+    return gsx_voxel_clusters_dev(c, keys3, m, keep_multicluster, keep_out, info);
+}
+
+int gsx_density_stage_clocks(gsx_ctx *c, double *ms_out)
+{
+    if (!c || !ms_out) GSX_FAIL("gsx_density_stage_clocks: null argument");
+    for (int i = 0; i < GSX_DENSITY_STAGES; ++i) ms_out[i] = c->density_stage_ms[i];
+    return 0;
 }
 
 int gsx_density_mask_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n,

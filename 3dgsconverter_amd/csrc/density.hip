@@ -5,8 +5,10 @@
 //   data_processor.py:43      np.unique(keys, axis=0, return_counts=True)   -> voxel_count_kernel
 //   data_processor.py:48-52   dense = counts >= min_points                  -> voxel_collect_kernel
 //   data_processor.py:111-114 mask = voxel(point) in kept clusters          -> voxel_mask_kernel
-// The 6-connected BFS over the (<= ~1000) dense voxels stays on the host
-// (3dgsconverter_amd/processing/clusters.py), as SURVEY.md 7.6 plans.
+//   data_processor.py:57-112  6-connected clusters of the dense voxels, keep rule -> voxel_cluster_kernel (<= 1024 dense voxels),
+//                             cc_*_kernel (any number: union-find over the table)
+// Only a tie for the largest cluster goes back to the host (3dgsconverter_amd/processing/clusters.py rebuilds the reference's
+// python set, whose iteration order decides it).
 //
 // Only counts per voxel and membership reach the mask, never np.unique's order, so the
 // lexicographic sort (the reference's O(N log N) hot spot) is replaced by an open-addressing
@@ -1089,6 +1091,468 @@ int density_filter_dev(gsx_ctx *c, const float *x, const float *y, const float *
     info->n_kept_voxels = h.n_kept_voxels;
     info->kept_clusters = h.kept_clusters;
     info->largest = h.largest;
+    return 0;
+}
+
+// ---- clusters of ANY number of dense voxels (gsx_density_filter_large_dev, gsx_voxel_clusters): data_processor.py:57-112 on the
+// open-addressing table itself -- no list of the dense voxels, no sort, no LDS cap.  Every dense SLOT is a node of a lock-free
+// union-find forest (`parent`, one word per slot; CC_NONE = not dense): the hook kernel probes the table for the three +1
+// neighbours of every dense voxel and unites the two trees by a compare-and-swap on the larger root, so parent[s] <= s always
+// holds, every walk towards a root strictly descends and ends, and a compare-and-swap fails only because another thread's
+// succeeded.  The number of launches is fixed (init, hook, flatten + sizes, largest, counts, membership) whatever the diameter
+// of a cluster; no workgroup waits for another.
+constexpr unsigned CC_NONE = 0xffffffffu;
+
+struct CcOut {               // device-side result block of the large path
+    unsigned n_unique, n_dense, largest, ties, kept_clusters, n_kept_voxels;
+    unsigned oob, pad;       // oob: see ClusterOut
+};
+
+__device__ __forceinline__ unsigned cc_load(const unsigned *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x; halves the path on the way (any ancestor is a valid parent, and atomicMin only ever moves a pointer down)
+__device__ __forceinline__ unsigned cc_find(unsigned *parent, unsigned x)
+{
+    for (;;) {
+        const unsigned p = cc_load(&parent[x]);
+        if (p == x) return x;
+        const unsigned g = cc_load(&parent[p]);
+        if (g == p) return p;
+        atomicMin(&parent[x], g);
+        x = g;
+    }
+}
+
+__device__ __forceinline__ void cc_unite(unsigned *parent, unsigned a, unsigned b)
+{
+    for (;;) {
+        a = cc_find(parent, a);
+        b = cc_find(parent, b);
+        if (a == b) return;
+        const unsigned hi = a > b ? a : b, lo = a > b ? b : a;
+        const unsigned old = atomicCAS(&parent[hi], hi, lo);
+        if (old == hi) return;
+        a = old;   // hi was hooked by somebody else in the meantime: on from where it points now
+        b = lo;
+    }
+}
+
+// slot of `key`, or CC_NONE.  The table is at most half full, so the probe ends at an empty slot; a wide slot whose second word
+// is still 0 matches nothing
+template <bool WIDE>
+__device__ __forceinline__ unsigned cc_probe(const unsigned long long *__restrict__ tkeys, const unsigned *__restrict__ tkb,
+                                             unsigned tmask, const VKey &key)
+{
+    unsigned h = hash_vkey<WIDE>(key) & tmask;
+    for (unsigned step = 0; step <= tmask; ++step) {
+        const unsigned long long ka = tkeys[h];
+        if (ka == 0ull) return CC_NONE;
+        if (ka == key.a && (!WIDE || tkb[h] == key.b)) return h;
+        h = (h + 1) & tmask;
+    }
+    return CC_NONE;
+}
+
+__global__ __launch_bounds__(256) void cc_init_kernel(const unsigned long long *__restrict__ tkeys, const unsigned *__restrict__ tcnt,
+                                                      unsigned tsize, unsigned min_points, unsigned *__restrict__ parent,
+                                                      unsigned *__restrict__ size, CcOut *__restrict__ out)
+{
+    unsigned uniq = 0, dense = 0;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) {
+        const unsigned c = tcnt[i];
+        const bool occupied = tkeys[i] != 0ull && c != 0u;   // c == 0: a wide slot that was claimed but never completed
+        const bool is_dense = occupied && c >= min_points;
+        uniq += occupied;
+        dense += is_dense;
+        parent[i] = is_dense ? i : CC_NONE;
+        size[i] = 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        uniq += __shfl_xor(uniq, off);
+        dense += __shfl_xor(dense, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (uniq) atomicAdd(&out->n_unique, uniq);
+        if (dense) atomicAdd(&out->n_dense, dense);
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void cc_hook_kernel(const unsigned long long *__restrict__ tkeys, const unsigned *__restrict__ tkb,
+                                                      unsigned tsize, VoxelFrame f, unsigned *parent)
+{
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) {
+        if (cc_load(&parent[i]) == CC_NONE) continue;
+        const unsigned long long k = tkeys[i] - 1ull;
+        unsigned c[3];
+        if (WIDE) {
+            c[0] = (unsigned)(k >> 32);
+            c[1] = (unsigned)(k & 0xffffffffull);
+            c[2] = tkb[i] - 1u;
+        } else {
+            c[0] = (unsigned)(k >> 42);
+            c[1] = (unsigned)((k >> 21) & 0x1fffffu);
+            c[2] = (unsigned)(k & 0x1fffffu);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            // the +1 neighbour on axis a (data_processor.py:67-68; the -1 edges are the other voxel's +1 edges); one past the
+            // frame's face is no voxel, and packed it would carry into the next field
+            if (c[a] + 1u >= (unsigned)f.dim[a]) continue;
+            unsigned t[3] = {c[0], c[1], c[2]};
+            t[a] += 1u;
+            VKey nk;
+            if (WIDE) {
+                nk.a = (((unsigned long long)t[0] << 32) | (unsigned long long)t[1]) + 1ull;
+                nk.b = t[2] + 1u;
+            } else {
+                nk.a = (((unsigned long long)t[0] << 42) | ((unsigned long long)t[1] << 21) | (unsigned long long)t[2]) + 1ull;
+                nk.b = 0u;
+            }
+            const unsigned j = cc_probe<WIDE>(tkeys, tkb, tsize - 1u, nk);
+            if (j == CC_NONE || cc_load(&parent[j]) == CC_NONE) continue;
+            cc_unite(parent, i, j);
+        }
+    }
+}
+
+// parent[s] = root(s); size[root] = voxels of the cluster (data_processor.py:95 sorts by it).  A scene is mostly one cluster:
+// one global add per voxel would queue hundreds of thousands of atomics on one word (2.7 of the call's 4.2 ms at 710 000 dense
+// voxels, profiles/density_components_10m.txt), so every workgroup first adds up its slots per root in a small LDS table, the way
+// voxel_count_kernel aggregates its tile, and flushes one global add per (workgroup, root)
+constexpr int CC_LDS = 1024;
+
+__global__ __launch_bounds__(256) void cc_flatten_kernel(unsigned tsize, unsigned *parent, unsigned *__restrict__ size)
+{
+    __shared__ unsigned lroot[CC_LDS];   // CC_NONE = free
+    __shared__ unsigned lcnt[CC_LDS];
+    for (int i = threadIdx.x; i < CC_LDS; i += 256) {
+        lroot[i] = CC_NONE;
+        lcnt[i] = 0u;
+    }
+    __syncthreads();
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) {
+        if (cc_load(&parent[i]) == CC_NONE) continue;
+        const unsigned root = cc_find(parent, i);
+        __hip_atomic_store(&parent[i], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned h = (root * 0x9e3779b1u) >> 22;   // 10 bits: CC_LDS slots
+        bool done = false;
+        for (int probe = 0; probe < 4 && !done; ++probe) {
+            unsigned old = lroot[h];
+            if (old == CC_NONE) old = atomicCAS(&lroot[h], CC_NONE, root);
+            if (old == CC_NONE || old == root) {
+                atomicAdd(&lcnt[h], 1u);
+                done = true;
+            } else {
+                h = (h + 1) & (CC_LDS - 1);
+            }
+        }
+        if (!done) atomicAdd(&size[root], 1u);   // LDS table crowded (dust of many small clusters): straight to HBM
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CC_LDS; i += 256)
+        if (lcnt[i]) atomicAdd(&size[lroot[i]], lcnt[i]);
+}
+
+__global__ __launch_bounds__(256) void cc_largest_kernel(const unsigned *__restrict__ parent, const unsigned *__restrict__ size,
+                                                         unsigned tsize, CcOut *__restrict__ out)
+{
+    unsigned m = 0;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x)
+        if (parent[i] == i) m = max(m, size[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor(m, off));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&out->largest, m);
+}
+
+// keep rule (data_processor.py:96-106): all clusters of at least 5 % of the largest, or the largest alone
+__device__ __forceinline__ bool cc_keeps(unsigned size, unsigned largest, int keep_multi)
+{
+    return (double)size >= (keep_multi ? (double)largest * 0.05 : (double)largest);
+}
+
+__global__ __launch_bounds__(256) void cc_counts_kernel(const unsigned *__restrict__ parent, const unsigned *__restrict__ size,
+                                                        unsigned tsize, int keep_multi, CcOut *__restrict__ out)
+{
+    const unsigned largest = out->largest;
+    unsigned ties = 0, kept = 0, voxels = 0;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) {
+        if (parent[i] != i) continue;
+        const unsigned s = size[i];
+        ties += s == largest;
+        if (cc_keeps(s, largest, keep_multi)) {
+            ++kept;
+            voxels += s;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ties += __shfl_xor(ties, off);
+        kept += __shfl_xor(kept, off);
+        voxels += __shfl_xor(voxels, off);
+    }
+    if ((threadIdx.x & 63) == 0 && kept + ties) {
+        atomicAdd(&out->ties, ties);
+        atomicAdd(&out->kept_clusters, kept);
+        atomicAdd(&out->n_kept_voxels, voxels);
+    }
+}
+
+// membership (data_processor.py:111-114) straight from the table: the point's slot is dense and its cluster passes the floor.
+// A tie without keep_multicluster is the host's to break: nothing is written
+template <bool WIDE>
+__global__ __launch_bounds__(256) void cc_member_kernel(const float *__restrict__ x, const float *__restrict__ y,
+                                                        const float *__restrict__ z, int64_t stride, int64_t n, float voxel,
+                                                        VoxelFrame f, const unsigned long long *__restrict__ tkeys,
+                                                        const unsigned *__restrict__ tkb, unsigned tmask,
+                                                        const unsigned *__restrict__ parent, const unsigned *__restrict__ size,
+                                                        int keep_multi, const CcOut *__restrict__ out, uint8_t *__restrict__ mask)
+{
+    const unsigned largest = out->largest;
+    if (!keep_multi && out->ties > 1u) return;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int kx = voxel_key(x[i * stride], voxel), ky = voxel_key(y[i * stride], voxel), kz = voxel_key(z[i * stride], voxel);
+        bool hit = false;
+        // (a row outside a caller's box: the count kernel has raised `oob` and the call is repeated; it must not wrap here either)
+        if ((unsigned)(kx - f.kmin[0]) < (unsigned)f.dim[0] && (unsigned)(ky - f.kmin[1]) < (unsigned)f.dim[1] &&
+            (unsigned)(kz - f.kmin[2]) < (unsigned)f.dim[2]) {
+            const unsigned s = cc_probe<WIDE>(tkeys, tkb, tmask, pack_key<WIDE>(f, kx, ky, kz));
+            if (s != CC_NONE) {
+                const unsigned root = parent[s];
+                hit = root != CC_NONE && cc_keeps(size[root], largest, keep_multi);
+            }
+        }
+        mask[i] = hit ? 1 : 0;
+    }
+}
+
+// gsx_voxel_clusters: distinct absolute keys -> table (merge_insert_kernel's insertion, one point per key; kmin64 is subtracted
+// in 64 bits, the frame handed to pack_key starts at 0)
+template <bool WIDE>
+__global__ __launch_bounds__(256) void cc_insert_keys_kernel(const long long *__restrict__ keys3, int64_t m, const long long *__restrict__ kmin64,
+                                                             VoxelFrame f, unsigned long long *__restrict__ tkeys,
+                                                             unsigned *__restrict__ tkb, unsigned *__restrict__ tcnt, unsigned tmask)
+{
+    const long long m0 = kmin64[0], m1 = kmin64[1], m2 = kmin64[2];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const VKey key = pack_key<WIDE>(f, (int)(keys3[3 * i] - m0), (int)(keys3[3 * i + 1] - m1), (int)(keys3[3 * i + 2] - m2));
+        table_add<WIDE>(tkeys, tkb, tcnt, tmask, key, 1u);
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void cc_keep_keys_kernel(const long long *__restrict__ keys3, int64_t m, const long long *__restrict__ kmin64,
+                                                           VoxelFrame f, const unsigned long long *__restrict__ tkeys,
+                                                           const unsigned *__restrict__ tkb, unsigned tmask,
+                                                           const unsigned *__restrict__ parent, const unsigned *__restrict__ size,
+                                                           int keep_multi, const CcOut *__restrict__ out, uint8_t *__restrict__ keep)
+{
+    const unsigned largest = out->largest;
+    const long long m0 = kmin64[0], m1 = kmin64[1], m2 = kmin64[2];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const VKey key = pack_key<WIDE>(f, (int)(keys3[3 * i] - m0), (int)(keys3[3 * i + 1] - m1), (int)(keys3[3 * i + 2] - m2));
+        const unsigned s = cc_probe<WIDE>(tkeys, tkb, tmask, key);
+        const unsigned root = s != CC_NONE ? parent[s] : CC_NONE;
+        keep[i] = (root != CC_NONE && cc_keeps(size[root], largest, keep_multi)) ? 1 : 0;
+    }
+}
+
+// stage clocks of the large path for tools/probe_density.py (only while the context's timing is on)
+struct CcClock {
+    gsx_ctx *c;
+    hipEvent_t ev[GSX_DENSITY_STAGES + 1];
+    int n = 0;
+    explicit CcClock(gsx_ctx *ctx) : c(ctx) {}
+    ~CcClock()
+    {
+        for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]);
+    }
+    int mark()
+    {
+        if (!c->timing || n > GSX_DENSITY_STAGES) return 0;
+        GSX_HIP(hipEventCreate(&ev[n]));
+        ++n;
+        GSX_HIP(hipEventRecord(ev[n - 1], c->stream));
+        return 0;
+    }
+    int read()   // after the stream has been synchronised
+    {
+        for (int i = 0; i < GSX_DENSITY_STAGES; ++i) {
+            float ms = 0.f;
+            if (i + 1 < n) GSX_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            c->density_stage_ms[i] = ms;
+        }
+        return 0;
+    }
+};
+
+// kernels 1-4 on a filled table; parent | size live in scratch3
+static int cc_components(gsx_ctx *c, const VoxelFrame &hvf, const VoxTable &t, int64_t min_points, int keep_multi, CcOut *dco,
+                         unsigned **parent_out, unsigned **size_out, CcClock &clk)
+{
+    const unsigned tsize = (unsigned)t.tsize;
+    GSX_CHECK(c->scratch3.reserve(2 * sizeof(unsigned) * (size_t)t.tsize + 64));
+    unsigned *parent = c->scratch3.as<unsigned>(), *size = parent + t.tsize;
+    const unsigned mp = (unsigned)std::min<int64_t>(std::max<int64_t>(min_points, 0), 0xffffffffll);
+    const dim3 grid(blocks_for(c, (int64_t)t.tsize, 1024)), block(256);
+    hipLaunchKernelGGL(cc_init_kernel, grid, block, 0, c->stream, t.tkeys, t.tcnt, tsize, mp, parent, size, dco);
+    GSX_CHECK(clk.mark());
+    if (t.wide)
+        hipLaunchKernelGGL((cc_hook_kernel<true>), grid, block, 0, c->stream, t.tkeys, t.tkb, tsize, hvf, parent);
+    else
+        hipLaunchKernelGGL((cc_hook_kernel<false>), grid, block, 0, c->stream, t.tkeys, t.tkb, tsize, hvf, parent);
+    GSX_CHECK(clk.mark());
+    hipLaunchKernelGGL(cc_flatten_kernel, grid, block, 0, c->stream, tsize, parent, size);
+    GSX_CHECK(clk.mark());
+    hipLaunchKernelGGL(cc_largest_kernel, grid, block, 0, c->stream, parent, size, tsize, dco);
+    hipLaunchKernelGGL(cc_counts_kernel, grid, block, 0, c->stream, parent, size, tsize, keep_multi, dco);
+    GSX_CHECK(clk.mark());
+    GSX_HIP(hipGetLastError());
+    *parent_out = parent;
+    *size_out = size;
+    return 0;
+}
+
+static void cc_fill_info(const CcOut &h, int keep_multi, gsx_density_info *info)
+{
+    info->n_unique = h.n_unique;
+    info->n_dense = h.n_dense;
+    info->n_kept_voxels = info->kept_clusters = info->largest = 0;
+    if (h.n_dense == 0) {
+        info->status = GSX_DENSITY_EMPTY;
+    } else if (!keep_multi && h.ties > 1u) {   // which of the equally large clusters survives is the reference's set-iteration order
+        info->status = GSX_DENSITY_HOST;
+    } else {
+        info->status = GSX_DENSITY_OK;
+        info->n_kept_voxels = h.n_kept_voxels;
+        info->kept_clusters = h.kept_clusters;
+        info->largest = h.largest;
+    }
+}
+
+// the frame of a caller's box with voxel_frame_kernel's arithmetic, as density_filter_dev derives it
+static bool frame_from_box(const float *box6, float voxel, VoxelFrame *hvf)
+{
+    hvf->ok = 1;
+    hvf->pad = 0;
+    for (int a = 0; a < 3; ++a) {
+        const float lo = floorf(box6[a] / voxel), hi = floorf(box6[3 + a] / voxel);
+        if (!(fabsf(lo) < 1.0e9f) || !(fabsf(hi) < 1.0e9f) || !(box6[a] <= box6[3 + a])) return false;
+        const long long d = (long long)hi - (long long)lo + 1;
+        if (d > (1 << 21) - 1) return false;
+        hvf->kmin[a] = (int)lo;
+        hvf->dim[a] = (int)d;
+    }
+    return true;
+}
+
+int density_filter_large_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n, double voxel_size,
+                             int64_t min_points, int keep_multi, const float *box6, uint8_t *mask_dev, gsx_density_info *info)
+{
+    const float voxel = (float)voxel_size;
+    if (!(voxel > 0.0f)) GSX_FAIL("density: voxel_size must be > 0");
+    GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
+    CcClock clk(c);
+    GSX_CHECK(clk.mark());
+    GSX_CHECK(c->scratch5.reserve(sizeof(VoxelFrame) + sizeof(CcOut) + 64));
+    VoxelFrame *dvf = c->scratch5.as<VoxelFrame>();
+    CcOut *dco = reinterpret_cast<CcOut *>(c->scratch5.as<char>() + 64);
+    VoxelFrame hvf;
+    const bool from_box = box6 != nullptr && frame_from_box(box6, voxel, &hvf);
+    if (from_box)
+        GSX_HIP(hipMemcpyAsync(dvf, &hvf, sizeof(hvf), hipMemcpyHostToDevice, c->stream));
+    else
+        GSX_CHECK(compute_frame(c, x, y, z, stride, n, voxel, dvf, &hvf));
+    VoxTable t;
+    GSX_CHECK(alloc_table(c, hvf, n, 64, &t));
+    GSX_HIP(hipMemsetAsync(dco, 0, sizeof(CcOut), c->stream));
+    GSX_CHECK(count_points(c, x, y, z, stride, n, voxel, dvf, t, from_box ? &dco->oob : nullptr, &hvf));
+    GSX_CHECK(clk.mark());
+    unsigned *parent, *size;
+    GSX_CHECK(cc_components(c, hvf, t, min_points, keep_multi, dco, &parent, &size, clk));
+    if (t.wide)
+        hipLaunchKernelGGL((cc_member_kernel<true>), dim3(blocks_for(c, n, 1024)), dim3(256), 0, c->stream, x, y, z, stride, n, voxel, hvf,
+                           t.tkeys, t.tkb, (unsigned)(t.tsize - 1), parent, size, keep_multi, dco, mask_dev);
+    else
+        hipLaunchKernelGGL((cc_member_kernel<false>), dim3(blocks_for(c, n, 1024)), dim3(256), 0, c->stream, x, y, z, stride, n, voxel, hvf,
+                           t.tkeys, t.tkb, (unsigned)(t.tsize - 1), parent, size, keep_multi, dco, mask_dev);
+    GSX_HIP(hipGetLastError());
+    GSX_CHECK(clk.mark());
+    GSX_CHECK(timing_end(c, GSX_T_DENSITY));
+    CcOut h;
+    GSX_HIP(hipMemcpyAsync(&h, dco, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipStreamSynchronize(c->stream));      // the call's one synchronisation
+    if (from_box && h.oob)   // the box was not a superset of the rows: once more with the frame of the rows themselves
+        return density_filter_large_dev(c, x, y, z, stride, n, voxel_size, min_points, keep_multi, nullptr, mask_dev, info);
+    if (c->timing) GSX_CHECK(clk.read());
+    cc_fill_info(h, keep_multi, info);
+    return 0;
+}
+
+int voxel_clusters_dev(gsx_ctx *c, const int64_t *keys3, int64_t m, int keep_multi, uint8_t *keep_out, gsx_density_info *info)
+{
+    long long kmin[3], kmax[3];
+    for (int a = 0; a < 3; ++a) kmin[a] = kmax[a] = keys3[a];
+    for (int64_t i = 1; i < m; ++i)
+        for (int a = 0; a < 3; ++a) {
+            kmin[a] = std::min<long long>(kmin[a], keys3[3 * i + a]);
+            kmax[a] = std::max<long long>(kmax[a], keys3[3 * i + a]);
+        }
+    VoxelFrame hvf;
+    hvf.ok = 1;
+    hvf.pad = 0;
+    for (int a = 0; a < 3; ++a) {
+        // (unsigned difference: keys at both ends of int64 must not overflow the subtraction)
+        const unsigned long long span = (unsigned long long)kmax[a] - (unsigned long long)kmin[a];
+        if (span >= (1ull << 31) - 1) GSX_FAIL("gsx_voxel_clusters: the keys span 2^31 voxels or more on an axis");
+        if (span + 1 > (1ull << 21) - 1) hvf.ok = 2;
+        hvf.kmin[a] = 0;
+        hvf.dim[a] = (int)(span + 1);
+    }
+    GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
+    CcClock clk(c);
+    GSX_CHECK(clk.mark());
+    const size_t key_bytes = sizeof(long long) * 3 * (size_t)m;
+    GSX_CHECK(c->scratch.reserve(key_bytes + 64));
+    GSX_CHECK(c->scratch4.reserve((size_t)m + 16));
+    GSX_CHECK(c->scratch5.reserve(64 + sizeof(CcOut) + 64));
+    long long *dk = c->scratch.as<long long>();
+    long long *dmin = c->scratch5.as<long long>();
+    CcOut *dco = reinterpret_cast<CcOut *>(c->scratch5.as<char>() + 64);
+    uint8_t *dkeep = c->scratch4.as<uint8_t>();
+    GSX_HIP(hipMemcpyAsync(dk, keys3, key_bytes, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(hipMemcpyAsync(dmin, kmin, sizeof(kmin), hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(hipMemsetAsync(dco, 0, sizeof(CcOut), c->stream));
+    VoxTable t;
+    GSX_CHECK(alloc_table(c, hvf, m, 64, &t));
+    const dim3 grid(blocks_for(c, m, 1024)), block(256);
+    const unsigned tmask = (unsigned)(t.tsize - 1);
+    if (t.wide)
+        hipLaunchKernelGGL((cc_insert_keys_kernel<true>), grid, block, 0, c->stream, dk, m, dmin, hvf, t.tkeys, t.tkb, t.tcnt, tmask);
+    else
+        hipLaunchKernelGGL((cc_insert_keys_kernel<false>), grid, block, 0, c->stream, dk, m, dmin, hvf, t.tkeys, t.tkb, t.tcnt, tmask);
+    GSX_CHECK(clk.mark());
+    unsigned *parent, *size;
+    GSX_CHECK(cc_components(c, hvf, t, 1, keep_multi, dco, &parent, &size, clk));
+    if (t.wide)
+        hipLaunchKernelGGL((cc_keep_keys_kernel<true>), grid, block, 0, c->stream, dk, m, dmin, hvf, t.tkeys, t.tkb, tmask, parent, size,
+                           keep_multi, dco, dkeep);
+    else
+        hipLaunchKernelGGL((cc_keep_keys_kernel<false>), grid, block, 0, c->stream, dk, m, dmin, hvf, t.tkeys, t.tkb, tmask, parent, size,
+                           keep_multi, dco, dkeep);
+    GSX_HIP(hipGetLastError());
+    GSX_CHECK(clk.mark());
+    GSX_CHECK(timing_end(c, GSX_T_DENSITY));
+    CcOut h;
+    GSX_HIP(hipMemcpyAsync(&h, dco, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipMemcpyAsync(keep_out, dkeep, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipStreamSynchronize(c->stream));      // (the host key array, pageable memory, must outlive its copy too)
+    if (c->timing) GSX_CHECK(clk.read());
+    cc_fill_info(h, keep_multi, info);
     return 0;
 }
 

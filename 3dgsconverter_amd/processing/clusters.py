@@ -1,8 +1,11 @@
 """Host side of the voxel-density filter: connected components of the dense voxels.
 
-Mirrors data_processor.py:57-106.  At most 100/threshold% voxels are dense (<= 1000 for
-sensitivity 0, <= 181 for 0.5), so this stays on the host exactly like the reference; the
-O(N) parts (voxel keys, occupancy counts, per-point membership) run on the GPU.
+Mirrors data_processor.py:57-106.  The device finds the clusters itself -- up to 1024 dense
+voxels inside gsx_density_filter_dev, any number in gsx_density_filter_large_dev and
+gsx_voxel_clusters (csrc/density.hip) -- so these functions run in two places only: the eager
+class at 1024 dense voxels or fewer (<= 1000 for sensitivity 0, <= 181 for 0.5: what the
+reference's own thresholds give), and wherever two clusters tie for the largest, which the
+device hands back undecided (below).  dist_density.py's step 5 still calls them on every rank.
 
 Tie-break parity: when two clusters have the same voxel count and keep_multicluster is
 False the reference keeps whichever its python ``set`` iteration meets first (the sort at

@@ -31,6 +31,7 @@ from . import clusters as _clusters
 
 
 XYZ = ("x", "y", "z")
+DEVICE_CLUSTERS_ABOVE = 1024  # eager density filter: more dense voxels than this are clustered by gsx_voxel_clusters, fewer by clusters.py
 MAX_SOR_K = 2047  # include/gsx_hip.h: 1 <= k <= 64 on the fast kernels, 65..2047 through the exact list-free kernel (slow)
 
 
@@ -281,12 +282,20 @@ class DataProcessor:
                 status_print("Warning: Density filter removed all points.")
                 self.data = self.data[:0]
                 return self.data
-            comps = _clusters.connected_clusters(map(tuple, occ["dense_keys"].tolist()))
-            kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
-            if not kept:
-                self.data = self.data[:0]
-                return self.data
-            kept_keys = np.array(sorted(kept), dtype=np.int64).reshape(-1, 3)
+            # more dense voxels than the reference's own thresholds can give (--density_threshold near 0: every occupied voxel
+            # is dense): their clusters on the device too; only a tie for the largest comes back for the host steps
+            res = (_lib.voxel_clusters(occ["dense_keys"], bool(keep_multicluster))
+                   if len(occ["dense_keys"]) > DEVICE_CLUSTERS_ABOVE else None)
+            if res is not None and res["status"] == _lib.DENSITY_OK:
+                kept_keys = occ["dense_keys"][res["keep"]]      # (np.unique's row order already)
+                kept_clusters, max_len = res["kept_clusters"], res["largest"]
+            else:
+                comps = _clusters.connected_clusters(map(tuple, occ["dense_keys"].tolist()))
+                kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
+                if not kept:
+                    self.data = self.data[:0]
+                    return self.data
+                kept_keys = np.array(sorted(kept), dtype=np.int64).reshape(-1, 3)
             mask = _lib.density_mask(cols, float(voxel_size), kept_keys)
         self.data = _lib.host_compact_rows(vertices, mask)  # reference :114
         status_print(f"Density Filter: Kept {kept_clusters} clusters (largest: {max_len} voxels).")
@@ -298,10 +307,12 @@ class DataProcessor:
         ch = self._chain_for(self._data)
         n = ch.n
         min_points = int(n * (threshold_percentage / 100.0))  # reference :48
-        # the whole filter in one device call (occupancy, clusters of the dense voxels, keep rule, mask, compaction); only a
-        # tie for the largest cluster -- the reference's set-iteration order decides it -- or > 1024 dense voxels come back
-        # undecided and take the steps below
+        # the whole filter in one device call (occupancy, clusters of the dense voxels, keep rule, mask, compaction); > 1024
+        # dense voxels come back undecided and take the call without a cap; only a tie for the largest cluster -- the
+        # reference's set-iteration order decides it -- comes back from that one too and takes the steps below
         res = ch.density_filter(float(voxel_size), min_points, bool(keep_multicluster))
+        if res["status"] == _lib.DENSITY_HOST:
+            res = ch.density_filter_large(float(voxel_size), min_points, bool(keep_multicluster))
         if res["status"] != _lib.DENSITY_HOST:
             debug_print(f"[DEBUG] Found {res['n_unique']} unique voxels.")
             if res["status"] == _lib.DENSITY_EMPTY:

@@ -457,7 +457,9 @@ int gsx_density_merge_dev(gsx_ctx *ctx, const int64_t *keys3_dev, const int64_t 
  * (saves the box pass and its synchronisation).  info->status: GSX_DENSITY_OK (mask_out_dev holds the mask),
  * GSX_DENSITY_EMPTY (no dense voxel: the filter removes everything, :54-57), GSX_DENSITY_HOST (more than 1024 dense voxels,
  * or two clusters tie for the largest without keep_multicluster -- which one survives is the reference's python-set
- * iteration order: decide with gsx_density_voxels_dev + processing/clusters.py + gsx_density_mask_dev). */
+ * iteration order).  On GSX_DENSITY_HOST nothing was applied: gsx_density_filter_large_dev below takes any number of dense
+ * voxels and answers GSX_DENSITY_HOST for the tie alone, which gsx_density_voxels_dev + processing/clusters.py +
+ * gsx_density_mask_dev then decide. */
 enum { GSX_DENSITY_OK = 0, GSX_DENSITY_EMPTY = 1, GSX_DENSITY_HOST = 2 };
 typedef struct gsx_density_info {
     int32_t status;
@@ -469,6 +471,25 @@ int gsx_density_filter_dev(gsx_ctx *ctx, const float *x, const float *y, const f
 int gsx_density_mask_dev(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride,
                          int64_t n, double voxel_size, const int64_t *kept_keys, int64_t n_kept,
                          uint8_t *mask_out_dev);
+/* The same call with no cap on the number of dense voxels -- replaces data_processor.py:57-112 (the set of dense voxels, the
+ * BFS over their six face neighbours, the keep rule, the per-point membership) for any size: the 6-connected components are
+ * found on the voxel hash table itself by a lock-free union-find (a fixed number of launches, whatever a cluster's diameter).
+ * Same contract as gsx_density_filter_dev (box6, one synchronisation); GSX_DENSITY_HOST only for a tie for the largest cluster
+ * without keep_multicluster. */
+int gsx_density_filter_large_dev(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride, int64_t n,
+                                 double voxel_size, int64_t min_points, int keep_multicluster, const float *box6,
+                                 uint8_t *mask_out_dev, gsx_density_info *info);
+/* Clusters of a HOST list of m distinct absolute voxel keys (3 x int64 each) -- of data_processor.py:57-112 the part that
+ * needs no rows, :57-108 (dense_set, BFS, sort by size, keep rule): keep_out[i] = 1 when key i belongs to a kept cluster, in
+ * input order; info->kept_clusters, largest, n_kept_voxels and status as above (GSX_DENSITY_HOST: a tie without
+ * keep_multicluster, keep_out is undefined).  The keys may span at most 2^31 - 1 voxels on an axis. */
+int gsx_voxel_clusters(const int64_t *keys3, int64_t m, int keep_multicluster, uint8_t *keep_out, gsx_density_info *info);
+int gsx_voxel_clusters_dev(gsx_ctx *ctx, const int64_t *keys3, int64_t m, int keep_multicluster, uint8_t *keep_out,
+                           gsx_density_info *info);
+/* Stage clocks (ms) of the context's last gsx_density_filter_large_dev / gsx_voxel_clusters_dev call, recorded while
+ * gsx_ctx_set_timing is on: table fill, init, hook, flatten + sizes, reduce, membership. */
+#define GSX_DENSITY_STAGES 6
+int gsx_density_stage_clocks(gsx_ctx *ctx, double *ms_out);
 
 /* ---- K-Means codebook (SOG writer) ------------------------------------- */
 /*

@@ -172,6 +172,24 @@ class SogScan(C.Structure):
                 ("rest_nonzero", C.c_uint64)]
 
 
+class ProfileLayout(C.Structure):
+    """gsx_profile_layout (include/gsx_hip.h): where x y z and f_rest_0..44 sit inside a row, -1 = absent"""
+    _fields_ = [("row_bytes", C.c_int64), ("xyz_offset", C.c_int32 * 3), ("rest_offset", C.c_int32 * 45)]
+
+
+class TableProfile(C.Structure):
+    """gsx_table_profile (include/gsx_hip.h)"""
+    _fields_ = [("rest_nonzero", C.c_uint64), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("nan_axes", C.c_uint32), ("n", C.c_int64)]
+
+    def as_dict(self):
+        """what a reader's ``profile=`` dict receives: an axis that holds a NaN reports nan for both bounds"""
+        nan = float("nan")
+        return {"rest_nonzero": int(self.rest_nonzero),
+                "lo": tuple(nan if (self.nan_axes >> a) & 1 else float(self.lo[a]) for a in range(3)),
+                "hi": tuple(nan if (self.nan_axes >> a) & 1 else float(self.hi[a]) for a in range(3)),
+                "nan_axes": int(self.nan_axes), "n": int(self.n)}
+
+
 DENSITY_OK, DENSITY_EMPTY, DENSITY_HOST = range(3)
 DENSITY_STAGES = ("table", "init", "hook", "flatten", "reduce", "membership")   # GSX_DENSITY_STAGES
 SLAB_OK, SLAB_EMPTY, SLAB_NONFINITE, SLAB_SMALL_SHARD, SLAB_NO_STRUCTURE = range(5)
@@ -326,6 +344,8 @@ SIGNATURES = {
     "gsx_parquet_rows_host": (_I, [_P, _I64, _I64, C.POINTER(ParquetRowsLayout), _P]),
     "gsx_parquet_columns_dev": (_I, [_P, _P, _I64, C.POINTER(ParquetColumnsLayout), _P, _I64, _P]),
     "gsx_parquet_columns_host": (_I, [_P, _I64, C.POINTER(ParquetColumnsLayout), _P, _I64, _P]),
+    "gsx_table_profile_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(ProfileLayout), C.POINTER(TableProfile)]),
+    "gsx_table_profile_host": (_I, [_P, _I64, C.POINTER(ProfileLayout), _I, C.POINTER(TableProfile)]),
 }
 
 _lib = None
@@ -1212,6 +1232,132 @@ def rest_nonzero_word(lib, ctx, d_rows, lay: SpzLayout, n: int, scan_fields) -> 
     return word.value
 
 
+PROFILE_AXES = ("x", "y", "z")
+PROFILE_REST = tuple("f_rest_%d" % i for i in range(45))
+PROFILE_MAX_ROW_BYTES = 512   # csrc/row_tile.h SPZ_MAX_ROW_BYTES
+
+
+def profile_layout(dtype: np.dtype):
+    """gsx_profile_layout of a structured dtype -> (layout, foreign): the '<f4' fields among x y z and f_rest_0..44 take part;
+    `foreign` names the fields of another type, which stay absent in the layout (the caller takes the reference's numpy
+    expressions for those quantities: profile_foreign)"""
+    fields = dtype.fields or {}
+    lay, foreign = ProfileLayout(), []
+    lay.row_bytes = dtype.itemsize
+    for k, nm in enumerate(PROFILE_AXES + PROFILE_REST):
+        ok = nm in fields and fields[nm][0] == np.dtype("<f4")
+        if nm in fields and not ok:
+            foreign.append(nm)
+        if k < 3:
+            lay.xyz_offset[k] = int(fields[nm][1]) if ok else -1
+        else:
+            lay.rest_offset[k - 3] = int(fields[nm][1]) if ok else -1
+    return lay, foreign
+
+
+def profile_foreign(prof: dict, table: np.ndarray, foreign) -> dict:
+    """the quantities of `foreign` fields (profile_layout) from the reference's own numpy expressions on `table`, into `prof`"""
+    with np.errstate(all="ignore"):
+        for nm in foreign:
+            col = table[nm]
+            if nm in PROFILE_AXES:
+                a = PROFILE_AXES.index(nm)
+                lo, hi = float(np.min(col)), float(np.max(col))
+                isnan = lo != lo or hi != hi
+                prof["lo"] = prof["lo"][:a] + (float("nan") if isnan else lo,) + prof["lo"][a + 1:]
+                prof["hi"] = prof["hi"][:a] + (float("nan") if isnan else hi,) + prof["hi"][a + 1:]
+                prof["nan_axes"] |= int(isnan) << a
+            elif bool(np.any(col != 0)):
+                prof["rest_nonzero"] |= 1 << PROFILE_REST.index(nm)
+    return prof
+
+
+def empty_profile() -> dict:
+    """the profile of a table without rows"""
+    return {"rest_nonzero": 0, "lo": (float("inf"),) * 3, "hi": (float("-inf"),) * 3, "nan_axes": 0, "n": 0}
+
+
+def table_profile_dev(ctx: "Context", d_rows, first_byte: int, n: int, dtype: np.dtype) -> dict:
+    """gsx_table_profile_dev: one device pass over `n` resident rows of `dtype` (row 0 at byte `first_byte` of `d_rows`, a
+    DeviceArray or a device address; 15 readable bytes behind the last row) -> the profile dict of the '<f4' fields"""
+    lay, _ = profile_layout(np.dtype(dtype))
+    res = TableProfile()
+    ptr = d_rows.ptr if hasattr(d_rows, "ptr") else int(d_rows)
+    check(load().gsx_table_profile_dev(ctx.handle, ptr, int(first_byte), int(n), C.byref(lay), C.byref(res)), "gsx_table_profile_dev")
+    return res.as_dict()
+
+
+def host_table_profile(table: np.ndarray, threads: int = 0) -> dict:
+    """The profile of a host table: gsx_table_profile_host's threaded pass over the rows for the '<f4' fields, the reference's
+    numpy expressions for fields of another type, for a table wider than 512 bytes or not C-contiguous, and none at all for an
+    empty one"""
+    n = len(table)
+    if n == 0:
+        return empty_profile()
+    lay, foreign = profile_layout(table.dtype)
+    if table.ndim != 1 or not table.flags.c_contiguous or table.dtype.itemsize > PROFILE_MAX_ROW_BYTES:
+        prof = dict(empty_profile(), n=n)
+        return profile_foreign(prof, table, [nm for nm in PROFILE_AXES + PROFILE_REST if nm in (table.dtype.fields or {})])
+    res = TableProfile()
+    check(load().gsx_table_profile_host(table.ctypes.data, n, C.byref(lay), int(threads), C.byref(res)), "gsx_table_profile_host")
+    return profile_foreign(res.as_dict(), table, foreign)
+
+
+def finish_profile(profile: "dict | None", table: np.ndarray):
+    """A public reader's last step with a `profile` dict, which it emptied before the read: the session has filled it and only
+    the fields that are not '<f4' are added from numpy; or no rows were resident -- the canonical PLY read on the host, an empty
+    file, a row over 512 bytes, a fallback's table -- and host_table_profile fills it."""
+    if profile is None:
+        return
+    if "rest_nonzero" in profile and profile.get("n") == len(table):
+        foreign = profile_layout(table.dtype)[1]
+        if foreign:
+            profile_foreign(profile, table, foreign)
+    else:
+        profile.clear()
+        profile.update(host_table_profile(table))
+
+
+def with_profile(profile: "dict | None", read):
+    """A public reader with its ``profile=`` keyword: read() -> a table or (table, ...), handed on as it is; a given dict is
+    emptied before the read and holds the returned table's profile after it (finish_profile)"""
+    if profile is None:
+        return read()
+    profile.clear()
+    res = read()
+    finish_profile(profile, res[0] if isinstance(res, tuple) else res)
+    return res
+
+
+def profile_kw(profile: "dict | None") -> dict:
+    """the keyword a public reader hands to its *_unpack_table: none at all without a profile dict (the call is then the one it
+    was before the keyword existed)"""
+    return {} if profile is None else {"profile": profile}
+
+
+def profile_slack(profile: "dict | None") -> int:
+    """bytes a reader adds behind its decoded rows when it is asked for a profile: the pass's 16-byte loads reach up to 15 bytes
+    past the last row"""
+    return 0 if profile is None else 16
+
+
+def session_profile(s: "ArenaSession", profile: "dict | None", d_rows, n_dev: int, n: int, dtype: np.dtype):
+    """A reader's hook between its decode launch and download_rows: with a `profile` dict, the device pass over the `n_dev`
+    decoded rows of `d_rows`, the stage mark "profile", and the dict filled for the table of `n` rows the reader returns (the
+    rows past n_dev are zero: the compressed-PLY reader's tail).  Without one, nothing."""
+    if profile is None:
+        return
+    prof = table_profile_dev(s.ctx, d_rows, 0, n_dev, dtype)
+    if n > n_dev:
+        fields = dtype.fields or {}
+        axes = [nm in fields and fields[nm][0] == np.dtype("<f4") for nm in PROFILE_AXES]
+        prof["lo"] = tuple(min(v, 0.0) if on else v for v, on in zip(prof["lo"], axes))   # (nan stays nan)
+        prof["hi"] = tuple(max(v, 0.0) if on else v for v, on in zip(prof["hi"], axes))
+        prof["n"] = n
+    s.mark("profile")
+    profile.update(prof)
+
+
 def pack_listed(s: "ArenaSession", n: int, run):
     """run(d_list, cap, d_cnt) launches a packer that lists the entries it leaves to numpy in d_list, `cap` of them at most, and
     counts all of them in d_cnt.  More listed entries than room: once more, with room for every one of them.
@@ -1764,7 +1910,7 @@ def cply_read_tables() -> np.ndarray:
 
 
 def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunks: int, n_vertices: int, dtype: np.dtype,
-                      stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+                      stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
     """The compressed-PLY reader's rows (formats/compressed_ply.py:14-124) from a binary little-endian file: the elements' bodies
     are read from `path` (segments: "chunk", "vertex", "sh" -> (file offset, bytes) or None) straight into page-locked staging,
     uploaded once, decoded by gsx_cply_unpack_dev and downloaded into a prefaulted array of `dtype` (68 + 4 n_sh bytes of
@@ -1794,11 +1940,12 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
         host, join = stage_in(s, out, total, fill, "file_read")
         d_in, d_tab = s.upload_in(lib, host, total, cply_read_tables())
         s.mark("upload")
-        d_out = s.buf("out", n_dec * rb)
+        d_out = s.buf("out", n_dec * rb + profile_slack(profile))
         ptr = {k: d_in.ptr + place[k] for k in place}
         check(lib.gsx_cply_unpack_dev(s.ctx.handle, ptr["chunk"], int(n_chunks), ptr["vertex"], n, ptr.get("sh"), C.byref(layout), d_tab.ptr,
                                       d_out.ptr), "gsx_cply_unpack_dev")
         s.mark("kernel")
+        session_profile(s, profile, d_out, n_dec, n, dtype)
         s.download_rows(lib, out, d_out, n_dec * rb, join)
         out.view(np.uint8)[n_dec * rb:] = 0        # rows past 256 n_chunks
         s.mark("download")
@@ -1821,7 +1968,8 @@ def ksplat_read_tables() -> np.ndarray:
 
 
 def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int, sections, prefix: np.ndarray, n_coeffs: int,
-                        n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+                        n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0,
+                        profile: "dict | None" = None) -> np.ndarray:
     """The .ksplat reader's rows (formats/ksplat.py:104-317) from a file whose headers the caller has parsed and checked
     (formats/ksplat_reader.py): `body_bytes` bytes from file offset `body_offset` are read straight into page-locked staging,
     uploaded once, decoded by gsx_ksplat_unpack_dev (sections: KsplatReadSection records with offsets inside that body; prefix:
@@ -1847,10 +1995,11 @@ def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int
         if prefix.size:
             d_prefix.upload(prefix)
         s.mark("upload")
-        d_out = s.buf("out", n * rb)
+        d_out = s.buf("out", n * rb + profile_slack(profile))
         check(lib.gsx_ksplat_unpack_dev(s.ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
                                         d_tab.ptr, int(n_coeffs), d_out.ptr, n), "gsx_ksplat_unpack_dev")
         s.mark("kernel")
+        session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
@@ -1899,7 +2048,7 @@ def spz_body_bytes(version: int, degree: int, n: int) -> int:
 
 
 def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractional_bits: int, n_rows: int, dtype: np.dtype,
-                     stage_ms: "dict | None" = None, device: int = 0, fill_stage: str = "file_read") -> np.ndarray:
+                     stage_ms: "dict | None" = None, device: int = 0, fill_stage: str = "file_read", profile: "dict | None" = None) -> np.ndarray:
     """The SPZ reader's rows (formats/spz.py:175-251) from a file whose header the caller has parsed and checked
     (formats/spz_reader.py): ``fill(view)`` puts the `body_bytes` bytes behind the header straight into page-locked staging
     (it raises what the reference raises on a damaged or short file: nothing has been uploaded then), one upload, decoded by
@@ -1919,10 +2068,11 @@ def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractiona
         host, join = stage_in(s, out, total, fill, fill_stage)
         d_in, d_tab = s.upload_in(lib, host, total + 32, host_tab)   # 16-byte loads reach up to 15 bytes past the last section
         s.mark("upload")
-        d_out = s.buf("out", n * rb)
+        d_out = s.buf("out", n * rb + profile_slack(profile))
         check(lib.gsx_spz_unpack_dev(s.ctx.handle, d_in.ptr, total, int(version), int(degree), int(fractional_bits), d_tab.ptr, d_out.ptr, n),
               "gsx_spz_unpack_dev")
         s.mark("kernel")
+        session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
@@ -1992,7 +2142,7 @@ def sog_texel_layout(n: int, bands: int, palette: int):
 
 
 def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, dtype: np.dtype, on_flag=None,
-                     stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+                     stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
     """The SOG reader's rows (formats/sog.py:60-247) from a bundle whose meta.json the caller has parsed and checked
     (formats/sog_reader.py): ``fill(view, place)`` decodes the textures' texels straight into page-locked staging
     (sog_texel_layout; it raises what the reference raises on a missing or short texture: nothing has been uploaded then), one
@@ -2015,7 +2165,7 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
         d_flag = s.buf("flag", 16)
         check(lib.gsx_dev_memset(s.ctx.handle, d_flag.ptr, 0, 16), "gsx_dev_memset")
         s.mark("upload")
-        d_out = s.buf("out", n * rb)
+        d_out = s.buf("out", n * rb + profile_slack(profile))
         offsets = (_I64 * 7)(*[place[t][0] if t in place else -1 for t in SOG_READ_TEXTURES])
         check(lib.gsx_sog_unpack_dev(s.ctx.handle, d_in.ptr, total, offsets, bands, palette, d_tab.ptr, d_out.ptr, n, d_flag.ptr),
               "gsx_sog_unpack_dev")
@@ -2025,6 +2175,7 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
             if on_flag is not None:
                 on_flag(host, place)
             raise IndexError("sog_unpack_table: a label at or above the palette's %d entries" % palette)
+        session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
@@ -2090,7 +2241,8 @@ def splat_read_tables() -> dict:
     return dict(zip(SPLAT_READ_TABLES, (f_dc, opa)))
 
 
-def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0,
+                       profile: "dict | None" = None) -> np.ndarray:
     """The .splat reader's rows (formats/splat.py:9-80): the first 32 `n_rows` bytes of `path` are read straight into page-locked
     staging, uploaded once, decoded by gsx_splat_unpack_dev and downloaded into a prefaulted array of `dtype` (packed rows of 71
     bytes; formats/splat_reader.py builds it).  When np_log_probe() fails, the three scale columns are numpy's, computed on the
@@ -2111,9 +2263,10 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
         host, join = stage_in(s, out, total, lambda view: read_file(path, 0, view, unit="record bytes"), "file_read")
         d_in, d_tab = s.upload_in(lib, host, total, host_tab)
         s.mark("upload")
-        d_out = s.buf("out", n * rb)
+        d_out = s.buf("out", n * rb + profile_slack(profile))
         check(lib.gsx_splat_unpack_dev(s.ctx.handle, d_in.ptr, n, d_tab.ptr, d_out.ptr), "gsx_splat_unpack_dev")
         s.mark("kernel")
+        session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         if not log_ok:
             recs = host.view(SPLAT_READ_RECORD)
@@ -2125,7 +2278,7 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
 
 
 def ply_unpack_table(path: str, body_offset: int, n_rows: int, layout: PlyReadLayout, dtype: np.dtype, stage_ms: "dict | None" = None,
-                     device: int = 0) -> np.ndarray:
+                     device: int = 0, profile: "dict | None" = None) -> np.ndarray:
     """The 3DGS / CloudCompare PLY readers' rows (formats/ply_3dgs.py:45-58, formats/ply_cc.py:45-60): the vertex element's body
     (`n_rows` rows of layout.in_stride bytes at byte `body_offset` of `path`) is read straight into page-locked staging, from
     the 16-byte boundary at or below it (so row 0 sits at byte 0 ... 15 of the buffer), uploaded once, transcoded by
@@ -2146,9 +2299,10 @@ def ply_unpack_table(path: str, body_offset: int, n_rows: int, layout: PlyReadLa
         host, join = stage_in(s, out, total, lambda view: read_file(path, start, view[:used], " in element 'vertex'"), "file_read")
         d_in, _ = s.upload_in(lib, host, total)
         s.mark("upload")
-        d_out = s.buf("out", n * rb)
+        d_out = s.buf("out", n * rb + profile_slack(profile))
         check(lib.gsx_ply_unpack_dev(s.ctx.handle, d_in.ptr, first, n, C.byref(layout), d_out.ptr), "gsx_ply_unpack_dev")
         s.mark("kernel")
+        session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
@@ -2299,7 +2453,8 @@ def _parquet_fill(parts):
     return fill
 
 
-def parquet_rows_table(columns, n_rows: int, fields, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+def parquet_rows_table(columns, n_rows: int, fields, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0,
+                       profile: "dict | None" = None) -> np.ndarray:
     """The Parquet reader's rows (formats/parquet.py:51-55): Arrow's column chunks are laid end to end in page-locked staging
     (parquet_rows_plan: the one host copy a pageable upload makes anyway), uploaded once, transposed and cast by
     gsx_parquet_rows_dev and downloaded into a prefaulted array of `dtype`.  n_rows = 0 -> the empty array, no launch.
@@ -2316,9 +2471,10 @@ def parquet_rows_table(columns, n_rows: int, fields, dtype: np.dtype, stage_ms: 
         host, join = stage_in(s, out, total, _parquet_fill(parts), "gather")
         d_in, _ = s.upload_in(lib, host, total)
         s.mark("upload")
-        d_out = s.buf("out", n * rb)
+        d_out = s.buf("out", n * rb + profile_slack(profile))
         check(lib.gsx_parquet_rows_dev(s.ctx.handle, d_in.ptr, total, n, C.byref(lay), d_out.ptr), "gsx_parquet_rows_dev")
         s.mark("kernel")
+        session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
         return out
@@ -2746,7 +2902,8 @@ class ArenaSession:
 
     The six table readers share one sequence: stage_in() -- staging, the caller's fill, the fill stage's mark, all on the host --
     then ``s.upload_in``, the caller's own uploads and mark("upload"), its launch and mark("kernel"), ``s.download_rows`` and
-    mark("download")."""
+    mark("download").  A reader that is handed a ``profile`` dict runs session_profile() between the launch and the download:
+    one more pass over the decoded rows (gsx_table_profile_dev) and a mark("profile")."""
 
     def __init__(self, group: str, device: int = 0, stage_ms: "dict | None" = None, ctx: "Context | None" = None, shared: bool = True):
         self.group, self.device, self.stage_ms, self.ctx = group, device, stage_ms, ctx

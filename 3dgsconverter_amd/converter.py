@@ -1,0 +1,264 @@
+"""``Converter`` -- the orchestrator of a conversion (the reference's gsconverter/converter.py:12-294) on this package's own
+readers, filter chain and writers: a file is converted on a machine that has this repository and an MI355X, and nothing else.
+
+  | step (converter.py)                               | here                                                                |
+  |---------------------------------------------------|---------------------------------------------------------------------|
+  | :27-61 format by extension, then the header sniff | detect_format: the same tests, host only                            |
+  | :63-72, :112-115 the handler's read               | the format's read_* with ``profile={}``: the decoded rows are       |
+  |                                                   | profiled in HBM before their download (csrc/table_profile.hip)      |
+  | :121-146 45 strided `np.any(col != 0)` scans      | plan_conversion on the profile's 64-bit word                        |
+  | :150-252 DataProcessor, the filters in order      | processing.ChainedDataProcessor: one device-resident chain          |
+  | :263-288 extra elements, the handler's write      | the format's write_*                                                |
+
+What the user sees -- the ``status_print`` / ``debug_print`` lines, their order, the exceptions and their messages -- is the
+reference's.  A file the device readers do not take raises that reader's ``Unsupported*Error``: there is no second reader to
+fall back to.  The reference's SOR branch without Taichi computes its mask and returns the table unfiltered;
+``remove_flyers`` here applies it, as everywhere in this package.
+"""
+from __future__ import annotations
+
+import contextlib
+
+from .utils import debug_print, status_print
+
+VALID_FORMATS = ["3dgs", "cc", "parquet", "splat", "ksplat", "spz", "sog", "compressed_ply"]              # :19
+FORMAT_MAX_SH = {"3dgs": 3, "cc": 3, "parquet": 3, "ksplat": 2, "splat": 0, "spz": 3, "sog": 3, "compressed_ply": 3}   # :154-163
+EXTENSIONS = {"3dgs": ".ply", "cc": ".ply", "compressed_ply": ".ply", "sog": ".sog", "splat": ".splat", "ksplat": ".ksplat",
+              "spz": ".spz", "parquet": ".parquet"}                                                       # main.py:354-358
+FORMATS_NEEDING_RGB = ["cc", "splat", "ksplat", "sogs", "sog"]                                             # :244
+EXTRA_ELEMENT_FORMATS = ["3dgs", "cc"]                                                                     # :275
+CC_MARKERS = ("property float scal_f_dc_0", "property float scalar_scal_f_dc_0", "property float scalar_f_dc_0")   # :56
+
+
+def detect_format(path: str):
+    """:27-61 -> the format's name, or None: the extension, then for anything else the first 2048 bytes as a PLY header"""
+    lower = path.lower()
+    for ext, name in ((".parquet", "parquet"), (".splat", "splat"), (".ksplat", "ksplat"), (".spz", "spz"), (".sog", "sog")):
+        if lower.endswith(ext):
+            return name
+    debug_print("[DEBUG] Executing '_text_based_detect'...")
+    try:
+        with open(path, "rb") as f:
+            header = f.read(2048).decode("utf-8", errors="ignore")
+        if "element chunk" in header:
+            return "compressed_ply"
+        if "property float f_dc_0" in header:
+            return "3dgs"
+        if any(m in header for m in CC_MARKERS):
+            return "cc"
+    except Exception as e:   # noqa: BLE001  (:58 the reference reports any error and detects nothing)
+        debug_print(f"[DEBUG] Error identifying PLY flavor: {e}")
+    return None
+
+
+def degree_of_count(n_rest: int) -> int:
+    """:125-127: 45 / 24 / 9 f_rest columns -> degree 3 / 2 / 1"""
+    return 3 if n_rest >= 45 else 2 if n_rest >= 24 else 1 if n_rest >= 9 else 0
+
+
+def plan_conversion(names, rest_nonzero: int, target_format: str, kwargs: dict) -> dict:
+    """Every decision :121-188 and :244-252 take, from the table's field names and the profile's word alone (bit i: f_rest_i
+    holds a value != 0) -> {"source_degree", "final_degree", "messages": the warning and `SH Reduction` lines in order,
+    "add_rgb": add_rgb_from_sh is called, "rgb_message": its status line or None}.
+
+    The column COUNT picks the index the backward search starts from (:125-133): 30 columns search f_rest_23 downward, so a
+    value in f_rest_29 is not seen."""
+    names = tuple(names)
+    source = degree_of_count(sum(1 for f in names if f.startswith("f_rest_")))
+    if source > 0:
+        last = next((i for i in range({3: 44, 2: 23, 1: 8}[source], -1, -1)
+                     if f"f_rest_{i}" in names and (rest_nonzero >> i) & 1), -1)
+        source = 3 if last >= 24 else 2 if last >= 9 else 1 if last >= 0 else 0                            # :143-146
+    limit = FORMAT_MAX_SH.get(target_format, 3)
+    requested = kwargs.get("sh_level")
+    final, messages = source, []
+    if requested is not None:
+        if requested > limit:
+            messages.append(f"Warning: Requested SH degree {requested} exceeds limit for '{target_format}' ({limit}). Capping to {limit}.")
+        if requested > source:
+            messages.append(f"Warning: Requested SH degree {requested} exceeds source data degree ({source}). Capping to {source}.")
+        final = min(final, requested)
+    final = min(final, limit)
+    if final < source:
+        messages.append(f"SH Reduction: Source degree {source} -> Target degree {final}")
+    has_rgb = "red" in names
+    add_rgb = ((target_format in FORMATS_NEEDING_RGB and not has_rgb) or bool(kwargs.get("rgb", False))) and not has_rgb
+    return {"source_degree": source, "final_degree": final, "messages": messages, "add_rgb": add_rgb,
+            "rgb_message": f"Target format '{target_format}' requires RGB. Auto-calculating from SH..." if add_rgb else None}
+
+
+class SourceHandler:
+    """what the orchestrator and ``report_info`` use of a reference format handler: ``read`` (with the table's profile beside
+    it), ``metadata`` after a .ksplat or compressed-PLY read, ``extra_elements`` after a read of either PLY dialect"""
+
+    def __init__(self, format_name: str):
+        if format_name not in VALID_FORMATS:
+            raise ValueError(f"Unsupported format: {format_name}")                                         # :92
+        self.format_name = format_name
+        self.profile = None
+        self.opens = 0              # decodes of a source file through this handler
+
+    def read(self, path: str, stage_ms: "dict | None" = None):
+        name, profile = self.format_name, {}
+        self.opens += 1
+        if name in ("3dgs", "cc"):
+            from .formats import ply_reader
+            data, self.extra_elements = (ply_reader.read_ply_3dgs if name == "3dgs" else ply_reader.read_ply_cc)(path, stage_ms=stage_ms, profile=profile)
+        elif name == "compressed_ply":
+            from .formats.compressed_ply_reader import read_compressed_ply
+            data, _ = read_compressed_ply(path, stage_ms=stage_ms, on_metadata=lambda m: setattr(self, "metadata", m), profile=profile)
+        elif name == "ksplat":
+            from .formats.ksplat_reader import read_ksplat
+            data, _ = read_ksplat(path, stage_ms=stage_ms, on_metadata=lambda m: setattr(self, "metadata", m), profile=profile)
+        else:
+            from .formats import parquet_reader, sog_reader, splat_reader, spz_reader
+            read = {"parquet": parquet_reader.read_parquet, "splat": splat_reader.read_splat, "spz": spz_reader.read_spz,
+                    "sog": sog_reader.read_sog}[name]
+            data = read(path, stage_ms=stage_ms, profile=profile)
+        self.profile = profile
+        return data
+
+    def write(self, data, path: str, stage_ms: "dict | None" = None, **kwargs):
+        name = self.format_name
+        import importlib
+        module, function = {"3dgs": ("ply_writer", "write_ply_3dgs"), "cc": ("ply_writer", "write_ply_cc"), "parquet": ("parquet_writer", "write_parquet"),
+                            "splat": ("splat_writer", "write_splat"), "ksplat": ("ksplat_writer", "write_ksplat"), "spz": ("spz_writer", "write_spz"),
+                            "sog": ("sog_writer", "write_sog"), "compressed_ply": ("compressed_ply_writer", "write_compressed_ply")}[name]
+        write = getattr(importlib.import_module(".formats." + module, __package__), function)
+        if name == "parquet":       # (the reference's writer ignores every keyword)
+            return write(data, path, **({} if stage_ms is None else {"stage_ms": stage_ms}))
+        if stage_ms is not None and name not in ("sog", "compressed_ply"):
+            kwargs = dict(kwargs, stage_ms=stage_ms)
+        return write(data, path, **kwargs)
+
+
+@contextlib.contextmanager
+def progress_bar():
+    """:103 the tqdm bar when tqdm is importable, no bar otherwise"""
+    try:
+        from tqdm import tqdm
+    except ImportError:
+        class _NoBar:
+            def update(self, n):
+                pass
+
+            def set_description(self, text):
+                pass
+
+            def refresh(self):
+                pass
+        yield _NoBar()
+        return
+    with tqdm(total=100, desc="Converting", bar_format="{desc}: {percentage:3.0f}% |{bar}| {n_fmt}/{total_fmt}") as pbar:
+        yield pbar
+
+
+class Converter:
+    def __init__(self, input_path, output_path, target_format):
+        self.input_path = input_path
+        self.output_path = output_path
+        self.target_format = target_format.lower()
+        if self.target_format not in VALID_FORMATS:
+            raise ValueError(f"Unknown target format '{self.target_format}'. Supported: {', '.join(VALID_FORMATS)}")
+        self.data = None
+        self.source_format = None
+        self.source_handler = None
+        self.profile = None
+        self.stage_ms = {}          # the last run's stage clocks: read_*, process, write_*
+        self._loaded = None         # (path, handler, data, profile) of load_source_only: run() decodes the source no second time
+
+    def _detect_format(self, path):
+        return detect_format(path)
+
+    def _get_format_handler(self, format_name):
+        return SourceHandler(format_name)
+
+    def load_source_only(self):
+        """:63-72: detect, read, keep -- and remember the table with its profile for a run() on the same path"""
+        self.source_format = self._detect_format(self.input_path)
+        if not self.source_format:
+            raise ValueError("Could not detect source format")
+        debug_print(f"[DEBUG] Detected source format: {self.source_format}")
+        self.source_handler = self._get_format_handler(self.source_format)
+        self.data = self.source_handler.read(self.input_path)
+        self.profile = self.source_handler.profile
+        self._loaded = (self.input_path, self.source_handler, self.data, self.profile)
+        return self.data
+
+    def run(self, **kwargs):
+        import time
+        from .processing.data_processor import ChainedDataProcessor
+        debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
+        clocks = self.stage_ms = {}
+        with progress_bar() as pbar:
+            source_format = self._detect_format(self.input_path)
+            if not source_format:
+                raise ValueError("Could not detect source format")
+            debug_print(f"[DEBUG] Detected source format: {source_format}")
+            pbar.update(5)
+
+            pbar.set_description("Reading Source")
+            if self._loaded is not None and self._loaded[0] == self.input_path:
+                _, self.source_handler, self.data, self.profile = self._loaded
+            else:
+                self.source_handler = self._get_format_handler(source_format)
+                read_ms = {}
+                self.data = self.source_handler.read(self.input_path, stage_ms=read_ms)
+                self.profile = self.source_handler.profile
+                clocks.update({"read_" + k: v for k, v in read_ms.items()})
+            self._loaded = None     # (the table is about to change in place: cap_sh_degree)
+            pbar.update(25)
+
+            plan = plan_conversion(self.data.dtype.names, self.profile["rest_nonzero"], self.target_format, kwargs)
+            pbar.set_description("Processing")
+            t0 = time.perf_counter()
+            processor = ChainedDataProcessor(self.data)
+            self.format_max_sh = dict(FORMAT_MAX_SH)
+            for line in plan["messages"]:
+                status_print(line)
+            processor.cap_sh_degree(plan["final_degree"])
+            pbar.update(5)
+
+            pbar.set_description("Filtering")
+            if kwargs.get("bbox"):
+                processor.crop_by_bbox(*kwargs["bbox"])
+            min_opacity = kwargs.get("min_opacity")
+            if min_opacity is not None and min_opacity > 0:
+                processor.apply_alpha_filter(min_opacity)
+            d_voxel, d_thresh, d_sens = kwargs.get("density_voxel_size"), kwargs.get("density_threshold"), kwargs.get("density_sensitivity")
+            if (d_voxel is not None and d_thresh is not None) or d_sens is not None:
+                processor.apply_density_filter(1.0 if d_voxel is None else float(d_voxel), 0.32 if d_thresh is None else float(d_thresh),
+                                               sensitivity=d_sens, keep_multicluster=kwargs.get("keep_multicluster", False))
+            pbar.update(10)
+            s_k, s_sigma, s_intensity = kwargs.get("sor_k"), kwargs.get("sor_sigma"), kwargs.get("sor_intensity")
+            if (s_k is not None and s_sigma is not None) or s_intensity is not None:
+                pbar.set_description("Filtering (SOR)")
+                processor.remove_flyers(25 if s_k is None else int(s_k), 10.5 if s_sigma is None else float(s_sigma), intensity=s_intensity)
+            pbar.update(10)
+            if kwargs.get("auto_bbox"):
+                processor.apply_auto_bbox()
+            if plan["add_rgb"]:
+                status_print(plan["rgb_message"])
+                processor.add_rgb_from_sh()
+            pbar.update(5)
+            self.data = processor.data
+            clocks["process"] = round((time.perf_counter() - t0) * 1e3, 3)
+
+            pbar.set_description(f"Writing {self.target_format.upper()}")
+            extras = getattr(self.source_handler, "extra_elements", None)
+            if kwargs.get("maintain_extra_elements", False):
+                if extras:
+                    kwargs["extra_elements"] = extras
+                    if self.target_format not in EXTRA_ELEMENT_FORMATS:
+                        status_print(f"Warning: Target format '{self.target_format}' does not support preserving extra elements. These will be ignored.")
+                else:
+                    status_print("Warning: --extra_elements passed but no extra elements found in source.")
+            elif extras:
+                status_print(f"Stripping {len(extras)} extra PLY elements (use --extra_elements to preserve).")
+            write_ms = {}
+            self._get_format_handler(self.target_format).write(self.data, self.output_path, stage_ms=write_ms, **kwargs)
+            clocks.update({"write_" + k: v for k, v in write_ms.items()})
+            pbar.update(40)
+            pbar.refresh()
+            pbar.set_description("Completed")
+        status_print(f"Conversion completed: Saved to {self.output_path}")

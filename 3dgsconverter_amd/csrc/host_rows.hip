@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "gsx_common.h"
+#include "table_profile.h"
 
 namespace {
 
@@ -310,6 +311,91 @@ extern "C" int gsx_host_take_rows_shape(const void *rows, int64_t row_bytes, int
     });
     for (int t = 0; t < nt; ++t)
         if (bad[t]) GSX_FAIL("gsx_host_take_rows_shape: the index list is not strictly ascending inside [0, n)");
+    return 0;
+}
+
+// converter.py:121-146 (the source SH degree: np.any(self.data[f'f_rest_{i}'] != 0), one strided column at a time) and
+// main.py:109-114,190-209 (the info block's six strided min / max reductions and 45 more np.any scans) as ONE threaded pass over
+// the rows: the host twin of gsx_table_profile_dev (csrc/table_profile.hip), for a table that is not resident in HBM.  Same
+// rules: the bit test of rest_scan.h, minima and maxima by value with a zero extreme returned as +0.0, a NaN sets its axis' bit
+// and takes no part in the bounds, an axis without a value (absent, or NaN in every row) gives lo = +inf, hi = -inf.
+extern "C" int gsx_table_profile_host(const void *rows, int64_t n, const gsx_profile_layout *layout, int threads, gsx_table_profile *out)
+{
+    if (!rows || !out) GSX_FAIL("gsx_table_profile_host: null argument");
+    gsx::ProfileOffsets O;
+    GSX_CHECK(gsx::profile_layout_check(layout, n, &O, "gsx_table_profile_host"));
+    if (threads > 1024) GSX_FAIL("gsx_table_profile_host: %d threads", threads);
+    const int64_t rb = layout->row_bytes;
+    const int nt = (int)std::min<int64_t>(n, threads > 0 ? threads : worker_count(n * rb));
+    int rest_off[45], rest_bit[45], nrest = 0;
+    for (int i = 0; i < 45; ++i)
+        if (O.off[3 + i] >= 0) {
+            rest_off[nrest] = O.off[3 + i];
+            rest_bit[nrest++] = i;
+        }
+    struct Part {
+        uint64_t rest = 0;
+        float lo[3], hi[3];
+        uint32_t nan = 0;
+        char pad[64];   // a cache line of its own
+    };
+    std::vector<Part> parts(nt);
+    const char *src = static_cast<const char *>(rows);
+    run_threads(nt, [&](int t) {
+        const int64_t r0 = n * t / nt, r1 = n * (t + 1) / nt;
+        uint64_t rest = 0;
+        uint32_t nan = 0;
+        float lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = __builtin_inff();
+            hi[a] = -__builtin_inff();
+        }
+        for (int64_t r = r0; r < r1; ++r) {
+            const char *p = src + r * rb;
+            for (int a = 0; a < 3; ++a) {
+                if (O.off[a] < 0) continue;
+                float v;
+                memcpy(&v, p + O.off[a], 4);
+                if (v != v) {
+                    nan |= 1u << a;
+                } else {
+                    if (v < lo[a]) lo[a] = v;
+                    if (v > hi[a]) hi[a] = v;
+                }
+            }
+            for (int k = 0; k < nrest; ++k) {
+                uint32_t w;
+                memcpy(&w, p + rest_off[k], 4);
+                rest |= (uint64_t)((w & 0x7fffffffu) != 0u) << rest_bit[k];
+            }
+        }
+        Part &P = parts[t];
+        P.rest = rest;
+        P.nan = nan;
+        for (int a = 0; a < 3; ++a) {
+            P.lo[a] = lo[a];
+            P.hi[a] = hi[a];
+        }
+    });
+    out->rest_nonzero = 0;
+    out->nan_axes = 0;
+    for (int a = 0; a < 3; ++a) {
+        out->lo[a] = __builtin_inff();
+        out->hi[a] = -__builtin_inff();
+    }
+    for (const Part &P : parts) {
+        out->rest_nonzero |= P.rest;
+        out->nan_axes |= P.nan;
+        for (int a = 0; a < 3; ++a) {
+            if (P.lo[a] < out->lo[a]) out->lo[a] = P.lo[a];
+            if (P.hi[a] > out->hi[a]) out->hi[a] = P.hi[a];
+        }
+    }
+    for (int a = 0; a < 3; ++a) {   // -0.0 -> +0.0
+        if (out->lo[a] == 0.0f) out->lo[a] = 0.0f;
+        if (out->hi[a] == 0.0f) out->hi[a] = 0.0f;
+    }
+    out->n = n;
     return 0;
 }
 

@@ -238,14 +238,20 @@ def _installed_original():
     return fallback
 
 
-def read_ksplat(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, on_metadata=None):
+def read_ksplat(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, on_metadata=None,
+                profile: "dict | None" = None):
     """:29-317 -> (rows, metadata): the reference's structured array (define_dtype of the largest section degree, all <f4; nx ny
     nz and the f_rest fields a section does not carry are 0) and its metadata dict.
 
     fallback: a function path -> (rows, metadata) for the files the device path does not take; by default the reference's own
     read when install() has saved one, else such files raise UnsupportedKSplatError.  on_metadata: called with the metadata as
     soon as the reference would have set ``self.metadata``.  stage_ms: a dict that receives the stage clocks parse, file_read,
-    upload, kernel, download (tools/probe_ksplat_read.py)."""
+    upload, kernel, download (tools/probe_ksplat_read.py).  profile: a dict that receives the returned table's profile
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
+    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, on_metadata, profile))
+
+
+def _read(path, stage_ms, device, fallback, on_metadata, profile):
     debug_print(f"[DEBUG] Reading .ksplat file from {path}")
     t0 = time.perf_counter()
     try:
@@ -264,7 +270,7 @@ def read_ksplat(path: str, stage_ms: "dict | None" = None, device: int = 0, *, f
     if p.n_rows == 0:                      # :275-277, or sections without rows
         return np.zeros(0, dtype), metadata
     rows = _lib.ksplat_unpack_table(path, p.payload_offset, p.body_bytes, p.level, device_sections(p), p.prefix, n_coeffs_of(p.degree),
-                                    p.n_rows, dtype, stage_ms=stage_ms, device=device)
+                                    p.n_rows, dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
     debug_print(f"[DEBUG] KSplat read completed. {p.n_rows} splats in {len(p.sections)} sections.")
     return rows, metadata
 

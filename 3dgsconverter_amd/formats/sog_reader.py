@@ -148,14 +148,19 @@ def _installed_original():
     return fallback
 
 
-def read_sog(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None) -> np.ndarray:
+def read_sog(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, profile: "dict | None" = None) -> np.ndarray:
     """:23-247 -> the reference's structured array: define_dtype(has_scal=False, has_rgb=False) of the file's bands, float32
     fields, packed; nx ny nz zero.
 
     fallback: a function path -> rows for the files the device path does not take (bands outside 1 ... 3, a palette outside
     1 ... 65 536, a count that is no non-negative int, anything in meta.json of another type than the writer's); by default the
     reference's own read when install() has saved one, else such files raise UnsupportedSogError.  stage_ms: a dict that
-    receives the stage clocks parse, decode, upload, kernel, download (tools/probe_sog_read.py)."""
+    receives the stage clocks parse, decode, upload, kernel, download (tools/probe_sog_read.py).  profile: a dict that receives the returned table's profile
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
+    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, profile))
+
+
+def _read(path, stage_ms, device, fallback, profile):
     debug_print(f"[DEBUG] Reading .sog file from {path}")
     t0 = time.perf_counter()
     if not Image:
@@ -223,7 +228,7 @@ def read_sog(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fall
             place, total = _lib.sog_texel_layout(0, bands, palette)
             fill(np.empty(total, np.uint8), place)
             return np.zeros(0, dtype)
-        rows = _lib.sog_unpack_table(fill, n, bands, palette, tables, dtype, on_flag=on_flag, stage_ms=stage_ms, device=device)
+        rows = _lib.sog_unpack_table(fill, n, bands, palette, tables, dtype, on_flag=on_flag, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
     debug_print(f"[DEBUG] SOG read completed. {n} splats, {bands} SH bands.")
     return rows
 

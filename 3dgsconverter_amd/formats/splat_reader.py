@@ -27,11 +27,16 @@ from .spz_reader import define_dtype
 RECORD_BYTES = 32                                                                  # splat.py:15
 
 
-def read_splat(path: str, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+def read_splat(path: str, stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
     """:9-80 -> the reference's structured array: define_dtype(has_scal=False, has_rgb=True, sh_degree=0), float32 fields then
     red green blue as bytes, packed; nx ny nz and red green blue zero.
 
-    stage_ms: a dict that receives the stage clocks parse, file_read, upload, kernel, download (tools/probe_splat_read.py)."""
+    stage_ms: a dict that receives the stage clocks parse, file_read, upload, kernel, download (tools/probe_splat_read.py).  profile: a dict that receives the returned table's profile
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
+    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, profile))
+
+
+def _read(path, stage_ms, device, profile):
     debug_print(f"[DEBUG] Reading .splat file from {path}")
     t0 = time.perf_counter()
     file_size = os.path.getsize(path)
@@ -46,7 +51,7 @@ def read_splat(path: str, stage_ms: "dict | None" = None, device: int = 0) -> np
         stage_ms["parse"] = round((time.perf_counter() - t0) * 1e3, 3)
     if n == 0:
         return np.zeros(0, dtype)
-    rows = _lib.splat_unpack_table(path, n, dtype, stage_ms=stage_ms, device=device)
+    rows = _lib.splat_unpack_table(path, n, dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
     debug_print(f"[DEBUG] Loaded {n} points from .splat")
     return rows
 

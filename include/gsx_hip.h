@@ -1045,6 +1045,33 @@ int gsx_parquet_columns_dev(gsx_ctx *ctx, const void *rows_dev, int64_t n, const
 int gsx_parquet_columns_host(const void *rows, int64_t n, const gsx_parquet_columns_layout *layout, void *out, int64_t out_bytes,
                              uint64_t *null_counts);
 
+
+/* ---- the table profile: what the orchestrator and `--info` ask of a decoded table, in one pass (csrc/table_profile.hip) ----
+ * converter.py:121-146 finds the source SH degree with `np.any(self.data[f'f_rest_{i}'] != 0)` on one strided column at a time
+ * and main.py:109-114,190-209 takes six strided min / max reductions and up to 45 more `np.any` scans for the info block.  All of
+ * them are reductions over rows a reader holds decoded in HBM just before its download: one pass there, or one threaded pass over
+ * a host table (csrc/host_rows.hip). */
+typedef struct {
+    int64_t row_bytes;                 /* 1 ... 512 */
+    int32_t xyz_offset[3];             /* byte offsets of the float32 (little-endian) fields x y z inside a row, -1 = absent */
+    int32_t rest_offset[45];           /* ... of f_rest_0..44, -1 = absent */
+} gsx_profile_layout;
+typedef struct {
+    uint64_t rest_nonzero;             /* bit i: some row has (bits(f_rest_i) & 0x7fffffff) != 0 -- np.any(col != 0) and np.any(col):
+                                          NaN and denormals count, -0.0 does not.  An absent field leaves its bit clear */
+    float    lo[3], hi[3];             /* np.min / np.max of x y z by value (the sign of a zero extreme is unspecified; +-inf pass
+                                          through).  An absent axis: lo = +inf, hi = -inf */
+    uint32_t nan_axes;                 /* bit a: axis a holds a NaN; its lo and hi are then unspecified */
+    int64_t  n;
+} gsx_table_profile;
+/* rows_dev: 16-byte aligned, row 0 at byte first_byte (0 ... 15), n >= 1 rows, readable up to 15 bytes past the last row.  Every
+ * present field lies inside a row (any byte offset).  *out is a HOST struct.  One launch; synchronises the context's stream. */
+int gsx_table_profile_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t n, const gsx_profile_layout *layout,
+                          gsx_table_profile *out);
+/* the same on the HOST, threaded (threads <= 0: by the table's size); nothing outside the rows is read.  The model the host tests
+ * hold against numpy, and the product path for a table that is not resident. */
+int gsx_table_profile_host(const void *rows, int64_t n, const gsx_profile_layout *layout, int threads, gsx_table_profile *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -346,6 +346,9 @@ SIGNATURES = {
     "gsx_parquet_columns_host": (_I, [_P, _I64, C.POINTER(ParquetColumnsLayout), _P, _I64, _P]),
     "gsx_table_profile_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(ProfileLayout), C.POINTER(TableProfile)]),
     "gsx_table_profile_host": (_I, [_P, _I64, C.POINTER(ProfileLayout), _I, C.POINTER(TableProfile)]),
+    "gsx_rows_columns_f32_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(C.c_int32), _I, _P]),
+    "gsx_rows_take_dev": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _P, _I64]),
+    "gsx_dev_patch_u8": (_I, [_P, _P, _I64, _P, _P, _I64]),
 }
 
 _lib = None
@@ -1180,6 +1183,24 @@ def prefault(large: bool, *arrays):
     return th.join
 
 
+def prefault_parallel(a: np.ndarray, threads: int = 8):
+    """prefault() for one large array on `threads` helper threads, each touching a contiguous share of its pages (numpy's strided
+    fill releases the GIL): where nothing else runs meanwhile -- the resident materialise has only a few milliseconds of device
+    work to hide the faults of a 2.5 GB table behind -- one thread's 100 ms of page faults are the whole stage.  -> join()"""
+    flat = a.reshape(-1).view(np.uint8)
+    n = flat.size
+    if n < (1 << 22):
+        return lambda: None
+    cuts = [(n * i // threads) & ~4095 for i in range(threads)] + [n]
+
+    def run(lo, hi):
+        flat[lo:hi:4096] = 0
+    ths = [threading.Thread(target=run, args=(lo, hi), name="gsx-prefault", daemon=True) for lo, hi in zip(cuts, cuts[1:]) if hi > lo]
+    for th in ths:
+        th.start()
+    return lambda: [th.join() for th in ths] and None
+
+
 def stage_in(s: "ArenaSession", out: np.ndarray, nbytes: int, fill, stage: str):
     """A table reader's host half, all of it before any device work: prefault `out` when it is at least 4 MiB, take the
     session's staging buffer "in" of `nbytes`, let ``fill(host)`` put the file's bytes there and mark `stage`.  What `fill`
@@ -1356,6 +1377,238 @@ def session_profile(s: "ArenaSession", profile: "dict | None", d_rows, n_dev: in
         prof["n"] = n
     s.mark("profile")
     profile.update(prof)
+
+
+RESIDENT_MAX_ROW_BYTES = 512   # csrc/row_tile.h SPZ_MAX_ROW_BYTES
+
+
+class ResidentRows:
+    """A table's rows in HBM, as a reader decoded them, beyond the reader's call: `n` packed rows of `dtype` from byte
+    `first_byte` (0 ... 15) of the 16-byte aligned device address `ptr`, with 16 readable bytes behind the last row -- what
+    gsx_table_profile_dev, gsx_rows_columns_f32_dev and gsx_rows_take_dev take.
+
+    The buffer is an allocation of a Context this object owns, and no named arena buffer: those are overwritten by the next call
+    of their lease group and freed by release_arenas().  A device address is valid in every context of this process on the same
+    device, so a reader's session writes into it and a chain's or a writer's context reads it.  ``close()`` frees the buffer and
+    the context (idempotent; ``__del__`` calls it).  ``ResidentRows.open_count`` counts the objects not closed yet."""
+
+    open_count = 0
+
+    def __init__(self, n: int, dtype, device: int = 0, first_byte: int = 0):
+        self.n, self.dtype, self.device, self.first_byte = int(n), np.dtype(dtype), int(device), int(first_byte)
+        self.ptr = None
+        self._ctx = self._buf = None
+        if not 0 <= self.first_byte <= 15 or not 1 <= self.dtype.itemsize <= RESIDENT_MAX_ROW_BYTES or self.n < 0:
+            raise ValueError("ResidentRows: %d rows of %d bytes from byte %d" % (self.n, self.dtype.itemsize, self.first_byte))
+        self._ctx = Context(self.device)
+        try:
+            self._buf = self._ctx.alloc(self.first_byte + self.nbytes + 16)
+        except BaseException:
+            self._ctx.close()
+            self._ctx = None
+            raise
+        self.ptr = self._buf.ptr
+        ResidentRows.open_count += 1
+
+    @classmethod
+    def from_host(cls, table: np.ndarray, device: int = 0, first_byte: int = 0) -> "ResidentRows":
+        """the rows of a host table (1-D, structured or not, rows of up to 512 bytes) uploaded: for a caller that has no reader's
+        ``keep=`` at hand, and the tests"""
+        table = np.ascontiguousarray(table)
+        if table.ndim != 1:
+            raise ValueError("ResidentRows.from_host: a 1-D table")
+        rr = cls(len(table), table.dtype, device, first_byte)
+        try:
+            if table.nbytes:
+                upload_table(rr._ctx.lib, rr._ctx, rr.ptr + rr.first_byte, table)
+        except BaseException:
+            rr.close()
+            raise
+        return rr
+
+    @property
+    def nbytes(self) -> int:
+        return self.n * self.dtype.itemsize
+
+    @property
+    def closed(self) -> bool:
+        return self.ptr is None
+
+    def download(self) -> np.ndarray:
+        """-> a new host table of the `n` rows"""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        out = np.empty(self.n, self.dtype)
+        return self.download_into(out)
+
+    def download_into(self, out: np.ndarray) -> np.ndarray:
+        """the rows into the host table `out` (n rows of dtype, C-contiguous), through the staging lanes -> out"""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        if out.shape != (self.n,) or out.dtype != self.dtype or not out.flags.c_contiguous:
+            raise ValueError("ResidentRows.download_into: a table of %d rows of %s" % (self.n, self.dtype))
+        if self.n:
+            check(self._ctx.lib.gsx_dev_download_staged(self._ctx.handle, out.view(np.uint8).ctypes.data, self.ptr + self.first_byte, self.nbytes),
+                  "gsx_dev_download_staged")
+        return out
+
+    def close(self):
+        if self.ptr is None:
+            return
+        self.ptr = None
+        ResidentRows.open_count -= 1
+        buf, ctx, self._buf, self._ctx = self._buf, self._ctx, None, None
+        if buf is not None:
+            buf.free()
+        if ctx is not None:
+            ctx.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+RESIDENT_F4_FIELDS = ("x", "y", "z", "opacity", "f_dc_0", "f_dc_1", "f_dc_2") + PROFILE_REST   # what DataProcessor reads or zeroes as words
+
+
+def resident_same_rows(rr_dtype, rr_n: int, dtype, n: int) -> bool:
+    """are `rr_n` resident rows of `rr_dtype` the rows of a host table of `n` rows of `dtype`, as far as shapes tell?  The same
+    count, at least one row, the same structured dtype, rows of up to 512 bytes (the .splat writer's rule for its `resident`)"""
+    if rr_dtype is None or dtype is None:
+        return False
+    rr_dtype, dtype = np.dtype(rr_dtype), np.dtype(dtype)
+    return (int(rr_n) == int(n) and int(n) >= 1 and rr_dtype == dtype and dtype.fields is not None
+            and 1 <= dtype.itemsize <= RESIDENT_MAX_ROW_BYTES)
+
+
+def resident_eligible(rr_dtype, rr_n: int, dtype, n: int) -> bool:
+    """DataProcessor's rule for its `resident` rows: resident_same_rows, x y z present, and every field the processor reads or
+    zeroes as 32-bit words (RESIDENT_F4_FIELDS: x y z opacity f_dc_* f_rest_*) that the table has is '<f4'.  A pure function of
+    the two dtypes and the two counts: no device, no table."""
+    if not resident_same_rows(rr_dtype, rr_n, dtype, n):
+        return False
+    fields = np.dtype(dtype).fields
+    f4 = np.dtype("<f4")
+    return all(nm in fields for nm in ("x", "y", "z")) and all(fields[nm][0] == f4 for nm in RESIDENT_F4_FIELDS if nm in fields)
+
+
+def resident_matches(resident, data) -> bool:
+    """does the ResidentRows `resident` (or None) hold the rows of the host table `data`, by count and dtype?"""
+    return (resident is not None and not resident.closed and isinstance(data, np.ndarray) and data.ndim == 1
+            and resident_same_rows(resident.dtype, resident.n, data.dtype, len(data)))
+
+
+def keep_kw(keep: "dict | None") -> dict:
+    """the keyword a public reader hands to its *_unpack_table: none at all without a keep dict (profile_kw's rule)"""
+    return {} if keep is None else {"keep": keep}
+
+
+def with_keep(keep: "dict | None", read):
+    """A public reader with its ``keep=`` keyword: a given dict is emptied before the read; after it, keep["rows"] stays only when
+    it holds the rows of the very table the reader returns (a fallback's table, or a failed read, closes and drops it)"""
+    if keep is None:
+        return read()
+    keep.clear()
+    try:
+        res = read()
+    except BaseException:
+        rr = keep.pop("rows", None)
+        keep.clear()
+        if rr is not None:
+            rr.close()
+        raise
+    table = res[0] if isinstance(res, tuple) else res
+    rr, of = keep.pop("rows", None), keep.pop("table", None)
+    keep.clear()
+    if rr is not None:
+        if of is table and resident_matches(rr, table):
+            keep["rows"] = rr
+        else:
+            rr.close()
+    return res
+
+
+def session_out(s: "ArenaSession", keep: "dict | None", n_dev: int, n: int, dtype: np.dtype, profile: "dict | None"):
+    """The buffer a reader's decode kernel writes its `n_dev` rows into: the session's "out" (with the profile pass's slack), or --
+    with a `keep` dict, for rows of up to 512 bytes -- the buffer of a new ResidentRows of all `n` rows, the `n - n_dev` rows
+    behind the decoded ones zeroed on the device (the compressed-PLY reader's tail).  The session closes it when its block ends
+    with an exception.  -> an object with .ptr"""
+    rb = dtype.itemsize
+    if keep is None or rb > RESIDENT_MAX_ROW_BYTES or n < 1:
+        return s.buf("out", n_dev * rb + profile_slack(profile))
+    rr = s.kept = ResidentRows(n, dtype, s.device)
+    if n > n_dev:
+        check(s.ctx.lib.gsx_dev_memset(s.ctx.handle, rr.ptr + n_dev * rb, 0, (n - n_dev) * rb), "gsx_dev_memset")
+    return rr
+
+
+def session_keep(s: "ArenaSession", keep: "dict | None", out: np.ndarray):
+    """A reader's last step in its session: with a `keep` dict and rows that session_out() put into a ResidentRows, the session's
+    stream is joined (every byte of the rows is written) and the dict receives them as keep["rows"], with the table they belong
+    to as keep["table"] (with_keep checks it against what the public reader returns, and drops it).  Without, nothing."""
+    rr, s.kept = s.kept, None
+    if rr is None:
+        return
+    s.ctx.synchronize()
+    keep["rows"], keep["table"] = rr, out
+
+
+def rows_columns_dev(ctx: "Context", rows_ptr: int, first_byte: int, dtype: np.dtype, n: int, names, out_ptr: int):
+    """gsx_rows_columns_f32_dev: the '<f4' fields `names` (1 ... 4) of `n` resident rows -> a dense (n, len(names)) array of words
+    at the device address `out_ptr` (16-byte aligned).  Asynchronous."""
+    fields = np.dtype(dtype).fields
+    offs = (C.c_int32 * len(names))(*[int(fields[nm][1]) for nm in names])
+    check(ctx.lib.gsx_rows_columns_f32_dev(ctx.handle, rows_ptr, int(first_byte), np.dtype(dtype).itemsize, int(n), offs, len(names), out_ptr),
+          "gsx_rows_columns_f32_dev")
+
+
+def rows_take_dev(ctx: "Context", rows_ptr: int, first_byte: int, stride_in: int, n_in: int, idx_ptr, n_out: int, zero_offsets, extra_ptr,
+                  e: int, out_ptr: int):
+    """gsx_rows_take_dev: the device twin of host_take_rows_shape on device addresses -- out row j = row idx[j] (idx_ptr None: row
+    j) with the 4-byte fields at `zero_offsets` zeroed and `e` bytes of extra[idx[j]] appended"""
+    zero_offsets = [int(o) for o in zero_offsets]
+    offs = (C.c_int32 * max(len(zero_offsets), 1))(*zero_offsets)
+    check(ctx.lib.gsx_rows_take_dev(ctx.handle, rows_ptr, int(first_byte), int(stride_in), int(n_in), idx_ptr, int(n_out), offs, len(zero_offsets),
+                                    extra_ptr, int(e), out_ptr, int(stride_in) + int(e)), "gsx_rows_take_dev")
+
+
+def dev_patch_u8(ctx: "Context", dst_ptr: int, dst_len: int, idx: np.ndarray, val: np.ndarray):
+    """gsx_dev_patch_u8: dst[idx[i]] = val[i] on the device, from host arrays"""
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    val = np.ascontiguousarray(val, dtype=np.uint8)
+    assert idx.shape == val.shape and idx.ndim == 1
+    check(ctx.lib.gsx_dev_patch_u8(ctx.handle, dst_ptr, int(dst_len), idx.ctypes.data, val.ctypes.data, len(idx)), "gsx_dev_patch_u8")
+
+
+def resident_rgb_dev(ctx: "Context", rr: "ResidentRows", names3, d_fdc, d_rgb, d_list, d_cnt):
+    """add_rgb_from_sh's colours (data_processor.py:316-343) of resident rows, left in HBM: the three f_dc fields through
+    gsx_rows_columns_f32_dev into `d_fdc` (12 n bytes), gsx_rgb_from_sh_list_dev into `d_rgb` (3 n bytes), then numpy's own bytes
+    for the listed, uncertain elements -- their f_dc words come back in one small download each -- through gsx_dev_patch_u8.
+    d_list: 4 (3 n // 64 + 4096) bytes, d_cnt: 16.  -> the number of patched elements, or None when the list overflowed (NaNs by
+    the million: the caller takes the host path for the colours)"""
+    n3 = 3 * rr.n
+    cap = n3 // 64 + 4096
+    rows_columns_dev(ctx, rr.ptr, rr.first_byte, rr.dtype, rr.n, names3, d_fdc.ptr)
+    check(ctx.lib.gsx_rgb_from_sh_list_dev(ctx.handle, d_fdc.ptr, n3, d_rgb.ptr, d_list.ptr, cap, d_cnt.ptr), "gsx_rgb_from_sh_list_dev")
+    cnt = int(d_cnt.download(np.uint32, 1)[0])
+    if cnt > cap:
+        return None
+    if cnt:
+        idx = np.sort(d_list.download(np.uint32, cnt))
+        # the listed words, gathered on the device into the list's own buffer (a (cnt, 1) column of 4-byte "rows")
+        d_val = d_list.ptr + ((4 * cnt + 15) & ~15)
+        if 4 * cnt + 16 + 4 * cnt <= d_list.nbytes:
+            d_list.upload(idx)
+            rows_take_dev(ctx, d_fdc.ptr, 0, 4, n3, d_list.ptr, cnt, (), None, 0, d_val)
+            v = d_list.download_at(d_val - d_list.ptr, np.float32, cnt)
+        else:
+            v = d_fdc.download(np.float32, n3)[idx]
+        with np.errstate(all="ignore"):
+            lin = np.clip(0.5 + v * 0.28209479177387814, 0.0, 1.0)
+            dev_patch_u8(ctx, d_rgb.ptr, n3, idx, (np.power(lin, 1.0 / 2.2) * 255).astype(np.uint8))
+    return cnt
 
 
 def pack_listed(s: "ArenaSession", n: int, run):
@@ -1824,7 +2077,7 @@ def splat_metric_host(data: np.ndarray) -> np.ndarray:
 
 
 def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None" = None, listed: "dict | None" = None,
-                     variant: str = "pack", device: int = 0) -> np.ndarray:
+                     variant: str = "pack", device: int = 0, resident: "ResidentRows | None" = None) -> np.ndarray:
     """The .splat writer's whole file on a splat table (formats/splat.py:82-166): the raw rows are uploaded ONCE; one device pass
     keys every row by -metric and packs its 32-byte record in input order (gsx_splat_pack_dev), a stable radix sort orders the
     keys (gsx_splat_order_dev) and the records are permuted into that order (gsx_splat_permute_dev) -> uint8[32 n], the file.
@@ -1833,12 +2086,16 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
     True) the u1 fields red, green, blue (formats/splat_writer.py checks).  variant "gather": the sort-first alternative (keys
     pass, sort, records gathered from the raw rows in sorted order), kept for the measurement of tools/probe_splat.py.
     listed: a dict that receives "exp_host" (True when the numpy probe failed: the metric, the scales and alpha then come from
-    numpy, the sort and the rest from the device).
+    numpy, the sort and the rest from the device).  resident: the rows of `data` in HBM (ResidentRows, the caller's; the same
+    count and dtype, rows of up to 512 bytes from byte 0 of their buffer): the kernels read them where they are, nothing is
+    uploaded and stage_ms has no "upload".  Everything the host computes (the numpy-exp branch) still reads `data`.
 
     One ArenaSession of the "splat" lease group."""
     lib = require_hip()
     n = len(data)
     exp_ok = np_exp_probe()
+    if not (resident_matches(resident, data) and resident.first_byte == 0 and resident.device == device):
+        resident = None
     src = data
     data = narrow_rows(data, ("red", "green", "blue") if rgb else ())
     fields = data.dtype.fields
@@ -1850,9 +2107,12 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
             return out
         join = prefault(out.nbytes >= (1 << 22), out)
         lay = spz_layout(data.dtype)
-        d_rows = s.buf("rows", data.nbytes + 64)        # (the pack kernel reads up to 15 bytes past the last row)
-        upload_table(lib, ctx, d_rows.ptr, data)
-        s.mark("upload")
+        if resident is not None:
+            d_rows = resident                           # (.ptr: 16 readable bytes behind the last row)
+        else:
+            d_rows = s.buf("rows", data.nbytes + 64)    # (the pack kernel reads up to 15 bytes past the last row)
+            upload_table(lib, ctx, d_rows.ptr, data)
+            s.mark("upload")
         d_keys, d_order = s.buf("keys", 4 * n), s.buf("order", 4 * n)
         d_recs, d_out = s.buf("recs", 32 * n), s.buf("out", 32 * n)
 
@@ -1910,7 +2170,7 @@ def cply_read_tables() -> np.ndarray:
 
 
 def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunks: int, n_vertices: int, dtype: np.dtype,
-                      stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
+                      stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The compressed-PLY reader's rows (formats/compressed_ply.py:14-124) from a binary little-endian file: the elements' bodies
     are read from `path` (segments: "chunk", "vertex", "sh" -> (file offset, bytes) or None) straight into page-locked staging,
     uploaded once, decoded by gsx_cply_unpack_dev and downloaded into a prefaulted array of `dtype` (68 + 4 n_sh bytes of
@@ -1940,7 +2200,7 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
         host, join = stage_in(s, out, total, fill, "file_read")
         d_in, d_tab = s.upload_in(lib, host, total, cply_read_tables())
         s.mark("upload")
-        d_out = s.buf("out", n_dec * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n_dec, n, dtype, profile)
         ptr = {k: d_in.ptr + place[k] for k in place}
         check(lib.gsx_cply_unpack_dev(s.ctx.handle, ptr["chunk"], int(n_chunks), ptr["vertex"], n, ptr.get("sh"), C.byref(layout), d_tab.ptr,
                                       d_out.ptr), "gsx_cply_unpack_dev")
@@ -1949,6 +2209,7 @@ def cply_unpack_table(path: str, segments: dict, layout: CplyReadLayout, n_chunk
         s.download_rows(lib, out, d_out, n_dec * rb, join)
         out.view(np.uint8)[n_dec * rb:] = 0        # rows past 256 n_chunks
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
@@ -1969,7 +2230,7 @@ def ksplat_read_tables() -> np.ndarray:
 
 def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int, sections, prefix: np.ndarray, n_coeffs: int,
                         n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0,
-                        profile: "dict | None" = None) -> np.ndarray:
+                        profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The .ksplat reader's rows (formats/ksplat.py:104-317) from a file whose headers the caller has parsed and checked
     (formats/ksplat_reader.py): `body_bytes` bytes from file offset `body_offset` are read straight into page-locked staging,
     uploaded once, decoded by gsx_ksplat_unpack_dev (sections: KsplatReadSection records with offsets inside that body; prefix:
@@ -1995,13 +2256,14 @@ def ksplat_unpack_table(path: str, body_offset: int, body_bytes: int, level: int
         if prefix.size:
             d_prefix.upload(prefix)
         s.mark("upload")
-        d_out = s.buf("out", n * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n, n, dtype, profile)
         check(lib.gsx_ksplat_unpack_dev(s.ctx.handle, d_in.ptr, total, int(level), secs, len(sections), d_prefix.ptr, int(prefix.size),
                                         d_tab.ptr, int(n_coeffs), d_out.ptr, n), "gsx_ksplat_unpack_dev")
         s.mark("kernel")
         session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
@@ -2048,7 +2310,7 @@ def spz_body_bytes(version: int, degree: int, n: int) -> int:
 
 
 def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractional_bits: int, n_rows: int, dtype: np.dtype,
-                     stage_ms: "dict | None" = None, device: int = 0, fill_stage: str = "file_read", profile: "dict | None" = None) -> np.ndarray:
+                     stage_ms: "dict | None" = None, device: int = 0, fill_stage: str = "file_read", profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The SPZ reader's rows (formats/spz.py:175-251) from a file whose header the caller has parsed and checked
     (formats/spz_reader.py): ``fill(view)`` puts the `body_bytes` bytes behind the header straight into page-locked staging
     (it raises what the reference raises on a damaged or short file: nothing has been uploaded then), one upload, decoded by
@@ -2068,13 +2330,14 @@ def spz_unpack_table(fill, body_bytes: int, version: int, degree: int, fractiona
         host, join = stage_in(s, out, total, fill, fill_stage)
         d_in, d_tab = s.upload_in(lib, host, total + 32, host_tab)   # 16-byte loads reach up to 15 bytes past the last section
         s.mark("upload")
-        d_out = s.buf("out", n * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n, n, dtype, profile)
         check(lib.gsx_spz_unpack_dev(s.ctx.handle, d_in.ptr, total, int(version), int(degree), int(fractional_bits), d_tab.ptr, d_out.ptr, n),
               "gsx_spz_unpack_dev")
         s.mark("kernel")
         session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
@@ -2142,7 +2405,7 @@ def sog_texel_layout(n: int, bands: int, palette: int):
 
 
 def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, dtype: np.dtype, on_flag=None,
-                     stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
+                     stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The SOG reader's rows (formats/sog.py:60-247) from a bundle whose meta.json the caller has parsed and checked
     (formats/sog_reader.py): ``fill(view, place)`` decodes the textures' texels straight into page-locked staging
     (sog_texel_layout; it raises what the reference raises on a missing or short texture: nothing has been uploaded then), one
@@ -2165,7 +2428,7 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
         d_flag = s.buf("flag", 16)
         check(lib.gsx_dev_memset(s.ctx.handle, d_flag.ptr, 0, 16), "gsx_dev_memset")
         s.mark("upload")
-        d_out = s.buf("out", n * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n, n, dtype, profile)
         offsets = (_I64 * 7)(*[place[t][0] if t in place else -1 for t in SOG_READ_TEXTURES])
         check(lib.gsx_sog_unpack_dev(s.ctx.handle, d_in.ptr, total, offsets, bands, palette, d_tab.ptr, d_out.ptr, n, d_flag.ptr),
               "gsx_sog_unpack_dev")
@@ -2178,6 +2441,7 @@ def sog_unpack_table(fill, n_rows: int, bands: int, palette: int, tables: dict, 
         session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
@@ -2242,7 +2506,7 @@ def splat_read_tables() -> dict:
 
 
 def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0,
-                       profile: "dict | None" = None) -> np.ndarray:
+                       profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The .splat reader's rows (formats/splat.py:9-80): the first 32 `n_rows` bytes of `path` are read straight into page-locked
     staging, uploaded once, decoded by gsx_splat_unpack_dev and downloaded into a prefaulted array of `dtype` (packed rows of 71
     bytes; formats/splat_reader.py builds it).  When np_log_probe() fails, the three scale columns are numpy's, computed on the
@@ -2255,6 +2519,8 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
     if rb != 71 or n < 1:
         raise ValueError("splat_unpack_table: %d rows of %d bytes" % (n, rb))
     log_ok = np_log_probe()
+    if not log_ok:
+        keep = None                      # (the scales are patched on the host below: the device rows are not the table's)
     total = n * SPLAT_READ_RECORD.itemsize
     tabs = splat_read_tables()
     host_tab = np.concatenate([tabs[k] for k in SPLAT_READ_TABLES])
@@ -2263,7 +2529,7 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
         host, join = stage_in(s, out, total, lambda view: read_file(path, 0, view, unit="record bytes"), "file_read")
         d_in, d_tab = s.upload_in(lib, host, total, host_tab)
         s.mark("upload")
-        d_out = s.buf("out", n * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n, n, dtype, profile)
         check(lib.gsx_splat_unpack_dev(s.ctx.handle, d_in.ptr, n, d_tab.ptr, d_out.ptr), "gsx_splat_unpack_dev")
         s.mark("kernel")
         session_profile(s, profile, d_out, n, n, dtype)
@@ -2274,11 +2540,12 @@ def splat_unpack_table(path: str, n_rows: int, dtype: np.dtype, stage_ms: "dict 
                 for f in ("scale_0", "scale_1", "scale_2"):
                     out[f] = np.log(np.maximum(recs[f], 1e-6))                    # splat.py:43-48
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
 def ply_unpack_table(path: str, body_offset: int, n_rows: int, layout: PlyReadLayout, dtype: np.dtype, stage_ms: "dict | None" = None,
-                     device: int = 0, profile: "dict | None" = None) -> np.ndarray:
+                     device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The 3DGS / CloudCompare PLY readers' rows (formats/ply_3dgs.py:45-58, formats/ply_cc.py:45-60): the vertex element's body
     (`n_rows` rows of layout.in_stride bytes at byte `body_offset` of `path`) is read straight into page-locked staging, from
     the 16-byte boundary at or below it (so row 0 sits at byte 0 ... 15 of the buffer), uploaded once, transcoded by
@@ -2299,12 +2566,13 @@ def ply_unpack_table(path: str, body_offset: int, n_rows: int, layout: PlyReadLa
         host, join = stage_in(s, out, total, lambda view: read_file(path, start, view[:used], " in element 'vertex'"), "file_read")
         d_in, _ = s.upload_in(lib, host, total)
         s.mark("upload")
-        d_out = s.buf("out", n * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n, n, dtype, profile)
         check(lib.gsx_ply_unpack_dev(s.ctx.handle, d_in.ptr, first, n, C.byref(layout), d_out.ptr), "gsx_ply_unpack_dev")
         s.mark("kernel")
         session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
@@ -2454,7 +2722,7 @@ def _parquet_fill(parts):
 
 
 def parquet_rows_table(columns, n_rows: int, fields, dtype: np.dtype, stage_ms: "dict | None" = None, device: int = 0,
-                       profile: "dict | None" = None) -> np.ndarray:
+                       profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """The Parquet reader's rows (formats/parquet.py:51-55): Arrow's column chunks are laid end to end in page-locked staging
     (parquet_rows_plan: the one host copy a pageable upload makes anyway), uploaded once, transposed and cast by
     gsx_parquet_rows_dev and downloaded into a prefaulted array of `dtype`.  n_rows = 0 -> the empty array, no launch.
@@ -2471,12 +2739,13 @@ def parquet_rows_table(columns, n_rows: int, fields, dtype: np.dtype, stage_ms: 
         host, join = stage_in(s, out, total, _parquet_fill(parts), "gather")
         d_in, _ = s.upload_in(lib, host, total)
         s.mark("upload")
-        d_out = s.buf("out", n * rb + profile_slack(profile))
+        d_out = session_out(s, keep, n, n, dtype, profile)
         check(lib.gsx_parquet_rows_dev(s.ctx.handle, d_in.ptr, total, n, C.byref(lay), d_out.ptr), "gsx_parquet_rows_dev")
         s.mark("kernel")
         session_profile(s, profile, d_out, n, n, dtype)
         s.download_rows(lib, out, d_out, n * rb, join)
         s.mark("download")
+        session_keep(s, keep, out)
         return out
 
 
@@ -2911,6 +3180,7 @@ class ArenaSession:
         self.leased = self._ar is not None and self._ar.lease(group)
         self._own = ctx is None and not self.leased
         self._bufs = []
+        self.kept = None                # session_out's ResidentRows until session_keep hands it to the caller's dict
         self._t = time.perf_counter()
 
     def __enter__(self):
@@ -2923,6 +3193,9 @@ class ArenaSession:
         return self
 
     def __exit__(self, etype, exc, tb):
+        if self.kept is not None:       # (the block ended before session_keep: nobody else knows these rows)
+            kept, self.kept = self.kept, None
+            kept.close()
         if self.leased and etype is not None and issubclass(etype, GsxError):
             self._ar.unlease(self.group)
             self.leased = False
@@ -2985,11 +3258,18 @@ class DeviceChain:
     filter leaves its mask in HBM, ``gsx_compact_rows_dev`` compacts the rows there, and the composed survivor list comes
     back once -- the 248-byte host rows are compacted once, after the last filter."""
 
-    def __init__(self, xyz_rows: "np.ndarray | None" = None, device: int = 0, keep_pristine: bool = False, table: "np.ndarray | None" = None):
+    def __init__(self, xyz_rows: "np.ndarray | None" = None, device: int = 0, keep_pristine: bool = False, table: "np.ndarray | None" = None,
+                 resident: "ResidentRows | None" = None):
         """xyz_rows: (n, 3) coordinates, or table: the structured splat table itself -- its x, y, z are then gathered (threaded, C ABI
         gsx_host_gather_f32) straight into a page-locked staging buffer of the arena: no 12n-byte temporary whose pages are faulted
-        in, copied from at pageable rate and unmapped again (9 + 5 + 9 ms of configs.dropin_e2e_10m's 37)"""
-        if table is None:
+        in, copied from at pageable rate and unmapped again (9 + 5 + 9 ms of configs.dropin_e2e_10m's 37) --, or resident: the
+        table's rows in HBM (ResidentRows, the caller's: not closed here) -- its '<f4' x, y, z are then gathered device to device
+        (gsx_rows_columns_f32_dev): no host gather, no pinned staging, no upload"""
+        self.resident = resident
+        a = None
+        if resident is not None:
+            device = resident.device
+        elif table is None:
             a = np.ascontiguousarray(xyz_rows, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != 3:
                 raise ValueError("Requires 3D data")
@@ -3005,7 +3285,7 @@ class DeviceChain:
         self.rows = self.spare = self.orig = self.mask = self.pristine = self._md = self._st = None
         self._pool = []
         try:
-            if table is not None:
+            if resident is None and table is not None:
                 n_t = len(table)
                 # (exact=False: a row filter may start the chain on any table; DataProcessor checks f32_inexact_field before SOR, the
                 #  density filter or the box take the float32 copy for the table's values)
@@ -3013,7 +3293,7 @@ class DeviceChain:
                     a = host_gather_xyz(table, out=ar.pinned("chain_xyz", 12 * n_t)[:12 * n_t].view(np.float32).reshape(n_t, 3), exact=False)
                 else:
                     a = host_gather_xyz(table, exact=False)
-            self._setup(a, device, keep_pristine, table is not None)
+            self._setup(a, device, keep_pristine, table is not None or resident is not None)
         except BaseException:
             self.close()                    # (gives the lease back; a private context and its buffers are freed)
             raise
@@ -3022,17 +3302,21 @@ class DeviceChain:
         self.ctx = self._ar.context("chain") if self._ar is not None else Context(device)
         self._names = iter(range(1 << 30))
         self.ctx.set_param("adaptive", 1)   # every step below synchronises anyway
-        self.n0 = self.n = int(a.shape[0])
-        self.rows = self._alloc(max(a.nbytes, 16), "rows")
-        if a.nbytes >= (32 << 20) and not pinned_source:      # through the pinned staging lanes: a caller's array is pageable memory
-            check(self.ctx.lib.gsx_dev_upload_staged(self.ctx.handle, self.rows.ptr, a.ctypes.data, a.nbytes), "gsx_dev_upload_staged")
+        rr = self.resident
+        self.n0 = self.n = rr.n if rr is not None else int(a.shape[0])
+        nbytes = 12 * self.n0
+        self.rows = self._alloc(max(nbytes, 16), "rows")
+        if rr is not None:
+            rows_columns_dev(self.ctx, rr.ptr, rr.first_byte, rr.dtype, rr.n, ("x", "y", "z"), self.rows.ptr)
+        elif nbytes >= (32 << 20) and not pinned_source:      # through the pinned staging lanes: a caller's array is pageable memory
+            check(self.ctx.lib.gsx_dev_upload_staged(self.ctx.handle, self.rows.ptr, a.ctypes.data, nbytes), "gsx_dev_upload_staged")
         else:
             self.rows.upload(a)
-        self.spare = self._alloc(max(a.nbytes, 16), "spare")
+        self.spare = self._alloc(max(nbytes, 16), "spare")
         # bench.py only: a second device copy of the uploaded rows, so that restart() can run the chain again without PCIe
-        self.pristine = self._alloc(max(a.nbytes, 16), "pristine") if keep_pristine else None
+        self.pristine = self._alloc(max(nbytes, 16), "pristine") if keep_pristine else None
         if self.pristine is not None:
-            check(self.ctx.lib.gsx_dev_copy(self.ctx.handle, self.pristine.ptr, self.rows.ptr, a.nbytes), "gsx_dev_copy")
+            check(self.ctx.lib.gsx_dev_copy(self.ctx.handle, self.pristine.ptr, self.rows.ptr, nbytes), "gsx_dev_copy")
         self.orig = None                    # None = identity
         self._pool = []                     # survivor-list buffers not in use (4 n0 bytes each; at most two ever exist)
         self.empty = False                  # keep_none(): no survivor, whatever self.orig says
@@ -3172,12 +3456,24 @@ class DeviceChain:
         check(self.ctx.lib.gsx_mask_bbox_dev(self.ctx.handle, self.rows.ptr, self.n, b.ctypes.data, self.mask.ptr), "gsx_mask_bbox_dev")
         return self._compact()
 
-    def ge_keep(self, column: np.ndarray, threshold: float) -> int:
-        """rows whose value in ``column`` (float32, one per row of the table the chain started from) is >= threshold"""
-        col = np.ascontiguousarray(column, dtype=np.float32)
-        if col.shape != (self.n0,):
-            raise ValueError("column must have one value per original row")
-        dev = self._alloc(max(col.nbytes, 16), "column").upload(col)
+    def resident_column(self, name: str):
+        """the '<f4' field `name` of the resident rows the chain started from as a device column for ge_keep (the chain's buffer
+        "column": the next ge_keep or resident_column overwrites it; a private one is freed by ge_keep)"""
+        rr = self.resident
+        dev = self._alloc(max(4 * self.n0, 16), "column")
+        rows_columns_dev(self.ctx, rr.ptr, rr.first_byte, rr.dtype, rr.n, (name,), dev.ptr)
+        return dev
+
+    def ge_keep(self, column, threshold: float) -> int:
+        """rows whose value in ``column`` (float32, one per row of the table the chain started from) is >= threshold; column: a
+        host array, or resident_column()'s device column"""
+        if isinstance(column, DeviceArray):
+            dev = column
+        else:
+            col = np.ascontiguousarray(column, dtype=np.float32)
+            if col.shape != (self.n0,):
+                raise ValueError("column must have one value per original row")
+            dev = self._alloc(max(col.nbytes, 16), "column").upload(col)
         try:
             check(self.ctx.lib.gsx_mask_ge_dev(self.ctx.handle, dev.ptr, self.orig.ptr if self.orig is not None else None, self.n,
                                                float(threshold), self.mask.ptr), "gsx_mask_ge_dev")

@@ -183,7 +183,7 @@ def report_info(input_path, converter_obj=None):
     try:
         print(f"Size: {os.path.getsize(abs_path) / (1024 * 1024):.2f} MB")
         if converter_obj is None:
-            converter_obj = Converter(abs_path, "dummy_out.ply", "3dgs")
+            converter_obj = Converter(abs_path, "dummy_out.ply", "3dgs", resident=False)   # (the info block reads the profile alone)
         if converter_obj.data is None:
             converter_obj.load_source_only()
         for line in info_lines(input_path, converter_obj):

@@ -10,6 +10,11 @@ readers, filter chain and writers: a file is converted on a machine that has thi
   | :150-252 DataProcessor, the filters in order      | processing.ChainedDataProcessor: one device-resident chain          |
   | :263-288 extra elements, the handler's write      | the format's write_*                                                |
 
+The decoded rows stay in HBM from the reader to the end of the run (``Converter(..., resident=True)``, the default; readers'
+``keep=``, _lib.ResidentRows): the chain's coordinates, the alpha filter's column and the colours' f_dc are gathered from them
+on the device, the survivors are taken there (csrc/resident_rows.hip) and downloaded once, and the .splat writer reads the
+result where it lies.  ``resident=False``, or a reader that kept nothing, is the path through the host table.
+
 What the user sees -- the ``status_print`` / ``debug_print`` lines, their order, the exceptions and their messages -- is the
 reference's.  A file the device readers do not take raises that reader's ``Unsupported*Error``: there is no second reader to
 fall back to.  The reference's SOR branch without Taichi computes its mask and returns the table unfiltered (SURVEY.md F3);
@@ -97,26 +102,43 @@ class SourceHandler:
         self.format_name = format_name
         self.profile = None
         self.opens = 0              # decodes of a source file through this handler
+        self.keep = True            # ask the reader to keep the decoded rows in HBM
+        self.resident = None        # ... the last read's _lib.ResidentRows (the caller takes them over and closes them), or None
 
     def read(self, path: str, stage_ms: "dict | None" = None):
         name, profile = self.format_name, {}
         self.opens += 1
+        self.close()
+        keep = {} if self.keep else None
+        kw = {"stage_ms": stage_ms, "profile": profile, **({} if keep is None else {"keep": keep})}
         if name in ("3dgs", "cc"):
             from .formats import ply_reader
-            data, self.extra_elements = (ply_reader.read_ply_3dgs if name == "3dgs" else ply_reader.read_ply_cc)(path, stage_ms=stage_ms, profile=profile)
+            data, self.extra_elements = (ply_reader.read_ply_3dgs if name == "3dgs" else ply_reader.read_ply_cc)(path, **kw)
         elif name == "compressed_ply":
             from .formats.compressed_ply_reader import read_compressed_ply
-            data, _ = read_compressed_ply(path, stage_ms=stage_ms, on_metadata=lambda m: setattr(self, "metadata", m), profile=profile)
+            data, _ = read_compressed_ply(path, on_metadata=lambda m: setattr(self, "metadata", m), **kw)
         elif name == "ksplat":
             from .formats.ksplat_reader import read_ksplat
-            data, _ = read_ksplat(path, stage_ms=stage_ms, on_metadata=lambda m: setattr(self, "metadata", m), profile=profile)
+            data, _ = read_ksplat(path, on_metadata=lambda m: setattr(self, "metadata", m), **kw)
         else:
             from .formats import parquet_reader, sog_reader, splat_reader, spz_reader
             read = {"parquet": parquet_reader.read_parquet, "splat": splat_reader.read_splat, "spz": spz_reader.read_spz,
                     "sog": sog_reader.read_sog}[name]
-            data = read(path, stage_ms=stage_ms, profile=profile)
+            data = read(path, **kw)
         self.profile = profile
+        self.resident = keep.get("rows") if keep else None
         return data
+
+    def take_resident(self):
+        """-> the last read's rows in HBM, which are the caller's from here on (None: nothing was kept)"""
+        rr, self.resident = self.resident, None
+        return rr
+
+    def close(self):
+        """free the rows the last read kept, unless somebody took them over (idempotent)"""
+        rr = self.take_resident()
+        if rr is not None:
+            rr.close()
 
     def write(self, data, path: str, stage_ms: "dict | None" = None, **kwargs):
         name = self.format_name
@@ -129,6 +151,8 @@ class SourceHandler:
             return write(data, path, **({} if stage_ms is None else {"stage_ms": stage_ms}))
         if stage_ms is not None and name not in ("sog", "compressed_ply"):
             kwargs = dict(kwargs, stage_ms=stage_ms)
+        if name != "splat":         # (the one writer that reads resident rows)
+            kwargs.pop("resident", None)
         return write(data, path, **kwargs)
 
 
@@ -154,7 +178,10 @@ def progress_bar():
 
 
 class Converter:
-    def __init__(self, input_path, output_path, target_format):
+    def __init__(self, input_path, output_path, target_format, resident=True):
+        """resident: keep the reader's decoded rows in HBM for the filters, the one materialise and the .splat writer (module
+        docstring); False: every stage works from the host table"""
+        self.resident = bool(resident)
         self.input_path = input_path
         self.output_path = output_path
         self.target_format = target_format.lower()
@@ -171,7 +198,22 @@ class Converter:
         return detect_format(path)
 
     def _get_format_handler(self, format_name):
-        return SourceHandler(format_name)
+        handler = SourceHandler(format_name)
+        handler.keep = self.resident
+        return handler
+
+    def close(self):
+        """free what a load_source_only() without a run() left in HBM (idempotent; run() closes everything itself)"""
+        if self._loaded is not None and hasattr(self._loaded[1], "close"):
+            self._loaded[1].close()
+        if self.source_handler is not None and hasattr(self.source_handler, "close"):
+            self.source_handler.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def load_source_only(self):
         """:63-72: detect, read, keep -- and remember the table with its profile for a run() on the same path"""
@@ -186,10 +228,20 @@ class Converter:
         return self.data
 
     def run(self, **kwargs):
-        import time
-        from .processing.data_processor import ChainedDataProcessor
         debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
         clocks = self.stage_ms = {}
+        held = []                   # the processor of this run: whatever it still holds in HBM is freed on every exit path
+        try:
+            self._run(clocks, held, kwargs)
+        finally:
+            for p in held:
+                p.close()
+            self.close()
+        status_print(f"Conversion completed: Saved to {self.output_path}")
+
+    def _run(self, clocks, held, kwargs):
+        import time
+        from .processing.data_processor import ChainedDataProcessor
         with progress_bar() as pbar:
             source_format = self._detect_format(self.input_path)
             if not source_format:
@@ -212,7 +264,9 @@ class Converter:
             plan = plan_conversion(self.data.dtype.names, self.profile["rest_nonzero"], self.target_format, kwargs)
             pbar.set_description("Processing")
             t0 = time.perf_counter()
-            processor = ChainedDataProcessor(self.data)
+            kept = self.source_handler.take_resident() if hasattr(self.source_handler, "take_resident") else None
+            processor = ChainedDataProcessor(self.data, resident=kept) if kept is not None else ChainedDataProcessor(self.data)
+            held.append(processor)
             self.format_max_sh = dict(FORMAT_MAX_SH)
             for line in plan["messages"]:
                 status_print(line)
@@ -243,6 +297,9 @@ class Converter:
             pbar.update(5)
             self.data = processor.data
             clocks["process"] = round((time.perf_counter() - t0) * 1e3, 3)
+            clocks.update({"process_" + k: v for k, v in getattr(processor, "resident_ms", {}).items()})
+            if self.target_format == "splat" and getattr(processor, "resident", None) is not None:
+                kwargs = dict(kwargs, resident=processor.resident)
 
             pbar.set_description(f"Writing {self.target_format.upper()}")
             extras = getattr(self.source_handler, "extra_elements", None)
@@ -261,4 +318,3 @@ class Converter:
             pbar.update(40)
             pbar.refresh()
             pbar.set_description("Completed")
-        status_print(f"Conversion completed: Saved to {self.output_path}")

@@ -200,7 +200,7 @@ def layout_of(h: PlyHeader) -> "_lib.CplyReadLayout":
     return lay
 
 
-def read_compressed_ply(path: str, stage_ms: "dict | None" = None, fallback=None, on_metadata=None, profile: "dict | None" = None):
+def read_compressed_ply(path: str, stage_ms: "dict | None" = None, fallback=None, on_metadata=None, profile: "dict | None" = None, keep: "dict | None" = None):
     """:14-124 -> (rows, metadata): the reference's structured array (BASE_FIELDS, then the sh element's properties in file
     order, all <f4) and its metadata dict (count, sh_degree, chunks).
 
@@ -209,11 +209,12 @@ def read_compressed_ply(path: str, stage_ms: "dict | None" = None, fallback=None
     UnsupportedPlyError.  on_metadata: called with the metadata as soon as it is known (where the reference sets
     ``self.metadata``, before its loop can fail).  stage_ms: a dict that receives per-stage clocks (tools/probe_cply_read.py).
     profile: a dict that receives the returned table's profile (_lib.TableProfile.as_dict), the zero rows past 256 x chunks
-    included, from one more pass over the decoded rows before their download (stage clock "profile")."""
-    return _lib.with_profile(profile, lambda: _read(path, stage_ms, fallback, on_metadata, profile))
+    included, from one more pass over the decoded rows before their download (stage clock "profile").  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise.  The zero rows past 256 x chunks are zeroed on the device too."""
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, stage_ms, fallback, on_metadata, profile, keep)))
 
 
-def _read(path, stage_ms, fallback, on_metadata, profile):
+def _read(path, stage_ms, fallback, on_metadata, profile, keep=None):
     debug_print(f"[DEBUG] Reading Compressed PLY file from {path}")
     t0 = time.perf_counter()
     h = parse_header(path)
@@ -241,7 +242,7 @@ def _read(path, stage_ms, fallback, on_metadata, profile):
         return np.zeros(vertex.count, dtype), metadata
     segments = {"chunk": (chunk.body_offset, chunk.stride * chunk.count), "vertex": (vertex.body_offset, vertex.stride * n_dec),
                 "sh": (sh.body_offset, sh.stride * n_dec) if sh_names else None}
-    rows = _lib.cply_unpack_table(path, segments, layout_of(h), chunk.count, vertex.count, dtype, stage_ms=stage_ms, **_lib.profile_kw(profile))
+    rows = _lib.cply_unpack_table(path, segments, layout_of(h), chunk.count, vertex.count, dtype, stage_ms=stage_ms, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"Compressed PLY read completed. {vertex.count} points in {chunk.count} chunks.")
     return rows, metadata
 

@@ -239,7 +239,7 @@ def _installed_original():
 
 
 def read_ksplat(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, on_metadata=None,
-                profile: "dict | None" = None):
+                profile: "dict | None" = None, keep: "dict | None" = None):
     """:29-317 -> (rows, metadata): the reference's structured array (define_dtype of the largest section degree, all <f4; nx ny
     nz and the f_rest fields a section does not carry are 0) and its metadata dict.
 
@@ -247,11 +247,12 @@ def read_ksplat(path: str, stage_ms: "dict | None" = None, device: int = 0, *, f
     read when install() has saved one, else such files raise UnsupportedKSplatError.  on_metadata: called with the metadata as
     soon as the reference would have set ``self.metadata``.  stage_ms: a dict that receives the stage clocks parse, file_read,
     upload, kernel, download (tools/probe_ksplat_read.py).  profile: a dict that receives the returned table's profile
-    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
-    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, on_metadata, profile))
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile").  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise."""
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, on_metadata, profile, keep)))
 
 
-def _read(path, stage_ms, device, fallback, on_metadata, profile):
+def _read(path, stage_ms, device, fallback, on_metadata, profile, keep=None):
     debug_print(f"[DEBUG] Reading .ksplat file from {path}")
     t0 = time.perf_counter()
     try:
@@ -270,7 +271,7 @@ def _read(path, stage_ms, device, fallback, on_metadata, profile):
     if p.n_rows == 0:                      # :275-277, or sections without rows
         return np.zeros(0, dtype), metadata
     rows = _lib.ksplat_unpack_table(path, p.payload_offset, p.body_bytes, p.level, device_sections(p), p.prefix, n_coeffs_of(p.degree),
-                                    p.n_rows, dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
+                                    p.n_rows, dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"[DEBUG] KSplat read completed. {p.n_rows} splats in {len(p.sections)} sections.")
     return rows, metadata
 

@@ -191,7 +191,7 @@ def _clock(stage_ms, name, t0):
         stage_ms[name] = round(stage_ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3, 3)
 
 
-def read_parquet(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
+def read_parquet(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """parquet.py:8-57 -> the reference's structured array (define_dtype(has_scal=False, has_rgb) at sh_degree=3, packed,
     little-endian).
 
@@ -199,11 +199,12 @@ def read_parquet(path: str, stage_ms: "dict | None" = None, fallback=None, devic
     UnsupportedParquetError.  stage_ms: a dict that receives the stage clocks plan, decode (pq.read_table), gather (Arrow's
     chunks into page-locked staging), upload, kernel, download (tools/probe_parquet.py).  n = 0 returns the empty array of the
     plan's dtype without a launch.  profile: a dict that receives the returned table's profile (_lib.TableProfile.as_dict) from
-    one more pass over the transposed rows before their download (stage clock "profile")."""
-    return _lib.with_profile(profile, lambda: _read(path, stage_ms, fallback, device, profile))
+    one more pass over the transposed rows before their download (stage clock "profile").  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise."""
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, stage_ms, fallback, device, profile, keep)))
 
 
-def _read(path, stage_ms, fallback, device, profile):
+def _read(path, stage_ms, fallback, device, profile, keep=None):
     import pyarrow.parquet as pq
     debug_print(f"[DEBUG] Reading Parquet file from {path}")
 
@@ -237,7 +238,7 @@ def _read(path, stage_ms, fallback, device, profile):
     index_of = {c: k for k, c in enumerate(p.columns)}
     src_type = {f.source: f.src_type for f in p.fields if f.source is not None}
     columns = [arrow_chunks(table.column(c), src_type[c]) for c in p.columns]
-    rows = _lib.parquet_rows_table(columns, n, p.descriptors(index_of), p.dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
+    rows = _lib.parquet_rows_table(columns, n, p.descriptors(index_of), p.dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"[DEBUG] Loaded {n} rows from Parquet")
     return rows
 

@@ -212,7 +212,7 @@ def read_extra_elements(path: str, header: PlyHeader) -> list:
     return out
 
 
-def _read(path: str, dialect: str, stage_ms, fallback, device, profile=None):
+def _read(path: str, dialect: str, stage_ms, fallback, device, profile=None, keep=None):
     t0 = time.perf_counter()
     h = parse_header(path)
     p = plan(h, dialect)
@@ -236,12 +236,12 @@ def _read(path: str, dialect: str, stage_ms, fallback, device, profile=None):
         if stage_ms is not None:
             stage_ms["file_read"] = round((time.perf_counter() - t1) * 1e3, 3)
     else:
-        rows = _lib.ply_unpack_table(path, p.body_offset, p.count, p.layout(), p.dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
+        rows = _lib.ply_unpack_table(path, p.body_offset, p.count, p.layout(), p.dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"[DEBUG] Loaded {p.count} points from PLY ({dialect})")
     return rows, extras
 
 
-def read_ply_3dgs(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None):
+def read_ply_3dgs(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None):
     """ply_3dgs.py:8-60 -> (rows, extra_elements): the reference's structured array (define_dtype(has_scal=False, has_rgb,
     extra_fields) at sh_degree=3, packed, little-endian) and the non-vertex elements.
 
@@ -251,15 +251,16 @@ def read_ply_3dgs(path: str, stage_ms: "dict | None" = None, fallback=None, devi
     has no upload, kernel or download.  A body that ends early raises _lib.read_exact's ValueError (plyfile's own exception
     class cannot be matched without plyfile).  profile: a dict that receives the returned
     table's profile (_lib.TableProfile.as_dict): from one more pass over the transcoded rows before their download (stage clock
-    "profile"), or from the threaded host pass for a file that is read into the result."""
+    "profile"), or from the threaded host pass for a file that is read into the result.  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise (a file that is read into the result among them)."""
     debug_print(f"[DEBUG] Reading 3DGS PLY file from {path}")
-    return _lib.with_profile(profile, lambda: _read(path, "3dgs", stage_ms, fallback, device, profile))
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, "3dgs", stage_ms, fallback, device, profile, keep)))
 
 
-def read_ply_cc(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None):
+def read_ply_cc(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None):
     """ply_cc.py:8-62 -> (rows, extra_elements); see read_ply_3dgs"""
     debug_print(f"[DEBUG] Reading CC PLY file from {path}")
-    return _lib.with_profile(profile, lambda: _read(path, "cc", stage_ms, fallback, device, profile))
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, "cc", stage_ms, fallback, device, profile, keep)))
 
 
 def _bind(original, reader):

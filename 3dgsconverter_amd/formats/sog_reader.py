@@ -148,7 +148,7 @@ def _installed_original():
     return fallback
 
 
-def read_sog(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, profile: "dict | None" = None) -> np.ndarray:
+def read_sog(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """:23-247 -> the reference's structured array: define_dtype(has_scal=False, has_rgb=False) of the file's bands, float32
     fields, packed; nx ny nz zero.
 
@@ -156,11 +156,12 @@ def read_sog(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fall
     1 ... 65 536, a count that is no non-negative int, anything in meta.json of another type than the writer's); by default the
     reference's own read when install() has saved one, else such files raise UnsupportedSogError.  stage_ms: a dict that
     receives the stage clocks parse, decode, upload, kernel, download (tools/probe_sog_read.py).  profile: a dict that receives the returned table's profile
-    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
-    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, profile))
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile").  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise."""
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, profile, keep)))
 
 
-def _read(path, stage_ms, device, fallback, profile):
+def _read(path, stage_ms, device, fallback, profile, keep=None):
     debug_print(f"[DEBUG] Reading .sog file from {path}")
     t0 = time.perf_counter()
     if not Image:
@@ -228,7 +229,7 @@ def _read(path, stage_ms, device, fallback, profile):
             place, total = _lib.sog_texel_layout(0, bands, palette)
             fill(np.empty(total, np.uint8), place)
             return np.zeros(0, dtype)
-        rows = _lib.sog_unpack_table(fill, n, bands, palette, tables, dtype, on_flag=on_flag, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
+        rows = _lib.sog_unpack_table(fill, n, bands, palette, tables, dtype, on_flag=on_flag, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"[DEBUG] SOG read completed. {n} splats, {bands} SH bands.")
     return rows
 

@@ -27,16 +27,17 @@ from .spz_reader import define_dtype
 RECORD_BYTES = 32                                                                  # splat.py:15
 
 
-def read_splat(path: str, stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None) -> np.ndarray:
+def read_splat(path: str, stage_ms: "dict | None" = None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """:9-80 -> the reference's structured array: define_dtype(has_scal=False, has_rgb=True, sh_degree=0), float32 fields then
     red green blue as bytes, packed; nx ny nz and red green blue zero.
 
     stage_ms: a dict that receives the stage clocks parse, file_read, upload, kernel, download (tools/probe_splat_read.py).  profile: a dict that receives the returned table's profile
-    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
-    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, profile))
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile").  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise."""
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, stage_ms, device, profile, keep)))
 
 
-def _read(path, stage_ms, device, profile):
+def _read(path, stage_ms, device, profile, keep=None):
     debug_print(f"[DEBUG] Reading .splat file from {path}")
     t0 = time.perf_counter()
     file_size = os.path.getsize(path)
@@ -51,7 +52,7 @@ def _read(path, stage_ms, device, profile):
         stage_ms["parse"] = round((time.perf_counter() - t0) * 1e3, 3)
     if n == 0:
         return np.zeros(0, dtype)
-    rows = _lib.splat_unpack_table(path, n, dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile))
+    rows = _lib.splat_unpack_table(path, n, dtype, stage_ms=stage_ms, device=device, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"[DEBUG] Loaded {n} points from .splat")
     return rows
 

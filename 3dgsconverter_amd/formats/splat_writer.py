@@ -55,20 +55,21 @@ def check_fields(data: np.ndarray) -> bool:
     return rgb
 
 
-def encode(data: np.ndarray, listed: "dict | None" = None, stage_ms: "dict | None" = None) -> np.ndarray:
+def encode(data: np.ndarray, listed: "dict | None" = None, stage_ms: "dict | None" = None, resident=None) -> np.ndarray:
     """-> uint8[32 n]: the file's bytes"""
     rgb = check_fields(data)
     if len(data) == 0:
         return np.empty(0, np.uint8)
-    return _lib.splat_pack_table(data, rgb, stage_ms=stage_ms, listed=listed)
+    return _lib.splat_pack_table(data, rgb, stage_ms=stage_ms, listed=listed, **({} if resident is None else {"resident": resident}))
 
 
-def write_splat(data: np.ndarray, path: str, stage_ms: "dict | None" = None, listed: "dict | None" = None, **kwargs) -> None:
+def write_splat(data: np.ndarray, path: str, stage_ms: "dict | None" = None, listed: "dict | None" = None, resident=None, **kwargs) -> None:
     """splat.py:82-166.  stage_ms: a dict that receives per-stage clocks (tools/probe_splat.py); listed: see
-    _lib.splat_pack_table"""
+    _lib.splat_pack_table.  resident: the rows of `data` in HBM (_lib.ResidentRows, the caller's, not closed here): when they
+    match `data` by count and dtype the table is not uploaded and stage_ms has no "upload" key"""
     import time
     debug_print(f"[DEBUG] Writing .splat file to {path}")
-    out = encode(data, listed, stage_ms)
+    out = encode(data, listed, stage_ms, resident)
     t0 = time.perf_counter()
     with open(path, "wb") as f:
         f.write(memoryview(out))

@@ -145,7 +145,7 @@ def _installed_original():
     return fallback
 
 
-def _decode(path, src: "Source | None", head: bytes, avail: "int | None", fill_stage, t0, stage_ms, device, fallback, profile=None):
+def _decode(path, src: "Source | None", head: bytes, avail: "int | None", fill_stage, t0, stage_ms, device, fallback, profile=None, keep=None):
     """the header `head`, then the body: from `src` (an inflated stream; its length shows only at its end) or, without one,
     from byte 16 of the file (`avail` body bytes)"""
     try:
@@ -182,40 +182,41 @@ def _decode(path, src: "Source | None", head: bytes, avail: "int | None", fill_s
         src.drain()
         if got < need:
             raise ValueError(SMALLER)
-    rows = _lib.spz_unpack_table(fill, need, version, degree, bits, n, dtype, stage_ms=stage_ms, device=device, fill_stage=fill_stage, **_lib.profile_kw(profile))
+    rows = _lib.spz_unpack_table(fill, need, version, degree, bits, n, dtype, stage_ms=stage_ms, device=device, fill_stage=fill_stage, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
     debug_print(f"[DEBUG] SPZ read completed. {n} splats of degree {degree}.")
     return rows
 
 
-def read_spz(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, profile: "dict | None" = None) -> np.ndarray:
+def read_spz(path: str, stage_ms: "dict | None" = None, device: int = 0, *, fallback=None, profile: "dict | None" = None, keep: "dict | None" = None) -> np.ndarray:
     """:18-47 -> the reference's structured array: define_dtype(has_rgb=True) of the file's SH degree, float32 fields then red
     green blue as bytes, packed; nx ny nz zero.
 
     fallback: a function path -> rows for the files the device path does not take; by default the reference's own read when
     install() has saved one, else such files raise UnsupportedSpzError.  stage_ms: a dict that receives the stage clocks parse,
     inflate (file_read for a file that is not gzipped), upload, kernel, download (tools/probe_spz_read.py).  profile: a dict that receives the returned table's profile
-    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile")."""
-    return _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, profile))
+    (_lib.TableProfile.as_dict) from one more pass over the decoded rows before their download (stage clock "profile").  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
+    closes it) when the returned table's rows are resident; it stays empty otherwise."""
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, stage_ms, device, fallback, profile, keep)))
 
 
-def _read(path, stage_ms, device, fallback, profile):
+def _read(path, stage_ms, device, fallback, profile, keep=None):
     debug_print(f"[DEBUG] Reading .spz file from {path}")
     t0 = time.perf_counter()
     size = os.path.getsize(path)
     with open(path, "rb") as f:
         head = f.read(_lib.SPZ_HEADER_BYTES)
     if not (size > 2 and head[:2] == b"\x1f\x8b"):                                  # :25
-        return _decode(path, None, head, size - len(head), "file_read", t0, stage_ms, device, fallback, profile)
+        return _decode(path, None, head, size - len(head), "file_read", t0, stage_ms, device, fallback, profile, keep)
     try:
         with open(path, "rb") as f:
             src = Source(inflate_chunks(f))
-            return _decode(path, src, src.read(_lib.SPZ_HEADER_BYTES), None, "inflate", t0, stage_ms, device, fallback, profile)
+            return _decode(path, src, src.read(_lib.SPZ_HEADER_BYTES), None, "inflate", t0, stage_ms, device, fallback, profile, keep)
     except (zlib.error, EOFError):
         pass
     with open(path, "rb") as f:                                                      # :22, :29 -- the reference's statement raises
         raw = gzip.decompress(f.read())
     src = Source([memoryview(raw)[_lib.SPZ_HEADER_BYTES:]])                          # (a stream only gzip's own reader accepts)
-    return _decode(path, src, raw[:_lib.SPZ_HEADER_BYTES], None, "inflate", t0, stage_ms, device, fallback, profile)
+    return _decode(path, src, raw[:_lib.SPZ_HEADER_BYTES], None, "inflate", t0, stage_ms, device, fallback, profile, keep)
 
 
 def bind_read(original):

@@ -89,7 +89,21 @@ class DataProcessor:
 
     lazy_default = False
 
-    def __init__(self, data, lazy=None):
+    def __init__(self, data, lazy=None, resident=None):
+        """resident: the rows of `data` in HBM as a reader kept them (_lib.ResidentRows; this object owns them from here on and
+        ``close()`` frees them).  A lazy processor then gathers the chain's coordinates, the alpha filter's column and the colours'
+        f_dc from those rows on the device, and ``.data`` is ONE gsx_rows_take_dev -- survivors, zeroed fields, colours -- and
+        one download; ``.resident`` is the rows of ``.data`` in HBM.  Rows that are not `data`'s (_lib.resident_eligible), or an
+        eager processor: closed here, and everything runs as without them."""
+        self._rr = None             # the rows of self._data in HBM (owned), or None: the host path
+        self.resident_ms = {}       # clocks of the resident path: gather, take, download
+        if resident is not None:
+            lazy_now = DataProcessor.lazy_default if lazy is None else bool(lazy)
+            if (lazy_now and isinstance(data, np.ndarray) and data.ndim == 1 and not resident.closed
+                    and _lib.resident_eligible(resident.dtype, resident.n, data.dtype, len(data))):
+                self._rr = resident
+            else:
+                resident.close()
         self._data = data
         self._chain = None          # _lib.DeviceChain over the rows of self._data, or None
         self._pending_zero = []     # lazy cap_sh_degree: columns to zero once the host table has been compacted
@@ -115,17 +129,104 @@ class DataProcessor:
         self._pending_zero = []
         self._pending_rgb = None
         self._drop_chain()
+        self._drop_resident()       # (the rows in HBM were the old table's)
         self._data = value
+
+    @property
+    def resident(self):
+        """the rows of ``.data`` in HBM (_lib.ResidentRows, this object's: ``close()`` frees them), or None whenever the host path
+        produced ``.data``"""
+        self._materialize()
+        return self._rr
+
+    def close(self):
+        """give the device chain and the resident rows back (idempotent; ``.data`` stays)"""
+        self._drop_chain()
+        self._drop_resident()
 
     def _drop_chain(self):
         if self._chain is not None:
             self._chain.close()
             self._chain = None
 
+    def _drop_resident(self):
+        if self._rr is not None:
+            rr, self._rr = self._rr, None
+            rr.close()
+
+    def _clock(self, name, t0, ctx=None):
+        import time
+        if ctx is not None:
+            ctx.synchronize()
+        self.resident_ms[name] = round(self.resident_ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3, 3)
+
+    def _materialize_resident(self, copy_always):
+        """_materialize on the rows in HBM: one gsx_rows_take_dev for the chain's survivors, the pending zero fields and the pending
+        colours, one download into a prefaulted table.  -> False when this table is not taken (the widened dtype does not end in
+        the three bytes): the resident rows are dropped, pending device colours come to the host, and the host path runs"""
+        import time
+        rr, ch = self._rr, self._chain
+        rgb = self._pending_rgb
+        compact = ch is not None and (ch.n != ch.n0 or ch.empty)
+        if not (compact or copy_always or rgb is not None or self._pending_zero):
+            self._drop_chain()
+            self.resident_ms.setdefault("take", 0.0)        # (the resident path ran, and had nothing to take)
+            return True                                     # .data is the caller's table, .resident its rows
+        src = self._data
+        names = ("red", "green", "blue") if rgb is not None else ()
+        new_dtype = np.dtype(src.dtype.descr + [(nm, "u1") for nm in names]) if names else src.dtype
+        tail_ok = all(new_dtype.fields[nm][1] == src.dtype.itemsize + i for i, nm in enumerate(names))
+        if not tail_ok or new_dtype.itemsize != src.dtype.itemsize + len(names) or new_dtype.itemsize > _lib.RESIDENT_MAX_ROW_BYTES:
+            if isinstance(rgb, _lib.DeviceArray):
+                self._pending_rgb = rgb.download(np.uint8, 3 * rr.n).reshape(rr.n, 3)
+                ch._free(rgb)
+            self._drop_resident()
+            return False
+        self._chain = None
+        self._pending_rgb = None
+        zero, self._pending_zero = self._pending_zero, []
+        out_rr = d_extra = None
+        try:
+            n_out = 0 if (ch is not None and (ch.empty or ch.n == 0)) else (ch.n if ch is not None else rr.n)
+            out = np.empty(n_out, new_dtype)
+            out_rr = _lib.ResidentRows(n_out, new_dtype, rr.device)
+            if n_out:
+                join = _lib.prefault_parallel(out)
+                ctx = ch.ctx if ch is not None else rr._ctx
+                if rgb is not None:
+                    d_extra = rgb if isinstance(rgb, _lib.DeviceArray) else ch._alloc(3 * rr.n + 16, "rgbhost").upload(np.ascontiguousarray(rgb, np.uint8))
+                t0 = time.perf_counter()
+                idx = ch.orig.ptr if (ch is not None and ch.orig is not None and compact) else None
+                _lib.rows_take_dev(ctx, rr.ptr, rr.first_byte, src.dtype.itemsize, rr.n, idx, n_out,
+                                   [src.dtype.fields[nm][1] for nm in zero if nm in src.dtype.fields],
+                                   d_extra.ptr if d_extra is not None else None, len(names), out_rr.ptr)
+                self._clock("take", t0)
+                t0 = time.perf_counter()
+                join()
+                out_rr.download_into(out)
+                self._clock("download", t0)
+            else:
+                self.resident_ms.setdefault("take", 0.0)    # (no survivor: nothing to take)
+        except BaseException:
+            if out_rr is not None:
+                out_rr.close()
+            self._drop_resident()
+            raise
+        finally:
+            if ch is not None:
+                for b in (d_extra, rgb if isinstance(rgb, _lib.DeviceArray) and rgb is not d_extra else None):
+                    ch._free(b)
+                ch.close()
+        self._drop_resident()
+        self._data, self._rr = out, out_rr
+        return True
+
     def _materialize(self, copy_always=False):
         """apply the composed survivor list of the device chain to the host table (one threaded compaction), then the
         deferred column fills of cap_sh_degree on the rows that are left.  copy_always: a NEW table even when every row survives
         (the eager methods: `self.data = vertices[mask]` is a copy whatever the mask, data_processor.py:114,149,212,224)"""
+        if self._rr is not None and self._materialize_resident(copy_always):
+            return
         rgb, self._pending_rgb = self._pending_rgb, None
         if self._chain is not None:
             ch = self._chain
@@ -156,7 +257,13 @@ class DataProcessor:
 
     def _chain_for(self, vertices):
         if self._chain is None:
-            self._chain = _lib.DeviceChain(table=vertices)      # (coords gathered straight into a page-locked staging buffer)
+            if self._rr is not None:                            # (coords gathered out of the rows in HBM)
+                import time
+                t0 = time.perf_counter()
+                self._chain = _lib.DeviceChain(resident=self._rr)
+                self._clock("gather", t0, self._chain.ctx)
+            else:
+                self._chain = _lib.DeviceChain(table=vertices)  # (coords gathered straight into a page-locked staging buffer)
         return self._chain
 
     def _columns(self, names):
@@ -362,7 +469,14 @@ class DataProcessor:
             ch = self._chain_for(self._data)
             original_len = ch.n
             # (the column leaves the 248-byte rows through the threaded gather: numpy's strided copy takes ~45 ms at 10M splats)
-            left = ch.ge_keep(_lib.host_gather_columns(self._data, ["opacity"])[0], float(logit_thresh))   # np.float64 threshold: an f64 comparison
+            if self._rr is not None:
+                import time
+                t0 = time.perf_counter()
+                column = ch.resident_column("opacity")
+                self._clock("gather", t0, ch.ctx)
+            else:
+                column = _lib.host_gather_columns(self._data, ["opacity"])[0]
+            left = ch.ge_keep(column, float(logit_thresh))   # np.float64 threshold: an f64 comparison
             status_print(f"Alpha Filter (min {limit}): Retained {left} out of {original_len} splats.")
             return None
         # eager (host table in, host table out at every call): the reference's expression on the column as ONE contiguous array
@@ -434,10 +548,39 @@ class DataProcessor:
         with _xyz_rows(vertices, names3, buf_name="rgb_in") as mat:
             return _lib.rgb_from_sh(mat.reshape(-1)).reshape(n, 3)
 
+    def _add_rgb_resident(self):
+        """add_rgb_from_sh on the rows in HBM: the colours of every row of the table as it is, computed and left on the device
+        (_lib.resident_rgb_dev) for the one take of _materialize.  -> False when the host path takes the call: RGB fields exist,
+        no plain f_dc_0..2 fields, or more uncertain elements than the list holds"""
+        src = self._data
+        names = src.dtype.names
+        if "red" in names or any("f_dc_%d" % c not in names for c in range(3)):
+            return False
+        import time
+        ch = self._chain_for(src)
+        n = ch.n0
+        t0 = time.perf_counter()
+        d_fdc, d_rgb = ch._alloc(12 * n + 16, "fdc"), ch._alloc(3 * n + 16, "rgb")
+        d_list, d_cnt = ch._alloc(4 * (3 * n // 64 + 4096), "rgblist"), ch._alloc(16, "rgbcnt")
+        try:
+            done = _lib.resident_rgb_dev(ch.ctx, self._rr, ["f_dc_%d" % c for c in range(3)], d_fdc, d_rgb, d_list, d_cnt)
+        finally:
+            for b in (d_fdc, d_list, d_cnt):
+                ch._free(b)
+        self._clock("gather", t0, ch.ctx)
+        if done is None:
+            ch._free(d_rgb)
+            return False
+        self._pending_rgb = d_rgb
+        debug_print("[DEBUG] RGB added to data.")
+        return True
+
     def add_rgb_from_sh(self):
         """reference :233-274: append (red, green, blue) u1 fields computed from the SH DC term"""
         debug_print("[DEBUG] Executing 'add_rgb_from_sh' function...")
         self._flush_rgb()
+        if self.lazy and self._rr is not None and len(self) > 0 and self._add_rgb_resident():
+            return
         if self.lazy and self._chain is not None and self._chain.n != self._chain.n0 and isinstance(self._data, np.ndarray) \
                 and self._chain.n > 0:
             # a compaction is pending: colours for the rows of the table as it is (per-row arithmetic: the survivors' colours are what
@@ -521,5 +664,5 @@ class ChainedDataProcessor(DataProcessor):
     """what ``install()`` binds to ``gsconverter.converter.DataProcessor``: the orchestrator ignores the filters' return
     values (converter.py:196-236) and reads ``processor.data`` once at the end (:259), so the device-resident chain applies"""
 
-    def __init__(self, data):
-        super().__init__(data, lazy=True)
+    def __init__(self, data, resident=None):
+        super().__init__(data, lazy=True, resident=resident)

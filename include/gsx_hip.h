@@ -1072,6 +1072,27 @@ int gsx_table_profile_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte
  * hold against numpy, and the product path for a table that is not resident. */
 int gsx_table_profile_host(const void *rows, int64_t n, const gsx_profile_layout *layout, int threads, gsx_table_profile *out);
 
+
+/* ---- a reader's decoded rows, kept in HBM for the filters and a writer (csrc/resident_rows.hip) ----
+ * rows_dev as gsx_table_profile_dev takes it: 16-byte aligned, row 0 at byte first_byte (0 ... 15), rows of 1 ... 512 bytes, readable
+ * up to 15 bytes past the last row; fields at any byte offset.  Every value is a bit copy (NaN payloads, -0.0).
+ *
+ * m (1 ... 4) 4-byte fields of every row -> out_dev (16-byte aligned): a dense (n, m) array of 32-bit words -- the coordinates of
+ * data_processor.py:38,139, the opacity column of :210, the f_dc of :316-343.  One launch.  Asynchronous. */
+int gsx_rows_columns_f32_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t stride, int64_t n, const int32_t *offsets,
+                             int m, void *out_dev);
+/* gsx_host_take_rows_shape on the device: out row j = source row idx_dev[j] (strictly ascending uint32 in HBM; NULL = row j), the
+ * n_zero 4-byte fields at zero_offsets (host array) zeroed, then e (0 ... 4) bytes of extra_dev[idx[j]] ((n_in, e) u8 in HBM)
+ * appended; stride_out = stride_in + e.  out_dev: 16-byte aligned, n_out * stride_out bytes (nothing behind them is written).
+ * A list that leaves [0, n_in) or does not ascend is refused after the launch (no row outside the table is read).  One launch;
+ * synchronises the context's stream. */
+int gsx_rows_take_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t stride_in, int64_t n_in, const uint32_t *idx_dev,
+                      int64_t n_out, const int32_t *zero_offsets, int n_zero, const uint8_t *extra_dev, int e, void *out_dev,
+                      int64_t stride_out);
+/* dst_dev[idx[i]] = val[i] for cnt entries of HOST arrays (every idx[i] < dst_len, checked): numpy's own bytes for the elements
+ * gsx_rgb_from_sh_list_dev lists, so that the colours stay in HBM.  Synchronises the context's stream. */
+int gsx_dev_patch_u8(gsx_ctx *ctx, uint8_t *dst_dev, int64_t dst_len, const uint32_t *idx, const uint8_t *val, int64_t cnt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,11 @@
 coordinate rows), then the host twin (gsx_table_profile_host) and numpy's strided column expressions on the host table.  Each
 device figure is a host clock around a call that ends in a stream synchronisation: 2 warm-up calls, PROBE_REPS timed ones, the
 minimum and the median.  The scene is degree 1 in 45 columns (the padded table a 3DGS read hands over).
+On the same resident rows, in the same run, csrc/resident_rows.hip's kernels: gsx_rows_columns_f32_dev for the chain's (n, 3)
+coordinates and for one column, gsx_rows_take_dev for every row (36 fields zeroed, three colour bytes appended) and for a
+scattered quarter of them -- each beside the profile pass, which reads the same bytes.  Then two conversions, each without and
+with the resident rows (``Converter(resident=False)`` is the path through the host table): .ply -> .splat with no filter, and
+.ply -> alpha, density, SOR, auto_bbox -> .spz.
     python tools/probe_converter.py            # PROBE_N=10000000 PROBE_REPS=10"""
 import importlib, json, os, statistics, sys, time
 import numpy as np
@@ -53,6 +58,7 @@ def main():
     scan = clock(lambda: lib.rest_nonzero_word(lib.load(), ctx, d, lay, n, range(45)), reps)
     prof = lib.table_profile_dev(ctx, d, 0, n, table.dtype)
     assert prof["rest_nonzero"] == lib.rest_nonzero_word(lib.load(), ctx, d, lay, n, range(45)) == (1 << 9) - 1
+    resident_kernels(lib, ctx, d, table, n, reps, fused)
     d.free()
     chain = lib.DeviceChain(table=table)
     box = clock(chain._bbox_dev, reps)
@@ -78,8 +84,44 @@ def main():
     conversion(table, n)
 
 
+def resident_kernels(lib, ctx, d, table, n, reps, fused):
+    """csrc/resident_rows.hip on the uploaded rows `d`, each call ending in a stream synchronisation like the profile's"""
+    rb = table.dtype.itemsize
+    fields = table.dtype.fields
+    d_cols, d_take = ctx.alloc(16 * n + 16), ctx.alloc(n * (rb + 3) + 64)
+    d_extra, d_idx = ctx.alloc(3 * n + 16), ctx.alloc(4 * n + 16)
+    lib.check(lib.load().gsx_dev_memset(ctx.handle, d_extra.ptr, 7, 3 * n), "gsx_dev_memset")
+    idx = np.flatnonzero(np.random.default_rng(5).random(n) < 0.25).astype(np.uint32)
+    d_idx.upload(idx)
+    zero = [fields["f_rest_%d" % i][1] for i in range(9, 45)]
+
+    def columns(names):
+        lib.rows_columns_dev(ctx, d.ptr, 0, table.dtype, n, names, d_cols.ptr)
+        ctx.synchronize()
+    try:
+        xyz = clock(lambda: columns(("x", "y", "z")), reps)
+        one = clock(lambda: columns(("opacity",)), reps)
+        assert np.array_equal(d_cols.download(np.float32, 1000), table["opacity"][:1000])
+        take_all = clock(lambda: lib.rows_take_dev(ctx, d.ptr, 0, rb, n, None, n, zero, d_extra.ptr, 3, d_take.ptr), reps)
+        take_quarter = clock(lambda: lib.rows_take_dev(ctx, d.ptr, 0, rb, n, d_idx.ptr, len(idx), zero, d_extra.ptr, 3, d_take.ptr), reps)
+        got = d_take.download(np.uint8, 4 * (rb + 3)).reshape(4, rb + 3)
+        assert got[:, :36].tobytes() == table[idx[:4]].view(np.uint8).reshape(4, rb)[:, :36].tobytes() and (got[:, rb:] == 7).all()
+    finally:
+        for b in (d_cols, d_take, d_extra, d_idx):
+            b.free()
+    base = fused["min_ms"]
+    print(json.dumps({"what": "resident_rows.hip on the same rows", "n": n, "row_bytes": rb, "table_profile_dev_min_ms": base,
+                      "columns_xyz": xyz, "columns_one": one, "take_all_rows_zero36_rgb": take_all,
+                      "take_scattered_quarter_zero36_rgb": dict(take_quarter, n_out=int(len(idx))),
+                      "times_the_profile_pass": {"columns_xyz": round(xyz["min_ms"] / base, 2), "columns_one": round(one["min_ms"] / base, 2),
+                                                 "take_all": round(take_all["min_ms"] / base, 2),
+                                                 "take_quarter": round(take_quarter["min_ms"] / base, 2)},
+                      "take_all_GBps_read_plus_written": round(n * (2 * rb + 6) / take_all["min_ms"] / 1e6, 1)}), flush=True)
+
+
 def conversion(table, n):
-    """the stage clocks of one .ply -> filters -> .spz conversion; the file has no normals, so its 236-byte rows are not the
+    """the stage clocks of .ply -> .splat (no filter) and of .ply -> filters -> .spz, each through the host table
+    (resident=False) and with the reader's rows kept in HBM; the file has no normals, so its 236-byte rows are not the
     table's and the read takes the device path (upload, transcode, profile, download)"""
     import tempfile
     import numpy.lib.recfunctions as rfn
@@ -90,12 +132,20 @@ def conversion(table, n):
         with open(src, "wb") as f:
             f.write(pn.header_text([("vertex", n, [(nm, "f4") for nm in names])]))
             f.write(memoryview(rfn.repack_fields(table[names])))
-        c = conv.Converter(src, dst, "spz")
-        t = time.perf_counter()
-        c.run(min_opacity=5, density_sensitivity=0.3, sor_intensity=5, auto_bbox=True, compression_level=1)
-        total = round((time.perf_counter() - t) * 1e3, 1)
-        print(json.dumps({"what": ".ply -> alpha, density, SOR, auto_bbox -> .spz", "n_in": n, "n_out": len(c.data), "total_ms": total,
-                          "stage_ms": c.stage_ms}), flush=True)
+        jobs = ((".ply -> .splat, no filter", "splat", os.path.join(tmp, "scene.splat"), {}),
+                (".ply -> alpha, density, SOR, auto_bbox -> .spz", "spz", dst,
+                 dict(min_opacity=5, density_sensitivity=0.3, sor_intensity=5, auto_bbox=True, compression_level=1)))
+        for what, target, out, kwargs in jobs:
+            for resident in (False, True, False, True):             # (twice each: the first run of a kind warms the arenas)
+                c = conv.Converter(src, out, target, resident=resident)
+                t = time.perf_counter()
+                c.run(**kwargs)
+                total = round((time.perf_counter() - t) * 1e3, 1)
+                ms = c.stage_ms
+                print(json.dumps({"what": what, "resident": resident, "n_in": n, "n_out": len(c.data), "total_ms": total,
+                                  "process_plus_write_upload_ms": round(ms["process"] + ms.get("write_upload", 0.0), 3),
+                                  "stage_ms": ms}), flush=True)
+                del c
 
 
 if __name__ == "__main__":

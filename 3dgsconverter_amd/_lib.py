@@ -11,6 +11,7 @@ import contextlib
 import ctypes as C
 import functools
 import os
+import re
 import threading
 import time
 
@@ -123,6 +124,17 @@ class PlyReadLayout(C.Structure):
     _fields_ = [("in_stride", C.c_int32), ("out_stride", C.c_int32), ("n_fields", C.c_int32), ("big_endian", C.c_int32),
                 ("src_offset", C.c_int32 * PLY_READ_MAX_FIELDS), ("src_type", C.c_int32 * PLY_READ_MAX_FIELDS),
                 ("dst_offset", C.c_int32 * PLY_READ_MAX_FIELDS), ("dst_bytes", C.c_int32 * PLY_READ_MAX_FIELDS)]
+
+
+PLY_TEXT_MAX_PROPS = 512    # GSX_PLY_TEXT_MAX_PROPS
+PLY_TEXT_RESULT_WORDS = 6   # GSX_PLY_TEXT_TOKENS, _LINES, _ROWS, _BAD_LINE, _FLAGGED, _END
+DEC_FLAGGED = 2             # GSX_DEC_FLAGGED
+
+
+class PlyTextLayout(C.Structure):
+    """gsx_ply_text_layout (include/gsx_hip.h): the properties of an ASCII PLY element, one token each"""
+    _fields_ = [("n_props", C.c_int32), ("in_stride", C.c_int32), ("offset", C.c_int32 * PLY_TEXT_MAX_PROPS),
+                ("type", C.c_int32 * PLY_TEXT_MAX_PROPS)]
 
 
 PLY_WRITE_MAX_RUNS = 128    # GSX_PLY_WRITE_MAX_RUNS
@@ -337,6 +349,13 @@ SIGNATURES = {
     "gsx_np_logf_host": (_I, [_P, _P, _I64]),
     "gsx_ply_unpack_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(PlyReadLayout), _P]),
     "gsx_ply_unpack_host": (_I, [_P, _I64, C.POINTER(PlyReadLayout), _P]),
+    "gsx_ply_text_padded_bytes": (_I64, [_I64]),
+    "gsx_ply_text_work_bytes": (_I64, [_I64]),
+    "gsx_ply_text_scan_dev": (_I, [_P, _P, _I64, _P, _I64]),
+    "gsx_ply_text_parse_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(PlyTextLayout), _P, _P, _I64, _P, _I64, C.POINTER(_I64)]),
+    "gsx_ply_text_host": (_I, [_P, _I64, _I64, C.POINTER(PlyTextLayout), _P, _P, _I64, C.POINTER(_I64)]),
+    "gsx_dec_to_f64": (_I, [_P, C.c_int32, C.POINTER(C.c_uint64)]),
+    "gsx_dec_pow5_entry": (_I, [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "gsx_ply_pack_dev": (_I, [_P, _P, _I64, C.POINTER(PlyWriteLayout), _P]),
     "gsx_ply_pack_host": (_I, [_P, _I64, C.POINTER(PlyWriteLayout), _P]),
     "gsx_ply_rest_nonzero_dev": (_I, [_P, _P, _I64, _I64, C.POINTER(C.c_int32), C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -2586,6 +2605,242 @@ def ply_unpack_host(body: np.ndarray, n_rows: int, layout: PlyReadLayout, dtype:
     out = np.empty(n, dtype)
     check(lib.gsx_ply_unpack_host(src.ctypes.data, n, C.byref(layout), out.ctypes.data), "gsx_ply_unpack_host")
     return out
+
+
+class PlyTextError(ValueError):
+    """the body of an ASCII PLY element breaks the rules of DESIGN.md "ASCII PLY bodies"; str(): the reason, which names the
+    element and the 1-based line"""
+
+
+PLY_TEXT_BLANKS = b" \t\x0b\x0c\r"                 # what separates the tokens of a line (\n ends the line)
+PLY_TEXT_CHUNK_BYTES = 64 << 20                    # text per upload: about 100 000 rows of a degree-3 scene
+PLY_TEXT_MAX_CHUNK_BYTES = 1 << 29                 # (a chunk's rows are patched through 32-bit byte indices)
+_PLY_TEXT_FLOAT = re.compile(rb"[+-]?(?:(?:[0-9]+(?:\.[0-9]*)?|\.[0-9]+)(?:[eE][+-]?[0-9]+)?|[nN][aA][nN]|[iI][nN][fF](?:[iI][nN][iI][tT][yY])?)\Z")
+_PLY_TEXT_INT = re.compile(rb"[+-]?[0-9]+\Z")
+
+
+def ply_text_value(token: bytes, typ: str) -> bytes:
+    """one token of an ASCII PLY body -> the little-endian bytes of its value as a property of numpy type `typ` ("f4", "u1" ...),
+    the rule the device's number code is held against: a float token of the grammar is Python's float(token), and for "f4" that
+    double cast to float32; an integer token is [+-]?D+ and must fit the type.  ValueError with the reason otherwise."""
+    if typ in ("f4", "f8"):
+        if not _PLY_TEXT_FLOAT.match(token):
+            raise ValueError("%r is no decimal number" % token.decode("latin-1"))
+        v = np.float64(float(token))
+        with np.errstate(over="ignore", under="ignore"):
+            return (v.astype("<f4") if typ == "f4" else v.astype("<f8")).tobytes()
+    if not _PLY_TEXT_INT.match(token):
+        raise ValueError("%r is no integer" % token.decode("latin-1"))
+    v, info = int(token), np.iinfo(typ)
+    if not info.min <= v <= info.max:
+        raise ValueError("%d does not fit a property of type %s" % (v, np.dtype(typ).name))
+    return np.array(v, "<" + typ).tobytes()
+
+
+def ply_text_layout(props) -> PlyTextLayout:
+    """[(name, numpy type str)] of an element -> gsx_ply_text_layout: the packed binary row of those properties"""
+    if not 1 <= len(props) <= PLY_TEXT_MAX_PROPS:
+        raise ValueError("ply_text_layout: %d properties (1 ... %d are supported)" % (len(props), PLY_TEXT_MAX_PROPS))
+    tl, off = PlyTextLayout(), 0
+    for i, (_, t) in enumerate(props):
+        tl.offset[i], tl.type[i] = off, PLY_TYPE_CODES[t]
+        off += np.dtype(t).itemsize
+    tl.n_props, tl.in_stride = len(props), off
+    return tl
+
+
+def ply_text_chunk_host(text: np.ndarray, length: int, rows_left: int, tl: PlyTextLayout, rows: np.ndarray, list_cap: "int | None" = None):
+    """gsx_ply_text_host on the first `length` bytes of `text` (uint8) into `rows` (uint8, rows_left rows of room)
+    -> (result words, the (k, 4) uint32 entries of the listed tokens or None when more were listed than list_cap)"""
+    lib = load()
+    res = (C.c_int64 * PLY_TEXT_RESULT_WORDS)()
+    cap = int(list_cap) if list_cap is not None else length // 2 + 1
+    lst = np.zeros((max(cap, 1), 4), np.uint32)
+    check(lib.gsx_ply_text_host(text.ctypes.data, int(length), int(rows_left), C.byref(tl), rows.ctypes.data, lst.ctypes.data, cap, res), "gsx_ply_text_host")
+    return list(res), (lst[:res[4]] if res[4] <= cap else None)
+
+
+def _ply_text_chunks(path: str, body_offset: int, n_rows: int, tl: PlyTextLayout, props, element: str, chunk_bytes: int, stats: "dict | None",
+                     staging, run_chunk, patch, mark):
+    """The ASCII reader's host loop, shared by the device path and its host model: windows of `chunk_bytes` of the file from
+    `body_offset` on, each cut behind its last newline (the file's last line gets the newline it may lack), handed to
+    ``run_chunk(host, length, rows_done, rows_left) -> (result words, listed tokens)``; the listed tokens are settled by
+    ply_text_value and handed to ``patch(rows_done, byte indices, bytes)``.  Whatever breaks the rules raises PlyTextError.
+    -> the byte offset of the file just past the element's last line"""
+    lib = load()
+    chunk_bytes = int(min(max(int(chunk_bytes), 1), PLY_TEXT_MAX_CHUNK_BYTES))
+    host = staging(int(lib.gsx_ply_text_padded_bytes(chunk_bytes + 1)))
+    P, stride = tl.n_props, tl.in_stride
+    pos, done = int(body_offset), 0
+    tokens = host_tokens = chunks = 0
+    with open(path, "rb") as f:
+        while done < n_rows:
+            f.seek(pos)
+            view, got = memoryview(host)[:chunk_bytes], 0
+            while got < chunk_bytes:
+                r = f.readinto(view[got:])
+                if not r:
+                    break
+                got += r
+            at_end = got < chunk_bytes
+            window = host[:got]
+            cut = _ply_text_last_newline(window) + 1
+            if at_end and got > cut:                   # the file's last line has no newline of its own
+                host[got] = 10
+                cut = got + 1
+            if cut == 0:
+                if at_end:
+                    raise PlyTextError("element %r ends after %d of %d lines (line %d is missing)" % (element, done, n_rows, done + 1))
+                raise PlyTextError("element %r, line %d: longer than %d bytes" % (element, done + 1, chunk_bytes))
+            host[cut:int(lib.gsx_ply_text_padded_bytes(cut))] = 10
+            mark("file_read")
+            res, listed = run_chunk(host, cut, done, n_rows - done)
+            rows, bad = int(res[2]), int(res[3])
+            listed = listed[np.argsort(listed[:, 0], kind="stable")]
+            if bad >= 0:                               # (the lines before it are whole: their tokens' rows and columns hold)
+                listed = listed[listed[:, 0] < bad * P]
+            if len(listed):
+                idx, val = [], []
+                for t, off, _, _ in listed.tolist():
+                    end = off
+                    while host[end] != 10 and host[end] not in PLY_TEXT_BLANKS:
+                        end += 1
+                    row, col = divmod(t, P)
+                    try:
+                        b = ply_text_value(bytes(host[off:end]), props[col][1])
+                    except ValueError as e:
+                        raise PlyTextError("element %r, line %d, property %r: %s" % (element, done + row + 1, props[col][0], e)) from None
+                    at = row * stride + tl.offset[col]
+                    idx += range(at, at + len(b))
+                    val += b
+                if bad < 0:
+                    patch(done, np.array(idx, np.uint32), np.array(val, np.uint8), rows * stride)
+                    mark("patch")
+            if bad >= 0:
+                words = bytes(_ply_text_line(host, cut, bad)).split()
+                why = ("is blank" if not words else "begins with '#'" if words[0].startswith(b"#") else
+                       "holds %d values for %d properties" % (len(words), P))
+                raise PlyTextError("element %r, line %d: %s" % (element, done + bad + 1, why))
+            tokens, host_tokens, chunks = tokens + rows * P, host_tokens + len(listed), chunks + 1
+            done += rows
+            pos += int(res[5])
+            if done < n_rows and at_end:
+                raise PlyTextError("element %r ends after %d of %d lines (line %d is missing)" % (element, done, n_rows, done + 1))
+    if stats is not None:
+        stats.update(tokens=tokens, host_tokens=host_tokens, chunks=chunks, end_offset=pos)
+    return pos
+
+
+def _ply_text_last_newline(window: np.ndarray) -> int:
+    """index of the last \\n of the uint8 array, or -1 (searched from the end in blocks: the whole window is not touched)"""
+    hi = len(window)
+    while hi > 0:
+        lo = max(hi - 65536, 0)
+        hit = np.flatnonzero(window[lo:hi] == 10)
+        if len(hit):
+            return lo + int(hit[-1])
+        hi = lo
+    return -1
+
+
+def _ply_text_line(host: np.ndarray, length: int, k: int) -> np.ndarray:
+    """line k (0-based, without its newline) of the chunk"""
+    ends = np.flatnonzero(host[:length] == 10)
+    return host[(ends[k - 1] + 1 if k else 0):ends[k]]
+
+
+def ply_text_table(path: str, body_offset: int, n_rows: int, props, layout: PlyReadLayout, dtype: np.dtype, stage_ms: "dict | None" = None,
+                   device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None, stats: "dict | None" = None,
+                   chunk_bytes: "int | None" = None, element: str = "vertex") -> np.ndarray:
+    """The 3DGS / CloudCompare PLY readers' rows from an ASCII body (formats/ply_3dgs.py:10,45-58, formats/ply_cc.py:10,45-60): the
+    text of the element's `n_rows` lines, from byte `body_offset` of `path`, is read into page-locked staging in chunks of
+    `chunk_bytes` (default PLY_TEXT_CHUNK_BYTES; each cut behind its last newline), uploaded, scanned (gsx_ply_text_scan_dev) and
+    parsed (gsx_ply_text_parse_dev) into ONE device buffer of n_rows x layout.in_stride bytes: the element as plyfile would hand
+    it on, in the declared types `props` ([(name, numpy type str)]).  The tokens the device lists are settled on the host
+    (ply_text_value) and patched into the rows (gsx_dev_patch_u8); a chunk that lists more than there is room for is converted
+    by the host twin.  Then gsx_ply_unpack_dev, the profile pass, the download and `keep` as in ply_unpack_table.
+    A body that breaks the rules raises PlyTextError.  stats receives tokens, host_tokens, chunks and end_offset (the byte just
+    past the element's last line).  Stage clocks: file_read, upload, scan, kernel, patch, unpack, download.
+
+    One ArenaSession of the "plytext" lease group."""
+    lib = require_hip()
+    n, rb = int(n_rows), dtype.itemsize
+    tl = ply_text_layout(props)
+    if n < 1 or rb != layout.out_stride or tl.in_stride != layout.in_stride:
+        raise ValueError("ply_text_table: %d rows of %d bytes for a layout of %d, properties of %d for %d" % (n, rb, layout.out_stride, tl.in_stride, layout.in_stride))
+    cb = int(chunk_bytes or PLY_TEXT_CHUNK_BYTES)
+    cb = max(min(cb, os.path.getsize(path) - int(body_offset) + 1), 1)        # (no more staging than the file has text)
+    out = np.empty(n, dtype)
+    with ArenaSession("plytext", device, stage_ms) as s:
+        join = prefault(out.nbytes >= (1 << 22), out)
+        h = s.ctx.handle
+        d_body = s.buf("body", n * tl.in_stride + 32)            # (the unpack kernel's 16-byte loads read past the last row)
+        cap = int(min(max(cb, 1), PLY_TEXT_MAX_CHUNK_BYTES)) + 1
+        d_text = s.buf("in", int(lib.gsx_ply_text_padded_bytes(cap)))
+        work_bytes = int(lib.gsx_ply_text_work_bytes(cap))
+        d_work = s.buf("work", work_bytes)
+        list_cap = cap // 1024 + 4096
+        d_list = s.buf("list", 16 * list_cap)
+        res = (C.c_int64 * PLY_TEXT_RESULT_WORDS)()
+
+        def run_chunk(host, length, done, left):
+            s.upload_staging(lib, d_text.ptr, host[:int(lib.gsx_ply_text_padded_bytes(length))])
+            s.mark("upload")
+            check(lib.gsx_ply_text_scan_dev(h, d_text.ptr, length, d_work.ptr, work_bytes), "gsx_ply_text_scan_dev")
+            s.mark("scan")
+            rows_ptr = d_body.ptr + done * tl.in_stride
+            check(lib.gsx_ply_text_parse_dev(h, d_text.ptr, length, left, C.byref(tl), rows_ptr, d_work.ptr, work_bytes, d_list.ptr, list_cap, res),
+                  "gsx_ply_text_parse_dev")
+            s.mark("kernel")
+            r = list(res)
+            if r[4] == 0:
+                return r, np.zeros((0, 4), np.uint32)
+            if r[4] <= list_cap:
+                return r, d_list.download(np.uint32, 4 * r[4]).reshape(-1, 4)
+            rows = np.zeros(r[2] * tl.in_stride, np.uint8)       # more listed tokens than room: the host twin takes the chunk
+            r, listed = ply_text_chunk_host(host, length, left, tl, rows)
+            check(lib.gsx_dev_upload(h, rows_ptr, rows.ctypes.data, rows.nbytes), "gsx_dev_upload")
+            s.mark("patch")
+            return r, listed
+
+        def patch(done, idx, val, nbytes):
+            dev_patch_u8(s.ctx, d_body.ptr + done * tl.in_stride, nbytes, idx, val)
+
+        _ply_text_chunks(path, body_offset, n, tl, props, element, cb, stats, lambda nb: s.staging("in", nb), run_chunk, patch, s.mark)
+        d_out = session_out(s, keep, n, n, dtype, profile)
+        check(lib.gsx_ply_unpack_dev(h, d_body.ptr, 0, n, C.byref(layout), d_out.ptr), "gsx_ply_unpack_dev")
+        s.mark("unpack")
+        session_profile(s, profile, d_out, n, n, dtype)
+        s.download_rows(lib, out, d_out, n * rb, join)
+        s.mark("download")
+        session_keep(s, keep, out)
+        return out
+
+
+def ply_text_host(path: str, body_offset: int, n_rows: int, props, layout: "PlyReadLayout | None" = None, dtype: "np.dtype | None" = None,
+                  stats: "dict | None" = None, chunk_bytes: "int | None" = None, element: str = "vertex") -> np.ndarray:
+    """ply_text_table without a device: the same chunk loop, gsx_ply_text_host for the kernels and gsx_ply_unpack_host for the
+    transcode -- the host tests' model of the device, and the readers' parse of the non-vertex elements (layout None: the
+    element's own rows, a structured array of `props`)"""
+    n = int(n_rows)
+    tl = ply_text_layout(props)
+    own = np.dtype([(nm, "<" + t if np.dtype(t).itemsize > 1 else t) for nm, t in props])
+    body = np.zeros(n * tl.in_stride + 4, np.uint8)
+
+    def run_chunk(host, length, done, left):
+        return ply_text_chunk_host(host, length, left, tl, body[done * tl.in_stride:])
+
+    def patch(done, idx, val, nbytes):
+        body[done * tl.in_stride + idx.astype(np.int64)] = val
+
+    if n:
+        _ply_text_chunks(path, body_offset, n, tl, props, element, int(chunk_bytes or PLY_TEXT_CHUNK_BYTES), stats,
+                         lambda nb: np.empty(nb, np.uint8), run_chunk, patch, lambda name: None)
+    elif stats is not None:
+        stats.update(tokens=0, host_tokens=0, chunks=0, end_offset=int(body_offset))
+    if layout is None:
+        return body[:n * tl.in_stride].view(own).copy()
+    return ply_unpack_host(body, n, layout, dtype)
 
 
 def ply_pack_table(data: np.ndarray, plan_of, scan=None, stage_ms: "dict | None" = None, device: int = 0):

@@ -113,7 +113,7 @@ class SourceHandler:
         kw = {"stage_ms": stage_ms, "profile": profile, **({} if keep is None else {"keep": keep})}
         if name in ("3dgs", "cc"):
             from .formats import ply_reader
-            data, self.extra_elements = (ply_reader.read_ply_3dgs if name == "3dgs" else ply_reader.read_ply_cc)(path, **kw)
+            data, self.extra_elements = (ply_reader.read_ply_3dgs if name == "3dgs" else ply_reader.read_ply_cc)(path, ascii_body=True, **kw)
         elif name == "compressed_ply":
             from .formats.compressed_ply_reader import read_compressed_ply
             data, _ = read_compressed_ply(path, on_metadata=lambda m: setattr(self, "metadata", m), **kw)

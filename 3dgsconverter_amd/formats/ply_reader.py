@@ -5,6 +5,9 @@
   |----------------------------------------------------|--------------------------------------------------------------------|
   | :10 PlyData.read                                   | compressed_ply_reader.parse_header; the vertex body is read        |
   |                                                    | straight into page-locked staging, the other elements on the host  |
+  | :10 PlyData.read of a `format ascii` file          | ascii_body=True: the vertex lines are tokenised and parsed on the  |
+  |                                                    | device (csrc/ply_text.hip) into the binary rows plyfile would hand |
+  |                                                    | on, the other elements on the host under the same token rules      |
   | :12-13 no `vertex` element: ValueError             | the same message, before anything else                             |
   | :16 self.extra_elements                            | read_extra_elements(): objects with .name, .data (bind_read_*: real |
   |                                                    | plyfile elements when plyfile is there)                            |
@@ -16,7 +19,8 @@
   |                                                    | (csrc/ply_read.hip): one launch, whole rows                        |
 
 The rows are the reference's bit for bit ("3DGS / CloudCompare PLY reader").  What the device path does not take is
-refused with a reason (Plan.refusal): an ascii body, list properties, a duplicated vertex property, red / green / blue of
+refused with a reason (Plan.refusal): an ascii body without ascii_body=True (with it: one whose lines or numbers break the rules
+of DESIGN.md "ASCII PLY bodies", named with element and line), list properties, a duplicated vertex property, red / green / blue of
 another type than uchar, an extra field whose source has another type, a big-endian file with extra fields, rows wider than
 512 bytes, more than 128 output fields.  A refused file goes to `fallback` (the reference's own read, when plyfile is there),
 else UnsupportedPlyError.
@@ -94,7 +98,7 @@ class Plan:
 
     def __init__(self):
         self.dialect = self.prefix = self.dtype = self.fields = self.refusal = None
-        self.has_rgb = self.big_endian = False
+        self.has_rgb = self.big_endian = self.ascii = False
         self.extra_fields = []
         self.count = self.in_stride = self.out_stride = 0
         self.body_offset = None
@@ -102,7 +106,7 @@ class Plan:
     @property
     def identity(self) -> bool:
         """the file's rows ARE the output rows: little-endian, equal strides, every field a bit copy from its own offset"""
-        return (self.refusal is None and not self.big_endian and self.in_stride == self.out_stride
+        return (self.refusal is None and not self.big_endian and not self.ascii and self.in_stride == self.out_stride
                 and all(f.source is not None and f.src_offset == f.dst_offset and (f.raw or f.src_type == "f4") for f in self.fields))
 
     def descriptors(self):
@@ -116,8 +120,10 @@ class Plan:
         return lay
 
 
-def plan(header: PlyHeader, dialect: str) -> Plan:
+def plan(header: PlyHeader, dialect: str, ascii_body: bool = False) -> Plan:
     """ply_3dgs.py:12-58 (dialect "3dgs") or ply_cc.py:12-60 ("cc") on a parsed header -> Plan.  Touches no device.
+    ascii_body: an ascii body is no refusal (Plan.ascii is set: the rows come from the text, body_offset is not known from the
+    header); every other refusal stays.
 
     :12-13 a missing `vertex` raises the reference's ValueError; :21-28 / :21-26 the source prefix; :30-40 / :28-40 the extra
     fields (source names outside {prefix + std} | {std}, std = get_standard_order(has_rgb=True), which holds nx ny nz already --
@@ -131,7 +137,8 @@ def plan(header: PlyHeader, dialect: str) -> Plan:
     p = Plan()
     p.dialect, p.count, p.big_endian = dialect, vertex.count, header.format == "binary_big_endian"
     # what no reading of the header can be planned for
-    if header.format == "ascii":
+    p.ascii = header.format == "ascii"
+    if p.ascii and not ascii_body:
         p.refusal = "an ascii body"
     for e in header.elements:
         if p.refusal is None and e.has_list():
@@ -212,16 +219,53 @@ def read_extra_elements(path: str, header: PlyHeader) -> list:
     return out
 
 
-def _read(path: str, dialect: str, stage_ms, fallback, device, profile=None, keep=None):
+def _refused(path: str, reason: str, fallback):
+    if fallback is None:
+        raise UnsupportedPlyError("%s: %s -- the GPU PLY reader takes binary files, and with ascii_body=True ascii files, of scalar "
+                                  "properties with rows of up to %d bytes; this one needs the reference's reader (plyfile)" % (path, reason, MAX_STRIDE))
+    debug_print(f"[DEBUG] PLY: {reason}; the reference's reader takes it")
+    return fallback(path)
+
+
+def _read_ascii(path: str, h: PlyHeader, p: Plan, t0, stage_ms, device, profile, keep, stats, chunk_bytes):
+    """the elements of an ascii file in the file's order: `vertex` through _lib.ply_text_table, the others on the host under the
+    same token rules (_lib.ply_text_host); each element starts where the one before it ended -> (rows, extras)"""
+    vertex = h.element("vertex")
+    pos, extras, rows = h.header_bytes, [], None
+    for e in h.elements:
+        st = {}
+        if e is not vertex:
+            data = _lib.ply_text_host(path, pos, e.count, e.props, stats=st, element=e.name)
+            extras.append(PlyExtraElement(e.name, data))
+            pos = st["end_offset"]
+            continue
+        if stage_ms is not None:
+            stage_ms["parse"] = round((time.perf_counter() - t0) * 1e3, 3)
+        if p.count == 0:                                                            # :45 np.zeros(0, dtype): no launch
+            rows = np.zeros(0, p.dtype)
+            st = {"tokens": 0, "host_tokens": 0, "chunks": 0, "end_offset": pos}
+        else:
+            rows = _lib.ply_text_table(path, pos, p.count, vertex.props, p.layout(), p.dtype, stage_ms=stage_ms, device=device, stats=st,
+                                       chunk_bytes=chunk_bytes, **_lib.profile_kw(profile), **_lib.keep_kw(keep))
+        pos = st["end_offset"]
+        if stats is not None:
+            stats.update(st)
+    return rows, extras
+
+
+def _read(path: str, dialect: str, stage_ms, fallback, device, profile=None, keep=None, ascii_body=False, stats=None, chunk_bytes=None):
     t0 = time.perf_counter()
     h = parse_header(path)
-    p = plan(h, dialect)
+    p = plan(h, dialect, ascii_body)
     if p.refusal is not None:
-        if fallback is None:
-            raise UnsupportedPlyError("%s: %s -- the GPU PLY reader takes binary files of scalar properties with rows of up to %d "
-                                      "bytes; this one needs the reference's reader (plyfile)" % (path, p.refusal, MAX_STRIDE))
-        debug_print(f"[DEBUG] PLY: {p.refusal}; the reference's reader takes it")
-        return fallback(path)
+        return _refused(path, p.refusal, fallback)
+    if p.ascii:
+        try:
+            rows, extras = _read_ascii(path, h, p, t0, stage_ms, device, profile, keep, stats, chunk_bytes)
+        except _lib.PlyTextError as e:
+            return _refused(path, "an ascii body that plyfile's two generations read differently or not at all: %s" % e, fallback)
+        debug_print(f"[DEBUG] Loaded {p.count} points from ascii PLY ({dialect})")
+        return rows, extras
     extras = read_extra_elements(path, h)
     if stage_ms is not None:
         stage_ms["parse"] = round((time.perf_counter() - t0) * 1e3, 3)
@@ -241,7 +285,8 @@ def _read(path: str, dialect: str, stage_ms, fallback, device, profile=None, kee
     return rows, extras
 
 
-def read_ply_3dgs(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None):
+def read_ply_3dgs(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None,
+                  ascii_body: bool = False, stats: "dict | None" = None, chunk_bytes: "int | None" = None):
     """ply_3dgs.py:8-60 -> (rows, extra_elements): the reference's structured array (define_dtype(has_scal=False, has_rgb,
     extra_fields) at sh_degree=3, packed, little-endian) and the non-vertex elements.
 
@@ -252,15 +297,21 @@ def read_ply_3dgs(path: str, stage_ms: "dict | None" = None, fallback=None, devi
     class cannot be matched without plyfile).  profile: a dict that receives the returned
     table's profile (_lib.TableProfile.as_dict): from one more pass over the transcoded rows before their download (stage clock
     "profile"), or from the threaded host pass for a file that is read into the result.  keep: a dict that receives the decoded rows in HBM as keep["rows"] (_lib.ResidentRows; the caller
-    closes it) when the returned table's rows are resident; it stays empty otherwise (a file that is read into the result among them)."""
+    closes it) when the returned table's rows are resident; it stays empty otherwise (a file that is read into the result among them).
+    ascii_body: take a file of `format ascii` too (off by default: such a file is refused like the others): its vertex lines are
+    parsed on the device (_lib.ply_text_table; stage clocks parse, file_read, upload, scan, kernel, patch, unpack, download), its
+    other elements on the host under the same token rules; a body that breaks them ("ASCII PLY bodies") is refused
+    with the element and the line.  stats: a dict that receives tokens, host_tokens (the tokens the host settled) and chunks of
+    an ascii read.  chunk_bytes: the text per upload of an ascii read (default _lib.PLY_TEXT_CHUNK_BYTES)."""
     debug_print(f"[DEBUG] Reading 3DGS PLY file from {path}")
-    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, "3dgs", stage_ms, fallback, device, profile, keep)))
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, "3dgs", stage_ms, fallback, device, profile, keep, ascii_body, stats, chunk_bytes)))
 
 
-def read_ply_cc(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None):
+def read_ply_cc(path: str, stage_ms: "dict | None" = None, fallback=None, device: int = 0, profile: "dict | None" = None, keep: "dict | None" = None,
+                ascii_body: bool = False, stats: "dict | None" = None, chunk_bytes: "int | None" = None):
     """ply_cc.py:8-62 -> (rows, extra_elements); see read_ply_3dgs"""
     debug_print(f"[DEBUG] Reading CC PLY file from {path}")
-    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, "cc", stage_ms, fallback, device, profile, keep)))
+    return _lib.with_keep(keep, lambda: _lib.with_profile(profile, lambda: _read(path, "cc", stage_ms, fallback, device, profile, keep, ascii_body, stats, chunk_bytes)))
 
 
 def _bind(original, reader):

@@ -951,6 +951,50 @@ int gsx_ply_unpack_dev(gsx_ctx *ctx, const void *body_dev, int64_t first_byte, i
  * HOST pointers; body readable up to 4 bytes past the last row. */
 int gsx_ply_unpack_host(const void *body, int64_t n, const gsx_ply_read_layout *layout, void *out);
 
+/* ---- ASCII bodies of the 3DGS / CloudCompare PLY readers (csrc/ply_text.hip, csrc/dec_to_f64.h) ----
+ * gsconverter/formats/ply_3dgs.py:10 and gsconverter/formats/ply_cc.py:10 (`PlyData.read`) on a file of `format ascii 1.0`: the
+ * element's text -> its rows in binary little-endian form, in the declared property types -- what plyfile hands the mapping loops
+ * of ply_3dgs.py:45-58 / ply_cc.py:45-60, which gsx_ply_unpack_dev then runs as it does for a binary body.  Lines end at \n;
+ * tokens are separated by runs of 0x20 0x09 0x0b 0x0c 0x0d; every line holds one token per property; float and double tokens are
+ * [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)? or [+-]?(nan|inf|infinity), rounded correctly to a double (a `float` is that double cast to
+ * float32); integer tokens are [+-]?D+ within the type's range.  A chunk of text starts at a line start and ends with a newline. */
+#define GSX_PLY_TEXT_MAX_PROPS 512
+typedef struct gsx_ply_text_layout {
+    int32_t n_props;                    /* properties of the element = tokens of a line, 1 ... GSX_PLY_TEXT_MAX_PROPS */
+    int32_t in_stride;                  /* bytes of a binary row, 1 ... 512 */
+    int32_t offset[GSX_PLY_TEXT_MAX_PROPS];   /* byte offset of the property inside a row */
+    int32_t type[GSX_PLY_TEXT_MAX_PROPS];     /* GSX_PLY_T_I1 ... GSX_PLY_T_F8 */
+} gsx_ply_text_layout;
+/* result words of gsx_ply_text_parse_dev and gsx_ply_text_host */
+#define GSX_PLY_TEXT_TOKENS 0           /* tokens of the chunk */
+#define GSX_PLY_TEXT_LINES 1            /* newlines of the chunk */
+#define GSX_PLY_TEXT_ROWS 2             /* rows taken from it: min(rows_left, lines) */
+#define GSX_PLY_TEXT_BAD_LINE 3         /* the first of those lines (0-based) that does not hold n_props tokens, or -1 */
+#define GSX_PLY_TEXT_FLAGGED 4          /* tokens left to the host (all of them, beyond list_cap too) */
+#define GSX_PLY_TEXT_END 5              /* byte offset just past the last of those lines */
+#define GSX_PLY_TEXT_RESULT_WORDS 6
+/* bytes the text buffer must hold for a chunk of text_len bytes (the bytes from text_len on filled with \n), and bytes of `work` */
+int64_t gsx_ply_text_padded_bytes(int64_t text_len);
+int64_t gsx_ply_text_work_bytes(int64_t text_len);
+/* token starts and newlines per tile of text, their exclusive scan: text_dev 16-byte aligned, the chunk from its byte 0,
+ * 1 ... 2^30 bytes.  Asynchronous. */
+int gsx_ply_text_scan_dev(gsx_ctx *ctx, const void *text_dev, int64_t text_len, void *work_dev, int64_t work_bytes);
+/* after gsx_ply_text_scan_dev on the same chunk: its first min(rows_left, lines) lines -> rows of in_stride bytes from rows_dev on
+ * (rows_left rows of room).  list_dev: list_cap entries of four uint32 (token of the chunk, its byte offset, its length or 0
+ * beyond 63 bytes, 0) for the tokens the device does not settle, whose bytes are zero in the rows: not of the grammar, out of
+ * range, a rounding it cannot certify, a subnormal double.  result: GSX_PLY_TEXT_RESULT_WORDS HOST words.  Synchronises. */
+int gsx_ply_text_parse_dev(gsx_ctx *ctx, const void *text_dev, int64_t text_len, int64_t rows_left, const gsx_ply_text_layout *layout,
+                           void *rows_dev, void *work_dev, int64_t work_bytes, void *list_dev, int64_t list_cap, int64_t *result);
+/* the same tokeniser and number code on the HOST (the host tests hold it against Python; it converts a chunk whose list
+ * overflowed).  HOST pointers. */
+int gsx_ply_text_host(const void *text, int64_t text_len, int64_t rows_left, const gsx_ply_text_layout *layout, void *rows, uint32_t *list,
+                      int64_t list_cap, int64_t *result);
+/* one float token of n bytes -> the float64 bits of Python's float(token): 0, or GSX_DEC_FLAGGED when the code leaves it to the host */
+#define GSX_DEC_FLAGGED 2
+int gsx_dec_to_f64(const void *token, int32_t n, uint64_t *bits);
+/* entry q (-342 ... 308) of the certificate's table: floor(5^q normalised to 128 bits) and exp2 with 5^q in [m, m + 1) * 2^exp2 */
+int gsx_dec_pow5_entry(int32_t q, uint64_t *hi, uint64_t *lo, int32_t *exp2);
+
 
 /* ---- the 3DGS / CloudCompare PLY writers (csrc/ply_write.hip) ----
  * gsconverter/formats/ply_3dgs.py:62-121 (Ply3DGSFormat.write) and gsconverter/formats/ply_cc.py:64-132 (PlyCCFormat.write): the

@@ -1401,6 +1401,32 @@ def session_profile(s: "ArenaSession", profile: "dict | None", d_rows, n_dev: in
 RESIDENT_MAX_ROW_BYTES = 512   # csrc/row_tile.h SPZ_MAX_ROW_BYTES
 
 
+@contextlib.contextmanager
+def stage_clock(stage_ms: "dict | None", name: str, ctx: "Context | None" = None):
+    """``with stage_clock(stage_ms, "take"):`` adds the block's milliseconds to stage_ms[name] (no dict: no clock), after a
+    synchronisation of `ctx` when one is given.  A block that raises records nothing."""
+    t0 = time.perf_counter()
+    yield
+    if stage_ms is not None:
+        if ctx is not None:
+            ctx.synchronize()
+        stage_ms[name] = round(stage_ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3, 3)
+
+
+def resident_take_dtype(dtype, extra_names=()) -> "np.dtype | None":
+    """The dtype of the rows ResidentRows.take writes: `dtype`'s fields and one 'u1' field per extra name, or None when
+    gsx_rows_take_dev cannot write them -- it appends the extra bytes to the source row, so the widened row has to END in exactly
+    those bytes (numpy may place them elsewhere: `descr` of a dtype with padding names the gaps) and stay within
+    RESIDENT_MAX_ROW_BYTES.  A pure function of the dtype and the names."""
+    dtype = np.dtype(dtype)
+    names = tuple(extra_names)
+    new = np.dtype(dtype.descr + [(nm, "u1") for nm in names]) if names else dtype
+    at_the_end = all(new.fields[nm][1] == dtype.itemsize + i for i, nm in enumerate(names))
+    if not at_the_end or new.itemsize != dtype.itemsize + len(names) or new.itemsize > RESIDENT_MAX_ROW_BYTES:
+        return None
+    return new
+
+
 class ResidentRows:
     """A table's rows in HBM, as a reader decoded them, beyond the reader's call: `n` packed rows of `dtype` from byte
     `first_byte` (0 ... 15) of the 16-byte aligned device address `ptr`, with 16 readable bytes behind the last row -- what
@@ -1409,7 +1435,10 @@ class ResidentRows:
     The buffer is an allocation of a Context this object owns, and no named arena buffer: those are overwritten by the next call
     of their lease group and freed by release_arenas().  A device address is valid in every context of this process on the same
     device, so a reader's session writes into it and a chain's or a writer's context reads it.  ``close()`` frees the buffer and
-    the context (idempotent; ``__del__`` calls it).  ``ResidentRows.open_count`` counts the objects not closed yet."""
+    the context (idempotent; ``__del__`` calls it).  ``ResidentRows.open_count`` counts the objects not closed yet.
+
+    The rows own the device work on their bytes: ``take()`` is the one gsx_rows_take_dev into new rows -- its dtype, the rule that
+    refuses it (resident_take_dtype), the field offsets -- and ``download_into()`` the copy to the host."""
 
     open_count = 0
 
@@ -1469,6 +1498,32 @@ class ResidentRows:
         if self.n:
             check(self._ctx.lib.gsx_dev_download_staged(self._ctx.handle, out.view(np.uint8).ctypes.data, self.ptr + self.first_byte, self.nbytes),
                   "gsx_dev_download_staged")
+        return out
+
+    def take(self, idx_ptr, n_out: int, zero_names=(), extra_ptr=None, extra_names=(), ctx: "Context | None" = None,
+             stage_ms: "dict | None" = None) -> "ResidentRows | None":
+        """-> NEW rows (the caller's to close) of resident_take_dtype(dtype, extra_names): row j is this object's row idx[j] --
+        `idx_ptr`: the device address of `n_out` ascending uint32 row numbers, None: row j itself -- with the '<f4' fields among
+        `zero_names` that the rows have zeroed, and behind it the len(extra_names) bytes of row idx[j] of the (n, len(extra_names))
+        uint8 device array at `extra_ptr`.  One gsx_rows_take_dev on `ctx` (this object's own context without one), which returns
+        when the rows are written; stage_ms["take"] is that call alone.  n_out == 0 launches nothing.  None, and nothing done,
+        when the widened dtype cannot be written (resident_take_dtype).  These rows stay as they are and open."""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        extra_names = tuple(extra_names)
+        new_dtype = resident_take_dtype(self.dtype, extra_names)
+        if new_dtype is None:
+            return None
+        fields = self.dtype.fields or {}
+        out = ResidentRows(n_out, new_dtype, self.device)
+        try:
+            if out.n:
+                with stage_clock(stage_ms, "take"):
+                    rows_take_dev(ctx if ctx is not None else self._ctx, self.ptr, self.first_byte, self.dtype.itemsize, self.n, idx_ptr, out.n,
+                                  [fields[nm][1] for nm in zero_names if nm in fields], extra_ptr, len(extra_names), out.ptr)
+        except BaseException:
+            out.close()
+            raise
         return out
 
     def close(self):
@@ -1714,9 +1769,7 @@ def cply_pack_table(data: np.ndarray, sh_names, order: "np.ndarray | None" = Non
         if resident:
             pitch = (data.dtype.itemsize + 3) & ~3
             rd = pitch // 4
-            d_rows = s.buf("rows", data.nbytes + 16)
-            upload_table(lib, ctx, d_rows.ptr, data)
-            s.mark("upload")
+            d_rows = s.upload_rows(lib, data, slack=16)
             if pitch != data.dtype.itemsize:
                 d_raw, d_rows = d_rows, s.buf("rows_aligned", n * pitch)
                 check(lib.gsx_rows_repack_dev(ctx.handle, d_raw.ptr, data.dtype.itemsize, n, d_rows.ptr, pitch), "gsx_rows_repack_dev")
@@ -1814,10 +1867,7 @@ def spz_pack_table(data: np.ndarray, sh_degree, scan_fields=(), stage_ms: "dict 
     with ArenaSession("spz", device, stage_ms) as s:
         ctx = s.ctx
         lay = spz_layout(data.dtype)
-        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernels read up to 15 bytes past the last row)
-        if n:
-            upload_table(lib, ctx, d_rows.ptr, data)
-        s.mark("upload")
+        d_rows = s.upload_rows(lib, data)
         degree = sh_degree
         if callable(sh_degree):
             word = rest_nonzero_word(lib, ctx, d_rows, lay, n, scan_fields)
@@ -2033,10 +2083,7 @@ def ksplat_pack_table(data: np.ndarray, degree, scan_fields, geometry, stage_ms:
     with ArenaSession("ksplat", device, stage_ms) as s:
         ctx = s.ctx
         lay = spz_layout(data.dtype)
-        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernels read up to 15 bytes past the last row)
-        if n:
-            upload_table(lib, ctx, d_rows.ptr, data)
-        s.mark("upload")
+        d_rows = s.upload_rows(lib, data)
         if callable(degree):
             degree = int(degree(rest_nonzero_word(lib, ctx, d_rows, lay, n, scan_fields)))
             s.mark("sh_detect")
@@ -2126,12 +2173,7 @@ def splat_pack_table(data: np.ndarray, rgb: bool = False, stage_ms: "dict | None
             return out
         join = prefault(out.nbytes >= (1 << 22), out)
         lay = spz_layout(data.dtype)
-        if resident is not None:
-            d_rows = resident                           # (.ptr: 16 readable bytes behind the last row)
-        else:
-            d_rows = s.buf("rows", data.nbytes + 64)    # (the pack kernel reads up to 15 bytes past the last row)
-            upload_table(lib, ctx, d_rows.ptr, data)
-            s.mark("upload")
+        d_rows = s.upload_rows(lib, data, resident=resident)    # (resident rows: 16 readable bytes behind the last one)
         d_keys, d_order = s.buf("keys", 4 * n), s.buf("order", 4 * n)
         d_recs, d_out = s.buf("recs", 32 * n), s.buf("out", 32 * n)
 
@@ -2862,9 +2904,7 @@ def ply_pack_table(data: np.ndarray, plan_of, scan=None, stage_ms: "dict | None"
         raise ValueError("ply_pack_table: %d rows of %d bytes (C-contiguous rows of up to %d)" % (n, data.dtype.itemsize, PLY_WRITE_MAX_STRIDE))
     with ArenaSession("plyw", device, stage_ms) as s:
         ctx = s.ctx
-        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernels read up to 15 bytes past the last row)
-        upload_table(lib, ctx, d_rows.ptr, data)
-        s.mark("upload")
+        d_rows = s.upload_rows(lib, data)
         last_idx = None
         if scan is not None:
             offsets, present = scan
@@ -3066,9 +3106,7 @@ def parquet_columns_table(data: np.ndarray, fields, stage_ms: "dict | None" = No
     lay, total, places = parquet_columns_plan(data.dtype.itemsize, n, fields)
     with ArenaSession("pqw", device, stage_ms) as s:
         ctx = s.ctx
-        d_rows = s.buf("rows", data.nbytes + 64)        # (the kernel's 16-byte loads read up to 15 bytes past the last row)
-        upload_table(lib, ctx, d_rows.ptr, data)
-        s.mark("upload")
+        d_rows = s.upload_rows(lib, data)
         d_out, d_cnt = s.buf("out", total), s.buf("count", 8 * PARQUET_MAX_FIELDS)
         check(lib.gsx_parquet_columns_dev(ctx.handle, d_rows.ptr, n, C.byref(lay), d_out.ptr, total, d_cnt.ptr), "gsx_parquet_columns_dev")
         s.mark("kernel")
@@ -3427,7 +3465,8 @@ class ArenaSession:
     The six table readers share one sequence: stage_in() -- staging, the caller's fill, the fill stage's mark, all on the host --
     then ``s.upload_in``, the caller's own uploads and mark("upload"), its launch and mark("kernel"), ``s.download_rows`` and
     mark("download").  A reader that is handed a ``profile`` dict runs session_profile() between the launch and the download:
-    one more pass over the decoded rows (gsx_table_profile_dev) and a mark("profile")."""
+    one more pass over the decoded rows (gsx_table_profile_dev) and a mark("profile").  The six table writers open with
+    ``s.upload_rows``: the table into the buffer "rows" and mark("upload"), or a caller's resident rows where they are."""
 
     def __init__(self, group: str, device: int = 0, stage_ms: "dict | None" = None, ctx: "Context | None" = None, shared: bool = True):
         self.group, self.device, self.stage_ms, self.ctx = group, device, stage_ms, ctx
@@ -3498,6 +3537,19 @@ class ArenaSession:
             d_tab.upload(tables)
         return d_in, d_tab
 
+    def upload_rows(self, lib, data: np.ndarray, slack: int = 64, resident: "ResidentRows | None" = None):
+        """a table writer's first step, upload_in's mirror: the table `data` into the buffer "rows" of data.nbytes + `slack` (the
+        kernels' 16-byte loads read up to 15 bytes past the last row), one upload_table when the table has bytes, and
+        mark("upload") either way.  With the caller's `resident` rows of the table: those, where they are -- no buffer, no upload
+        and no "upload" mark.  -> an object with .ptr"""
+        if resident is not None:
+            return resident
+        d_rows = self.buf("rows", data.nbytes + slack)
+        if data.nbytes:
+            upload_table(lib, self.ctx, d_rows.ptr, data)
+        self.mark("upload")
+        return d_rows
+
     def download_rows(self, lib, out: np.ndarray, d_out: DeviceArray, nbytes: int, join):
         """the last step of a reader and of the PLY writer: the prefault joined, then the first `nbytes` of `d_out` through the
         staging lanes into the first `nbytes` of `out`"""
@@ -3511,7 +3563,12 @@ class DeviceChain:
     The reference ends every filter with ``self.data = vertices[mask]`` on the host table (data_processor.py:114,149)
     and re-gathers ``coords`` at the start of the next one (:38,139).  Here the (n,3) rows are uploaded once, every
     filter leaves its mask in HBM, ``gsx_compact_rows_dev`` compacts the rows there, and the composed survivor list comes
-    back once -- the 248-byte host rows are compacted once, after the last filter."""
+    back once -- the 248-byte host rows are compacted once, after the last filter.
+
+    Over resident rows (``resident=``) the chain also owns every buffer that work on them needs, by name and size, and gives
+    each back: ``resident_column`` for ge_keep, ``resident_rgb`` / ``rgb_to_host`` for add_rgb_from_sh's colours, and ``take``,
+    which picks the survivor list and has the rows write the survivors into new resident rows.  DataProcessor calls these and
+    holds no device buffer itself."""
 
     def __init__(self, xyz_rows: "np.ndarray | None" = None, device: int = 0, keep_pristine: bool = False, table: "np.ndarray | None" = None,
                  resident: "ResidentRows | None" = None):
@@ -3718,6 +3775,49 @@ class DeviceChain:
         dev = self._alloc(max(4 * self.n0, 16), "column")
         rows_columns_dev(self.ctx, rr.ptr, rr.first_byte, rr.dtype, rr.n, (name,), dev.ptr)
         return dev
+
+    def resident_rgb(self, names3) -> "DeviceArray | None":
+        """add_rgb_from_sh's colours of EVERY resident row the chain started from, out of its '<f4' fields `names3`, left in HBM
+        (resident_rgb_dev, in the sizes it asks for) -> the (n0, 3) uint8 device array for take() or rgb_to_host(), which
+        release it; None when more uncertain elements were listed than the list holds: the caller computes them on the host"""
+        n = self.n0
+        d_fdc, d_rgb = self._alloc(12 * n + 16, "fdc"), self._alloc(3 * n + 16, "rgb")
+        d_list, d_cnt = self._alloc(4 * (3 * n // 64 + 4096), "rgblist"), self._alloc(16, "rgbcnt")
+        done = None
+        try:
+            done = resident_rgb_dev(self.ctx, self.resident, names3, d_fdc, d_rgb, d_list, d_cnt)
+        finally:
+            for b in (d_fdc, d_list, d_cnt) + ((d_rgb,) if done is None else ()):
+                self._free(b)
+        return d_rgb if done is not None else None
+
+    def rgb_to_host(self, d_rgb: DeviceArray) -> np.ndarray:
+        """resident_rgb()'s colours as a host (n0, 3) uint8 array; the device array is released"""
+        try:
+            return d_rgb.download(np.uint8, 3 * self.n0).reshape(self.n0, 3)
+        finally:
+            self._free(d_rgb)
+
+    def take(self, zero_names=(), rgb=None, stage_ms: "dict | None" = None) -> "ResidentRows | None":
+        """The chain's survivors out of the resident rows it started from, as NEW resident rows (ResidentRows.take on the chain's
+        context; the caller's to close): the composed survivor list when a filter removed rows, every row when none did, no row
+        after keep_none().  rgb: None, resident_rgb()'s device colours, or a host (n0, 3) uint8 array (uploaded into the chain's
+        "rgbhost") -- one row per ORIGINAL row, appended to the survivors as red, green, blue.  The colour buffers are released on
+        every way out; the source rows and the chain stay open.  None when the widened rows cannot be written."""
+        compact = self.n != self.n0 or self.empty
+        n_out = 0 if (self.empty or self.n == 0) else self.n
+        device_rgb = rgb if isinstance(rgb, DeviceArray) else None
+        uploaded = None
+        try:
+            if rgb is not None and device_rgb is None and n_out:
+                uploaded = self._alloc(3 * self.n0 + 16, "rgbhost").upload(np.ascontiguousarray(rgb, np.uint8))
+            extra = device_rgb if device_rgb is not None else uploaded
+            return self.resident.take(self.orig.ptr if (self.orig is not None and compact) else None, n_out, zero_names,
+                                      extra.ptr if extra is not None else None, ("red", "green", "blue") if rgb is not None else (),
+                                      ctx=self.ctx, stage_ms=stage_ms)
+        finally:
+            self._free(uploaded)
+            self._free(device_rgb)
 
     def ge_keep(self, column, threshold: float) -> int:
         """rows whose value in ``column`` (float32, one per row of the table the chain started from) is >= threshold; column: a

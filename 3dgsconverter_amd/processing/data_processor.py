@@ -18,6 +18,9 @@ Differences from the reference, all deliberate:
 Every method of the reference class is implemented here (round 3: ``cap_sh_degree``, ``add_rgb_from_sh``,
 ``apply_auto_bbox`` too -- SURVEY.md 8(f) rank 4); ``__getattr__`` only forwards names a FUTURE reference version
 might add.
+
+This class holds the reference's semantics -- messages, order of checks, return values -- and decides what ``.data`` still owes
+the table; the device work behind it belongs to the objects that own the memory (``_lib.DeviceChain``, ``_lib.ResidentRows``).
 """
 from __future__ import annotations
 
@@ -31,6 +34,7 @@ from . import clusters as _clusters
 
 
 XYZ = ("x", "y", "z")
+RGB = ("red", "green", "blue")
 DEVICE_CLUSTERS_ABOVE = 1024  # eager density filter: more dense voxels than this are clustered by gsx_voxel_clusters, fewer by clusters.py
 MAX_SOR_K = 2047  # include/gsx_hip.h: 1 <= k <= 64 on the fast kernels, 65..2047 through the exact list-free kernel (slow)
 
@@ -81,6 +85,25 @@ def _xyz_rows(vertices, names=("x", "y", "z"), buf_name="eager_xyz"):
         yield _lib.host_gather_xyz(vertices, names, out=out)
 
 
+def _require_sor_k(k):
+    """the reference's cKDTree path takes any k and its Taichi kernel silently caps K at 50 (gpu_ops.py:244); here k <= 64 runs on
+    the register-resident kernels, 65..2047 on the exact list-free kernel"""
+    if not 1 <= int(k) <= MAX_SOR_K:
+        raise ValueError(f"SOR: k={k} is outside the supported range 1..{MAX_SOR_K} of the MI355X path "
+                         f"(--sor_intensity maps to k = 10..50, the CLI default is 25)")
+
+
+def _host_clusters(dense_keys, keep_multicluster):
+    """the density filter's clustering on the host (clusters.py: the reference's set-iteration order decides a tie for the largest)
+    -> (keys of the kept voxels (m, 3) int64 in np.unique's row order, clusters kept, voxels of the largest), or None when no
+    cluster is kept"""
+    comps = _clusters.connected_clusters(map(tuple, dense_keys.tolist()))
+    kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
+    if not kept:
+        return None
+    return np.array(sorted(kept), dtype=np.int64).reshape(-1, 3), kept_clusters, max_len
+
+
 class DataProcessor:
     """Drop-in for the reference's class (module docstring).  ``lazy=True`` (what ``install()`` gives the reference's orchestrator, which ignores the filters' return values,
     converter.py:196-236): consecutive density / SOR filters keep the coordinates in HBM (``_lib.DeviceChain``) and the
@@ -107,7 +130,8 @@ class DataProcessor:
         self._data = data
         self._chain = None          # _lib.DeviceChain over the rows of self._data, or None
         self._pending_zero = []     # lazy cap_sh_degree: columns to zero once the host table has been compacted
-        self._pending_rgb = None    # lazy add_rgb_from_sh: (n0, 3) u8 colours of the UNcompacted table, appended by the compaction pass
+        self._pending_rgb = None    # lazy add_rgb_from_sh: (n0, 3) u8 colours of the UNcompacted table (a host array, or the chain's
+        #                             device array), appended by the compaction pass
         self.lazy = DataProcessor.lazy_default if lazy is None else bool(lazy)
 
     @property
@@ -122,8 +146,7 @@ class DataProcessor:
         # -- unless a filter's compaction is still pending in the chain: the reference had by then replaced self.data
         # with the filtered COPY and zeroed that, leaving the caller's array alone; the copy would be discarded here, so
         # the pending fills are simply dropped
-        compaction_pending = self._chain is not None and self._chain.n != self._chain.n0
-        if self._pending_zero and isinstance(self._data, np.ndarray) and not compaction_pending:
+        if self._pending_zero and isinstance(self._data, np.ndarray) and not self._compaction_pending():
             names, self._pending_zero = self._pending_zero, []
             _lib.host_zero_columns(self._data, names)
         self._pending_zero = []
@@ -154,114 +177,97 @@ class DataProcessor:
             rr, self._rr = self._rr, None
             rr.close()
 
-    def _clock(self, name, t0, ctx=None):
-        import time
-        if ctx is not None:
-            ctx.synchronize()
-        self.resident_ms[name] = round(self.resident_ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3, 3)
+    def _timed(self, name, ctx=None):
+        """``with self._timed("gather", ctx):`` -- the block's milliseconds, after a synchronisation of `ctx` when one is given,
+        added to resident_ms[name]"""
+        return _lib.stage_clock(self.resident_ms, name, ctx)
 
-    def _materialize_resident(self, copy_always):
-        """_materialize on the rows in HBM: one gsx_rows_take_dev for the chain's survivors, the pending zero fields and the pending
-        colours, one download into a prefaulted table.  -> False when this table is not taken (the widened dtype does not end in
-        the three bytes): the resident rows are dropped, pending device colours come to the host, and the host path runs"""
-        import time
-        rr, ch = self._rr, self._chain
-        rgb = self._pending_rgb
-        compact = ch is not None and (ch.n != ch.n0 or ch.empty)
-        if not (compact or copy_always or rgb is not None or self._pending_zero):
-            self._drop_chain()
-            self.resident_ms.setdefault("take", 0.0)        # (the resident path ran, and had nothing to take)
-            return True                                     # .data is the caller's table, .resident its rows
-        src = self._data
-        names = ("red", "green", "blue") if rgb is not None else ()
-        new_dtype = np.dtype(src.dtype.descr + [(nm, "u1") for nm in names]) if names else src.dtype
-        tail_ok = all(new_dtype.fields[nm][1] == src.dtype.itemsize + i for i, nm in enumerate(names))
-        if not tail_ok or new_dtype.itemsize != src.dtype.itemsize + len(names) or new_dtype.itemsize > _lib.RESIDENT_MAX_ROW_BYTES:
-            if isinstance(rgb, _lib.DeviceArray):
-                self._pending_rgb = rgb.download(np.uint8, 3 * rr.n).reshape(rr.n, 3)
-                ch._free(rgb)
-            self._drop_resident()
-            return False
-        self._chain = None
-        self._pending_rgb = None
-        zero, self._pending_zero = self._pending_zero, []
-        out_rr = d_extra = None
+    def _compaction_pending(self):
+        """has a filter of the device chain removed rows that the table still holds?  A chain is only ever built over a table
+        that has rows, so this holds after keep_none() (n = 0) too"""
+        return self._chain is not None and self._chain.n != self._chain.n0
+
+    def _materialize(self):
+        """``.data``'s pending work, decided once for both executors: the chain's survivor list when a filter removed rows, the
+        fields cap_sh_degree deferred and the colours add_rgb_from_sh deferred.  On the rows in HBM (_take_resident) when this
+        object has them and they can take it, else on the host table (_take_host).  The chain is closed either way; a take's
+        new rows replace the source rows, which are closed, after that."""
+        compact, ch, zero, rgb = self._compaction_pending(), self._chain, self._pending_zero, self._pending_rgb
+        self._chain, self._pending_zero, self._pending_rgb = None, [], None
+        taken = None
         try:
-            n_out = 0 if (ch is not None and (ch.empty or ch.n == 0)) else (ch.n if ch is not None else rr.n)
+            if self._rr is not None:
+                if not (compact or zero or rgb is not None):
+                    self.resident_ms.setdefault("take", 0.0)    # (the resident path ran, and had nothing to take)
+                    return                                      # .data is the caller's table, .resident its rows
+                new_dtype = _lib.resident_take_dtype(self._rr.dtype, RGB if rgb is not None else ())
+                if new_dtype is not None and (rgb is None or ch is not None):   # (only a chain can hand colours to the take)
+                    taken = self._take_resident(ch, zero, rgb, new_dtype)
+                else:
+                    # this table is not taken (the widened row does not end in the three bytes, or is too long): device colours
+                    # come to the host, the resident rows are dropped and the host path runs
+                    if isinstance(rgb, _lib.DeviceArray):
+                        rgb = ch.rgb_to_host(rgb)
+                    self._drop_resident()
+            if taken is None:
+                self._take_host(ch if compact else None, zero, rgb)
+        finally:
+            if ch is not None:
+                ch.close()
+        if taken is not None:
+            self._drop_resident()
+            self._data, self._rr = taken
+
+    def _take_resident(self, ch, zero, rgb, new_dtype):
+        """the pending work on the rows in HBM: one take -- the chain's when there is one, the rows' own otherwise -- into new
+        resident rows and one download into a prefaulted table of `new_dtype` -> (the table, its rows in HBM).  When anything
+        raises the new rows and the source rows are closed"""
+        n_out = ch.n if ch is not None else self._rr.n
+        out_rr = None
+        try:
             out = np.empty(n_out, new_dtype)
-            out_rr = _lib.ResidentRows(n_out, new_dtype, rr.device)
+            join = _lib.prefault_parallel(out)
+            out_rr = (ch.take(zero, rgb, stage_ms=self.resident_ms) if ch is not None
+                      else self._rr.take(None, n_out, zero, stage_ms=self.resident_ms))
             if n_out:
-                join = _lib.prefault_parallel(out)
-                ctx = ch.ctx if ch is not None else rr._ctx
-                if rgb is not None:
-                    d_extra = rgb if isinstance(rgb, _lib.DeviceArray) else ch._alloc(3 * rr.n + 16, "rgbhost").upload(np.ascontiguousarray(rgb, np.uint8))
-                t0 = time.perf_counter()
-                idx = ch.orig.ptr if (ch is not None and ch.orig is not None and compact) else None
-                _lib.rows_take_dev(ctx, rr.ptr, rr.first_byte, src.dtype.itemsize, rr.n, idx, n_out,
-                                   [src.dtype.fields[nm][1] for nm in zero if nm in src.dtype.fields],
-                                   d_extra.ptr if d_extra is not None else None, len(names), out_rr.ptr)
-                self._clock("take", t0)
-                t0 = time.perf_counter()
-                join()
-                out_rr.download_into(out)
-                self._clock("download", t0)
+                with self._timed("download"):
+                    join()
+                    out_rr.download_into(out)
             else:
-                self.resident_ms.setdefault("take", 0.0)    # (no survivor: nothing to take)
+                self.resident_ms.setdefault("take", 0.0)        # (no survivor: nothing to take)
         except BaseException:
             if out_rr is not None:
                 out_rr.close()
             self._drop_resident()
             raise
-        finally:
-            if ch is not None:
-                for b in (d_extra, rgb if isinstance(rgb, _lib.DeviceArray) and rgb is not d_extra else None):
-                    ch._free(b)
-                ch.close()
-        self._drop_resident()
-        self._data, self._rr = out, out_rr
-        return True
+        return out, out_rr
 
-    def _materialize(self, copy_always=False):
-        """apply the composed survivor list of the device chain to the host table (one threaded compaction), then the
-        deferred column fills of cap_sh_degree on the rows that are left.  copy_always: a NEW table even when every row survives
-        (the eager methods: `self.data = vertices[mask]` is a copy whatever the mask, data_processor.py:114,149,212,224)"""
-        if self._rr is not None and self._materialize_resident(copy_always):
-            return
-        rgb, self._pending_rgb = self._pending_rgb, None
-        if self._chain is not None:
-            ch = self._chain
-            self._chain = None
-            try:
-                if ch.n != ch.n0 or copy_always:
-                    # the chain's survivor list (ascending row indices) applied to the host table directly -- round 5: the
-                    # boolean mask numpy would index with (`mask[survivors] = True` on 8M indices) cost more than the compaction
-                    if rgb is not None or self._pending_zero:
-                        # round 6: ... and add_rgb_from_sh's widened copy (:262-274; the reference's converter calls it after the filters
-                        # for every target that needs colours, converter.py:243-252) and cap_sh_degree's deferred column fill (:310-313)
-                        # in the same pass: one read of the survivors, one write of the new table
-                        zero, self._pending_zero = self._pending_zero, []
-                        self._data = _lib.host_take_rows_shape(self._data, ch.survivors(), ("red", "green", "blue") if rgb is not None else (),
-                                                               rgb, zero)
-                        rgb = None
-                    else:
-                        self._data = _lib.host_take_rows(self._data, ch.survivors())
-            finally:
-                ch.close()
+    def _take_host(self, ch, zero, rgb):
+        """the pending work on the host table: the survivor list of `ch` (None: no compaction is pending) applied in one threaded
+        pass, then the deferred column fills of cap_sh_degree on the rows that are left"""
+        if ch is not None:
+            # the chain's survivor list (ascending row indices) applied to the host table directly -- round 5: the
+            # boolean mask numpy would index with (`mask[survivors] = True` on 8M indices) cost more than the compaction
+            if rgb is not None or zero:
+                # round 6: ... and add_rgb_from_sh's widened copy (:262-274; the reference's converter calls it after the filters
+                # for every target that needs colours, converter.py:243-252) and cap_sh_degree's deferred column fill (:310-313)
+                # in the same pass: one read of the survivors, one write of the new table
+                self._data = _lib.host_take_rows_shape(self._data, ch.survivors(), RGB if rgb is not None else (), rgb, zero)
+                rgb, zero = None, []
+            else:
+                self._data = _lib.host_take_rows(self._data, ch.survivors())
         if rgb is not None:
-            self._data = _lib.host_append_u8_columns(self._data, ("red", "green", "blue"), rgb)
-        if self._pending_zero:
-            names, self._pending_zero = self._pending_zero, []
-            if isinstance(self._data, np.ndarray):
-                _lib.host_zero_columns(self._data, names)   # in place, like the reference (:313): the caller's array when
-                #                                             no filter has compacted the table, the compacted copy otherwise
+            self._data = _lib.host_append_u8_columns(self._data, RGB, rgb)
+        if zero and isinstance(self._data, np.ndarray):
+            _lib.host_zero_columns(self._data, zero)    # in place, like the reference (:313): the caller's array when
+            #                                             no filter has compacted the table, the compacted copy otherwise
 
     def _chain_for(self, vertices):
         if self._chain is None:
             if self._rr is not None:                            # (coords gathered out of the rows in HBM)
-                import time
-                t0 = time.perf_counter()
-                self._chain = _lib.DeviceChain(resident=self._rr)
-                self._clock("gather", t0, self._chain.ctx)
+                with self._timed("gather"):
+                    self._chain = _lib.DeviceChain(resident=self._rr)
+                    self._chain.ctx.synchronize()
             else:
                 self._chain = _lib.DeviceChain(table=vertices)  # (coords gathered straight into a page-locked staging buffer)
         return self._chain
@@ -330,9 +336,7 @@ class DataProcessor:
         debug_print(f"SOR Filter (Remove Flyers) Params: K={k}, Sigma={threshold_factor:.2f}")
 
         if self.lazy and isinstance(self._data, np.ndarray) and len(self) > 0:
-            if not 1 <= int(k) <= MAX_SOR_K:
-                raise ValueError(f"SOR: k={k} is outside the supported range 1..{MAX_SOR_K} of the MI355X path "
-                                 f"(--sor_intensity maps to k = 10..50, the CLI default is 25)")
+            _require_sor_k(k)
             ch = self._chain_for(self._data)
             num_points = ch.n
             status_print("[SOR] Determining outliers on GPU (HIP gfx950, exact KNN, device-resident chain)...")
@@ -347,11 +351,7 @@ class DataProcessor:
             status_print("[SOR] Determining outliers on GPU (HIP gfx950, exact KNN)...")
             status_print("After removing flyers (GPU), retained 0 out of 0 vertices.")
             return self.data
-        if not 1 <= int(k) <= MAX_SOR_K:
-            # the reference's cKDTree path takes any k and its Taichi kernel silently caps K at 50 (gpu_ops.py:244); here
-            # k <= 64 runs on the register-resident kernels, 65..2047 on the exact list-free kernel
-            raise ValueError(f"SOR: k={k} is outside the supported range 1..{MAX_SOR_K} of the MI355X path "
-                             f"(--sor_intensity maps to k = 10..50, the CLI default is 25)")
+        _require_sor_k(k)
         status_print("[SOR] Determining outliers on GPU (HIP gfx950, exact KNN)...")
         with _xyz_rows(vertices) as xyz:
             res = _lib.sor_filter(xyz, int(k), float(threshold_factor), want_mean=False)
@@ -379,16 +379,12 @@ class DataProcessor:
         n = len(vertices)
         min_points = int(n * (threshold_percentage / 100.0))  # reference :48
         if n == 0:
-            status_print("Warning: Density filter removed all points.")
-            self.data = self.data[:0]
-            return self.data
+            return self._density_keeps_nothing()
         with _xyz_rows(vertices) as cols:        # (the staging buffer is held across both device calls)
             occ = _lib.density_voxels(cols, float(voxel_size), min_points)
             debug_print(f"[DEBUG] Found {occ['n_unique']} unique voxels.")
             if len(occ["dense_keys"]) == 0:
-                status_print("Warning: Density filter removed all points.")
-                self.data = self.data[:0]
-                return self.data
+                return self._density_keeps_nothing()
             # more dense voxels than the reference's own thresholds can give (--density_threshold near 0: every occupied voxel
             # is dense): their clusters on the device too; only a tie for the largest comes back for the host steps
             res = (_lib.voxel_clusters(occ["dense_keys"], bool(keep_multicluster))
@@ -397,16 +393,25 @@ class DataProcessor:
                 kept_keys = occ["dense_keys"][res["keep"]]      # (np.unique's row order already)
                 kept_clusters, max_len = res["kept_clusters"], res["largest"]
             else:
-                comps = _clusters.connected_clusters(map(tuple, occ["dense_keys"].tolist()))
-                kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
-                if not kept:
-                    self.data = self.data[:0]
-                    return self.data
-                kept_keys = np.array(sorted(kept), dtype=np.int64).reshape(-1, 3)
+                found = _host_clusters(occ["dense_keys"], keep_multicluster)
+                if found is None:
+                    return self._density_keeps_nothing(warn=False)
+                kept_keys, kept_clusters, max_len = found
             mask = _lib.density_mask(cols, float(voxel_size), kept_keys)
         self.data = _lib.host_compact_rows(vertices, mask)  # reference :114
         status_print(f"Density Filter: Kept {kept_clusters} clusters (largest: {max_len} voxels).")
         status_print(f"After density filter, retained {len(self.data)} out of {len(vertices)} vertices.")
+        return self.data
+
+    def _density_keeps_nothing(self, ch=None, warn=True):
+        """the density filter's exit when no row survives (reference :54-57, :91-93; without the warning when the dense voxels
+        gave no cluster to keep): `ch`, the lazy filter's chain, keeps none; the eager filter sets and returns the empty table"""
+        if warn:
+            status_print("Warning: Density filter removed all points.")
+        if ch is not None:
+            ch.keep_none()
+            return None
+        self.data = self.data[:0]
         return self.data
 
     def _density_lazy(self, voxel_size, threshold_percentage, keep_multicluster):
@@ -423,25 +428,18 @@ class DataProcessor:
         if res["status"] != _lib.DENSITY_HOST:
             debug_print(f"[DEBUG] Found {res['n_unique']} unique voxels.")
             if res["status"] == _lib.DENSITY_EMPTY:
-                status_print("Warning: Density filter removed all points.")
-                ch.keep_none()
-                return None
-            status_print(f"Density Filter: Kept {res['kept_clusters']} clusters (largest: {res['largest']} voxels).")
-            status_print(f"After density filter, retained {res['left']} out of {n} vertices.")
-            return None
-        occ = ch.density_voxels(float(voxel_size), min_points)
-        debug_print(f"[DEBUG] Found {occ['n_unique']} unique voxels.")
-        if len(occ["dense_keys"]) == 0:
-            status_print("Warning: Density filter removed all points.")
-            ch.keep_none()
-            return None
-        comps = _clusters.connected_clusters(map(tuple, occ["dense_keys"].tolist()))
-        kept, kept_clusters, max_len = _clusters.select_clusters(comps, keep_multicluster)
-        if not kept:
-            ch.keep_none()
-            return None
-        kept_keys = np.array(sorted(kept), dtype=np.int64).reshape(-1, 3)
-        left = ch.density_keep(float(voxel_size), kept_keys)
+                return self._density_keeps_nothing(ch)
+            kept_clusters, max_len, left = res["kept_clusters"], res["largest"], res["left"]
+        else:
+            occ = ch.density_voxels(float(voxel_size), min_points)
+            debug_print(f"[DEBUG] Found {occ['n_unique']} unique voxels.")
+            if len(occ["dense_keys"]) == 0:
+                return self._density_keeps_nothing(ch)
+            found = _host_clusters(occ["dense_keys"], keep_multicluster)
+            if found is None:
+                return self._density_keeps_nothing(ch, warn=False)
+            kept_keys, kept_clusters, max_len = found
+            left = ch.density_keep(float(voxel_size), kept_keys)
         status_print(f"Density Filter: Kept {kept_clusters} clusters (largest: {max_len} voxels).")
         status_print(f"After density filter, retained {left} out of {n} vertices.")
         return None
@@ -470,10 +468,8 @@ class DataProcessor:
             original_len = ch.n
             # (the column leaves the 248-byte rows through the threaded gather: numpy's strided copy takes ~45 ms at 10M splats)
             if self._rr is not None:
-                import time
-                t0 = time.perf_counter()
-                column = ch.resident_column("opacity")
-                self._clock("gather", t0, ch.ctx)
+                with self._timed("gather", ch.ctx):
+                    column = ch.resident_column("opacity")
             else:
                 column = _lib.host_gather_columns(self._data, ["opacity"])[0]
             left = ch.ge_keep(column, float(logit_thresh))   # np.float64 threshold: an f64 comparison
@@ -550,30 +546,31 @@ class DataProcessor:
 
     def _add_rgb_resident(self):
         """add_rgb_from_sh on the rows in HBM: the colours of every row of the table as it is, computed and left on the device
-        (_lib.resident_rgb_dev) for the one take of _materialize.  -> False when the host path takes the call: RGB fields exist,
-        no plain f_dc_0..2 fields, or more uncertain elements than the list holds"""
-        src = self._data
-        names = src.dtype.names
+        (DeviceChain.resident_rgb) for the one take of _materialize.  -> False when the host path takes the call: RGB fields
+        exist, no plain f_dc_0..2 fields, or more uncertain elements than the chain's list holds"""
+        names = self._data.dtype.names
         if "red" in names or any("f_dc_%d" % c not in names for c in range(3)):
             return False
-        import time
-        ch = self._chain_for(src)
-        n = ch.n0
-        t0 = time.perf_counter()
-        d_fdc, d_rgb = ch._alloc(12 * n + 16, "fdc"), ch._alloc(3 * n + 16, "rgb")
-        d_list, d_cnt = ch._alloc(4 * (3 * n // 64 + 4096), "rgblist"), ch._alloc(16, "rgbcnt")
-        try:
-            done = _lib.resident_rgb_dev(ch.ctx, self._rr, ["f_dc_%d" % c for c in range(3)], d_fdc, d_rgb, d_list, d_cnt)
-        finally:
-            for b in (d_fdc, d_list, d_cnt):
-                ch._free(b)
-        self._clock("gather", t0, ch.ctx)
-        if done is None:
-            ch._free(d_rgb)
+        ch = self._chain_for(self._data)
+        with self._timed("gather", ch.ctx):
+            colors = ch.resident_rgb(["f_dc_%d" % c for c in range(3)])
+        if colors is None:
             return False
-        self._pending_rgb = d_rgb
+        self._pending_rgb = colors
         debug_print("[DEBUG] RGB added to data.")
         return True
+
+    def _colors_of(self, table):
+        """add_rgb_from_sh's colours for the rows of `table` (reference :236-248, with its two debug lines), or None when the
+        table has colours already or no SH DC term to compute them from"""
+        names = table.dtype.names
+        if "red" in names:
+            debug_print("[DEBUG] RGB fields already exist.")
+            return None
+        if "f_dc_0" not in names and "scalar_f_dc_0" not in names:
+            debug_print("[DEBUG] No SH DC components found, cannot compute RGB.")
+            return None
+        return self._compute_rgb_from_sh(table)
 
     def add_rgb_from_sh(self):
         """reference :233-274: append (red, green, blue) u1 fields computed from the SH DC term"""
@@ -581,36 +578,19 @@ class DataProcessor:
         self._flush_rgb()
         if self.lazy and self._rr is not None and len(self) > 0 and self._add_rgb_resident():
             return
-        if self.lazy and self._chain is not None and self._chain.n != self._chain.n0 and isinstance(self._data, np.ndarray) \
-                and self._chain.n > 0:
+        if self.lazy and self._compaction_pending() and isinstance(self._data, np.ndarray) and self._chain.n > 0:
             # a compaction is pending: colours for the rows of the table as it is (per-row arithmetic: the survivors' colours are what
             # the reference computes on the filtered table), appended by the ONE pass that compacts it (_materialize)
-            src = self._data
-            if "red" in src.dtype.names:
-                debug_print("[DEBUG] RGB fields already exist.")
-                return
-            if "f_dc_0" not in src.dtype.names and "scalar_f_dc_0" not in src.dtype.names:
-                debug_print("[DEBUG] No SH DC components found, cannot compute RGB.")
-                return
-            colors = self._compute_rgb_from_sh(src)
-            if colors is None:
-                return
-            self._pending_rgb = colors
-            debug_print("[DEBUG] RGB added to data.")
+            colors = self._colors_of(self._data)
+            if colors is not None:
+                self._pending_rgb = colors
+                debug_print("[DEBUG] RGB added to data.")
             return
         data = self.data
-        names = data.dtype.names
-        if "red" in names:
-            debug_print("[DEBUG] RGB fields already exist.")
-            return
-        if "f_dc_0" not in names and "scalar_f_dc_0" not in names:
-            debug_print("[DEBUG] No SH DC components found, cannot compute RGB.")
-            return
-        colors = self._compute_rgb_from_sh(data)
-        if colors is None:
-            return
-        self.data = _lib.host_append_u8_columns(data, ("red", "green", "blue"), colors)   # :262-274 in one threaded pass
-        debug_print("[DEBUG] RGB added to data.")
+        colors = self._colors_of(data)
+        if colors is not None:
+            self.data = _lib.host_append_u8_columns(data, RGB, colors)   # :262-274 in one threaded pass
+            debug_print("[DEBUG] RGB added to data.")
 
     def apply_auto_bbox(self):
         """reference :345-354: prints the tight bounding box of what is left (no change to the data).  On the device chain

@@ -128,6 +128,35 @@ def test_a_table_with_a_float64_x_takes_the_host_path(lib, table):
     assert lib.ResidentRows.open_count == before
 
 
+def test_colours_that_do_not_fit_the_widened_row_come_back_to_the_host_path(lib):
+    """510-byte rows are resident-eligible, 513 with red / green / blue are over RESIDENT_MAX_ROW_BYTES: the take is refused at
+    ``.data``, the colours computed on the device come to the host, the resident rows are closed and the host path compacts"""
+    dt = np.dtype([(nm, "<f4") for nm in ["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity"] + ["f_rest_%d" % i for i in range(45)]]
+                  + [("more_%d" % i, "<f4") for i in range(75)] + [("tail", "u1", (2,))])
+    assert dt.itemsize == 510 and lib.resident_eligible(dt, 33, dt, 33)
+    rng = np.random.default_rng(0x353130)
+    table = np.zeros(33, dt)
+    for nm in dt.names[:-1]:
+        table[nm] = rng.standard_normal(33).astype(np.float32)
+    table["opacity"] = np.linspace(-6, 6, 33, dtype=np.float32)[rng.permutation(33)]
+    table["tail"] = rng.integers(0, 256, (33, 2), dtype=np.uint8)
+    steps = (("apply_alpha_filter", (40,)), ("add_rgb_from_sh", ()))
+    before = lib.ResidentRows.open_count
+    host_p, want, want_lines, want_exc = run(lambda: dp.ChainedDataProcessor(table.copy()), steps)
+    assert want_exc is None and 0 < len(want) < 33 and want.dtype.itemsize == 513
+    src = table.copy()
+    p, got, lines, exc = run(lambda: dp.ChainedDataProcessor(src, resident=lib.ResidentRows.from_host(src)), steps)
+    try:
+        assert exc is None
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+        assert lines == want_lines
+        assert p.resident is None
+    finally:
+        p.close()
+        host_p.close()
+    assert lib.ResidentRows.open_count == before
+
+
 def test_rows_of_another_table_are_refused(lib, table):
     other = lib.ResidentRows.from_host(table[:100].copy())
     p = dp.ChainedDataProcessor(table.copy(), resident=other)

@@ -16,7 +16,8 @@ entry points raise ``GsxError``.
 from . import _lib
 from ._lib import GsxError, has_hip, device_count, release_arenas as release_device_cache  # noqa: F401
 from . import processing  # noqa: F401
+from . import transform  # noqa: F401
 from .processing import DataProcessor, gpu_ops  # noqa: F401
 from .install import install, uninstall  # noqa: F401
 
-__all__ = ["processing", "DataProcessor", "gpu_ops", "GsxError", "has_hip", "device_count", "install", "uninstall", "release_device_cache"]
+__all__ = ["processing", "transform", "DataProcessor", "gpu_ops", "GsxError", "has_hip", "device_count", "install", "uninstall", "release_device_cache"]

@@ -202,6 +202,15 @@ class TableProfile(C.Structure):
                 "nan_axes": int(self.nan_axes), "n": int(self.n)}
 
 
+class TransformLayout(C.Structure):
+    """gsx_transform_layout (include/gsx_hip.h): the parts a scene transform rewrites, where their fields sit inside a row, and
+    the numbers -- M = s R, R, t, q_R, the band matrices D1..D3 (row-major float64) and float32 log(s)"""
+    _fields_ = [("parts", C.c_uint32), ("rest_m", C.c_int32), ("xyz_offset", C.c_int32 * 3), ("normal_offset", C.c_int32 * 3),
+                ("scale_offset", C.c_int32 * 3), ("rot_offset", C.c_int32 * 4), ("rest_offset", C.c_int32 * 45), ("log_scale", C.c_float),
+                ("M", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3), ("q", C.c_double * 4), ("D1", C.c_double * 9),
+                ("D2", C.c_double * 25), ("D3", C.c_double * 49)]
+
+
 DENSITY_OK, DENSITY_EMPTY, DENSITY_HOST = range(3)
 DENSITY_STAGES = ("table", "init", "hook", "flatten", "reduce", "membership")   # GSX_DENSITY_STAGES
 SLAB_OK, SLAB_EMPTY, SLAB_NONFINITE, SLAB_SMALL_SHARD, SLAB_NO_STRUCTURE = range(5)
@@ -367,6 +376,8 @@ SIGNATURES = {
     "gsx_table_profile_host": (_I, [_P, _I64, C.POINTER(ProfileLayout), _I, C.POINTER(TableProfile)]),
     "gsx_rows_columns_f32_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(C.c_int32), _I, _P]),
     "gsx_rows_take_dev": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _P, _I64]),
+    "gsx_rows_transform_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(TransformLayout), _P]),
+    "gsx_rows_transform_host": (_I, [_P, _I64, _I64, C.POINTER(TransformLayout), _P]),
     "gsx_dev_patch_u8": (_I, [_P, _P, _I64, _P, _P, _I64]),
 }
 
@@ -1526,6 +1537,21 @@ class ResidentRows:
             raise
         return out
 
+    def transform(self, plan, stage_ms: "dict | None" = None, ctx: "Context | None" = None):
+        """the scene transform `plan` (transform.plan_transform of this dtype) applied to these rows where they lie: one
+        gsx_rows_transform_dev in place on `ctx` (this object's own context without one), joined; stage_ms["transform"] is that
+        call alone.  A plan without work, or no rows, launches nothing."""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        if np.dtype(plan.dtype) != self.dtype:
+            raise ValueError("ResidentRows.transform: a plan for %s, rows of %s" % (plan.dtype, self.dtype))
+        if plan.identity or not self.n:
+            return
+        ctx = ctx if ctx is not None else self._ctx
+        with stage_clock(stage_ms, "transform"):
+            rows_transform_dev(ctx, self.ptr, self.first_byte, self.dtype.itemsize, self.n, transform_layout(plan), self.ptr)
+            ctx.synchronize()
+
     def close(self):
         if self.ptr is None:
             return
@@ -1646,6 +1672,63 @@ def rows_take_dev(ctx: "Context", rows_ptr: int, first_byte: int, stride_in: int
     offs = (C.c_int32 * max(len(zero_offsets), 1))(*zero_offsets)
     check(ctx.lib.gsx_rows_take_dev(ctx.handle, rows_ptr, int(first_byte), int(stride_in), int(n_in), idx_ptr, int(n_out), offs, len(zero_offsets),
                                     extra_ptr, int(e), out_ptr, int(stride_in) + int(e)), "gsx_rows_take_dev")
+
+
+def transform_layout(plan) -> TransformLayout:
+    """gsx_transform_layout of a transform.TransformPlan"""
+    lay = TransformLayout()
+    lay.parts, lay.rest_m, lay.log_scale = int(plan.parts), int(plan.m), float(plan.log_scale)
+    for name, offs in (("xyz_offset", plan.xyz), ("normal_offset", plan.normals), ("scale_offset", plan.scales), ("rot_offset", plan.rots)):
+        getattr(lay, name)[:] = [int(o) for o in offs]
+    lay.rest_offset[:] = [int(o) for o in plan.rest] + [-1] * (45 - len(plan.rest))
+    for name, a in (("M", plan.M), ("R", plan.R), ("t", plan.t), ("q", plan.q), ("D1", plan.D[0]), ("D2", plan.D[1]), ("D3", plan.D[2])):
+        getattr(lay, name)[:] = [float(v) for v in np.asarray(a, dtype=np.float64).reshape(-1)]
+    return lay
+
+
+def rows_transform_dev(ctx: "Context", rows_ptr: int, first_byte: int, stride: int, n: int, layout: TransformLayout, out_ptr: int):
+    """gsx_rows_transform_dev: the scene transform of `n` resident rows -> rows at byte `first_byte` of `out_ptr` (which may be
+    `rows_ptr`: in place).  Asynchronous."""
+    check(ctx.lib.gsx_rows_transform_dev(ctx.handle, rows_ptr, int(first_byte), int(stride), int(n), C.byref(layout), out_ptr),
+          "gsx_rows_transform_dev")
+
+
+def rows_transform_host(table: np.ndarray, plan, out: "np.ndarray | None" = None) -> np.ndarray:
+    """gsx_rows_transform_host: the kernel's per-row functions on a host table (1-D, C-contiguous, of plan.dtype) -> a new table,
+    or `out` (which may be `table`: in place) -- the host tests' model of the device; no device is touched"""
+    lib = load()
+    if table.ndim != 1 or not table.flags.c_contiguous or table.dtype != np.dtype(plan.dtype):
+        raise ValueError("rows_transform_host: a 1-D C-contiguous table of %s" % np.dtype(plan.dtype))
+    if out is None:
+        out = np.empty_like(table)
+    elif out.shape != table.shape or out.dtype != table.dtype or not out.flags.c_contiguous:
+        raise ValueError("rows_transform_host: an output of the table's shape")
+    lay = transform_layout(plan)
+    check(lib.gsx_rows_transform_host(table.ctypes.data, table.dtype.itemsize, len(table), C.byref(lay), out.ctypes.data), "gsx_rows_transform_host")
+    return out
+
+
+def rows_transform_table(data: np.ndarray, plan, stage_ms: "dict | None" = None, device: int = 0) -> np.ndarray:
+    """The scene transform of a host table through the device: the rows uploaded once (ArenaSession.upload_rows), one
+    gsx_rows_transform_dev in place there, and one download into a NEW, prefaulted table -- the caller's array is left alone.
+    data: 1-D structured table of plan.dtype, rows of up to 512 bytes.  A plan without work, or no rows: a copy.
+    One ArenaSession of the "transform" lease group; stage_ms: upload, transform, download."""
+    data = np.ascontiguousarray(data)
+    if data.ndim != 1 or data.dtype != np.dtype(plan.dtype) or not 1 <= data.dtype.itemsize <= RESIDENT_MAX_ROW_BYTES:
+        raise ValueError("rows_transform_table: a 1-D table of %s, rows of up to %d bytes" % (np.dtype(plan.dtype), RESIDENT_MAX_ROW_BYTES))
+    n = len(data)
+    if plan.identity or n == 0:
+        return data.copy()
+    lib = require_hip()
+    with ArenaSession("transform", device, stage_ms) as s:
+        out = np.empty(n, data.dtype)
+        join = prefault_parallel(out)
+        d_rows = s.upload_rows(lib, data)
+        rows_transform_dev(s.ctx, d_rows.ptr, 0, data.dtype.itemsize, n, transform_layout(plan), d_rows.ptr)
+        s.mark("transform")
+        s.download_rows(lib, out, d_rows, data.nbytes, join)
+        s.mark("download")
+    return out
 
 
 def dev_patch_u8(ctx: "Context", dst_ptr: int, dst_len: int, idx: np.ndarray, val: np.ndarray):

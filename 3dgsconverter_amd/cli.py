@@ -206,6 +206,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--force", action="store_true", help="Overwrite an existing output file without asking.")
     p.add_argument("--rgb", action="store_true", help="Add red / green / blue computed from the SH DC term when the table has none.")
     p.add_argument("--bbox", nargs=6, type=float, metavar=("minX", "minY", "minZ", "maxX", "maxY", "maxZ"), help="Keep the splats inside this box.")
+    p.add_argument("--rotate", nargs=3, type=float, metavar=("RX", "RY", "RZ"),
+                   help="Rotate the scene: degrees about the fixed X axis, then Y, then Z. Positions, orientations, normals and SH bands turn with it.")
+    p.add_argument("--scale", type=float, metavar="S", help="Scale the scene uniformly by S > 0 (positions and splat sizes).")
+    p.add_argument("--translate", nargs=3, type=float, metavar=("X", "Y", "Z"),
+                   help="Shift the scene, after rotation and scale. --bbox and the filters work in the transformed frame.")
     p.add_argument("--auto_bbox", action="store_true", help="Report the tight bounding box of what the filters leave.")
     p.add_argument("--extra_elements", action="store_true", help="Carry a PLY's non-vertex elements over (3dgs and cc targets).")
     p.add_argument("--density_voxel_size", type=float, help=argparse.SUPPRESS)
@@ -238,6 +243,9 @@ def main(argv=None):
         return
     if args.min_opacity is not None and not (0 <= args.min_opacity <= 255):
         print(f"Error: --min_opacity must be between 0 and 255. Got {args.min_opacity}.")
+        return
+    if args.scale is not None and not (np.isfinite(args.scale) and args.scale > 0):
+        print(f"Error: --scale must be a finite number greater than 0. Got {args.scale}.")
         return
     if args.compression_level < 0 or args.compression_level > 9:
         print(f"Error: --compression_level must be between 0 and 9. Got {args.compression_level}.")
@@ -272,6 +280,7 @@ def main(argv=None):
     has_source_extras = check_source_extras(args.input)
     filters_active = any([args.density_voxel_size, args.density_threshold, args.sor_k, args.sor_sigma, args.crop_sh,
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
+                          args.rotate is not None, args.scale is not None, args.translate is not None,
                           has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
@@ -305,7 +314,7 @@ def main(argv=None):
                       sor_sigma=args.sor_sigma, sor_intensity=args.sor_intensity, min_opacity=args.min_opacity, bbox=args.bbox,
                       rgb=args.rgb, sh_level=args.sh_level, bucket_size=args.bucket_size, block_size=args.block_size,
                       crop_sh=args.crop_sh, auto_bbox=args.auto_bbox, compression_level=args.compression_level,
-                      maintain_extra_elements=args.extra_elements)
+                      maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate)
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

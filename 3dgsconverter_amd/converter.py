@@ -8,6 +8,7 @@ readers, filter chain and writers: a file is converted on a machine that has thi
   |                                                   | profiled in HBM before their download (csrc/table_profile.hip)      |
   | :121-146 45 strided `np.any(col != 0)` scans      | plan_conversion on the profile's 64-bit word                        |
   | :150-252 DataProcessor, the filters in order      | processing.ChainedDataProcessor: one device-resident chain          |
+  | (none: the reference cannot move a scene)         | run(rotate=, scale=, translate=): apply_transform before the filters|
   | :263-288 extra elements, the handler's write      | the format's write_*                                                |
 
 The decoded rows stay in HBM from the reader to the end of the run (``Converter(..., resident=True)``, the default; readers'
@@ -228,6 +229,8 @@ class Converter:
         return self.data
 
     def run(self, **kwargs):
+        """the reference's keywords, and ``rotate=(rx, ry, rz)`` (degrees: about the fixed X, then Y, then Z axis), ``scale=s`` and
+        ``translate=(tx, ty, tz)``: the scene transform p' = s R p + t, applied right after the SH cap and before every filter"""
         debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
         clocks = self.stage_ms = {}
         held = []                   # the processor of this run: whatever it still holds in HBM is freed on every exit path
@@ -271,6 +274,15 @@ class Converter:
             for line in plan["messages"]:
                 status_print(line)
             processor.cap_sh_degree(plan["final_degree"])
+            # the scene transform is the first processing step: the box, the voxel size and SOR all work in the output frame
+            rotate, scale, translate = kwargs.pop("rotate", None), kwargs.pop("scale", None), kwargs.pop("translate", None)
+            if rotate is not None or scale is not None or translate is not None:
+                from . import transform
+                rx, ry, rz = (float(v) for v in (rotate if rotate is not None else (0.0, 0.0, 0.0)))
+                tx, ty, tz = (float(v) for v in (translate if translate is not None else (0.0, 0.0, 0.0)))
+                s = 1.0 if scale is None else float(scale)
+                status_print(f"Transform: scale {s:g}, rotate [{rx:g}, {ry:g}, {rz:g}] deg, translate [{tx:g}, {ty:g}, {tz:g}]")
+                processor.apply_transform(rotation=transform.rotation_from_euler_deg(rx, ry, rz), translation=(tx, ty, tz), scale=s)
             pbar.update(5)
 
             pbar.set_description("Filtering")

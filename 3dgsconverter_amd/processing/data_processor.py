@@ -29,6 +29,7 @@ import contextlib
 import numpy as np
 
 from .. import _lib
+from .. import transform as _transform
 from ..utils import debug_print, status_print
 from . import clusters as _clusters
 
@@ -132,6 +133,8 @@ class DataProcessor:
         self._pending_zero = []     # lazy cap_sh_degree: columns to zero once the host table has been compacted
         self._pending_rgb = None    # lazy add_rgb_from_sh: (n0, 3) u8 colours of the UNcompacted table (a host array, or the chain's
         #                             device array), appended by the compaction pass
+        self._host_stale = False    # lazy apply_transform moved the rows in HBM: the host table still holds the old frame, and
+        #                             .data owes a download even when no filter removes a row
         self.lazy = DataProcessor.lazy_default if lazy is None else bool(lazy)
 
     @property
@@ -151,6 +154,7 @@ class DataProcessor:
             _lib.host_zero_columns(self._data, names)
         self._pending_zero = []
         self._pending_rgb = None
+        self._host_stale = False
         self._drop_chain()
         self._drop_resident()       # (the rows in HBM were the old table's)
         self._data = value
@@ -163,7 +167,10 @@ class DataProcessor:
         return self._rr
 
     def close(self):
-        """give the device chain and the resident rows back (idempotent; ``.data`` stays)"""
+        """give the device chain and the resident rows back (idempotent; ``.data`` stays: a transform the rows in HBM took and
+        the host table has not seen yet is materialised first)"""
+        if self._host_stale and self._rr is not None:
+            self._materialize()
         self._drop_chain()
         self._drop_resident()
 
@@ -193,13 +200,16 @@ class DataProcessor:
         object has them and they can take it, else on the host table (_take_host).  The chain is closed either way; a take's
         new rows replace the source rows, which are closed, after that."""
         compact, ch, zero, rgb = self._compaction_pending(), self._chain, self._pending_zero, self._pending_rgb
-        self._chain, self._pending_zero, self._pending_rgb = None, [], None
+        stale = self._host_stale and self._rr is not None
+        self._chain, self._pending_zero, self._pending_rgb, self._host_stale = None, [], None, False
         taken = None
         try:
             if self._rr is not None:
                 if not (compact or zero or rgb is not None):
+                    if stale:
+                        self._data = self._download_resident()  # (the transformed rows: a new table, the caller's stays)
                     self.resident_ms.setdefault("take", 0.0)    # (the resident path ran, and had nothing to take)
-                    return                                      # .data is the caller's table, .resident its rows
+                    return                                      # .data is the table, .resident its rows
                 new_dtype = _lib.resident_take_dtype(self._rr.dtype, RGB if rgb is not None else ())
                 if new_dtype is not None and (rgb is None or ch is not None):   # (only a chain can hand colours to the take)
                     taken = self._take_resident(ch, zero, rgb, new_dtype)
@@ -208,6 +218,8 @@ class DataProcessor:
                     # come to the host, the resident rows are dropped and the host path runs
                     if isinstance(rgb, _lib.DeviceArray):
                         rgb = ch.rgb_to_host(rgb)
+                    if stale:
+                        self._data = self._download_resident()
                     self._drop_resident()
             if taken is None:
                 self._take_host(ch if compact else None, zero, rgb)
@@ -217,6 +229,19 @@ class DataProcessor:
         if taken is not None:
             self._drop_resident()
             self._data, self._rr = taken
+
+    def _download_resident(self):
+        """the rows in HBM as a new, prefaulted host table (one download, clock "download"); when it raises the rows are closed"""
+        try:
+            out = np.empty(self._rr.n, self._rr.dtype)
+            join = _lib.prefault_parallel(out)
+            with self._timed("download"):
+                join()
+                self._rr.download_into(out)
+        except BaseException:
+            self._drop_resident()
+            raise
+        return out
 
     def _take_resident(self, ch, zero, rgb, new_dtype):
         """the pending work on the rows in HBM: one take -- the chain's when there is one, the rows' own otherwise -- into new
@@ -502,6 +527,35 @@ class DataProcessor:
         status_print(f"After cropping, retained {len(self.data)} vertices.")
         return self.data
 
+    # ------------------------------------------------------------------ scene transform (no counterpart in the reference)
+    def apply_transform(self, rotation=None, translation=None, scale=None):
+        """The similarity transform p' = scale * rotation @ p + translation of the whole table (csrc/transform.hip): positions,
+        log-scales, orientation quaternions, normals and every SH band above DC move with the scene.  rotation: a proper 3x3
+        rotation matrix (transform.rotation_from_euler_deg makes one), scale > 0; None: identity.  Every refusal
+        (transform.plan_transform) is raised before any device work; identity arguments return at once.  Pending filters are
+        materialised first.  Lazy with resident rows: they are transformed in HBM in place, and ``.data`` owes one download;
+        otherwise the host table goes through the device into a new table (the caller's array is left alone)."""
+        debug_print("[DEBUG] Executing 'apply_transform' function...")
+        self._flush_rgb()
+        if not isinstance(self._data, np.ndarray) or self._data.dtype.fields is None:
+            raise TypeError("self.data must be a numpy structured array.")
+        plan = _transform.plan_transform(self._data.dtype, rotation, scale, translation)
+        if plan.identity:
+            return None if self.lazy else self.data
+        if self._chain is not None:
+            self._materialize()
+        n = len(self._data)
+        if n:
+            if self.lazy and self._rr is not None:
+                self._rr.transform(plan, stage_ms=self.resident_ms)
+                self._host_stale = True
+            elif self.lazy:
+                self._data = _lib.rows_transform_table(self._data, plan, stage_ms=self.resident_ms)   # (deferred fills stay deferred)
+            else:
+                self.data = _lib.rows_transform_table(self.data, plan)
+        status_print(f"Transform applied to {n} splats.")
+        return None if self.lazy else self.data
+
     # ------------------------------------------------------------------ table-shaping methods (SURVEY.md 8(f) rank 4)
     def cap_sh_degree(self, degree):
         """reference :276-314: zero the f_rest_* columns above `degree`.  One threaded pass over the rows (the reference
@@ -578,6 +632,8 @@ class DataProcessor:
         self._flush_rgb()
         if self.lazy and self._rr is not None and len(self) > 0 and self._add_rgb_resident():
             return
+        if self._host_stale:
+            self._materialize()         # (the host path reads the table: the transformed rows first)
         if self.lazy and self._compaction_pending() and isinstance(self._data, np.ndarray) and self._chain.n > 0:
             # a compaction is pending: colours for the rows of the table as it is (per-row arithmetic: the survivors' colours are what
             # the reference computes on the filtered table), appended by the ONE pass that compacts it (_materialize)

@@ -1137,6 +1137,39 @@ int gsx_rows_take_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, in
  * gsx_rgb_from_sh_list_dev lists, so that the colours stay in HBM.  Synchronises the context's stream. */
 int gsx_dev_patch_u8(gsx_ctx *ctx, uint8_t *dst_dev, int64_t dst_len, const uint32_t *idx, const uint8_t *val, int64_t cnt);
 
+
+/* ---- a similarity transform p' = s R p + t of a whole table (csrc/transform.hip) ----
+ * R a proper rotation, s > 0, t a translation.  Four parts of a splat depend on the frame: the position, the log-scales, the
+ * orientation quaternion and every spherical-harmonic band above DC (and the normals of a table that has them).  Every product
+ * and sum is float64, rounded once per operation, left to right, the result cast to float32; the log-scales take one float32
+ * add.  A part whose bit is clear, and every other byte of a row, is a bit copy.  The caller computes the numbers (the Python
+ * package: transform.plan_transform); nothing here checks that R is a rotation or that the D matrices belong to it. */
+enum { GSX_TF_POSITION = 1, GSX_TF_NORMALS = 2, GSX_TF_SCALES = 4, GSX_TF_ROTATION = 8, GSX_TF_SH1 = 16, GSX_TF_SH2 = 32, GSX_TF_SH3 = 64,
+       GSX_TF_ALL = 127 };
+typedef struct {
+    uint32_t parts;                    /* GSX_TF_* bits: the parts that are rewritten */
+    int32_t  rest_m;                   /* f_rest coefficients per colour channel: 3, 8 or 15 when an SH bit is set */
+    int32_t  xyz_offset[3];            /* byte offsets of the float32 (little-endian) fields inside a row; read for set bits only */
+    int32_t  normal_offset[3];
+    int32_t  scale_offset[3];
+    int32_t  rot_offset[4];            /* rot_0..3 = (w, x, y, z) */
+    int32_t  rest_offset[45];          /* f_rest_i; channel c, coefficient k is f_rest_(c * rest_m + k), band l starts at k = l*l - 1 */
+    float    log_scale;                /* float32(log(s)): scale_i' = scale_i + log_scale */
+    double   M[9];                     /* s R, row-major: x' = f32(((M00 x + M01 y) + M02 z) + t0) */
+    double   R[9];                     /* the normals: the same without the translation */
+    double   t[3];
+    double   q[4];                     /* q_R = (w, x, y, z): rot' = q_R (x) rot (Hamilton product), the norm is kept */
+    double   D1[9], D2[25], D3[49];    /* band l of every channel: c'_j = f32((...(D[j][0] c_0 + D[j][1] c_1) + ...)), row-major */
+} gsx_transform_layout;
+/* rows_dev as gsx_rows_take_dev takes it; out_dev (16-byte aligned, row 0 at byte first_byte too) may be rows_dev: in place.
+ * Only the n * stride bytes of the rows are written.  A field of a set part outside a row, or two written fields that share a
+ * byte, are refused.  n = 0 launches nothing.  One launch.  Asynchronous. */
+int gsx_rows_transform_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t stride, int64_t n,
+                           const gsx_transform_layout *layout, void *out_dev);
+/* the same on the HOST, from the same per-row functions (the host tests hold it against the definition, bit for bit).  HOST
+ * pointers, rows at any address, out may be rows; nothing outside the rows is read or written. */
+int gsx_rows_transform_host(const void *rows, int64_t stride, int64_t n, const gsx_transform_layout *layout, void *out);
+
 #ifdef __cplusplus
 }
 #endif

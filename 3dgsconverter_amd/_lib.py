@@ -379,6 +379,9 @@ SIGNATURES = {
     "gsx_rows_transform_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(TransformLayout), _P]),
     "gsx_rows_transform_host": (_I, [_P, _I64, _I64, C.POINTER(TransformLayout), _P]),
     "gsx_dev_patch_u8": (_I, [_P, _P, _I64, _P, _P, _I64]),
+    "gsx_limit_keys_dev": (_I, [_P, _P, _I64, _P]),
+    "gsx_limit_select_dev": (_I, [_P, _P, _P, _I64, _I64, _P, _P]),
+    "gsx_limit_select_host": (_I, [_P, _P, _I64, _I64, _P, _P]),
 }
 
 _lib = None
@@ -1728,6 +1731,79 @@ def rows_transform_table(data: np.ndarray, plan, stage_ms: "dict | None" = None,
         s.mark("transform")
         s.download_rows(lib, out, d_rows, data.nbytes, join)
         s.mark("download")
+    return out
+
+
+LIMIT_FIELDS = ("scale_0", "scale_1", "scale_2", "opacity")   # the fields of the splat budget's metric, in gsx_limit_keys_dev's order
+
+
+def limit_count(max_count) -> int:
+    """a splat budget as an int: ValueError for anything but an integer >= 1 (a bool and a float are no counts)"""
+    if isinstance(max_count, (bool, np.bool_)) or not isinstance(max_count, (int, np.integer)) or int(max_count) < 1:
+        raise ValueError(f"max_count must be an integer of at least 1. Got {max_count!r}.")
+    return int(max_count)
+
+
+def limit_info(info) -> dict:
+    """gsx_limit_select_*'s three words -> dict(kept, threshold, ties_kept, threshold_key); threshold: the metric of the last
+    row kept, float32(-sort_unkey(T)) (csrc/sog_math.h)"""
+    key = int(info[0])
+    bits = (key & 0x7fffffff) if key & 0x80000000 else (~key & 0xffffffff)
+    return {"kept": int(info[2]), "threshold": -np.array([bits], np.uint32).view(np.float32)[0], "ties_kept": int(info[1]),
+            "threshold_key": key}
+
+
+def limit_columns_host(data: np.ndarray) -> np.ndarray:
+    """(n, 4) float32: LIMIT_FIELDS of every row of a host table, one threaded pass (gsx_host_gather_f32) -- the array
+    gsx_rows_columns_f32_dev writes for resident rows, gsx_limit_keys_dev's input"""
+    return host_gather_xyz(data, LIMIT_FIELDS)
+
+
+def limit_keys_dev(ctx: "Context", cols_ptr: int, n0: int, keys_ptr: int):
+    """gsx_limit_keys_dev: (n0, 4) device columns -> n0 device keys.  Asynchronous."""
+    check(ctx.lib.gsx_limit_keys_dev(ctx.handle, cols_ptr, int(n0), keys_ptr), "gsx_limit_keys_dev")
+
+
+def limit_select_dev(ctx: "Context", keys_ptr: int, orig_ptr, n: int, max_count: int, mask_ptr: int) -> dict:
+    """gsx_limit_select_dev: the mask of the `max_count` smallest keys among the chain's n rows at `mask_ptr` -> limit_info"""
+    info = (C.c_uint32 * 3)()
+    check(ctx.lib.gsx_limit_select_dev(ctx.handle, keys_ptr, orig_ptr, int(n), int(max_count), mask_ptr, info), "gsx_limit_select_dev")
+    return limit_info(info)
+
+
+def limit_select_host(keys: np.ndarray, max_count: int, orig: "np.ndarray | None" = None):
+    """gsx_limit_select_host: the select's host twin (csrc/limit_select.h's digit walk and tie rule) on uint32 keys; orig: the
+    ascending uint32 rows of `keys` the select runs over (None: all) -> (bool mask, one per selected row; limit_info).  No
+    device is touched."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    if orig is not None:
+        orig = np.ascontiguousarray(orig, dtype=np.uint32)
+    n = len(keys) if orig is None else len(orig)
+    mask = np.zeros(n, np.uint8)
+    info = (C.c_uint32 * 3)()
+    check(load().gsx_limit_select_host(keys.ctypes.data, orig.ctypes.data if orig is not None else None, n, int(max_count),
+                                       mask.ctypes.data, info), "gsx_limit_select_host")
+    return mask.view(np.bool_), limit_info(info)
+
+
+def limit_mask(columns4: np.ndarray, max_count: int, device: int = 0) -> dict:
+    """The splat budget on host columns, for the eager DataProcessor (sor_filter's place in remove_flyers): columns4, the (n, 4)
+    float32 LIMIT_FIELDS of a table, uploaded once, gsx_limit_keys_dev and gsx_limit_select_dev there, and the n mask bytes
+    back -> limit_info and mask (bool[n]) for host_compact_rows.  One ArenaSession of the "limit" lease group."""
+    max_count = limit_count(max_count)
+    cols = np.ascontiguousarray(columns4, dtype=np.float32)
+    if cols.ndim != 2 or cols.shape[1] != 4:
+        raise ValueError("limit_mask: an (n, 4) array of scale_0, scale_1, scale_2, opacity")
+    n = len(cols)
+    if n == 0:
+        return dict(limit_info((0, 0, 0)), mask=np.zeros(0, np.bool_))
+    require_hip()
+    with ArenaSession("limit", device) as s:
+        d_cols, d_keys, d_mask = s.buf("cols", 16 * n), s.buf("keys", 4 * n), s.buf("mask", n + 16)
+        d_cols.upload(cols)
+        limit_keys_dev(s.ctx, d_cols.ptr, n, d_keys.ptr)
+        out = limit_select_dev(s.ctx, d_keys.ptr, None, n, max_count, d_mask.ptr)
+        out["mask"] = d_mask.download(np.uint8, n).view(np.bool_)
     return out
 
 
@@ -3918,6 +3994,34 @@ class DeviceChain:
             return self._compact()
         finally:
             self._free(dev)
+
+    def limit_keep(self, max_count: int, columns: "np.ndarray | None" = None) -> dict:
+        """the splat budget (csrc/limit.hip): of the rows the chain has, the `max_count` with the smallest .splat sort keys, equal
+        keys by row index, in input order.  The keys are those of EVERY row the chain started from: their (n0, 4) LIMIT_FIELDS
+        gathered out of the resident rows on the device, or `columns` (limit_columns_host of the host table) uploaded once, into
+        the chain's "limit_cols"; the keys go to "limit_keys" and the select reads them through the survivor list.  Both buffers
+        are released like "column".  -> dict(kept, threshold, ties_kept, threshold_key)"""
+        max_count = limit_count(max_count)
+        n0 = self.n0
+        if max_count >= self.n:             # nothing to remove: no device work
+            return {"kept": self.n, "threshold": None, "ties_kept": 0, "threshold_key": None}
+        d_cols, d_keys = self._alloc(max(16 * n0, 16), "limit_cols"), self._alloc(max(4 * n0, 16), "limit_keys")
+        try:
+            rr = self.resident
+            if rr is not None:
+                rows_columns_dev(self.ctx, rr.ptr, rr.first_byte, rr.dtype, rr.n, LIMIT_FIELDS, d_cols.ptr)
+            else:
+                cols = np.ascontiguousarray(columns, dtype=np.float32)
+                if cols.shape != (n0, 4):
+                    raise ValueError("columns must hold scale_0, scale_1, scale_2, opacity of every original row")
+                d_cols.upload(cols)
+            limit_keys_dev(self.ctx, d_cols.ptr, n0, d_keys.ptr)
+            out = limit_select_dev(self.ctx, d_keys.ptr, self.orig.ptr if self.orig is not None else None, self.n, max_count, self.mask.ptr)
+            out["kept"] = self._compact()
+            return out
+        finally:
+            self._free(d_cols)
+            self._free(d_keys)
 
     def sor_keep(self, k: int, threshold_factor: float):
         numpy_reduction_selfcheck(self.ctx)

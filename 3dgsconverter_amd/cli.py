@@ -224,6 +224,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--density_sensitivity", type=float, help="Density filter, 0.0-1.0: higher keeps only denser regions.")
     p.add_argument("--sor_intensity", type=float, help="Statistical outlier removal, 1.0-10.0: higher removes more floaters.")
     p.add_argument("--min_opacity", type=int, help="Drop splats whose opacity is below this value (0-255).")
+    p.add_argument("--max_splats", type=int, metavar="N",
+                   help="Keep at most N splats: the most visible ones by the .splat writer's metric (size times opacity), after every other filter.")
     p.add_argument("--keep_multicluster", action="store_true", help="Density filter: keep every dense cluster, not only the largest.")
     p.add_argument("--compression_level", type=int, default=0,
                    help="0-9, per format: .ksplat 0 = float32, 1 = float16 blocks, 2+ = 8-bit SH; .spz the gzip level; .sog the palette size.")
@@ -243,6 +245,9 @@ def main(argv=None):
         return
     if args.min_opacity is not None and not (0 <= args.min_opacity <= 255):
         print(f"Error: --min_opacity must be between 0 and 255. Got {args.min_opacity}.")
+        return
+    if args.max_splats is not None and args.max_splats < 1:
+        print(f"Error: --max_splats must be at least 1. Got {args.max_splats}.")
         return
     if args.scale is not None and not (np.isfinite(args.scale) and args.scale > 0):
         print(f"Error: --scale must be a finite number greater than 0. Got {args.scale}.")
@@ -280,7 +285,7 @@ def main(argv=None):
     has_source_extras = check_source_extras(args.input)
     filters_active = any([args.density_voxel_size, args.density_threshold, args.sor_k, args.sor_sigma, args.crop_sh,
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
-                          args.rotate is not None, args.scale is not None, args.translate is not None,
+                          args.rotate is not None, args.scale is not None, args.translate is not None, args.max_splats is not None,
                           has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
@@ -314,7 +319,8 @@ def main(argv=None):
                       sor_sigma=args.sor_sigma, sor_intensity=args.sor_intensity, min_opacity=args.min_opacity, bbox=args.bbox,
                       rgb=args.rgb, sh_level=args.sh_level, bucket_size=args.bucket_size, block_size=args.block_size,
                       crop_sh=args.crop_sh, auto_bbox=args.auto_bbox, compression_level=args.compression_level,
-                      maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate)
+                      maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate,
+                      max_splats=args.max_splats)
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

@@ -230,7 +230,8 @@ class Converter:
 
     def run(self, **kwargs):
         """the reference's keywords, and ``rotate=(rx, ry, rz)`` (degrees: about the fixed X, then Y, then Z axis), ``scale=s`` and
-        ``translate=(tx, ty, tz)``: the scene transform p' = s R p + t, applied right after the SH cap and before every filter"""
+        ``translate=(tx, ty, tz)``: the scene transform p' = s R p + t, applied right after the SH cap and before every filter;
+        and ``max_splats=N``: keep the N most visible splats (DataProcessor.limit_splats), applied after every other filter"""
         debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
         clocks = self.stage_ms = {}
         held = []                   # the processor of this run: whatever it still holds in HBM is freed on every exit path
@@ -300,6 +301,10 @@ class Converter:
             if (s_k is not None and s_sigma is not None) or s_intensity is not None:
                 pbar.set_description("Filtering (SOR)")
                 processor.remove_flyers(25 if s_k is None else int(s_k), 10.5 if s_sigma is None else float(s_sigma), intensity=s_intensity)
+            # the splat budget is the last filter: the box that is printed and the colours belong to what is written
+            max_splats = kwargs.pop("max_splats", None)
+            if max_splats is not None:
+                processor.limit_splats(max_splats)
             pbar.update(10)
             if kwargs.get("auto_bbox"):
                 processor.apply_auto_bbox()

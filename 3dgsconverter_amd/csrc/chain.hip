@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "gsx_common.h"
+#include "tile_scan.h"
 
 namespace gsx {
 
@@ -30,33 +31,7 @@ __global__ __launch_bounds__(256) void compact_count_kernel(const uint8_t *__res
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
-// exclusive scan of the tile counts in place (one workgroup); total -> *total_out
-__global__ __launch_bounds__(1024) void compact_scan_kernel(unsigned *__restrict__ tile_cnt, int ntiles, unsigned *__restrict__ total_out)
-{
-    __shared__ unsigned s_w[16];
-    __shared__ unsigned s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int b = 0; b < ntiles; b += 1024) {
-        const int i = b + threadIdx.x;
-        const unsigned v = i < ntiles ? tile_cnt[i] : 0u;
-        unsigned inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned o = __shfl_up(inc, off);
-            if ((int)(threadIdx.x & 63) >= off) inc += o;
-        }
-        if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        unsigned pre = s_carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) pre += s_w[w];
-        if (i < ntiles) tile_cnt[i] = pre + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = pre + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = s_carry;
-}
+// (compact_scan_kernel, the exclusive scan of the tile counts between the two: tile_scan.h)
 
 __global__ __launch_bounds__(256) void compact_write_kernel(const float *__restrict__ rows, const unsigned *__restrict__ orig,
                                                             const uint8_t *__restrict__ mask, int64_t n,

@@ -22,6 +22,7 @@
 #include "np_exp.h"
 #include "row_tile.h"
 #include "sog_math.h"
+#include "splat_metric.h"
 
 namespace gsx {
 
@@ -35,9 +36,7 @@ struct SplatRgb {
 template <class Fld>
 __device__ __forceinline__ unsigned splat_metric_key(Fld fld)
 {
-    const float ssum = __fadd_rn(__fadd_rn(fld(SPZ_F_SCALE), fld(SPZ_F_SCALE + 1)), fld(SPZ_F_SCALE + 2));
-    const float opa = __fdiv_rn(1.0f, __fadd_rn(1.0f, np_expf(-fld(SPZ_F_OPACITY))));
-    return sort_key(-__fmul_rn(np_expf(ssum), opa));
+    return splat_metric_key_of(fld(SPZ_F_SCALE), fld(SPZ_F_SCALE + 1), fld(SPZ_F_SCALE + 2), fld(SPZ_F_OPACITY));
 }
 
 // :104-161 -> the record's eight words.  byte(k): the k-th colour byte (red, green, blue) in the fallback of :140-143

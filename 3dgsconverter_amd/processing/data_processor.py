@@ -556,6 +556,54 @@ class DataProcessor:
         status_print(f"Transform applied to {n} splats.")
         return None if self.lazy else self.data
 
+    # ------------------------------------------------------------------ splat budget (no counterpart in the reference)
+    def limit_splats(self, max_count):
+        """Keep the `max_count` most visible splats, in input order (csrc/limit.hip).  Visibility is the .splat writer's metric,
+        exp((scale_0 + scale_1) + scale_2) * (1 / (1 + exp(-opacity))) in float32 with the exp of csrc/np_exp.h; rows are ranked
+        by the writer's sort key of its negative -- a NaN metric goes first, an infinite one last --, equal keys by row index.
+        Refusals come before any device work: ValueError for a budget that is no integer >= 1, TypeError for a field that is
+        not float32; a table without the four fields is left as it is, with a warning.  Lazy: one more step of the device
+        chain (the keys from the resident rows when there are some), returns None; eager: updates and returns ``.data``.
+        ``last_limit``: the metric of the last row kept and how many rows of exactly that metric were kept."""
+        debug_print(f"[DEBUG] Executing 'limit_splats' with max={max_count}")
+        self._flush_rgb()
+        N = _lib.limit_count(max_count)
+        if not isinstance(self._data, np.ndarray) or self._data.dtype.fields is None:
+            raise TypeError("self.data must be a numpy structured array.")
+        if any(nm not in self._data.dtype.names for nm in _lib.LIMIT_FIELDS):
+            status_print("Warning: Splat limit needs scale_0..2 and opacity. Limit skipped.")
+            return None if self.lazy else self.data
+        _lib.require_f4_fields(self._data, _lib.LIMIT_FIELDS, "limit_splats")
+        for nm in _lib.LIMIT_FIELDS:        # (the device gather of resident rows copies words: no byte-swapped fields either)
+            if self._data.dtype[nm] != np.dtype("<f4"):
+                raise TypeError(f"limit_splats: field {nm!r} is {self._data.dtype[nm].str}; the keys are computed from little-endian "
+                                f"float32 ('<f4') fields only")
+        n = len(self)
+        if N >= n:
+            status_print(f"Splat Limit (max {N}): {n} splats, nothing to remove.")
+            return None if self.lazy else self.data
+        if self.lazy:
+            columns = None
+            if self._rr is None:
+                if self._host_stale:
+                    self._materialize()     # (the host path reads the table: the transformed rows first)
+                columns = _lib.limit_columns_host(self._data)
+            ch = self._chain_for(self._data)
+            if self._rr is not None:
+                with self._timed("limit", ch.ctx):
+                    res = ch.limit_keep(N)
+            else:
+                res = ch.limit_keep(N, columns)
+            kept = res["kept"]
+        else:
+            data = self.data
+            res = _lib.limit_mask(_lib.limit_columns_host(data), N)
+            self.data = _lib.host_compact_rows(data, res["mask"])
+            kept = len(self.data)
+        self.last_limit = {"threshold": res["threshold"], "ties_kept": res["ties_kept"]}
+        status_print(f"Splat Limit (max {N}): Retained {kept} out of {n} splats.")
+        return None if self.lazy else self.data
+
     # ------------------------------------------------------------------ table-shaping methods (SURVEY.md 8(f) rank 4)
     def cap_sh_degree(self, degree):
         """reference :276-314: zero the f_rest_* columns above `degree`.  One threaded pass over the rows (the reference

@@ -1170,6 +1170,30 @@ int gsx_rows_transform_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byt
  * pointers, rows at any address, out may be rows; nothing outside the rows is read or written. */
 int gsx_rows_transform_host(const void *rows, int64_t stride, int64_t n, const gsx_transform_layout *layout, void *out);
 
+
+/* ---- the splat budget: keep the N most visible rows (csrc/limit.hip) ----
+ * The metric of a row is the .splat writer's (formats/splat.py:92-94): m = E((s0 + s1) + s2) * (1 / (1 + E(-opacity))), every
+ * operation float32 in this order, E the float32 exp of csrc/np_exp.h (on the host: gsx_np_expf_host) whatever numpy the process
+ * runs.  Its key is the writer's sort key of -m: an order-preserving map of float32 to uint32 after -0 -> +0, every NaN ->
+ * 0xffffffff (removed first), an infinite metric 0x007fffff (kept first).  The kept rows are the first N entries of the stable
+ * ascending order of the keys: among equal keys the lower row index wins.
+ *
+ * cols_dev (16-byte aligned): n0 rows of four float32 -- scale_0, scale_1, scale_2, opacity --, the (n0, 4) array that
+ * gsx_rows_columns_f32_dev writes for those four fields (and gsx_host_gather_f32 on the host) -> keys_dev[n0].  One launch.
+ * Asynchronous. */
+int gsx_limit_keys_dev(gsx_ctx *ctx, const float *cols_dev, int64_t n0, uint32_t *keys_dev);
+/* Row j of the n rows a chain currently has carries the key keys_dev[orig_dev ? orig_dev[j] : j] (gsx_mask_ge_dev's convention).
+ * mask_dev[j] (n bytes, nothing behind them is written) = 1 for exactly min(max_count, n) rows, the definition's, else 0.
+ * info_out (HOST, three words): the threshold key T -- the min(max_count, n)-th smallest --, how many of the rows with key == T
+ * are kept (>= 1; the first ones in row order), and min(max_count, n); all 0 when n = 0.  A radix select, 8 bits per pass, most
+ * significant digit first: four histogram passes over the keys, the digit walk on the device between them, then per-tile tie
+ * counts, one scan and the mask pass -- no sort, no host round trip between passes, n / 2048 + 1032 words of workspace.
+ * max_count < 1, n < 0, n >= 2^32 and null pointers are refused.  Synchronises the context's stream (the copy of info_out). */
+int gsx_limit_select_dev(gsx_ctx *ctx, const uint32_t *keys_dev, const uint32_t *orig_dev, int64_t n, int64_t max_count, uint8_t *mask_dev,
+                         uint32_t *info_out);
+/* the same on the HOST, from the same digit walk and tie rule (csrc/limit_select.h); HOST pointers, serial. */
+int gsx_limit_select_host(const uint32_t *keys, const uint32_t *orig, int64_t n, int64_t max_count, uint8_t *mask, uint32_t *info_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -378,6 +378,8 @@ SIGNATURES = {
     "gsx_rows_take_dev": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, C.POINTER(C.c_int32), _I, _P, _I, _P, _I64]),
     "gsx_rows_transform_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(TransformLayout), _P]),
     "gsx_rows_transform_host": (_I, [_P, _I64, _I64, C.POINTER(TransformLayout), _P]),
+    "gsx_rows_remap_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(C.c_int32), _I, _P, _I64, _I64, _I64, _I64]),
+    "gsx_rows_remap_host": (_I, [_P, _I64, _I64, _I64, C.POINTER(C.c_int32), _I, _P, _I64, _I64, _I64, _I64]),
     "gsx_dev_patch_u8": (_I, [_P, _P, _I64, _P, _P, _I64]),
     "gsx_limit_keys_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_limit_select_dev": (_I, [_P, _P, _P, _I64, _I64, _P, _P]),
@@ -1555,6 +1557,45 @@ class ResidentRows:
             rows_transform_dev(ctx, self.ptr, self.first_byte, self.dtype.itemsize, self.n, transform_layout(plan), self.ptr)
             ctx.synchronize()
 
+    def profile(self) -> dict:
+        """-> the profile dict of these rows: one gsx_table_profile_dev where they lie (no rows: empty_profile)"""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        return table_profile_dev(self._ctx, self.ptr, self.first_byte, self.n, self.dtype) if self.n else empty_profile()
+
+    @classmethod
+    def concat(cls, parts, dtype, runs_per_part, ctx: "Context | None" = None, stage_ms: "dict | None" = None) -> "ResidentRows":
+        """-> NEW rows (the caller's to close) of `dtype`: the rows of every part, one behind the other, each re-laid by its
+        runs (merge.remap_runs of the part's dtype and `dtype`).  One gsx_rows_remap_dev per part that has rows, at its running
+        row offset, on `ctx` (the new rows' own context without one), all of them joined once at the end; stage_ms["remap"] is
+        those launches and the join alone.  The parts stay as they are and open; when anything raises, the new rows are closed."""
+        parts, runs_per_part = list(parts), list(runs_per_part)
+        if len(parts) != len(runs_per_part):
+            raise ValueError("ResidentRows.concat: %d parts, runs for %d" % (len(parts), len(runs_per_part)))
+        if any(p.ptr is None for p in parts):
+            raise ValueError("ResidentRows: closed")
+        device = parts[0].device if parts else 0
+        if any(p.device != device for p in parts):
+            raise ValueError("ResidentRows.concat: parts on several devices")
+        out = cls(sum(p.n for p in parts), dtype, device)
+        use = ctx if ctx is not None else out._ctx
+        try:
+            with stage_clock(stage_ms, "remap"):
+                row0 = 0
+                for p, runs in zip(parts, runs_per_part):
+                    if p.n:
+                        rows_remap_dev(use, p.ptr, p.first_byte, p.dtype.itemsize, p.n, runs, out.ptr, out.first_byte, out.dtype.itemsize,
+                                       row0, out.n)
+                    row0 += p.n
+                use.synchronize()
+        except BaseException:
+            try:
+                use.synchronize()   # (a remap launched before the failure still writes into the rows that are freed next)
+            finally:
+                out.close()
+            raise
+        return out
+
     def close(self):
         if self.ptr is None:
             return
@@ -1675,6 +1716,41 @@ def rows_take_dev(ctx: "Context", rows_ptr: int, first_byte: int, stride_in: int
     offs = (C.c_int32 * max(len(zero_offsets), 1))(*zero_offsets)
     check(ctx.lib.gsx_rows_take_dev(ctx.handle, rows_ptr, int(first_byte), int(stride_in), int(n_in), idx_ptr, int(n_out), offs, len(zero_offsets),
                                     extra_ptr, int(e), out_ptr, int(stride_in) + int(e)), "gsx_rows_take_dev")
+
+
+def remap_runs_array(runs):
+    """merge.remap_runs' (source byte or -1, destination byte, byte count) triples as gsx_rows_remap_*'s int32 array -> (array, runs)"""
+    flat = [int(v) for run in runs for v in run]
+    if len(flat) % 3 or any(len(run) != 3 for run in runs):
+        raise ValueError("remap runs: (source byte or -1, destination byte, byte count) triples")
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in flat):
+        raise ValueError("remap runs: 32-bit values")
+    return (C.c_int32 * max(len(flat), 1))(*flat), len(flat) // 3
+
+
+def rows_remap_dev(ctx: "Context", src_ptr: int, src_first_byte: int, src_stride: int, n: int, runs, dst_ptr: int, dst_first_byte: int,
+                   dst_stride: int, dst_row0: int, dst_rows: int):
+    """gsx_rows_remap_dev: `n` resident rows re-laid by `runs` (merge.remap_runs) into rows [dst_row0, dst_row0 + n) of the
+    `dst_rows` resident rows at `dst_ptr`; nothing outside those rows is written.  Asynchronous."""
+    arr, n_runs = remap_runs_array(runs)
+    check(ctx.lib.gsx_rows_remap_dev(ctx.handle, src_ptr, int(src_first_byte), int(src_stride), int(n), arr, n_runs, dst_ptr, int(dst_first_byte),
+                                     int(dst_stride), int(dst_row0), int(dst_rows)), "gsx_rows_remap_dev")
+
+
+def rows_remap_host(src: np.ndarray, runs, dst: np.ndarray, dst_row0: int = 0) -> np.ndarray:
+    """gsx_rows_remap_host: the rows of the host table `src` re-laid by `runs` into rows [dst_row0, dst_row0 + len(src)) of the
+    host table `dst` (both 1-D and C-contiguous, rows of up to 512 bytes) -> dst.  The path of a merge without resident rows, and
+    the host tests' model of the kernel; no device is touched."""
+    for name, a in (("source", src), ("destination", dst)):
+        if not isinstance(a, np.ndarray) or a.ndim != 1 or not a.flags.c_contiguous:
+            raise ValueError("rows_remap_host: the %s is a 1-D C-contiguous table" % name)
+    if not dst.flags.writeable:
+        raise ValueError("rows_remap_host: the destination is read-only")
+    arr, n_runs = remap_runs_array(runs)
+    s_at, d_at = src.ctypes.data, dst.ctypes.data          # (the C side takes a 16-byte aligned base and the first row's byte)
+    check(load().gsx_rows_remap_host(s_at & ~15, s_at & 15, src.dtype.itemsize, len(src), arr, n_runs, d_at & ~15, d_at & 15, dst.dtype.itemsize,
+                                     int(dst_row0), len(dst)), "gsx_rows_remap_host")
+    return dst
 
 
 def transform_layout(plan) -> TransformLayout:

@@ -5,7 +5,8 @@ lines of the info block are the reference's (gsconverter/main.py:56-506); the wo
 and the two info blocks of a conversion decode each file once: the bounds and the SH activity come from the profile the reader
 took of its rows in HBM (csrc/table_profile.hip), the PLY property names from the header (formats/ply_reader.parse_header) and
 the compressed-PLY chunk count from the reader's metadata.  In conversion mode the source info block and ``Converter.run``
-share one load.
+share one load.  ``--merge FILE`` (repeatable, with ``--merge_rotate / --merge_scale / --merge_translate`` once per file) adds
+further scenes to the input: ``Converter.run(merge=...)``.
 """
 from __future__ import annotations
 
@@ -211,6 +212,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scale", type=float, metavar="S", help="Scale the scene uniformly by S > 0 (positions and splat sizes).")
     p.add_argument("--translate", nargs=3, type=float, metavar=("X", "Y", "Z"),
                    help="Shift the scene, after rotation and scale. --bbox and the filters work in the transformed frame.")
+    p.add_argument("--merge", action="append", metavar="FILE",
+                   help="Add another scene (any readable format) to the input; repeatable. The union is written in the common layout: the widest "
+                        "SH degree among the files, colours only when every file has them. The global transform and the filters act on the union.")
+    p.add_argument("--merge_rotate", action="append", nargs=3, type=float, metavar=("RX", "RY", "RZ"),
+                   help="Rotate a --merge file alone before the union; give it once per --merge file, in their order, or not at all.")
+    p.add_argument("--merge_scale", action="append", type=float, metavar="S", help="Scale a --merge file alone; once per --merge file, or not at all.")
+    p.add_argument("--merge_translate", action="append", nargs=3, type=float, metavar=("X", "Y", "Z"),
+                   help="Shift a --merge file alone, after its rotation and scale; once per --merge file, or not at all.")
     p.add_argument("--auto_bbox", action="store_true", help="Report the tight bounding box of what the filters leave.")
     p.add_argument("--extra_elements", action="store_true", help="Carry a PLY's non-vertex elements over (3dgs and cc targets).")
     p.add_argument("--density_voxel_size", type=float, help=argparse.SUPPRESS)
@@ -272,6 +281,24 @@ def main(argv=None):
         print(f"Error: Unknown target format '{args.target_format}'. Supported: {', '.join(VALID_FORMATS)}")
         return
 
+    merge_files = args.merge or []                                                              # (no counterpart in the reference)
+    for flag, given in (("--merge_rotate", args.merge_rotate), ("--merge_scale", args.merge_scale), ("--merge_translate", args.merge_translate)):
+        if given is not None and len(given) != len(merge_files):
+            print(f"Error: {flag} was given {len(given)} times for {len(merge_files)} --merge files (once per file, or not at all).")
+            return
+    for s in args.merge_scale or []:
+        if not (np.isfinite(s) and s > 0):
+            print(f"Error: --merge_scale must be a finite number greater than 0. Got {s}.")
+            return
+    for path in merge_files:
+        if not os.path.isfile(path):
+            print(f"Error: --merge file '{path}' does not exist.")
+            return
+    merge_transforms = None
+    if merge_files and any(g is not None for g in (args.merge_rotate, args.merge_scale, args.merge_translate)):
+        merge_transforms = [{"rotate": args.merge_rotate[k] if args.merge_rotate else None, "scale": args.merge_scale[k] if args.merge_scale else None,
+                             "translate": args.merge_translate[k] if args.merge_translate else None} for k in range(len(merge_files))]
+
     if not args.output:                                                                         # :349-371
         base_name, input_ext = os.path.splitext(args.input)
         target_ext = EXTENSIONS.get(args.target_format, "." + args.target_format)
@@ -286,7 +313,7 @@ def main(argv=None):
     filters_active = any([args.density_voxel_size, args.density_threshold, args.sor_k, args.sor_sigma, args.crop_sh,
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
                           args.rotate is not None, args.scale is not None, args.translate is not None, args.max_splats is not None,
-                          has_source_extras and not args.extra_elements])
+                          bool(merge_files), has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
         print("\n[INFO] Target is generic 3DGS PLY (same as input extension) and no filters are active.")
@@ -320,7 +347,7 @@ def main(argv=None):
                       rgb=args.rgb, sh_level=args.sh_level, bucket_size=args.bucket_size, block_size=args.block_size,
                       crop_sh=args.crop_sh, auto_bbox=args.auto_bbox, compression_level=args.compression_level,
                       maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate,
-                      max_splats=args.max_splats)
+                      max_splats=args.max_splats, **({"merge": merge_files, "merge_transforms": merge_transforms} if merge_files else {}))
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

@@ -6,6 +6,7 @@ readers, filter chain and writers: a file is converted on a machine that has thi
   | :27-61 format by extension, then the header sniff | detect_format: the same tests, host only                            |
   | :63-72, :112-115 the handler's read               | the format's read_* with ``profile={}``: the decoded rows are       |
   |                                                   | profiled in HBM before their download (csrc/table_profile.hip)      |
+  | (none: the reference reads one file)              | run(merge=[...]): the union of several sources, re-laid in HBM      |
   | :121-146 45 strided `np.any(col != 0)` scans      | plan_conversion on the profile's 64-bit word                        |
   | :150-252 DataProcessor, the filters in order      | processing.ChainedDataProcessor: one device-resident chain          |
   | (none: the reference cannot move a scene)         | run(rotate=, scale=, translate=): apply_transform before the filters|
@@ -91,6 +92,19 @@ def plan_conversion(names, rest_nonzero: int, target_format: str, kwargs: dict) 
     add_rgb = ((target_format in FORMATS_NEEDING_RGB and not has_rgb) or bool(kwargs.get("rgb", False))) and not has_rgb
     return {"source_degree": source, "final_degree": final, "messages": messages, "add_rgb": add_rgb,
             "rgb_message": f"Target format '{target_format}' requires RGB. Auto-calculating from SH..." if add_rgb else None}
+
+
+def transform_values(rotate, scale, translate):
+    """run()'s ``rotate= scale= translate=`` (None: none) -> ((rx, ry, rz), s, (tx, ty, tz)) as floats"""
+    rx, ry, rz = (float(v) for v in (rotate if rotate is not None else (0.0, 0.0, 0.0)))
+    tx, ty, tz = (float(v) for v in (translate if translate is not None else (0.0, 0.0, 0.0)))
+    return (rx, ry, rz), 1.0 if scale is None else float(scale), (tx, ty, tz)
+
+
+def transform_text(rotate, s, translate) -> str:
+    """what the `Transform:` status lines say of transform_values' numbers"""
+    (rx, ry, rz), (tx, ty, tz) = rotate, translate
+    return f"scale {s:g}, rotate [{rx:g}, {ry:g}, {rz:g}] deg, translate [{tx:g}, {ty:g}, {tz:g}]"
 
 
 class SourceHandler:
@@ -231,7 +245,9 @@ class Converter:
     def run(self, **kwargs):
         """the reference's keywords, and ``rotate=(rx, ry, rz)`` (degrees: about the fixed X, then Y, then Z axis), ``scale=s`` and
         ``translate=(tx, ty, tz)``: the scene transform p' = s R p + t, applied right after the SH cap and before every filter;
-        and ``max_splats=N``: keep the N most visible splats (DataProcessor.limit_splats), applied after every other filter"""
+        and ``max_splats=N``: keep the N most visible splats (DataProcessor.limit_splats), applied after every other filter;
+        and ``merge=[path, ...]`` with ``merge_transforms=[None | {"rotate":, "scale":, "translate":}, ...]``: further sources
+        whose rows follow the main source's in one table (_merge_sources), before everything else"""
         debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
         clocks = self.stage_ms = {}
         held = []                   # the processor of this run: whatever it still holds in HBM is freed on every exit path
@@ -242,6 +258,88 @@ class Converter:
                 p.close()
             self.close()
         status_print(f"Conversion completed: Saved to {self.output_path}")
+
+    def _merge_sources(self, clocks, paths, transforms):
+        """``run(merge=[path, ...], merge_transforms=[None | {"rotate":, "scale":, "translate":}, ...])``: the union of the main
+        source and the extra files, in that order, in the common row layout of merge.merged_dtype.  Every extra file is read
+        once by a handler of its own and moved by its own transform alone; then every source's rows are re-laid at their row
+        offset of one table -- in HBM when every reader kept its rows (ResidentRows.concat: csrc/rows_remap.hip; the host table
+        is ONE download of the union, its profile one pass over it there), else on the host (gsx_rows_remap_host).  Afterwards
+        ``self.data``, ``self.profile`` and the main handler's resident rows are the union's: the global transform and every
+        filter act on it as on a single source.  Clocks: merge_read (the extras' reads, summed), merge_transform, merge_remap,
+        and merge_download on the resident path."""
+        import time
+
+        import numpy as np
+
+        from . import _lib, merge, transform
+        transforms = [None] * len(paths) if transforms is None else list(transforms)
+        if len(transforms) != len(paths):
+            raise ValueError(f"merge_transforms: one entry per merge source (None: none), got {len(transforms)} for {len(paths)}")
+        main = self.source_handler
+        tables, rows = [self.data], [main.take_resident() if hasattr(main, "take_resident") else None]
+        stale = [False]             # a source's rows in HBM were moved: its host table still holds the old frame
+        ms = {}
+        try:
+            for k, (path, tf) in enumerate(zip(paths, transforms), 1):
+                fmt = self._detect_format(path)
+                if not fmt:
+                    raise ValueError(f"Could not detect source format of merge source '{path}'")
+                handler = self._get_format_handler(fmt)
+                with _lib.stage_clock(clocks, "merge_read"):
+                    table = handler.read(path)
+                tables.append(table)
+                rows.append(handler.take_resident())
+                stale.append(False)
+                status_print(f"Merge: {path} ({fmt.upper()}, {len(table):,} splats)")
+                if tf:
+                    rotate, s, translate = transform_values(tf.get("rotate"), tf.get("scale"), tf.get("translate"))
+                    status_print(f"Merge Transform [{k}]: {transform_text(rotate, s, translate)}")
+                    plan = transform.plan_transform(table.dtype, transform.rotation_from_euler_deg(*rotate), s, translate)
+                    with _lib.stage_clock(clocks, "merge_transform"):
+                        if rows[k] is not None:
+                            rows[k].transform(plan)
+                            stale[k] = not plan.identity and len(table) > 0
+                        else:
+                            tables[k] = _lib.rows_transform_table(table, plan)
+            labels = [repr(p) for p in [self.input_path] + paths]
+            merged, notes = merge.merged_dtype([t.dtype for t in tables], labels)
+            runs = [merge.remap_runs(t.dtype, merged) for t in tables]
+            if all(rr is not None for rr in rows):
+                union = _lib.ResidentRows.concat(rows, merged, runs, stage_ms=ms)
+                main.resident = union                       # (this run's from here on: run() closes the handler on every path)
+                while rows:
+                    rows.pop().close()
+                with _lib.stage_clock(ms, "download"):
+                    self.data = union.download()
+                self.profile = union.profile()
+            else:
+                for k, table in enumerate(tables):
+                    if stale[k]:
+                        tables[k] = rows[k].download()
+                while rows:
+                    rr = rows.pop()
+                    if rr is not None:
+                        rr.close()
+                out = np.empty(sum(len(t) for t in tables), merged)
+                with _lib.stage_clock(ms, "remap"):
+                    row0 = 0
+                    for table, table_runs in zip(tables, runs):
+                        if table.ndim == 1 and table.flags.c_contiguous and table.dtype.itemsize <= _lib.RESIDENT_MAX_ROW_BYTES:
+                            _lib.rows_remap_host(table, table_runs, out, row0)
+                        else:
+                            merge.remap_fields(table, out, row0)
+                        row0 += len(table)
+                self.data, self.profile = out, _lib.host_table_profile(out)
+        finally:
+            for rr in rows:
+                if rr is not None:
+                    rr.close()
+        clocks.update({"merge_" + k: v for k, v in ms.items()})
+        n_rest = sum(1 for nm in merged.names if nm.startswith("f_rest_"))
+        status_print(f"Merged {len(tables)} sources: {len(self.data):,} splats, {n_rest} SH columns.")
+        for line in notes:
+            status_print(line)
 
     def _run(self, clocks, held, kwargs):
         import time
@@ -263,6 +361,9 @@ class Converter:
                 self.profile = self.source_handler.profile
                 clocks.update({"read_" + k: v for k, v in read_ms.items()})
             self._loaded = None     # (the table is about to change in place: cap_sh_degree)
+            merge_paths, merge_transforms = kwargs.pop("merge", None), kwargs.pop("merge_transforms", None)
+            if merge_paths:
+                self._merge_sources(clocks, list(merge_paths), merge_transforms)
             pbar.update(25)
 
             plan = plan_conversion(self.data.dtype.names, self.profile["rest_nonzero"], self.target_format, kwargs)
@@ -279,10 +380,8 @@ class Converter:
             rotate, scale, translate = kwargs.pop("rotate", None), kwargs.pop("scale", None), kwargs.pop("translate", None)
             if rotate is not None or scale is not None or translate is not None:
                 from . import transform
-                rx, ry, rz = (float(v) for v in (rotate if rotate is not None else (0.0, 0.0, 0.0)))
-                tx, ty, tz = (float(v) for v in (translate if translate is not None else (0.0, 0.0, 0.0)))
-                s = 1.0 if scale is None else float(scale)
-                status_print(f"Transform: scale {s:g}, rotate [{rx:g}, {ry:g}, {rz:g}] deg, translate [{tx:g}, {ty:g}, {tz:g}]")
+                (rx, ry, rz), s, (tx, ty, tz) = transform_values(rotate, scale, translate)
+                status_print(f"Transform: {transform_text((rx, ry, rz), s, (tx, ty, tz))}")
                 processor.apply_transform(rotation=transform.rotation_from_euler_deg(rx, ry, rz), translation=(tx, ty, tz), scale=s)
             pbar.update(5)
 

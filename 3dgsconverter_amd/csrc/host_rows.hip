@@ -21,28 +21,11 @@
 #include <vector>
 
 #include "gsx_common.h"
+#include "host_threads.h"
 #include "table_profile.h"
 
-namespace {
-
-int worker_count(int64_t bytes)
-{
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int64_t by_size = bytes / (8LL << 20) + 1;  // ~8 MiB of traffic per thread at least
-    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 8), 64, by_size}));
-}
-
-template <class F>
-void run_threads(int nt, F &&body)  // body(t) for t in [0, nt); the caller is thread 0
-{
-    std::vector<std::thread> th;
-    th.reserve(nt > 1 ? nt - 1 : 0);
-    for (int t = 1; t < nt; ++t) th.emplace_back([&body, t] { body(t); });
-    body(0);
-    for (auto &x : th) x.join();
-}
-
-}  // namespace
+using gsx::run_threads;
+using gsx::worker_count;
 
 extern "C" int gsx_host_gather_f32(const void *rows, int64_t row_bytes, int64_t n, const int64_t *offsets, int ncols,
                                    float *out)

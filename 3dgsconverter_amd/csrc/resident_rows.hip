@@ -57,19 +57,6 @@ constexpr int TAKE_THREADS = 128;
 constexpr int TAKE_BATCH = 4;            // 16-byte loads a lane has in flight
 static inline int take_tile_rows(int stride_out) { return spz_tile_rows(stride_out) / 4; }
 
-// quads [q0, q0 + nq) of `rows` -> lds[0 .. nq), TAKE_BATCH loads per lane in flight
-__device__ __forceinline__ void take_stage_span(const uint4 *__restrict__ rows, int64_t q0, int nq, uint4 *lds)
-{
-    for (int k0 = threadIdx.x; k0 < nq; k0 += TAKE_BATCH * TAKE_THREADS) {
-        uint4 v[TAKE_BATCH];
-#pragma unroll
-        for (int u = 0; u < TAKE_BATCH; ++u)
-            if (k0 + u * TAKE_THREADS < nq) v[u] = rows[q0 + k0 + u * TAKE_THREADS];
-#pragma unroll
-        for (int u = 0; u < TAKE_BATCH; ++u)
-            if (k0 + u * TAKE_THREADS < nq) lds[k0 + u * TAKE_THREADS] = v[u];
-    }
-}
 constexpr size_t TAKE_MAX_LDS = 64 * 1024;   // (the default limit of dynamic LDS; the widest tile takes 17 KiB)
 
 struct TakeArgs {
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(TAKE_THREADS) void rows_take_kernel(const uint4 *__
     __syncthreads();
     if (s_run) {                               // (ascending and distinct: first and last cnt - 1 apart means consecutive)
         const int64_t b0 = first + (int64_t)s_src[0] * si, b1 = b0 + (int64_t)cnt * si;   // (spz_stage_tile's span)
-        take_stage_span(rows, b0 >> 4, (int)(((b1 + 15) >> 4) - (b0 >> 4)), tk_lds);
+        stage_span<TAKE_THREADS, TAKE_BATCH>(rows, b0 >> 4, (int)(((b1 + 15) >> 4) - (b0 >> 4)), tk_lds);
         if (t < cnt) s_pos[t] = (int)(b0 & 15) + t * si;
     } else {
         const int sq = A.slot_quads;
@@ -190,14 +177,6 @@ __global__ __launch_bounds__(256) void patch_u8_kernel(unsigned char *__restrict
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < cnt && (int64_t)idx[i] < dst_len) dst[idx[i]] = val[i];
-}
-
-static int rows_args(const void *rows_dev, int64_t first_byte, int64_t stride, const char *who)
-{
-    if (stride < 1 || stride > SPZ_MAX_ROW_BYTES) GSX_FAIL("%s: rows of %lld bytes (1 ... %d are supported)", who, (long long)stride, SPZ_MAX_ROW_BYTES);
-    if (reinterpret_cast<uintptr_t>(rows_dev) & 15) GSX_FAIL("%s: rows must be 16-byte aligned", who);
-    if (first_byte < 0 || first_byte > 15) GSX_FAIL("%s: the first row at byte %lld (0 ... 15)", who, (long long)first_byte);
-    return 0;
 }
 
 }  // namespace gsx

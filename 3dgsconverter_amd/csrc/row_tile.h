@@ -100,6 +100,26 @@ __device__ __forceinline__ int spz_stage_tile(const uint4 *__restrict__ rows, in
     return (int)(b0 & 15);
 }
 
+// quads [q0, q0 + nq) of `rows` -> lds[0 .. nq) by a workgroup of THREADS lanes, BATCH 16-byte loads per lane in flight: every
+// load of a round is issued before the first of them is stored to LDS (the resident-row kernels: csrc/resident_rows.hip,
+// csrc/rows_remap.hip)
+template <int THREADS, int BATCH>
+__device__ __forceinline__ void stage_span(const uint4 *__restrict__ rows, int64_t q0, int nq, uint4 *lds)
+{
+    for (int k0 = threadIdx.x; k0 < nq; k0 += BATCH * THREADS) {
+        uint4 v[BATCH];
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) v[u] = rows[q0 + min(k0 + u * THREADS, nq - 1)];   // (no branch between the loads: past the end, the last quad again)
+        // the loads stay above this line: without it the compiler sinks each of them into the branch of its store, where it is
+        // issued, waited for and stored before the next one starts
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) asm volatile("" : "+v"(v[u].x), "+v"(v[u].y), "+v"(v[u].z), "+v"(v[u].w) : : "memory");
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u)
+            if (k0 + u * THREADS < nq) lds[k0 + u * THREADS] = v[u];
+    }
+}
+
 // LDS image `img` -> bytes [g0, g1) of `out` (16-byte aligned), by the whole workgroup: bytes up to a 16-byte boundary, 16-byte
 // stores assembled from the image's words (the image may start at any byte; up to 19 bytes behind it are read, never used),
 // the tail bytes
@@ -156,6 +176,16 @@ static int layout_to_dev(const gsx_spz_layout *l, uint64_t required, SpzLayoutDe
         }
         out->off[f] = o < 0 ? -1 : o;
     }
+    return 0;
+}
+
+// the ResidentRows contract of a table in HBM (`what`: how the refusal calls it): rows of 1 ... 512 bytes, a 16-byte aligned
+// base, row 0 at byte 0 ... 15
+static int rows_args(const void *rows_dev, int64_t first_byte, int64_t stride, const char *who, const char *what = "rows")
+{
+    if (stride < 1 || stride > SPZ_MAX_ROW_BYTES) GSX_FAIL("%s: %s of %lld bytes (1 ... %d are supported)", who, what, (long long)stride, SPZ_MAX_ROW_BYTES);
+    if (reinterpret_cast<uintptr_t>(rows_dev) & 15) GSX_FAIL("%s: %s must be 16-byte aligned", who, what);
+    if (first_byte < 0 || first_byte > 15) GSX_FAIL("%s: the first row of the %s at byte %lld (0 ... 15)", who, what, (long long)first_byte);
     return 0;
 }
 

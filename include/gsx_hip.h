@@ -1138,6 +1138,22 @@ int gsx_rows_take_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, in
 int gsx_dev_patch_u8(gsx_ctx *ctx, uint8_t *dst_dev, int64_t dst_len, const uint32_t *idx, const uint8_t *val, int64_t cnt);
 
 
+/* ---- the rows of one table re-laid into another table's row layout (csrc/rows_remap.hip): the merge of several scenes ----
+ * Rows [dst_row0, dst_row0 + n) of the destination (dst_rows rows of dst_stride bytes) become the n source rows: run k of `runs`
+ * (HOST array, n_runs x 3 int32, 1 ... 128 runs) copies runs[3k+2] bytes from byte runs[3k] of a source row (-1: zero fill) to
+ * byte runs[3k+1] of its destination row.  Every run lies inside its rows and every byte of a destination row belongs to exactly
+ * one run, or the call is refused.  Source and destination as gsx_rows_take_dev takes its rows (16-byte aligned base, row 0 at
+ * byte *_first_byte = 0 ... 15, 15 readable bytes past the last row, rows of 1 ... 512 bytes); they must not overlap.  Every value
+ * is a bit copy; no byte outside the n destination rows is written, so remaps into neighbouring row ranges may run back to back.
+ * n, dst_rows in [0, 2^32); n = 0 launches nothing.  A single run of the whole row is a device-to-device copy on the context's
+ * stream, everything else one launch.  Asynchronous. */
+int gsx_rows_remap_dev(gsx_ctx *ctx, const void *src_dev, int64_t src_first_byte, int64_t src_stride, int64_t n, const int32_t *runs,
+                       int n_runs, void *dst_dev, int64_t dst_first_byte, int64_t dst_stride, int64_t dst_row0, int64_t dst_rows);
+/* the same on HOST pointers, with the same refusals, threaded; nothing outside the rows is read or written. */
+int gsx_rows_remap_host(const void *src, int64_t src_first_byte, int64_t src_stride, int64_t n, const int32_t *runs, int n_runs, void *dst,
+                        int64_t dst_first_byte, int64_t dst_stride, int64_t dst_row0, int64_t dst_rows);
+
+
 /* ---- a similarity transform p' = s R p + t of a whole table (csrc/transform.hip) ----
  * R a proper rotation, s > 0, t a translation.  Four parts of a splat depend on the frame: the position, the log-scales, the
  * orientation quaternion and every spherical-harmonic band above DC (and the normals of a table that has them).  Every product

@@ -266,6 +266,7 @@ SIGNATURES = {
     "gsx_sor_knn_share_dev": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, C.POINTER(SorInfo)]),
     "gsx_sor_debug_brick_plan": (_I, [_P, _P, _P, _P, _I64]),
     "gsx_sor_debug_work_queue": (_I, [_P, _P, _P, _P]),
+    "gsx_sor_debug_tree": (_I, [_P, _P, _P, _P, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "gsx_sor_debug_wave_stamps": (_I, [_P, _I, _P, _I64, _P]),
     "gsx_sor_debug_points_per_cell": (_D, [_I, _I64, _I]),
     "gsx_sor_debug_group_bricks": (_I, [_P, _I64, _I, _I, _I, _P, C.POINTER(C.c_int32)]),
@@ -3508,6 +3509,29 @@ class Context:
                                                 blocks.ctypes.data_as(C.c_void_p)), "gsx_sor_debug_work_queue")
         names = ("knn_brick", "knn_brick_extra", "knn_ring", "knn_ring_fast")
         return {nm: {"ctr": ctr[i].astype(np.int64), "items": int(items[i]), "blocks": int(blocks[i])} for i, nm in enumerate(names)}
+
+    def debug_tree(self, want_leaves: bool = False, cap: int | None = None):
+        """which stage of the Morton-tree path answered in this context's last tree run: dict(n, nleaves, fail_count = queries
+        knn_leaf handed to knn_tree_near, fail2_count = queries knn_tree_near handed to knn_tree_query, max_leaf (adaptive
+        mode's guard sets it), leaf_cap, defer_why = int array of 8: knn_tree_near's reasons); want_leaves: also keys = the n
+        sorted Morton keys (uint64) and leafstart = the nleaves + 1 leaf starts, through buffers of `cap` entries (None: as
+        many as the run needs)"""
+        import numpy as np
+        ctr = np.zeros(16, np.uint32)
+        n, nl = _I64(), _I64()
+        check(self.lib.gsx_sor_debug_tree(self.handle, ctr.ctypes.data_as(C.c_void_p), None, None, 0, C.byref(n), C.byref(nl)),
+              "gsx_sor_debug_tree")
+        res = {"n": int(ctr[0]), "nleaves": int(ctr[1]), "fail_count": int(ctr[2]), "fail2_count": int(ctr[3]), "max_leaf": int(ctr[4]),
+               "leaf_cap": int(ctr[5]), "defer_why": ctr[8:16].astype(np.int64)}
+        if want_leaves:
+            cap = max(int(n.value), int(nl.value) + 1) if cap is None else int(cap)
+            keys = np.zeros(max(cap, 1), np.uint64)
+            starts = np.zeros(max(cap, 1), np.uint32)
+            check(self.lib.gsx_sor_debug_tree(self.handle, ctr.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p),
+                                              starts.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(nl)), "gsx_sor_debug_tree")
+            res["keys"] = keys[:int(n.value)]
+            res["leafstart"] = starts[:int(nl.value) + 1].astype(np.int64)
+        return res
 
     def debug_wave_stamps(self, kernel: int):
         """diagnostic builds (-DGSX_WAVE_STAMPS) only: (waves, 16) uint64 records of knn_brick (kernel 0) or knn_ring_fast

@@ -83,6 +83,7 @@ int launch_pack_points(gsx_ctx *, const float *, const float *, const float *, i
 int launch_knn_brute(gsx_ctx *, const float4 *, int64_t, int64_t, int64_t, const unsigned *, const unsigned *,
                      int64_t, int, float *);
 int knn_tree_info(gsx_ctx *, gsx_sor_info *);
+int knn_tree_debug(gsx_ctx *, uint32_t *, uint64_t *, uint32_t *, int64_t, int64_t *, int64_t *);
 int launch_knn_tree(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, int64_t, int64_t, int, float *, double *,
                     gsx_sor_info *, int64_t, int, int, bool);
 int launch_knn_grid(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, int64_t, int64_t, int,
@@ -432,6 +433,15 @@ int gsx_sor_debug_work_queue(gsx_ctx *c, uint32_t *ctr, int64_t *items, int32_t 
     items[3] = c->ring_fast ? h.fail_count : 0;
     for (int q = 0; q < 4; ++q) blocks[q] = c->wq_grid[q];
     return 0;
+}
+
+// Debug / test download of the stage counters and the leaf partition of the context's last Morton-tree run (csrc/sor_tree.hip:
+// knn_tree_debug; the layout of counters[16] is in include/gsx_hip.h).  Synchronises; launches nothing.
+int gsx_sor_debug_tree(gsx_ctx *c, uint32_t *counters, uint64_t *keys, uint32_t *leafstart, int64_t cap, int64_t *n_out, int64_t *leaves_out)
+{
+    if (!c || !counters) GSX_FAIL("gsx_sor_debug_tree: null argument");
+    GSX_HIP(hipSetDevice(c->device));
+    return gsx::knn_tree_debug(c, counters, keys, leafstart, cap, n_out, leaves_out);
 }
 
 // Diagnostic builds (-DGSX_WAVE_STAMPS) only: the wave records of the context's last grid KNN call.  kernel 0 = knn_brick (first

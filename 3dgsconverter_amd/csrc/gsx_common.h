@@ -175,6 +175,7 @@ struct gsx_ctx {
     int tree_leaf_cap = 0;         // points per leaf of the Morton-tree path: 0 = by k (sor_tree.hip: tree_leaf_cap_for), else 64 ... 256 (A/B)
     int tree_cand_limit = 0;       // candidates per 64 points of leaf capacity above which a leaf's queries go to the per-query kernels (0 = 4096; A/B)
     double tree_near_cell = 0.5;   // knn_tree_near: edge of the cover's cells as a fraction of the ball's radius (A/B)
+    int tree_last_leaf_cap = 0;    // leaf capacity the last tree run of this context built its leaves with (gsx_sor_debug_tree)
     double tree_scale = 0.0;   // > 0: the Morton tree's fine cell edge is (extent / 2^21) x this (A/B of the leaf-shape rule); 0 = chosen by the density probe
     int km_exact_blocks = 4;   // workgroups per CU of kmeans_assign_exact_list (one uncertified point per workgroup and round: A/B)
     int km_seg_rows = 32;   // rows of the label-sorted permutation one wave of kmeans_segment_sum takes (64 / 32 / 16: A/B)

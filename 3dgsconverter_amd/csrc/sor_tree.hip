@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -1624,6 +1625,7 @@ int launch_knn_tree(gsx_ctx *ctx, const float *x, const float *y, const float *z
     TreeWs &w = ctx->tree_ws;
     ctx->last_knn_algo = GSX_KNN_TREE;
     const int leaf_cap = ctx->tree_leaf_cap > 0 ? std::min(std::max(ctx->tree_leaf_cap, LEAF_CAP), LEAF_CAP_MAX) : tree_leaf_cap_for(k);
+    ctx->tree_last_leaf_cap = leaf_cap;
     const size_t n = (size_t)n_ref;
     const int ntiles = div_up(n_ref, LEAF_TILE);
     const int bbox_blocks = std::min(tree_blocks(ctx, n_ref, 8), ctx->num_cu * 4);
@@ -1762,6 +1764,30 @@ int knn_tree_info(gsx_ctx *ctx, gsx_sor_info *info)
     info->n_bricks = h.nleaves;
     info->n_fallback = h.fail_count;
     info->n_exhaustive = h.fail2_count;
+    return 0;
+}
+
+// gsx_sor_debug_tree: the counters and the leaves of the last tree run of this context (synchronous; launches nothing)
+int knn_tree_debug(gsx_ctx *ctx, uint32_t *counters, uint64_t *keys, uint32_t *leafstart, int64_t cap, int64_t *n_out, int64_t *leaves_out)
+{
+    TreeWs &w = ctx->tree_ws;
+    if (!w.params.p || !ctx->tree_last_leaf_cap) GSX_FAIL("gsx_sor_debug_tree: no tree KNN call has run on this context");
+    TreeParams h;
+    GSX_HIP(hipMemcpyAsync(&h, w.params.p, sizeof(TreeParams), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t c[16] = {(uint32_t)h.n, h.nleaves, h.fail_count, h.fail2_count, h.max_leaf, (uint32_t)ctx->tree_last_leaf_cap, 0, 0,
+                            h.defer_why[0], h.defer_why[1], h.defer_why[2], h.defer_why[3], h.defer_why[4], h.defer_why[5], h.defer_why[6], h.defer_why[7]};
+    memcpy(counters, c, sizeof(c));
+    if (n_out) *n_out = h.n;
+    if (leaves_out) *leaves_out = h.nleaves;
+    if (!keys && !leafstart) return 0;
+    if (h.bad_input) GSX_FAIL("gsx_sor_debug_tree: the last tree run met non-finite coordinates and built no leaves");
+    if (cap < (int64_t)h.n || cap < (int64_t)h.nleaves + 1)
+        GSX_FAIL("gsx_sor_debug_tree: cap=%lld is too small for %d keys and %u + 1 leaf starts", (long long)cap, h.n, h.nleaves);
+    if ((size_t)h.n * sizeof(unsigned long long) > w.keys[1].cap || ((size_t)h.nleaves + 1) * sizeof(unsigned) > w.leafstart.cap)
+        GSX_FAIL("gsx_sor_debug_tree: the workspace of the last tree run is gone");
+    if (keys) GSX_HIP(hipMemcpy(keys, w.keys[1].p, sizeof(uint64_t) * (size_t)h.n, hipMemcpyDeviceToHost));
+    if (leafstart) GSX_HIP(hipMemcpy(leafstart, w.leafstart.p, sizeof(uint32_t) * ((size_t)h.nleaves + 1), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -115,7 +115,9 @@ int  gsx_ctx_get_timing(gsx_ctx *ctx, int slot, uint64_t *launches, double *tota
  * GSX_T_s records events while timing is enabled; default all -- every event pair costs stream time),
  * "tree_leaf_cap" (0, default: points per leaf of the tree path by k -- 64 up to k = 28, 96 up to 34, 128 above; 64 ... 256: that
  * capacity; results are bit-identical for every value), "tree_cand_limit" (candidates per 64 points of leaf capacity above which
- * a leaf hands its queries to the per-query kernels; 0 = 4096), "kmeans_cs_small" (1, default: the K-Means assign kernel uses
+ * a leaf hands its queries to the per-query kernels; 0 = 4096), "tree_near_cell" (0.5, default: knn_tree_near covers a query's
+ * ball with cells whose edge is at least this fraction of its radius; values up to 0.05 set the default; small fractions send
+ * every query on to the descent, large ones make the cells dense; results are bit-identical for every value), "kmeans_cs_small" (1, default: the K-Means assign kernel uses
  * 4-wave / 2-wave workgroups for K <= 256 / K <= 64), "km_small_wgs" (their workgroups per CU; 0 = 3), "debug_skip" (profiling only) */
 int  gsx_ctx_set_param(gsx_ctx *ctx, const char *name, double value);
 
@@ -253,6 +255,15 @@ int gsx_sor_debug_brick_plan(gsx_ctx *ctx, int32_t *grid, float *origin, uint32_
 /* Debug / tests: the work queues of the context's last grid KNN call, in the order knn_brick, knn_brick (second batches),
  * knn_ring, knn_ring_fast: ctr[4][8] = final tail counters of the eight groups, items[4], blocks[4] = workgroups per launch. */
 int gsx_sor_debug_work_queue(gsx_ctx *ctx, uint32_t *ctr, int64_t *items, int32_t *blocks);
+/* Debug / tests: which stage of the Morton-tree path (csrc/sor_tree.hip) answered, and the leaves, of the context's last tree
+ * run.  counters[16] = n, leaves, fail_count (queries knn_leaf handed to knn_tree_near), fail2_count (... knn_tree_near handed
+ * to knn_tree_query), max_leaf (set by adaptive mode's guard only), leaf capacity in force, 0, 0, defer_why[0..7] (knn_tree_near's
+ * reasons: 0 more than 512 cover cells, 1 a cell of more than 4096 points, 2 buffer full, 3 / 4 fewer than k points inside the
+ * last radius tried / a known bound, 5-7 reason 1 by attempt).  keys / leafstart (nullable, room for cap entries each): the n
+ * sorted Morton keys and the leaves + 1 leaf starts.  *n_out, *leaves_out (nullable) are set before cap is checked.  Fails when
+ * no tree run has happened on the context or cap is too small.  Synchronises; launches nothing. */
+int gsx_sor_debug_tree(gsx_ctx *ctx, uint32_t *counters, uint64_t *keys, uint32_t *leafstart, int64_t cap, int64_t *n_out,
+                       int64_t *leaves_out);
 /* Diagnostic builds (-DGSX_WAVE_STAMPS) only: per-wave records of knn_brick (kernel 0) and knn_ring_fast (kernel 1) of the
  * context's last grid KNN call, 16 words each (csrc/sor_grid_params.h); tools/wave_stamps.py prints them. */
 int gsx_sor_debug_wave_stamps(gsx_ctx *ctx, int kernel, uint64_t *out, int64_t cap, int64_t *count);

@@ -1,8 +1,9 @@
 """Shared by the -m gpu tests of the grid KNN (test_sor_gpu, test_brick_plan_gpu, test_knn_variants_gpu): one
-gsx_sor_knn_dev call through the device entry point, and the bit-for-bit comparison of mean distances."""
+gsx_sor_knn_dev call through the device entry point, and the bit-for-bit comparison of mean distances; test_tree_stages_gpu
+runs the same call with algo = TREE."""
 import numpy as np
 
-BRUTE, GRID = 1, 2
+BRUTE, GRID, TREE = 1, 2, 3
 
 
 def differ(a, b):
@@ -20,9 +21,9 @@ def explain(md_gpu, md_ref):
         len(bad), len(md_ref), bad[:8], md_gpu[bad[:8]], md_ref[bad[:8]], np.nanmax(rel))
 
 
-def knn(lib, xyz, k, want_plan=False, ctx=None, window=None, columns=False, **params):
-    """one gsx_sor_knn_dev call with algo = GRID (the grid path, adaptive mode off: nothing goes to the tree or to brute
-    force) -> (mean distances, info, brick plan or None).  A fresh context unless `ctx` is given (which stays open, `params`
+def knn(lib, xyz, k, want_plan=False, ctx=None, window=None, columns=False, algo=GRID, **params):
+    """one gsx_sor_knn_dev call with algo = GRID unless another is given (the grid path, adaptive mode off: nothing goes to the tree
+    or to brute force) -> (mean distances, info, brick plan or None).  A fresh context unless `ctx` is given (which stays open, `params`
     are set on it); window = (q_begin, q_count): the queries are that index range only; columns: x, y and z as three separate
     arrays instead of interleaved rows"""
     n = len(xyz)
@@ -39,7 +40,7 @@ def knn(lib, xyz, k, want_plan=False, ctx=None, window=None, columns=False, **pa
         bufs = [ctx.alloc(xyz.nbytes).upload(np.ascontiguousarray(xyz))]
         px, py, pz, stride = bufs[0].ptr, bufs[0].ptr + 4, bufs[0].ptr + 8, 3
     out = ctx.alloc(4 * qc)
-    info = ctx.sor_knn(px, py, pz, stride, n, q0, qc, k, out.ptr, algo=GRID, want_info=True)
+    info = ctx.sor_knn(px, py, pz, stride, n, q0, qc, k, out.ptr, algo=algo, want_info=True)
     got = out.download(np.float32, qc)
     plan = ctx.debug_brick_plan() if want_plan else None
     for b in bufs + [out]:

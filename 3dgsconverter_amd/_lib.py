@@ -211,6 +211,19 @@ class TransformLayout(C.Structure):
                 ("D2", C.c_double * 25), ("D3", C.c_double * 49)]
 
 
+DECIMATE_MAX_MEAN, DECIMATE_MAX_ZERO, DECIMATE_INFO_WORDS = 51, 128, 5   # GSX_DECIMATE_*
+DECIMATE_STAGES = ("keys", "order", "heads", "sums", "finish")        # GSX_DECIMATE_STAGES clocks, in gsx_rows_decimate_*_dev's order
+DECIMATE_OK, DECIMATE_CELL_RANGE, DECIMATE_BAD_LIST = range(3)
+
+
+class DecimateLayout(C.Structure):
+    """gsx_decimate_layout (include/gsx_hip.h): the voxel size and where the fields of a row sit -- geometry, averaged float32
+    fields, colour bytes, zeroed fields"""
+    _fields_ = [("voxel_size", C.c_double), ("xyz_offset", C.c_int32 * 3), ("scale_offset", C.c_int32 * 3), ("rot_offset", C.c_int32 * 4),
+                ("opacity_offset", C.c_int32), ("n_mean", C.c_int32), ("mean_offset", C.c_int32 * DECIMATE_MAX_MEAN), ("n_u8", C.c_int32),
+                ("u8_offset", C.c_int32 * 3), ("n_zero", C.c_int32), ("zero_offset", C.c_int32 * DECIMATE_MAX_ZERO)]
+
+
 DENSITY_OK, DENSITY_EMPTY, DENSITY_HOST = range(3)
 DENSITY_STAGES = ("table", "init", "hook", "flatten", "reduce", "membership")   # GSX_DENSITY_STAGES
 SLAB_OK, SLAB_EMPTY, SLAB_NONFINITE, SLAB_SMALL_SHARD, SLAB_NO_STRUCTURE = range(5)
@@ -385,6 +398,11 @@ SIGNATURES = {
     "gsx_limit_keys_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_limit_select_dev": (_I, [_P, _P, _P, _I64, _I64, _P, _P]),
     "gsx_limit_select_host": (_I, [_P, _P, _I64, _I64, _P, _P]),
+    "gsx_rows_decimate_work_dev": (_I, [_P, _I64, C.POINTER(_I64)]),
+    "gsx_rows_decimate_plan_dev": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, C.POINTER(DecimateLayout), _P, _I64, C.POINTER(_I64),
+                                        C.POINTER(C.c_float)]),
+    "gsx_rows_decimate_write_dev": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, C.POINTER(DecimateLayout), _P, _I64, _P, _I64, _I64,
+                                         C.POINTER(C.c_float)]),
 }
 
 _lib = None
@@ -1558,6 +1576,65 @@ class ResidentRows:
             rows_transform_dev(ctx, self.ptr, self.first_byte, self.dtype.itemsize, self.n, transform_layout(plan), self.ptr)
             ctx.synchronize()
 
+    def decimate(self, plan, idx_ptr=None, n_idx=None, zero_names=(), ctx: "Context | None" = None,
+                 stage_ms: "dict | None" = None) -> "ResidentRows":
+        """-> NEW rows (the caller's to close) of the same dtype: the voxel decimation `plan` (decimate.plan_decimate of this
+        dtype) of these rows, or of the rows idx[0 .. n_idx) -- `idx_ptr`: the device address of `n_idx` ascending uint32 row
+        numbers, as in take() -- with the fields among `zero_names` zeroed in every output row.  ``decimate_info`` of the new
+        rows: groups, merged_groups, passed_through.  gsx_rows_decimate_plan_dev and gsx_rows_decimate_write_dev on `ctx` (this
+        object's own context without one) with a workspace that lives for the call; stage_ms: the five DECIMATE_STAGES clocks,
+        joined.  ValueError, and no row written, when a cell index leaves +-2^20 (the voxel size is too small for the scene's
+        coordinates).  These rows stay as they are and open."""
+        from . import decimate as _decimate
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        if np.dtype(plan.dtype) != self.dtype:
+            raise ValueError("ResidentRows.decimate: a plan for %s, rows of %s" % (plan.dtype, self.dtype))
+        n = self.n if n_idx is None else int(n_idx)
+        if not 0 <= n <= self.n or (idx_ptr is None and n not in (0, self.n)) or (idx_ptr is not None and n_idx is None):
+            raise ValueError("ResidentRows.decimate: %d of %d rows (a survivor list and its length go together)" % (n, self.n))
+        lay = decimate_layout(plan, _decimate.zero_fields(self.dtype, zero_names))
+        ctx = ctx if ctx is not None else self._ctx
+        info = {"groups": 0, "merged_groups": 0, "passed_through": 0}
+        if n == 0:
+            out = ResidentRows(0, self.dtype, self.device)
+            out.decimate_info = info
+            return out
+        clocks = (C.c_float * len(DECIMATE_STAGES))() if stage_ms is not None else None
+        words = (C.c_int64 * DECIMATE_INFO_WORDS)()
+        work_bytes = C.c_int64(0)
+        check(ctx.lib.gsx_rows_decimate_work_dev(ctx.handle, n, C.byref(work_bytes)), "gsx_rows_decimate_work_dev")
+        work = ctx.alloc(work_bytes.value)
+        out = None
+        try:
+            check(ctx.lib.gsx_rows_decimate_plan_dev(ctx.handle, self.ptr, self.first_byte, self.dtype.itemsize, self.n, idx_ptr, n, C.byref(lay),
+                                                     work.ptr, work_bytes.value, words, clocks), "gsx_rows_decimate_plan_dev")
+            if words[0] == DECIMATE_CELL_RANGE:
+                raise ValueError("decimate: the voxel size %r is too small for the scene's coordinates (a cell index leaves +-2^20)"
+                                 % (plan.voxel_size,))
+            if words[0] != DECIMATE_OK:
+                raise GsxError("gsx_rows_decimate_plan_dev: the index list is not strictly ascending inside [0, n)")
+            out = ResidentRows(int(words[1]), self.dtype, self.device)
+            check(ctx.lib.gsx_rows_decimate_write_dev(ctx.handle, self.ptr, self.first_byte, self.dtype.itemsize, self.n, idx_ptr, n, C.byref(lay),
+                                                      work.ptr, work_bytes.value, out.ptr, out.first_byte, out.n, clocks),
+                  "gsx_rows_decimate_write_dev")
+            ctx.synchronize()
+        except BaseException:
+            try:
+                ctx.synchronize()       # (a launch before the failure may still write into what is freed next)
+            except GsxError:
+                pass
+            if out is not None:
+                out.close()
+            raise
+        finally:
+            work.free()
+        if stage_ms is not None:
+            for name, ms in zip(DECIMATE_STAGES, clocks):
+                stage_ms[name] = round(stage_ms.get(name, 0.0) + float(ms), 3)
+        out.decimate_info = {"groups": int(words[1]), "merged_groups": int(words[2]), "passed_through": int(words[4])}
+        return out
+
     def profile(self) -> dict:
         """-> the profile dict of these rows: one gsx_table_profile_dev where they lie (no rows: empty_profile)"""
         if self.ptr is None:
@@ -1809,6 +1886,52 @@ def rows_transform_table(data: np.ndarray, plan, stage_ms: "dict | None" = None,
         s.download_rows(lib, out, d_rows, data.nbytes, join)
         s.mark("download")
     return out
+
+
+def decimate_layout(plan, zero=()) -> DecimateLayout:
+    """gsx_decimate_layout of a decimate.DecimatePlan; zero: further (name, offset) fields zeroed in every output row"""
+    lay = DecimateLayout()
+    lay.voxel_size = float(plan.voxel_size)
+    lay.xyz_offset[:], lay.scale_offset[:], lay.rot_offset[:] = list(plan.xyz), list(plan.scales), list(plan.rots)
+    lay.opacity_offset = int(plan.opacity)
+    zero_offs = sorted({int(o) for _, o in tuple(plan.zero) + tuple(zero)})
+    if len(plan.mean) > DECIMATE_MAX_MEAN or len(zero_offs) > DECIMATE_MAX_ZERO:
+        raise ValueError("decimate: %d averaged and %d zeroed fields (at most %d and %d)" % (len(plan.mean), len(zero_offs), DECIMATE_MAX_MEAN,
+                                                                                          DECIMATE_MAX_ZERO))
+    lay.n_mean = len(plan.mean)
+    for k, (_, o) in enumerate(plan.mean):
+        lay.mean_offset[k] = int(o)
+    lay.n_u8 = len(plan.u8)
+    for k, (_, o) in enumerate(plan.u8):
+        lay.u8_offset[k] = int(o)
+    lay.n_zero = len(zero_offs)
+    for k, o in enumerate(zero_offs):
+        lay.zero_offset[k] = o
+    return lay
+
+
+def rows_decimate_table(data: np.ndarray, plan, zero_names=(), stage_ms: "dict | None" = None, device: int = 0):
+    """The voxel decimation of a host table through the device: the rows uploaded once (ResidentRows.from_host), the device path
+    of ResidentRows.decimate, and one download into a NEW table -- the caller's array is left alone.  data: 1-D structured table
+    of plan.dtype.  -> (the table, decimate_info).  stage_ms: upload, the DECIMATE_STAGES clocks, download."""
+    data = np.ascontiguousarray(data)
+    if data.ndim != 1 or data.dtype != np.dtype(plan.dtype):
+        raise ValueError("rows_decimate_table: a 1-D table of %s" % np.dtype(plan.dtype))
+    if len(data) == 0:
+        return data.copy(), {"groups": 0, "merged_groups": 0, "passed_through": 0}
+    require_hip()
+    with stage_clock(stage_ms, "upload"):
+        rr = ResidentRows.from_host(data, device)
+    out_rr = None
+    try:
+        out_rr = rr.decimate(plan, zero_names=zero_names, stage_ms=stage_ms)
+        with stage_clock(stage_ms, "download"):
+            out = out_rr.download()
+        return out, out_rr.decimate_info
+    finally:
+        rr.close()
+        if out_rr is not None:
+            out_rr.close()
 
 
 LIMIT_FIELDS = ("scale_0", "scale_1", "scale_2", "opacity")   # the fields of the splat budget's metric, in gsx_limit_keys_dev's order
@@ -4077,6 +4200,16 @@ class DeviceChain:
         finally:
             self._free(uploaded)
             self._free(device_rgb)
+
+    def decimate(self, plan, zero_names=(), stage_ms: "dict | None" = None) -> "ResidentRows":
+        """The voxel decimation `plan` of the chain's survivors out of the resident rows it started from, as NEW resident rows
+        (ResidentRows.decimate on the chain's context; the caller's to close): the key kernel reads the rows through the composed
+        survivor list, so the table before the decimation is neither taken nor downloaded.  The source rows and the chain stay
+        open."""
+        compact = self.n != self.n0 or self.empty
+        n = 0 if (self.empty or self.n == 0) else self.n
+        idx = self.orig.ptr if (self.orig is not None and compact and n) else None
+        return self.resident.decimate(plan, idx, n, zero_names, ctx=self.ctx, stage_ms=stage_ms)
 
     def ge_keep(self, column, threshold: float) -> int:
         """rows whose value in ``column`` (float32, one per row of the table the chain started from) is >= threshold; column: a

@@ -235,6 +235,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min_opacity", type=int, help="Drop splats whose opacity is below this value (0-255).")
     p.add_argument("--max_splats", type=int, metavar="N",
                    help="Keep at most N splats: the most visible ones by the .splat writer's metric (size times opacity), after every other filter.")
+    p.add_argument("--decimate_voxel_size", type=float, metavar="H",
+                   help="Replace all splats of every voxel of side H by one splat with their combined weight, mean and covariance: a lighter "
+                        "scene without holes. After SOR, before --max_splats; shares its cells with --density_voxel_size.")
     p.add_argument("--keep_multicluster", action="store_true", help="Density filter: keep every dense cluster, not only the largest.")
     p.add_argument("--compression_level", type=int, default=0,
                    help="0-9, per format: .ksplat 0 = float32, 1 = float16 blocks, 2+ = 8-bit SH; .spz the gzip level; .sog the palette size.")
@@ -260,6 +263,9 @@ def main(argv=None):
         return
     if args.scale is not None and not (np.isfinite(args.scale) and args.scale > 0):
         print(f"Error: --scale must be a finite number greater than 0. Got {args.scale}.")
+        return
+    if args.decimate_voxel_size is not None and not (np.isfinite(args.decimate_voxel_size) and args.decimate_voxel_size > 0):
+        print(f"Error: --decimate_voxel_size must be a finite number greater than 0. Got {args.decimate_voxel_size}.")
         return
     if args.compression_level < 0 or args.compression_level > 9:
         print(f"Error: --compression_level must be between 0 and 9. Got {args.compression_level}.")
@@ -313,7 +319,7 @@ def main(argv=None):
     filters_active = any([args.density_voxel_size, args.density_threshold, args.sor_k, args.sor_sigma, args.crop_sh,
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
                           args.rotate is not None, args.scale is not None, args.translate is not None, args.max_splats is not None,
-                          bool(merge_files), has_source_extras and not args.extra_elements])
+                          args.decimate_voxel_size is not None, bool(merge_files), has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
         print("\n[INFO] Target is generic 3DGS PLY (same as input extension) and no filters are active.")
@@ -347,7 +353,8 @@ def main(argv=None):
                       rgb=args.rgb, sh_level=args.sh_level, bucket_size=args.bucket_size, block_size=args.block_size,
                       crop_sh=args.crop_sh, auto_bbox=args.auto_bbox, compression_level=args.compression_level,
                       maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate,
-                      max_splats=args.max_splats, **({"merge": merge_files, "merge_transforms": merge_transforms} if merge_files else {}))
+                      max_splats=args.max_splats, **({"merge": merge_files, "merge_transforms": merge_transforms} if merge_files else {}),
+                      **({"decimate_voxel_size": args.decimate_voxel_size} if args.decimate_voxel_size is not None else {}))
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

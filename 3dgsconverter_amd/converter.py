@@ -245,6 +245,8 @@ class Converter:
     def run(self, **kwargs):
         """the reference's keywords, and ``rotate=(rx, ry, rz)`` (degrees: about the fixed X, then Y, then Z axis), ``scale=s`` and
         ``translate=(tx, ty, tz)``: the scene transform p' = s R p + t, applied right after the SH cap and before every filter;
+        and ``decimate_voxel_size=H``: one moment-matched splat per occupied voxel of side H (DataProcessor.decimate), applied
+        after SOR and before the budget;
         and ``max_splats=N``: keep the N most visible splats (DataProcessor.limit_splats), applied after every other filter;
         and ``merge=[path, ...]`` with ``merge_transforms=[None | {"rotate":, "scale":, "translate":}, ...]``: further sources
         whose rows follow the main source's in one table (_merge_sources), before everything else"""
@@ -400,6 +402,12 @@ class Converter:
             if (s_k is not None and s_sigma is not None) or s_intensity is not None:
                 pbar.set_description("Filtering (SOR)")
                 processor.remove_flyers(25 if s_k is None else int(s_k), 10.5 if s_sigma is None else float(s_sigma), intensity=s_intensity)
+            # the decimation follows SOR -- outliers are not averaged into their voxel's splat -- and precedes the budget, which
+            # stays the only step that names the final size
+            decimate_voxel_size = kwargs.pop("decimate_voxel_size", None)
+            if decimate_voxel_size is not None:
+                pbar.set_description("Decimating")
+                processor.decimate(decimate_voxel_size)
             # the splat budget is the last filter: the box that is printed and the colours belong to what is written
             max_splats = kwargs.pop("max_splats", None)
             if max_splats is not None:

@@ -29,6 +29,7 @@ import contextlib
 import numpy as np
 
 from .. import _lib
+from .. import decimate as _decimate
 from .. import transform as _transform
 from ..utils import debug_print, status_print
 from . import clusters as _clusters
@@ -347,7 +348,11 @@ class DataProcessor:
             self._materialize()
 
     def __len__(self):   # rows currently surviving, without materialising
-        return self._chain.n if self._chain is not None else len(self._data)
+        if self._chain is not None:
+            return self._chain.n
+        if self._host_stale and self._rr is not None:   # (a decimation in HBM: the host table still has the rows before it)
+            return self._rr.n
+        return len(self._data)
 
     # ------------------------------------------------------------------ SOR
     def remove_flyers(self, k=25, threshold_factor=10.5, chunk_size=50000, intensity=None):
@@ -602,6 +607,50 @@ class DataProcessor:
             kept = len(self.data)
         self.last_limit = {"threshold": res["threshold"], "ties_kept": res["ties_kept"]}
         status_print(f"Splat Limit (max {N}): Retained {kept} out of {n} splats.")
+        return None if self.lazy else self.data
+
+    # ------------------------------------------------------------------ voxel decimation (no counterpart in the reference)
+    def decimate(self, voxel_size):
+        """Replace all splats of every voxel of side `voxel_size` by the one Gaussian that has their combined visibility weight,
+        mean and covariance (csrc/decimate.hip).  The cells are the density filter's; a row the merge cannot use --
+        a non-finite position, a weight that is not a finite number above 0, a zero quaternion -- and a voxel's only row pass
+        through as they are; rows leave in the order of their voxel's first row.  Refusals come before any device work:
+        ValueError for a voxel size that is not a finite number above 0, TypeError for a needed field that is not '<f4'; a
+        table without x y z, scale_0..2, rot_0..3 or opacity is left as it is, with a warning.  A voxel size too small for the
+        scene's coordinates (a cell index beyond +-2^20) raises ValueError from the device's flag, and nothing changes.
+        Lazy with resident rows: the chain's pending survivor list and cap_sh_degree's deferred fills are consumed by the
+        kernels -- the table before the decimation is never downloaded --, ``.resident`` is the merged rows and ``.data``
+        owes one download of them; otherwise the host table goes through the same device path and back.
+        ``last_decimate``: groups, merged_groups, passed_through."""
+        debug_print(f"[DEBUG] Executing 'decimate' with voxel size {voxel_size}")
+        self._flush_rgb()
+        h = _decimate.check_voxel_size(voxel_size)
+        if not isinstance(self._data, np.ndarray) or self._data.dtype.fields is None:
+            raise TypeError("self.data must be a numpy structured array.")
+        if _decimate.missing_fields(self._data.dtype):
+            status_print("Warning: Decimation needs x y z, scale_0..2, rot_0..3 and opacity. Decimation skipped.")
+            return None if self.lazy else self.data
+        plan = _decimate.plan_decimate(self._data.dtype, h, self._pending_zero)
+        n = len(self)
+        if self.lazy and self._rr is not None:
+            ch, zero = self._chain, self._pending_zero
+            merged = (ch.decimate(plan, zero, stage_ms=self.resident_ms) if ch is not None
+                      else self._rr.decimate(plan, zero_names=zero, stage_ms=self.resident_ms))
+            # (a refusal raised above: the chain, its list and the deferred fills are as they were)
+            self._chain, self._pending_zero = None, []
+            if ch is not None:
+                ch.close()
+            self._drop_resident()
+            self._rr, self._host_stale = merged, True       # .data owes the one download of the merged rows
+            info = merged.decimate_info
+        else:
+            if self.lazy:
+                self._materialize()
+                self._data, info = _lib.rows_decimate_table(self._data, plan, stage_ms=self.resident_ms)
+            else:
+                self.data, info = _lib.rows_decimate_table(self.data, plan)
+        self.last_decimate = dict(info)
+        status_print(f"Decimate (voxel {h:g}): Merged {n} splats into {info['groups']} ({info['merged_groups']} voxels held more than one).")
         return None if self.lazy else self.data
 
     # ------------------------------------------------------------------ table-shaping methods (SURVEY.md 8(f) rank 4)

@@ -1221,6 +1221,56 @@ int gsx_limit_select_dev(gsx_ctx *ctx, const uint32_t *keys_dev, const uint32_t 
 /* the same on the HOST, from the same digit walk and tie rule (csrc/limit_select.h); HOST pointers, serial. */
 int gsx_limit_select_host(const uint32_t *keys, const uint32_t *orig, int64_t n, int64_t max_count, uint8_t *mask, uint32_t *info_out);
 
+
+/* ---- voxel decimation: one moment-matched splat per occupied voxel (csrc/decimate.hip) ----
+ * No reference counterpart: the definition is this project's own (tests/decimate_numpy.py) and the device
+ * reproduces it bit for bit.  The rows of one cell of side voxel_size (the density filter's cell, (int)floorf(v / (float)h) per
+ * axis) that are mergeable -- finite position, finite visibility weight > 0 (csrc/splat_metric.h's float32 expression), a
+ * quaternion of finite norm > 0 -- become ONE row: the Gaussian with their combined weight, mean and covariance.  Every other
+ * row, and a cell's only row, is a bit copy.  Groups leave in the order of their first member's row; members are summed in row
+ * order, in blocks of 256 (float64, every operation rounded once).
+ *
+ * The layout names the float32 ('<f4') fields of a row by byte offset: the eleven geometry fields, up to GSX_DECIMATE_MAX_MEAN
+ * fields that become the weighted mean of the members (f_dc_*, f_rest_*, nx ny nz), up to three uint8 colour fields (weighted
+ * mean, rounded to nearest even, clipped) and the 4-byte fields zeroed in every output row.  Every other byte of an output row
+ * is the first member's. */
+enum { GSX_DECIMATE_MAX_MEAN = 51, GSX_DECIMATE_MAX_ZERO = 128, GSX_DECIMATE_STAGES = 5, GSX_DECIMATE_INFO_WORDS = 5 };
+enum { GSX_DECIMATE_OK = 0, GSX_DECIMATE_CELL_RANGE = 1, GSX_DECIMATE_BAD_LIST = 2 };
+typedef struct {
+    double  voxel_size;                /* finite, > 0 */
+    int32_t xyz_offset[3];
+    int32_t scale_offset[3];
+    int32_t rot_offset[4];             /* rot_0..3 = (w, x, y, z) */
+    int32_t opacity_offset;
+    int32_t n_mean;                    /* 0 ... GSX_DECIMATE_MAX_MEAN */
+    int32_t mean_offset[GSX_DECIMATE_MAX_MEAN];
+    int32_t n_u8;                      /* 0 or 3 */
+    int32_t u8_offset[3];
+    int32_t n_zero;                    /* 0 ... GSX_DECIMATE_MAX_ZERO; none of them a geometry field */
+    int32_t zero_offset[GSX_DECIMATE_MAX_ZERO];
+} gsx_decimate_layout;
+/* bytes of device workspace that the two calls below need for n rows -> *bytes_out (HOST).  Launches nothing. */
+int gsx_rows_decimate_work_dev(gsx_ctx *ctx, int64_t n, int64_t *bytes_out);
+/* Keys, stable order, group heads and output slots of the n rows idx_dev[0 .. n) (strictly ascending uint32 in HBM; NULL: rows
+ * 0 .. n - 1, and n = n_in) of the n_in resident rows at rows_dev (as gsx_rows_take_dev takes them).  work_dev: 16-byte aligned,
+ * work_bytes >= gsx_rows_decimate_work_dev(n); it carries the plan to gsx_rows_decimate_write_dev and must not be touched in
+ * between.  info_out (HOST, GSX_DECIMATE_INFO_WORDS int64): status (GSX_DECIMATE_*), groups (the output's row count), groups of
+ * more than one row, 256-member blocks of those groups, groups of one row.  A status other than GSX_DECIMATE_OK -- a mergeable
+ * row whose cell leaves [-2^20, 2^20) on an axis, a list that leaves [0, n_in) or does not ascend -- returns 0 with the status
+ * set: the caller refuses, and nothing may be written.  stage_ms (HOST, GSX_DECIMATE_STAGES floats, or NULL): the stream clocks
+ * of keys, order and heads are ADDED to entries 0, 1, 2.  Synchronises the context's stream (the one readback of the step). */
+int gsx_rows_decimate_plan_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t stride, int64_t n_in, const uint32_t *idx_dev,
+                               int64_t n, const gsx_decimate_layout *layout, void *work_dev, int64_t work_bytes, int64_t *info_out,
+                               float *stage_ms);
+/* The n_out = info_out[1] output rows of a plan with status GSX_DECIMATE_OK -> out_dev (16-byte aligned, row 0 at byte
+ * out_first_byte = 0 ... 15, rows of `stride` bytes; it must not overlap the source).  The same rows, list, layout and workspace
+ * as the plan call.  No byte outside the n_out rows is written.  stage_ms: the clocks of the block sums and of the finish
+ * (partials of groups above 256 rows, eigen-solve, single rows' copies) are ADDED to entries 3, 4.  Synchronises the context's
+ * stream when stage_ms is given, else asynchronous. */
+int gsx_rows_decimate_write_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t stride, int64_t n_in, const uint32_t *idx_dev,
+                                int64_t n, const gsx_decimate_layout *layout, void *work_dev, int64_t work_bytes, void *out_dev,
+                                int64_t out_first_byte, int64_t n_out, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,51 @@ __device__ __forceinline__ float bound_from(double T)
     return __double2float_ru(T) * F32_SLACK + F32_TINY;
 }
 
+// Values the optimiser must not hoist out of a loop or a branch: whatever is computed from the result stays where the
+// call is (knn_brick: loop-invariant setup arithmetic hoisted to the kernel entry and parked in scratch cost 0.8 GB of
+// spill traffic per 10M-splat launch; recomputing it is a handful of instructions)
+__device__ __forceinline__ int pinned_here(int v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ float pinned_here(float v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ int pinned_here_s(int v) { asm volatile("" : "+s"(v)); return v; }
+// pinned_here_s on k: k is a kernel argument, and left alone every compare an unrolled chain makes with it (the L - 1 of a
+// k-th select, the `j < k` / `j < nfull` of a pairwise sum) is a loop invariant: the compiler hoists them all to the kernel
+// entry and keeps each for the whole kernel as a 64-bit lane mask -- 30 SGPRs for one select at L = 16, as many again for the
+// sums -- in kernels that sit at the SGPR cap and park the overflow in vector lanes (v_writelane at entry, v_readlane per brick
+// and per batch, both on the vector pipe).  Behind the pin the compares are made where the chain runs, on the
+// scalar side, and only when k is not the list's capacity.
+
+// A copy of a wave-uniform value into a scalar register of its OWN, made once at a kernel's entry for every argument and
+// every field of a parameter block.  Kernel arguments arrive eight dwords per s_load_dwordx8 and neighbouring fields four
+// per s_load_dwordx4; the register allocator treats such a group as one register tuple, parks the whole tuple in vector
+// lanes and fetches the whole tuple back for each use of any member (knn_brick fetched the eight dwords of {extra,
+// deferred, kth_out, plist} four times per brick to read plist).  The copy is a real s_mov: an empty asm with a tied
+// operand is coalesced straight back into the tuple.  One scalar instruction per value and wave, outside every loop.
+template <class T>
+__device__ __forceinline__ T own_scalar(T v)
+{
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two dwords");
+    T r;
+    if constexpr (sizeof(T) == 8) asm volatile("s_mov_b64 %0, %1" : "=s"(r) : "s"(v));
+    else asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "s"(v));
+    return r;
+}
+// Pointers keep their address space through the copy: a generic pointer that comes out of an asm statement is loaded
+// through with flat_load.  own_table: a table nothing writes while the kernel runs (the constant address space: its
+// wave-uniform loads stay scalar loads whatever is stored elsewhere); own_output: global memory.
+template <class T>
+__device__ __forceinline__ const T *own_table(const T *p)
+{
+    return (const T *)own_scalar((const __attribute__((address_space(4))) T *)p);
+}
+template <class T>
+__device__ __forceinline__ T *own_output(T *p)
+{
+    return (T *)own_scalar((__attribute__((address_space(1))) T *)p);
+}
+// (floating-point values go through their bit patterns: an "s" operand of a floating-point type is refused)
+__device__ __forceinline__ float own_scalar(float v) { return __int_as_float(own_scalar(__float_as_int(v))); }
+__device__ __forceinline__ double own_scalar(double v) { return __longlong_as_double(own_scalar(__double_as_longlong(v))); }
+
 // Ascending list of the KCAP smallest exact squared distances seen so far (+inf padded), all in
 // registers and only ever indexed with compile-time constants.  KCAP >= kk = k+1; entries
 // beyond kk are simply further neighbours that are never read.
@@ -59,6 +104,9 @@ struct TopList {
     }
 
     // the kk-th smallest (kk is wave-uniform: the selects are driven by scalar compares)
+    // (NOT behind pinned_here_s as TopNet::kth is: the kernels that use this list do not park scalars in vector lanes, and with
+    //  the compares made here -- as scalars or in a vector register -- knn_brick<51> and <33> without the network need two to
+    //  six VGPRs more and lose a wave)
     __device__ __forceinline__ double kth(int kk) const
     {
         double r = a[KCAP - 1];
@@ -165,9 +213,10 @@ struct TopNet {
     {
         if (j == L) return a[L - 1];  // wave-uniform: the power-of-two k of the headline configs skips the select chain
         double r = a[L - 1];
+        const int at = pinned_here_s(j - 1);   // after the early return: the headline path never gets here
 #pragma unroll
         for (int i = 0; i < L - 1; ++i) {
-            r = (j - 1 == i) ? a[i] : r;
+            r = (at == i) ? a[i] : r;
             asm("" : "+v"(r));
         }
         return r;
@@ -227,14 +276,14 @@ __device__ __forceinline__ float mean_finish(double sum, int k)
 
 // epilogue for TopNet: entries 0..k-1 are the neighbours (the query was never inserted)
 template <int L>
-__device__ __forceinline__ float mean_from_net(const TopNet<L> &lst, int k)
+__device__ __forceinline__ float mean_from_net(const TopNet<L> &lst, int k_arg)
 {
     double b[L];
 #pragma unroll
     for (int j = 0; j < L; ++j) b[j] = sqrt_rn_dist2(lst.a[j]);
     double res;
-    if (L % 8 == 0 && k == L) {  // wave-uniform; the headline k = 16 / 32: numpy's 8 accumulators over a MULTIPLE of 8, no scalar
-                                 // branches (L = 12, 20, 28 ...: numpy adds the last 4 sequentially -> the general branch)
+    if (L % 8 == 0 && k_arg == L) {  // wave-uniform; the headline k = 16 / 32: numpy's 8 accumulators over a MULTIPLE of 8, no scalar
+                                     // branches (L = 12, 20, 28 ...: numpy adds the last 4 sequentially -> the general branch)
         double r[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) r[t] = b[t];
@@ -242,7 +291,11 @@ __device__ __forceinline__ float mean_from_net(const TopNet<L> &lst, int k)
         for (int j = 8; j < L; ++j) r[j & 7] = __dadd_rn(r[j & 7], b[j]);
         res = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
                         __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    } else if (k < 8) {
+        return mean_finish(res, L);   // (the divisor is the constant: no (double)k carried through the kernel for it)
+    }
+    // every other compare with k is made in here, where it is used (pinned_here_s), not once at the kernel's entry
+    const int k = pinned_here_s(k_arg);
+    if (k < 8) {
         res = 0.0;
 #pragma unroll
         for (int j = 0; j < 7 && j < L; ++j)
@@ -376,11 +429,4 @@ __device__ __forceinline__ float wave_max_f32(float v)
 
 // wave-uniform value known to the compiler as scalar
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// Values the optimiser must not hoist out of a loop or a branch: whatever is computed from the result stays where the
-// call is (knn_brick: loop-invariant setup arithmetic hoisted to the kernel entry and parked in scratch cost 0.8 GB of
-// spill traffic per 10M-splat launch; recomputing it is a handful of instructions)
-__device__ __forceinline__ int pinned_here(int v) { asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ float pinned_here(float v) { asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ int pinned_here_s(int v) { asm volatile("" : "+s"(v)); return v; }
-
 }  // namespace gsx

@@ -1096,19 +1096,29 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
     unsigned *wbase = s_wbase[wv];
     uint2 *wseg = s_wseg[MF ? wv : 0];
 
-    const int nx = gp->nx, ny = gp->ny, nz = gp->nz;
-    const int nbx = gp->nbx, nby = gp->nby;
-    const int bdx = gp->bdx, bdy = gp->bdy, bdz = gp->bdz;
+    // Every field of *gp read here, and below every argument, becomes a scalar of its own (own_scalar, knn_common.h): the
+    // kernel needs more scalars than there are SGPRs, and what the allocator parks in vector lanes it parks and fetches by
+    // the group the value arrived in -- eight dwords to read one pointer.  The fields are read through a
+    // constant-address-space view: none of them is written while this kernel runs (the counters are, and stay with gp), and
+    // a load that follows an asm statement would otherwise count as clobbered and become a vector load.
+    // NET kernels only (the default form and its fixed-brick twin): the bubble-insert kernels do not park enough to gain, and
+    // stay as they were.
+    const auto *gk = (const __attribute__((address_space(4))) GridParams *)gp;
+#define GSX_OWN_FIELD(f) (NET ? own_scalar(gk->f) : gp->f)
+    const int nx = GSX_OWN_FIELD(nx), ny = GSX_OWN_FIELD(ny), nz = GSX_OWN_FIELD(nz);
+    const int nbx = GSX_OWN_FIELD(nbx), nby = GSX_OWN_FIELD(nby);
+    const int bdx = GSX_OWN_FIELD(bdx), bdy = GSX_OWN_FIELD(bdy), bdz = GSX_OWN_FIELD(bdz);
     const int cry = bdy + 2;                  // candidate rows per z-slab
     const int ncrows = cry * (bdz + 2);       // <= 16 candidate x-rows
     const int nqrows = bdy * bdz;             // <= 4 query x-rows
-    const double r1sq = gp->r1sq;
-    const double hp = gp->hprime;
-    const float tau1 = gp->tau1;
-    const float g_ox = gp->ox, g_oy = gp->oy, g_oz = gp->oz, g_inv_h = gp->inv_h;
-    const int bk_g = gp->bk_g, bk_ny = gp->bk_ny, bk_cells = gp->bk_cells;
-    auto row_base_g = [&](int cy, int cz) {  // bucket-major cell index of cell (0, cy, cz)
-        const int by_ = cy / bk_g, bz_ = cz / bk_g;
+    const double r1sq = GSX_OWN_FIELD(r1sq);
+    const double hp = GSX_OWN_FIELD(hprime);
+    const float tau1 = GSX_OWN_FIELD(tau1);
+    const float g_ox = GSX_OWN_FIELD(ox), g_oy = GSX_OWN_FIELD(oy), g_oz = GSX_OWN_FIELD(oz), g_inv_h = GSX_OWN_FIELD(inv_h);
+    const int bk_g = GSX_OWN_FIELD(bk_g), bk_ny = GSX_OWN_FIELD(bk_ny), bk_cells = GSX_OWN_FIELD(bk_cells);
+    auto row_base_g = [&](int cy, int cz) {  // bucket-major cell index of cell (0, cy, cz); cy, cz >= 0 wherever the result is used
+        // (unsigned: a signed division by a run-time divisor also keeps the divisor's sign and its absolute value for the kernel's length)
+        const int by_ = NET ? (int)((unsigned)cy / (unsigned)bk_g) : cy / bk_g, bz_ = NET ? (int)((unsigned)cz / (unsigned)bk_g) : cz / bk_g;
         return (bz_ * bk_ny + by_) * bk_cells + ((cz - bz_ * bk_g) * bk_g + (cy - by_ * bk_g)) * nx;
     };
 #ifdef GSX_ABLATE  // profiling build only (results become wrong): -DGSX_ABLATE + gsx_ctx_set_param("debug_skip")
@@ -1120,15 +1130,23 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
     const int kq = NET ? k : kk;  // position of the acceptance distance in the list (NET lists do not hold the query)
 
     WorkQueue wq;
-    const int part_lo = gp->part_lo;
+    const int part_lo = GSX_OWN_FIELD(part_lo);
     const int nq4 = 4 * nx;
-    const bool planned = PLAN && gp->plan != 0;   // kernel-uniform
-    const int dw = EXTRA ? 0 : gp->defer_words;  // loaded once: gp is written by atomics, the compiler would reload it per brick
+    const bool planned = PLAN && (NET ? gk->plan : gp->plan) != 0;   // kernel-uniform
+    const int dw = EXTRA ? 0 : GSX_OWN_FIELD(defer_words);  // loaded once: gp is written by atomics, the compiler would reload it per brick
 #ifdef GSX_WAVE_STAMPS
     const unsigned long long ws_t0 = ws_realtime();
 #endif
-    wq_init(wq, EXTRA ? gp->extra_ctr : gp->brick_ctr, EXTRA ? (int)gp->extra_count : gp->part_hi - part_lo,
+    wq_init(wq, EXTRA ? gp->extra_ctr : gp->brick_ctr, EXTRA ? (int)gp->extra_count : (NET ? gk->part_hi : gp->part_hi) - part_lo,
             BRICK_THREADS / 64);
+#undef GSX_OWN_FIELD
+    // (the arguments: after the last plain load through gp)
+    if constexpr (NET) {
+        refs = own_table(refs), rstart = own_table(rstart), qpts = own_table(qpts), qstart = own_table(qstart), plist = own_table(plist);
+        k = own_scalar(k), q_begin = own_scalar(q_begin);
+        mean_out = own_output(mean_out), faillist = own_output(faillist), extra = own_output(extra), deferred = own_output(deferred);
+        kth_out = own_output(kth_out);
+    }
     for (;;) {
         const int item = uniform(wq_next(wq));
         if (item < 0) break;
@@ -1148,11 +1166,14 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 qf = uniform((int)(e.y & 0xffffu));
                 ql = uniform((int)(e.y >> 16));
             } else {
-                bundle = b / nbx;
-                qf = 8 * (b - bundle * nbx);
+                // (the withdrawn plan only: its divisor is pinned in here, so that the division's reciprocal is made in this
+                //  branch and not kept, with the divisor, from the kernel's entry on)
+                const int nbx_h = pinned_here_s(nbx);
+                bundle = (int)((unsigned)b / (unsigned)nbx_h);
+                qf = 8 * (b - bundle * nbx_h);
                 ql = min(qf + 7, nq4 - 1);
             }
-            bz = bundle / nby;
+            bz = (int)((unsigned)bundle / (unsigned)nby);   // (b, bundle >= 0: unsigned, see row_base_g)
             by = bundle - bz * nby;
             bx = 0;
         } else {
@@ -1662,7 +1683,7 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 } else if (dbg & 4) {
                     mean_out[(int)__float_as_uint(qp.w) - q_begin] = (float)kth_d2;
                 } else if (kth_d2 <= racc_sq) {
-                    kth_emit(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth_d2, qx, qy, qz);
+                    kth_emit<NET>(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth_d2, qx, qy, qz);
                     if constexpr (NET) mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_from_net(lst, k);
                     else mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_from_list<KCAP>(lst, k);
                 } else {

@@ -63,9 +63,19 @@ struct GridParams {
 
 #ifdef __HIPCC__
 // every kernel of the grid path hands a finished query's (k+1)-th squared distance (the query itself included) here
+// OWN_GP (knn_brick): see below
+template <bool OWN_GP = false>
 __device__ __forceinline__ void kth_emit(GridParams *gp, double *kth_out, int idx, double kth, float qx, float qy, float qz)
 {
     if (!kth_out) return;   // the single-GPU path: nothing is loaded, nothing is written
+    if constexpr (OWN_GP) {
+        // the pointer made opaque in here: from the kernel's own, the addresses of the three certificate fields are formed at
+        // the kernel's entry and kept for its whole length -- six scalars parked in vector lanes in knn_brick.
+        // Through a global-address-space copy: a generic pointer out of an asm statement is loaded through with flat_load
+        auto g1 = (__attribute__((address_space(1))) GridParams *)gp;
+        asm volatile("" : "+s"(g1));
+        gp = (GridParams *)g1;
+    }
     const int axis = gp->cert_axis;
     if (axis >= 0) {
         const double v = (double)(axis == 0 ? qx : (axis == 1 ? qy : qz));

@@ -224,6 +224,25 @@ class DecimateLayout(C.Structure):
                 ("u8_offset", C.c_int32 * 3), ("n_zero", C.c_int32), ("zero_offset", C.c_int32 * DECIMATE_MAX_ZERO)]
 
 
+RENDER_INFO_WORDS, RENDER_RECORD_WORDS = 4, 16                          # GSX_RENDER_*
+RENDER_STAGES = ("project", "count", "emit", "sort", "ranges", "blend")   # GSX_RENDER_STAGES clocks, in gsx_rows_render_*_dev's order
+RENDER_OK, RENDER_TOO_MANY = range(2)
+# a record of gsx_rows_render_plan_dev's workspace, one per row (include/gsx_hip.h)
+RENDER_RECORD = np.dtype([("u", "<f4"), ("v", "<f4"), ("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("opac", "<f4"), ("r", "<f4"), ("g", "<f4"),
+                          ("bl", "<f4"), ("depth", "<f4"), ("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("visible", "<u4"),
+                          ("pad", "<u4")])
+
+
+class RenderLayout(C.Structure):
+    """gsx_render_layout (include/gsx_hip.h): where the fields the rasteriser reads sit inside a row, the SH degree, the image
+    size, the camera and the background"""
+    _fields_ = [("xyz_offset", C.c_int32 * 3), ("scale_offset", C.c_int32 * 3), ("rot_offset", C.c_int32 * 4), ("opacity_offset", C.c_int32),
+                ("dc_offset", C.c_int32 * 3), ("rgb_offset", C.c_int32 * 3), ("degree", C.c_int32), ("rest_m", C.c_int32),
+                ("rest_offset", C.c_int32 * 45), ("width", C.c_int32), ("height", C.c_int32), ("view", C.c_double * 12),
+                ("eye", C.c_double * 3), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("tan_fovx", C.c_double), ("tan_fovy", C.c_double), ("near", C.c_double), ("background", C.c_float * 3)]
+
+
 DENSITY_OK, DENSITY_EMPTY, DENSITY_HOST = range(3)
 DENSITY_STAGES = ("table", "init", "hook", "flatten", "reduce", "membership")   # GSX_DENSITY_STAGES
 SLAB_OK, SLAB_EMPTY, SLAB_NONFINITE, SLAB_SMALL_SHARD, SLAB_NO_STRUCTURE = range(5)
@@ -403,6 +422,9 @@ SIGNATURES = {
                                         C.POINTER(C.c_float)]),
     "gsx_rows_decimate_write_dev": (_I, [_P, _P, _I64, _I64, _I64, _P, _I64, C.POINTER(DecimateLayout), _P, _I64, _P, _I64, _I64,
                                          C.POINTER(C.c_float)]),
+    "gsx_rows_render_work_dev": (_I, [_P, _I64, C.c_int32, C.c_int32, C.POINTER(_I64)]),
+    "gsx_rows_render_plan_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(RenderLayout), _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float)]),
+    "gsx_rows_render_draw_dev": (_I, [_P, _I64, C.POINTER(RenderLayout), _P, _I64, _P, _I64, _P, C.POINTER(C.c_float)]),
 }
 
 _lib = None
@@ -1635,6 +1657,75 @@ class ResidentRows:
         out.decimate_info = {"groups": int(words[1]), "merged_groups": int(words[2]), "passed_through": int(words[4])}
         return out
 
+    def _render_plan(self, ctx, plan, clocks):
+        """gsx_rows_render_plan_dev of these rows into a workspace of its own -> (layout, workspace, its bytes, the info words);
+        the workspace is the caller's to free.  RenderRefused for 2^31 instances or more."""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        if np.dtype(plan.dtype) != self.dtype:
+            raise ValueError("ResidentRows.render: a plan for %s, rows of %s" % (plan.dtype, self.dtype))
+        lay = render_layout(plan)
+        words = (C.c_int64 * RENDER_INFO_WORDS)()
+        work_bytes = C.c_int64(0)
+        check(ctx.lib.gsx_rows_render_work_dev(ctx.handle, self.n, lay.width, lay.height, C.byref(work_bytes)), "gsx_rows_render_work_dev")
+        work = ctx.alloc(work_bytes.value)
+        try:
+            check(ctx.lib.gsx_rows_render_plan_dev(ctx.handle, self.ptr, self.first_byte, self.dtype.itemsize, self.n, C.byref(lay), work.ptr,
+                                                   work_bytes.value, words, clocks), "gsx_rows_render_plan_dev")
+        except BaseException:
+            work.free()
+            raise
+        return lay, work, work_bytes.value, words
+
+    def render_records(self, plan, ctx: "Context | None" = None) -> np.ndarray:
+        """-> the per-splat records of the rasteriser's first stage (RENDER_RECORD, one per row; an invisible row's is all zero):
+        gsx_rows_render_plan_dev alone and one download of the workspace's head.  For the tests of that stage on its own."""
+        ctx = ctx if ctx is not None else self._ctx
+        _, work, _, _ = self._render_plan(ctx, plan, None)
+        try:
+            return work.download(RENDER_RECORD, self.n) if self.n else np.zeros(0, RENDER_RECORD)
+        finally:
+            work.free()
+
+    def render(self, plan, stage_ms: "dict | None" = None, ctx: "Context | None" = None) -> np.ndarray:
+        """-> the (height, width, 3) uint8 image of these rows under `plan` (render.plan_render of this dtype):
+        gsx_rows_render_plan_dev and gsx_rows_render_draw_dev on `ctx` (this object's own context without one) with workspaces
+        that live for the call, and one download of the image.  The instance workspace is sized by the plan call's total; a size
+        above plan.max_work_bytes raises render.RenderRefused, naming the image size and the instance count, before that
+        workspace or the image is allocated.  ``render_info``: visible, instances, rows.  stage_ms: the six RENDER_STAGES
+        clocks, joined, and "download".  These rows stay as they are and open."""
+        from . import render as _render
+        ctx = ctx if ctx is not None else self._ctx
+        clocks = (C.c_float * len(RENDER_STAGES))() if stage_ms is not None else None
+        lay, work, work_bytes, words = self._render_plan(ctx, plan, clocks)
+        inst = image_dev = None
+        try:
+            visible, instances, inst_bytes = int(words[1]), int(words[2]), int(words[3])
+            if words[0] != RENDER_OK or inst_bytes > plan.max_work_bytes:
+                raise _render.RenderRefused("render: an image of %d x %d needs %d (tile, splat) instances and %d bytes of workspace for them; "
+                                            "max_work_bytes is %d" % (lay.width, lay.height, instances, inst_bytes, plan.max_work_bytes))
+            inst = ctx.alloc(inst_bytes) if inst_bytes else None
+            image_dev = ctx.alloc(lay.width * lay.height * 3)
+            check(ctx.lib.gsx_rows_render_draw_dev(ctx.handle, self.n, C.byref(lay), work.ptr, work_bytes, inst.ptr if inst else None, inst_bytes,
+                                                   image_dev.ptr, clocks), "gsx_rows_render_draw_dev")
+            with stage_clock(stage_ms, "download"):
+                image = image_dev.download(np.uint8, lay.width * lay.height * 3).reshape(lay.height, lay.width, 3)
+        except BaseException:
+            try:
+                ctx.synchronize()       # (a launch before the failure may still write into what is freed next)
+            except GsxError:
+                pass
+            raise
+        finally:
+            for buf in (image_dev, inst, work):
+                if buf is not None:
+                    buf.free()
+        if stage_ms is not None:
+            for name, ms in zip(RENDER_STAGES, clocks):
+                stage_ms[name] = round(stage_ms.get(name, 0.0) + float(ms), 3)
+        self.render_info = {"visible": visible, "instances": instances, "rows": self.n}
+        return image
+
     def profile(self) -> dict:
         """-> the profile dict of these rows: one gsx_table_profile_dev where they lie (no rows: empty_profile)"""
         if self.ptr is None:
@@ -1908,6 +1999,44 @@ def decimate_layout(plan, zero=()) -> DecimateLayout:
     for k, o in enumerate(zero_offs):
         lay.zero_offset[k] = o
     return lay
+
+
+def render_layout(plan) -> RenderLayout:
+    """gsx_render_layout of a render.RenderPlan"""
+    cam = plan.camera
+    lay = RenderLayout()
+    lay.xyz_offset[:], lay.scale_offset[:], lay.rot_offset[:] = list(plan.xyz), list(plan.scales), list(plan.rots)
+    lay.opacity_offset = int(plan.opacity)
+    lay.dc_offset[:], lay.rgb_offset[:] = list(plan.dc), list(plan.rgb)
+    lay.degree, lay.rest_m = int(plan.degree), int(plan.m)
+    for k in range(45):
+        lay.rest_offset[k] = int(plan.rest[k]) if k < len(plan.rest) else -1
+    lay.width, lay.height = int(cam.width), int(cam.height)
+    lay.view[:] = [float(v) for v in np.asarray(cam.view, dtype=np.float64).reshape(12)]
+    lay.eye[:] = [float(v) for v in cam.eye]
+    lay.fx, lay.fy, lay.cx, lay.cy = cam.fx, cam.fy, cam.cx, cam.cy
+    lay.tan_fovx, lay.tan_fovy, lay.near = cam.tan_fovx, cam.tan_fovy, cam.near
+    lay.background[:] = [float(v) for v in plan.background]
+    return lay
+
+
+def render_table(data: np.ndarray, plan, stage_ms: "dict | None" = None, device: int = 0, info: "dict | None" = None) -> np.ndarray:
+    """The image of a host table: the rows uploaded once (ResidentRows.from_host) and ResidentRows.render.  data: 1-D structured
+    table of plan.dtype; the caller's array is left alone.  -> the (height, width, 3) uint8 image; `info` receives render_info.
+    stage_ms: upload, the RENDER_STAGES clocks, download."""
+    data = np.ascontiguousarray(data)
+    if data.ndim != 1 or data.dtype != np.dtype(plan.dtype):
+        raise ValueError("render_table: a 1-D table of %s" % np.dtype(plan.dtype))
+    require_hip()
+    with stage_clock(stage_ms, "upload"):
+        rr = ResidentRows.from_host(data, device)
+    try:
+        image = rr.render(plan, stage_ms=stage_ms)
+        if info is not None:
+            info.update(rr.render_info)
+        return image
+    finally:
+        rr.close()
 
 
 def rows_decimate_table(data: np.ndarray, plan, zero_names=(), stage_ms: "dict | None" = None, device: int = 0):

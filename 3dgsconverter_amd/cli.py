@@ -6,7 +6,9 @@ and the two info blocks of a conversion decode each file once: the bounds and th
 took of its rows in HBM (csrc/table_profile.hip), the PLY property names from the header (formats/ply_reader.parse_header) and
 the compressed-PLY chunk count from the reader's metadata.  In conversion mode the source info block and ``Converter.run``
 share one load.  ``--merge FILE`` (repeatable, with ``--merge_rotate / --merge_scale / --merge_translate`` once per file) adds
-further scenes to the input: ``Converter.run(merge=...)``.
+further scenes to the input: ``Converter.run(merge=...)``.  ``--preview FILE`` (with ``--preview_size / _view / _up / _camera /
+_fov``) renders the table that was written to a PNG on the GPU: ``Converter.run(preview=...)``; it counts as an action in the
+no-op check, and the other preview flags are refused without it.
 """
 from __future__ import annotations
 
@@ -238,10 +240,57 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--decimate_voxel_size", type=float, metavar="H",
                    help="Replace all splats of every voxel of side H by one splat with their combined weight, mean and covariance: a lighter "
                         "scene without holes. After SOR, before --max_splats; shares its cells with --density_voxel_size.")
+    p.add_argument("--preview", metavar="FILE",
+                   help="Render the converted scene on the GPU and save it as an 8-bit RGB PNG. The image shows the table that was written, before "
+                        "the target format's quantisation.")
+    p.add_argument("--preview_size", nargs=2, type=int, metavar=("W", "H"), help="Preview image size in pixels, 1-8192 per side (default 960 540).")
+    p.add_argument("--preview_view", nargs=2, type=float, metavar=("AZ", "EL"),
+                   help="Preview camera: azimuth and elevation in degrees about the up axis, framed on the scene's bounding box (default 35 20).")
+    p.add_argument("--preview_up", metavar="AXIS", help="Preview up axis: +x -x +y -y +z -z (default -y, the COLMAP convention; write --preview_up=-y).")
+    p.add_argument("--preview_camera", nargs=6, type=float, metavar=("EX", "EY", "EZ", "TX", "TY", "TZ"),
+                   help="Preview camera given as eye and target points instead of --preview_view.")
+    p.add_argument("--preview_fov", type=float, metavar="DEG", help="Preview vertical field of view in degrees, between 0 and 170 (default 50).")
     p.add_argument("--keep_multicluster", action="store_true", help="Density filter: keep every dense cluster, not only the largest.")
     p.add_argument("--compression_level", type=int, default=0,
                    help="0-9, per format: .ksplat 0 = float32, 1 = float16 blocks, 2+ = 8-bit SH; .spz the gzip level; .sog the palette size.")
     return p
+
+
+PREVIEW_OPTIONS = ("preview_size", "preview_view", "preview_up", "preview_camera", "preview_fov")
+PREVIEW_UP = ("+x", "-x", "+y", "-y", "+z", "-z")
+
+
+def check_preview_args(args):
+    """-> the error line of the first preview flag that cannot be used, or None (no counterpart in the reference)"""
+    given = [name for name in PREVIEW_OPTIONS if getattr(args, name) is not None]
+    if args.preview is None:
+        return f"Error: --{given[0]} needs --preview FILE." if given else None
+    if args.info:
+        return "Error: --preview renders a conversion's result; it cannot be combined with --info."
+    if args.preview_size is not None and not all(1 <= v <= 8192 for v in args.preview_size):
+        return f"Error: --preview_size must be between 1 and 8192 per side. Got {args.preview_size[0]} {args.preview_size[1]}."
+    if args.preview_fov is not None and not (0.0 < args.preview_fov < 170.0):
+        return f"Error: --preview_fov must be between 0 and 170 (exclusive). Got {args.preview_fov}."
+    if args.preview_up is not None and args.preview_up.lower() not in PREVIEW_UP + ("x", "y", "z"):
+        return f"Error: --preview_up must be one of {' '.join(PREVIEW_UP)}. Got {args.preview_up}."
+    if args.preview_view is not None:
+        az, el = args.preview_view
+        if not (np.isfinite(az) and -90.0 <= el <= 90.0):
+            return f"Error: --preview_view must be a finite azimuth and an elevation between -90 and 90. Got {az} {el}."
+        if args.preview_camera is not None:
+            return "Error: --preview_view and --preview_camera cannot be combined (angles about the scene, or an explicit eye and target)."
+    if args.preview_camera is not None:
+        c = args.preview_camera
+        if not all(np.isfinite(v) for v in c) or list(c[:3]) == list(c[3:]):
+            return f"Error: --preview_camera must be six finite numbers with the eye apart from the target. Got {' '.join(f'{v:g}' for v in c)}."
+    return None
+
+
+def preview_kwargs(args) -> dict:
+    """Converter.run's preview keywords: none at all without --preview, and only the flags that were given"""
+    if args.preview is None:
+        return {}
+    return dict({"preview": args.preview}, **{name: getattr(args, name) for name in PREVIEW_OPTIONS if getattr(args, name) is not None})
 
 
 def main(argv=None):
@@ -269,6 +318,10 @@ def main(argv=None):
         return
     if args.compression_level < 0 or args.compression_level > 9:
         print(f"Error: --compression_level must be between 0 and 9. Got {args.compression_level}.")
+        return
+    preview_error = check_preview_args(args)
+    if preview_error:
+        print(preview_error)
         return
 
     if args.info:
@@ -319,7 +372,8 @@ def main(argv=None):
     filters_active = any([args.density_voxel_size, args.density_threshold, args.sor_k, args.sor_sigma, args.crop_sh,
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
                           args.rotate is not None, args.scale is not None, args.translate is not None, args.max_splats is not None,
-                          args.decimate_voxel_size is not None, bool(merge_files), has_source_extras and not args.extra_elements])
+                          args.decimate_voxel_size is not None, bool(merge_files), args.preview is not None,
+                          has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
         print("\n[INFO] Target is generic 3DGS PLY (same as input extension) and no filters are active.")
@@ -354,7 +408,8 @@ def main(argv=None):
                       crop_sh=args.crop_sh, auto_bbox=args.auto_bbox, compression_level=args.compression_level,
                       maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate,
                       max_splats=args.max_splats, **({"merge": merge_files, "merge_transforms": merge_transforms} if merge_files else {}),
-                      **({"decimate_voxel_size": args.decimate_voxel_size} if args.decimate_voxel_size is not None else {}))
+                      **({"decimate_voxel_size": args.decimate_voxel_size} if args.decimate_voxel_size is not None else {}),
+                      **preview_kwargs(args))
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

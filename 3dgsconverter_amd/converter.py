@@ -11,6 +11,7 @@ readers, filter chain and writers: a file is converted on a machine that has thi
   | :150-252 DataProcessor, the filters in order      | processing.ChainedDataProcessor: one device-resident chain          |
   | (none: the reference cannot move a scene)         | run(rotate=, scale=, translate=): apply_transform before the filters|
   | :263-288 extra elements, the handler's write      | the format's write_*                                                |
+  | (none: the reference renders nothing)             | run(preview=...): the written table as a PNG (_write_preview)       |
 
 The decoded rows stay in HBM from the reader to the end of the run (``Converter(..., resident=True)``, the default; readers'
 ``keep=``, _lib.ResidentRows): the chain's coordinates, the alpha filter's column and the colours' f_dc are gathered from them
@@ -207,6 +208,7 @@ class Converter:
         self.source_handler = None
         self.profile = None
         self.stage_ms = {}          # the last run's stage clocks: read_*, process, write_*
+        self.last_preview = {}      # the last run's preview: visible, instances, rows and the render plan (run(preview=...))
         self._loaded = None         # (path, handler, data, profile) of load_source_only: run() decodes the source no second time
 
     def _detect_format(self, path):
@@ -249,7 +251,10 @@ class Converter:
         after SOR and before the budget;
         and ``max_splats=N``: keep the N most visible splats (DataProcessor.limit_splats), applied after every other filter;
         and ``merge=[path, ...]`` with ``merge_transforms=[None | {"rotate":, "scale":, "translate":}, ...]``: further sources
-        whose rows follow the main source's in one table (_merge_sources), before everything else"""
+        whose rows follow the main source's in one table (_merge_sources), before everything else;
+        and ``preview=PATH`` with ``preview_size=(w, h)``, ``preview_view=(azimuth, elevation)``, ``preview_up=``,
+        ``preview_camera=(ex, ey, ez, tx, ty, tz)``, ``preview_fov=``: a PNG of the written table, rendered after the writer has
+        returned (_write_preview)"""
         debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
         clocks = self.stage_ms = {}
         held = []                   # the processor of this run: whatever it still holds in HBM is freed on every exit path
@@ -343,6 +348,28 @@ class Converter:
         for line in notes:
             status_print(line)
 
+    def _write_preview(self, processor, path, options, clocks):
+        """``run(preview=PATH, preview_size=, preview_view=, preview_up=, preview_camera=, preview_fov=)``: after the writer has
+        returned, the table that was written -- the processor's rows in HBM on the resident path, else ``self.data`` uploaded
+        once -- is rendered (DataProcessor.render_preview) and stored as an 8-bit RGB PNG.  The image shows the table before the
+        target format's quantisation.  Clocks: preview_* (the renderer's stages and preview_png).  A scene that needs more
+        instance workspace than the renderer's budget prints a warning and the conversion still completes; any other error
+        propagates."""
+        from . import _lib, render
+        kw = {k: v for k, v in options.items() if v is not None}
+        ms = {}
+        try:
+            image = processor.render_preview(stage_ms=ms, **kw)
+        except render.RenderRefused as e:
+            status_print(f"Warning: preview not written: {e}")
+            return
+        with _lib.stage_clock(ms, "png"):
+            render.write_png(path, image)
+        clocks.update({"preview_" + k: v for k, v in ms.items()})
+        info = self.last_preview = getattr(processor, "last_preview", {})
+        status_print(f"Preview: {image.shape[1]} x {image.shape[0]}, {info.get('visible', 0):,} of {info.get('rows', len(self.data)):,} splats visible, "
+                     f"saved to {path}")
+
     def _run(self, clocks, held, kwargs):
         import time
         from .processing.data_processor import ChainedDataProcessor
@@ -363,6 +390,8 @@ class Converter:
                 self.profile = self.source_handler.profile
                 clocks.update({"read_" + k: v for k, v in read_ms.items()})
             self._loaded = None     # (the table is about to change in place: cap_sh_degree)
+            preview = {k: kwargs.pop("preview_" + k) for k in ("size", "view", "up", "camera", "fov") if "preview_" + k in kwargs}
+            preview_path = kwargs.pop("preview", None)
             merge_paths, merge_transforms = kwargs.pop("merge", None), kwargs.pop("merge_transforms", None)
             if merge_paths:
                 self._merge_sources(clocks, list(merge_paths), merge_transforms)
@@ -439,6 +468,9 @@ class Converter:
             write_ms = {}
             self._get_format_handler(self.target_format).write(self.data, self.output_path, stage_ms=write_ms, **kwargs)
             clocks.update({"write_" + k: v for k, v in write_ms.items()})
+            if preview_path is not None:
+                pbar.set_description("Rendering Preview")
+                self._write_preview(processor, preview_path, preview, clocks)
             pbar.update(40)
             pbar.refresh()
             pbar.set_description("Completed")

@@ -30,6 +30,7 @@ import numpy as np
 
 from .. import _lib
 from .. import decimate as _decimate
+from .. import render as _render
 from .. import transform as _transform
 from ..utils import debug_print, status_print
 from . import clusters as _clusters
@@ -652,6 +653,34 @@ class DataProcessor:
         self.last_decimate = dict(info)
         status_print(f"Decimate (voxel {h:g}): Merged {n} splats into {info['groups']} ({info['merged_groups']} voxels held more than one).")
         return None if self.lazy else self.data
+
+    # ------------------------------------------------------------------ the preview image (no counterpart in the reference)
+    def render_preview(self, size=(960, 540), view=(35, 20), up="-y", fov=50, camera=None, sh_degree=None, background=(0, 0, 0),
+                       max_work_bytes=_render.DEFAULT_MAX_WORK_BYTES, stage_ms=None):
+        """-> the (height, width, 3) uint8 image of the table as it stands (csrc/render.hip), and ``.data`` is
+        unchanged.  The camera is render.plan_camera's: framed on the table's bounding box from the azimuth and elevation `view`
+        about `up`, or the explicit `camera` = (eye, target).  With resident rows the box comes from their profile and the
+        image is rendered where they lie; otherwise the box is the host table's profile and the table is uploaded once.  Every
+        refusal of render.plan_render comes before any device work; render.RenderRefused when the scene needs more instance
+        workspace than `max_work_bytes`.  ``last_preview``: visible, instances, rows and the plan."""
+        debug_print("[DEBUG] Executing 'render_preview'...")
+        data, rr = self.data, self.resident
+        if not isinstance(data, np.ndarray) or data.dtype.fields is None:
+            raise TypeError("self.data must be a numpy structured array.")
+        _render.check_size(size)
+        _render.plan_render(data.dtype, _render.plan_camera((0, 0, 0), (0, 0, 0), size, view, up, fov, camera), sh_degree, background,
+                            max_work_bytes)                     # (the refusals: none of them depends on the box)
+        prof = rr.profile() if rr is not None else _lib.host_table_profile(data)
+        cam = _render.plan_camera(prof["lo"], prof["hi"], size, view, up, fov, camera)
+        plan = _render.plan_render(data.dtype, cam, sh_degree, background, max_work_bytes)
+        info = {}
+        if rr is not None:
+            image = rr.render(plan, stage_ms=stage_ms)
+            info.update(rr.render_info)
+        else:
+            image = _lib.render_table(data, plan, stage_ms=stage_ms, info=info)
+        self.last_preview = dict(info, plan=plan)
+        return image
 
     # ------------------------------------------------------------------ table-shaping methods (SURVEY.md 8(f) rank 4)
     def cap_sh_degree(self, degree):

@@ -1271,6 +1271,59 @@ int gsx_rows_decimate_write_dev(gsx_ctx *ctx, const void *rows_dev, int64_t firs
                                 int64_t n, const gsx_decimate_layout *layout, void *work_dev, int64_t work_bytes, void *out_dev,
                                 int64_t out_first_byte, int64_t n_out, float *stage_ms);
 
+
+/* ---- the preview image: a tile-based forward rasteriser of the splats (csrc/render.hip) ----
+ * No reference counterpart: the definition is this project's own (tests/render_numpy.py) and the device reproduces
+ * it bit for bit.  A pinhole camera (x right, y down, z forward; pixel samples at integer coordinates, row 0 the top) projects
+ * every row in float64 to a record; the image is blended per pixel in float32, front to back in the order of (float32 depth,
+ * row), over the records whose pixel rectangle holds the pixel -- so it depends on the rows and the camera alone, never on the
+ * tile size, the launch geometry or the sort.
+ *
+ * The layout names the float32 ('<f4') fields of a row by byte offset.  Colour: f_dc (dc_offset) with the SH bands up to `degree`
+ * from rest_offset (channel c, coefficient k is f_rest_(c * rest_m + k)), or, with dc_offset[0] = -1, three uint8 at rgb_offset. */
+enum { GSX_RENDER_STAGES = 6, GSX_RENDER_INFO_WORDS = 4, GSX_RENDER_RECORD_WORDS = 16, GSX_RENDER_TILE = 16, GSX_RENDER_MAX_SIDE = 8192 };
+enum { GSX_RENDER_OK = 0, GSX_RENDER_TOO_MANY = 1 };
+typedef struct {
+    int32_t xyz_offset[3];
+    int32_t scale_offset[3];
+    int32_t rot_offset[4];             /* rot_0..3 = (w, x, y, z) */
+    int32_t opacity_offset;
+    int32_t dc_offset[3];              /* f_dc_0..2, or -1: the colour bytes */
+    int32_t rgb_offset[3];             /* red green blue (uint8); read when dc_offset[0] < 0 */
+    int32_t degree;                    /* SH degree that is evaluated, 0 ... 3 */
+    int32_t rest_m;                    /* f_rest coefficients per colour channel: 0, 3, 8 or 15, >= (degree + 1)^2 - 1 */
+    int32_t rest_offset[45];
+    int32_t width, height;             /* 1 ... GSX_RENDER_MAX_SIDE */
+    double  view[12];                  /* 3 x 4 row-major: p_cam = V (p, 1) */
+    double  eye[3];                    /* the camera's position: SH is evaluated along normalize(p - eye) */
+    double  fx, fy, cx, cy;            /* u = fx x / z + cx */
+    double  tan_fovx, tan_fovy;
+    double  near;                      /* > 0: a row with z_cam <= near is not drawn */
+    float   background[3];
+} gsx_render_layout;
+/* bytes of the fixed device workspace for n rows and a width x height image -> *bytes_out (HOST).  Launches nothing. */
+int gsx_rows_render_work_dev(gsx_ctx *ctx, int64_t n, int32_t width, int32_t height, int64_t *bytes_out);
+/* Projects the n resident rows at rows_dev (as gsx_rows_take_dev takes them), one lane per row, counts the 16 x 16 tiles every
+ * pixel rectangle touches and scans the counts.  work_dev: 16-byte aligned, work_bytes >= gsx_rows_render_work_dev; it carries
+ * the plan to gsx_rows_render_draw_dev and must not be touched in between.  Its first n * 64 bytes are the records, one per row,
+ * GSX_RENDER_RECORD_WORDS 32-bit words each: float32 u, v (the centre in pixels), a, b, c (the conic), opacity, red, green, blue,
+ * depth; int32 x0, x1, y0, y1 (the rectangle, inclusive, clipped to the image); uint32 visible; one zero word.  An invisible
+ * row's record is all zero.  info_out (HOST, GSX_RENDER_INFO_WORDS int64): status (GSX_RENDER_*), visible rows, instances
+ * (tile, row pairs), bytes of instance workspace the draw call needs.  GSX_RENDER_TOO_MANY -- 2^31 instances or more -- returns 0
+ * with the status set: the caller refuses.  stage_ms (HOST, GSX_RENDER_STAGES floats, or NULL): the stream clocks of project
+ * and of count + scan are ADDED to entries 0, 1.  n = 0 launches nothing.  Synchronises the context's stream (the one readback). */
+int gsx_rows_render_plan_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_byte, int64_t stride, int64_t n,
+                             const gsx_render_layout *layout, void *work_dev, int64_t work_bytes, int64_t *info_out, float *stage_ms);
+/* The image of a plan with status GSX_RENDER_OK -> image_dev (height * width * 3 bytes, RGB, row 0 the top; no byte outside them
+ * is written).  The same n, layout and workspace as the plan call; inst_dev: 16-byte aligned, inst_bytes >= the plan's
+ * info_out[3] (NULL and 0 when there are no instances: no sort is launched, the image is the background).  Emits
+ * (tile << 32 | depth bits, row) in row order, orders them by a stable radix sort of the keys -- ties fall to the lower row --,
+ * finds the tiles' ranges and blends: one workgroup of 256 lanes per tile, one pixel per lane, the tile's records staged in LDS
+ * in batches of 256.  stage_ms: the clocks of emit, sort, ranges and blend are ADDED to entries 2 ... 5.  Synchronises the
+ * context's stream. */
+int gsx_rows_render_draw_dev(gsx_ctx *ctx, int64_t n, const gsx_render_layout *layout, void *work_dev, int64_t work_bytes, void *inst_dev,
+                             int64_t inst_bytes, void *image_dev, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 
 #include "grid_policy.h"
 #include "gsx_common.h"
+#include "gsx_internal.h"
 #include "sor_grid_params.h"
 
 namespace gsx {
@@ -37,6 +38,22 @@ int DevBuf::reserve(size_t bytes)
 void DevBuf::release()
 {
     if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
+
+int PinnedBuf::reserve(size_t bytes)
+{
+    if (bytes <= cap) return 0;
+    release();
+    GSX_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    cap = bytes;
+    return 0;
+}
+
+void PinnedBuf::release()
+{
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
 }
@@ -77,34 +94,6 @@ static int timing_resolve(gsx_ctx *ctx, int slot)
     s.used = 0;
     return 0;
 }
-
-// kernels implemented in the other translation units
-int launch_pack_points(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, float4 *);  // flags non-finite input in ctx->devflags
-int launch_knn_brute(gsx_ctx *, const float4 *, int64_t, int64_t, int64_t, const unsigned *, const unsigned *,
-                     int64_t, int, float *);
-int knn_tree_info(gsx_ctx *, gsx_sor_info *);
-int knn_tree_debug(gsx_ctx *, uint32_t *, uint64_t *, uint32_t *, int64_t, int64_t *, int64_t *);
-int launch_knn_tree(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, int64_t, int64_t, int, float *, double *,
-                    gsx_sor_info *, int64_t, int, int, bool);
-int launch_knn_grid(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, int64_t, int64_t, int,
-                    float *, gsx_sor_info *, int share = 0, int nshares = 1);
-int launch_sor_stats(gsx_ctx *, const float *, int64_t, double, float *);
-int launch_sor_mask(gsx_ctx *, const float *, int64_t, const float *, uint8_t *);
-int density_voxels_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, int64_t, int64_t,
-                       int64_t *, int64_t *, int64_t *, int64_t *);
-int density_hist_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, int64_t, int64_t *, int64_t *,
-                     int64_t *);
-int density_merge_dev(gsx_ctx *, const int64_t *, const int64_t *, int64_t, int64_t, int64_t, int64_t *, int64_t *, int64_t *, int64_t *);
-int density_filter_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, int64_t, int, const float *,
-                       uint8_t *, gsx_density_info *);
-int density_filter_large_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, int64_t, int, const float *,
-                             uint8_t *, gsx_density_info *);
-int voxel_clusters_dev(gsx_ctx *, const int64_t *, int64_t, int, uint8_t *, gsx_density_info *);
-int density_mask_dev(gsx_ctx *, const float *, const float *, const float *, int64_t, int64_t, double, const int64_t *,
-                     int64_t, uint8_t *);
-int kmeans_lloyd_dev(gsx_ctx *, const float *, int64_t, int, int, int, float *, int32_t *);
-int kmeans_lloyd_batch_dev(gsx_ctx *, const float *, const int64_t *, int, int, int, int, float *, int32_t *);
-int quantize_dev(gsx_ctx *, const float *, int64_t, const float *, int, uint8_t *);
 
 }  // namespace gsx
 
@@ -175,8 +164,6 @@ int gsx_ctx_check(gsx_ctx *c)
     return 0;
 }
 
-int gsx_comm_destroy(gsx_ctx *c);
-
 void gsx_ctx_destroy(gsx_ctx *c)
 {
     if (!c) return;
@@ -185,13 +172,9 @@ void gsx_ctx_destroy(gsx_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     for (auto &s : c->slots)
         for (auto e : s.ev) (void)hipEventDestroy(e);
-    for (auto &w : c->ws) w.release_all();
-    c->tree_ws.release_all();
-    c->slab_ws.release_all();
-    gsx::DevBuf *bufs[] = {&c->commscratch, &c->devflags, &c->vox_ids, &c->nzmask, &c->statspart, &c->scratch, &c->scratch2, &c->scratch3, &c->scratch4, &c->scratch5, &c->ksplat_keys, &c->splat_sort};
-    for (auto b : bufs) b->release();
-    if (c->owned_stream) (void)hipStreamDestroy(c->owned_stream);
-    delete c;
+    const hipStream_t owned = c->owned_stream;
+    delete c;   // every DevBuf / PinnedBuf frees itself: the buffers go before the stream, as they always did
+    if (owned) (void)hipStreamDestroy(owned);
 }
 
 int gsx_ctx_set_stream(gsx_ctx *c, void *s)
@@ -557,52 +540,96 @@ static int host_ctx(gsx_ctx **out)
     return 0;
 }
 
-// stage strided host xyz as three device columns (SoA in HBM)
-static int upload_xyz(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n,
-                      float **dx, float **dy, float **dz, int64_t *dstride)
-{
-    if (stride == 1) {
-        GSX_CHECK(c->scratch.reserve(sizeof(float) * 3 * (size_t)n));
-        float *base = c->scratch.as<float>();
-        GSX_HIP(hipMemcpyAsync(base, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-        GSX_HIP(hipMemcpyAsync(base + n, y, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-        GSX_HIP(hipMemcpyAsync(base + 2 * n, z, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-        *dx = base; *dy = base + n; *dz = base + 2 * n; *dstride = 1;
+}  // extern "C"
+
+// One call of a host-pointer entry point: the process-wide lock for its whole length, the cached context, inputs staged into
+// the context's stage_* buffers, outputs queued for download, one synchronise.  (The stage_* buffers are touched here only.)
+struct HostCall {
+    std::lock_guard<std::mutex> lk{g_host_mu};
+    gsx_ctx *c = nullptr;
+
+    int open() { return host_ctx(&c); }
+    // room for `count` elements (+ `slack` bytes behind them) at the start of `buf`
+    template <class T>
+    int room(DevBuf &buf, size_t count, T **dev, size_t slack = 0)
+    {
+        GSX_CHECK(buf.reserve(sizeof(T) * count + slack));
+        *dev = buf.as<T>();
         return 0;
     }
-    if (stride == 3 && y == x + 1 && z == x + 2) {  // the reference's (N,3) coords: one contiguous copy
-        GSX_CHECK(c->scratch.reserve(sizeof(float) * 3 * (size_t)n));
-        float *base = c->scratch.as<float>();
-        GSX_HIP(hipMemcpyAsync(base, x, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
-        *dx = base; *dy = base + 1; *dz = base + 2; *dstride = 3;
+    template <class T>
+    int put(T *dev, const T *src, size_t count)
+    {
+        GSX_HIP(hipMemcpyAsync(dev, src, sizeof(T) * count, hipMemcpyHostToDevice, c->stream));
         return 0;
     }
-    GSX_FAIL("xyz layout not supported by the host entry points (use three contiguous columns or (N,3) rows)");
-}
+    template <class T>
+    int up(DevBuf &buf, const T *src, size_t count, T **dev)
+    {
+        GSX_CHECK(room(buf, count, dev));
+        return put(*dev, src, count);
+    }
+    template <class T>
+    int down(T *dst, const T *dev, size_t count)
+    {
+        GSX_HIP(hipMemcpyAsync(dst, dev, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }
+    int sync()
+    {
+        GSX_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    // strided host xyz as three device columns (SoA in HBM) of stage_in
+    int up_xyz(const float *x, const float *y, const float *z, int64_t stride, int64_t n, float **dx, float **dy, float **dz, int64_t *dstride)
+    {
+        float *base;
+        if (stride == 1) {
+            GSX_CHECK(room(c->stage_in, 3 * (size_t)n, &base));
+            GSX_CHECK(put(base, x, (size_t)n));
+            GSX_CHECK(put(base + n, y, (size_t)n));
+            GSX_CHECK(put(base + 2 * n, z, (size_t)n));
+            *dx = base; *dy = base + n; *dz = base + 2 * n; *dstride = 1;
+            return 0;
+        }
+        if (stride == 3 && y == x + 1 && z == x + 2) {  // the reference's (N,3) coords: one contiguous copy
+            GSX_CHECK(up(c->stage_in, x, 3 * (size_t)n, &base));
+            *dx = base; *dy = base + 1; *dz = base + 2; *dstride = 3;
+            return 0;
+        }
+        GSX_FAIL("xyz layout not supported by the host entry points (use three contiguous columns or (N,3) rows)");
+    }
+};
+
+// Bytes the byte-wide outputs have always had behind them.  None of the kernels that fill them (sor_mask_kernel,
+// voxel_mask_kernel, quantize_kernel, the SOG texel kernels) was found to touch the tail; it is kept all the same.
+constexpr size_t MASK_TAIL = 4, TEXEL_TAIL = 16;
+
+extern "C" {
 
 int gsx_sor_filter(const float *x, const float *y, const float *z, int64_t stride, int64_t n, int k, double factor,
                    int algo, uint8_t *mask_out, float *mean_out, float *stats_out, gsx_sor_info *info)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!x || !y || !z || !mask_out) GSX_FAIL("gsx_sor_filter: null argument");
     if (n <= 0) GSX_FAIL("gsx_sor_filter: empty cloud");
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    float *dx, *dy, *dz;
+    GSX_CHECK(h.open());
+    gsx_ctx *c = h.c;
+    float *dx, *dy, *dz, *dmd = nullptr, *dstats = nullptr;
     int64_t ds;
-    GSX_CHECK(upload_xyz(c, x, y, z, stride, n, &dx, &dy, &dz, &ds));
-    GSX_CHECK(c->scratch2.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch3.reserve(sizeof(float) * 4));
-    GSX_CHECK(c->scratch4.reserve((size_t)n + 4));
-    float *dmd = c->scratch2.as<float>();
-    float *dstats = c->scratch3.as<float>();
-    uint8_t *dmask = c->scratch4.as<uint8_t>();
+    uint8_t *dmask;
+    GSX_CHECK(h.up_xyz(x, y, z, stride, n, &dx, &dy, &dz, &ds));
+    GSX_CHECK(carve(c->stage_aux, [&](Carve &a) {
+        dmd = a.take<float>((size_t)n);   // (16-byte aligned: gsx_sor_stats_dev)
+        dstats = a.take<float>(4);        // mean, std, threshold
+    }));
+    GSX_CHECK(h.room(c->stage_out, (size_t)n, &dmask, MASK_TAIL));
     GSX_CHECK(gsx_sor_knn_dev(c, dx, dy, dz, ds, n, 0, n, k, algo, dmd, nullptr));
     GSX_CHECK(gsx_sor_stats_dev(c, dmd, n, factor, dstats));
     GSX_CHECK(gsx_sor_mask_dev(c, dmd, n, dstats + 2, dmask));
-    GSX_HIP(hipMemcpyAsync(mask_out, dmask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (mean_out) GSX_HIP(hipMemcpyAsync(mean_out, dmd, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (stats_out) GSX_HIP(hipMemcpyAsync(stats_out, dstats, sizeof(float) * 3, hipMemcpyDeviceToHost, c->stream));
+    GSX_CHECK(h.down(mask_out, dmask, (size_t)n));
+    if (mean_out) GSX_CHECK(h.down(mean_out, dmd, (size_t)n));
+    if (stats_out) GSX_CHECK(h.down(stats_out, dstats, 3));
     GSX_CHECK(gsx_ctx_check(c));  // synchronises; non-finite coordinates (either algorithm) are an error, like cKDTree's
     int used = k > 64 ? GSX_KNN_GRID : (algo == GSX_KNN_AUTO ? (n < c->brute_below ? GSX_KNN_BRUTE : GSX_KNN_GRID) : algo);
     if (used == GSX_KNN_GRID && c->last_knn_algo == GSX_KNN_TREE) used = GSX_KNN_TREE;   // adaptive mode chose the tree path
@@ -693,10 +720,9 @@ int gsx_voxel_clusters_dev(gsx_ctx *c, const int64_t *keys3, int64_t m, int keep
 
 int gsx_voxel_clusters(const int64_t *keys3, int64_t m, int keep_multicluster, uint8_t *keep_out, gsx_density_info *info)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    return gsx_voxel_clusters_dev(c, keys3, m, keep_multicluster, keep_out, info);
+    HostCall h;
+    GSX_CHECK(h.open());
+    return gsx_voxel_clusters_dev(h.c, keys3, m, keep_multicluster, keep_out, info);
 }
 
 int gsx_density_stage_clocks(gsx_ctx *c, double *ms_out)
@@ -719,34 +745,32 @@ int gsx_density_voxels(const float *x, const float *y, const float *z, int64_t s
                        int64_t min_points, int64_t dense_cap, int64_t *n_unique_out, int64_t *n_dense_out,
                        int64_t *dense_keys_out, int64_t *dense_counts_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!x || !y || !z) GSX_FAIL("gsx_density_voxels: null argument");
     if (n <= 0) GSX_FAIL("gsx_density_voxels: empty cloud");
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
+    GSX_CHECK(h.open());
     float *dx, *dy, *dz;
     int64_t ds;
-    GSX_CHECK(upload_xyz(c, x, y, z, stride, n, &dx, &dy, &dz, &ds));
-    return gsx_density_voxels_dev(c, dx, dy, dz, ds, n, voxel_size, min_points, dense_cap, n_unique_out, n_dense_out,
+    GSX_CHECK(h.up_xyz(x, y, z, stride, n, &dx, &dy, &dz, &ds));
+    return gsx_density_voxels_dev(h.c, dx, dy, dz, ds, n, voxel_size, min_points, dense_cap, n_unique_out, n_dense_out,
                                   dense_keys_out, dense_counts_out);
 }
 
 int gsx_density_mask(const float *x, const float *y, const float *z, int64_t stride, int64_t n, double voxel_size,
                      const int64_t *kept_keys, int64_t n_kept, uint8_t *mask_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!x || !y || !z || !mask_out) GSX_FAIL("gsx_density_mask: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
+    GSX_CHECK(h.open());
     float *dx, *dy, *dz;
     int64_t ds;
-    GSX_CHECK(upload_xyz(c, x, y, z, stride, n, &dx, &dy, &dz, &ds));
-    GSX_CHECK(c->scratch4.reserve((size_t)n + 4));
-    GSX_CHECK(gsx_density_mask_dev(c, dx, dy, dz, ds, n, voxel_size, kept_keys, n_kept, c->scratch4.as<uint8_t>()));
-    GSX_HIP(hipMemcpyAsync(mask_out, c->scratch4.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    uint8_t *dmask;
+    GSX_CHECK(h.up_xyz(x, y, z, stride, n, &dx, &dy, &dz, &ds));
+    GSX_CHECK(h.room(h.c->stage_out, (size_t)n, &dmask, MASK_TAIL));
+    GSX_CHECK(gsx_density_mask_dev(h.c, dx, dy, dz, ds, n, voxel_size, kept_keys, n_kept, dmask));
+    GSX_CHECK(h.down(mask_out, dmask, (size_t)n));
+    return h.sync();
 }
 
 // ------------------------------------------------------------------ K-Means
@@ -771,60 +795,53 @@ int gsx_kmeans_lloyd_batch_dev(gsx_ctx *c, const float *data_dev, const int64_t 
 int gsx_kmeans_lloyd(const float *data, int64_t n, int d, int k, int max_iter, const float *init_centroids,
                      float *centroids_out, int32_t *labels_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!data || !init_centroids || !centroids_out || !labels_out) GSX_FAIL("gsx_kmeans_lloyd: null argument");
     if (n <= 0 || d <= 0 || k <= 0) GSX_FAIL("gsx_kmeans_lloyd: bad shape");
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
+    GSX_CHECK(h.open());
     const size_t nd = (size_t)n * d, kd = (size_t)k * d;
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * nd));
-    GSX_CHECK(c->scratch2.reserve(sizeof(float) * kd));
-    GSX_CHECK(c->scratch4.reserve(sizeof(int32_t) * (size_t)n));
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, data, sizeof(float) * nd, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(hipMemcpyAsync(c->scratch2.p, init_centroids, sizeof(float) * kd, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(hipMemsetAsync(c->scratch4.p, 0, sizeof(int32_t) * (size_t)n, c->stream));  // max_iter == 0: labels stay 0 (gpu_ops.py:183)
-    GSX_CHECK(gsx_kmeans_lloyd_dev(c, c->scratch.as<float>(), n, d, k, max_iter, c->scratch2.as<float>(),
-                                   c->scratch4.as<int32_t>()));
-    GSX_HIP(hipMemcpyAsync(centroids_out, c->scratch2.p, sizeof(float) * kd, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipMemcpyAsync(labels_out, c->scratch4.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    float *d_data, *d_cent;
+    int32_t *d_labels;
+    GSX_CHECK(h.up(h.c->stage_in, data, nd, &d_data));
+    GSX_CHECK(h.up(h.c->stage_aux, init_centroids, kd, &d_cent));
+    GSX_CHECK(h.room(h.c->stage_out, (size_t)n, &d_labels));
+    GSX_HIP(hipMemsetAsync(d_labels, 0, sizeof(int32_t) * (size_t)n, h.c->stream));  // max_iter == 0: labels stay 0 (gpu_ops.py:183)
+    GSX_CHECK(gsx_kmeans_lloyd_dev(h.c, d_data, n, d, k, max_iter, d_cent, d_labels));
+    GSX_CHECK(h.down(centroids_out, d_cent, kd));
+    GSX_CHECK(h.down(labels_out, d_labels, (size_t)n));
+    return h.sync();
 }
 
 int gsx_kmeans_pp(const float *data, int64_t n, int d, int k, const double *uniforms, int n_local_trials, float *centroids_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!data || !uniforms || !centroids_out) GSX_FAIL("gsx_kmeans_pp: null argument");
     if (n <= 0 || d <= 0 || k <= 0) GSX_FAIL("gsx_kmeans_pp: bad shape");
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
+    GSX_CHECK(h.open());
     const size_t nd = (size_t)n * d, kd = (size_t)k * d;
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * nd));
-    GSX_CHECK(c->scratch2.reserve(sizeof(float) * kd));
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, data, sizeof(float) * nd, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_kmeans_pp_dev(c, c->scratch.as<float>(), n, d, k, uniforms, n_local_trials, c->scratch2.as<float>()));
-    GSX_HIP(hipMemcpyAsync(centroids_out, c->scratch2.p, sizeof(float) * kd, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    float *d_data, *d_cent;
+    GSX_CHECK(h.up(h.c->stage_in, data, nd, &d_data));
+    GSX_CHECK(h.room(h.c->stage_aux, kd, &d_cent));
+    GSX_CHECK(gsx_kmeans_pp_dev(h.c, d_data, n, d, k, uniforms, n_local_trials, d_cent));
+    GSX_CHECK(h.down(centroids_out, d_cent, kd));
+    return h.sync();
 }
 
 int gsx_kmeans1d(const float *vals, int64_t n, int k, int iters, float *centroids_out, int32_t *labels_out, double *inertia3_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!vals || !centroids_out) GSX_FAIL("gsx_kmeans1d: null argument");
     if (n <= 0 || k <= 0) GSX_FAIL("gsx_kmeans1d: bad shape");
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch2.reserve(sizeof(float) * (size_t)k));
-    if (labels_out) GSX_CHECK(c->scratch4.reserve(sizeof(int32_t) * (size_t)n));
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, vals, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_kmeans1d_dev(c, c->scratch.as<float>(), n, k, iters, 3, c->scratch2.as<float>(),
-                               labels_out ? c->scratch4.as<int32_t>() : nullptr, inertia3_out));
-    GSX_HIP(hipMemcpyAsync(centroids_out, c->scratch2.p, sizeof(float) * (size_t)k, hipMemcpyDeviceToHost, c->stream));
-    if (labels_out) GSX_HIP(hipMemcpyAsync(labels_out, c->scratch4.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    GSX_CHECK(h.open());
+    float *d_vals, *d_cent;
+    int32_t *d_labels = nullptr;
+    GSX_CHECK(h.up(h.c->stage_in, vals, (size_t)n, &d_vals));
+    GSX_CHECK(h.room(h.c->stage_aux, (size_t)k, &d_cent));
+    if (labels_out) GSX_CHECK(h.room(h.c->stage_out, (size_t)n, &d_labels));
+    GSX_CHECK(gsx_kmeans1d_dev(h.c, d_vals, n, k, iters, 3, d_cent, d_labels, inertia3_out));
+    GSX_CHECK(h.down(centroids_out, d_cent, (size_t)k));
+    if (labels_out) GSX_CHECK(h.down(labels_out, d_labels, (size_t)n));
+    return h.sync();
 }
 
 int gsx_quantize_sorted_codebook_dev(gsx_ctx *c, const float *vals_dev, int64_t n, const float *codebook_dev, int kcb,
@@ -837,143 +854,147 @@ int gsx_quantize_sorted_codebook_dev(gsx_ctx *c, const float *vals_dev, int64_t 
 
 int gsx_quantize_sorted_codebook(const float *vals, int64_t n, const float *codebook, int kcb, uint8_t *idx_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!vals || !codebook || !idx_out) GSX_FAIL("gsx_quantize_sorted_codebook: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch2.reserve(sizeof(float) * 256));
-    GSX_CHECK(c->scratch4.reserve((size_t)n + 4));
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, vals, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(hipMemcpyAsync(c->scratch2.p, codebook, sizeof(float) * (size_t)(kcb > 0 && kcb <= 256 ? kcb : 0),
-                           hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_quantize_sorted_codebook_dev(c, c->scratch.as<float>(), n, c->scratch2.as<float>(), kcb,
-                                               c->scratch4.as<uint8_t>()));
-    GSX_HIP(hipMemcpyAsync(idx_out, c->scratch4.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    GSX_CHECK(h.open());
+    float *d_vals, *d_cb;
+    uint8_t *d_idx;
+    GSX_CHECK(h.up(h.c->stage_in, vals, (size_t)n, &d_vals));
+    GSX_CHECK(h.room(h.c->stage_aux, 256, &d_cb));
+    GSX_CHECK(h.room(h.c->stage_out, (size_t)n, &d_idx, MASK_TAIL));
+    GSX_CHECK(h.put(d_cb, codebook, (size_t)(kcb > 0 && kcb <= 256 ? kcb : 0)));
+    GSX_CHECK(gsx_quantize_sorted_codebook_dev(h.c, d_vals, n, d_cb, kcb, d_idx));
+    GSX_CHECK(h.down(idx_out, d_idx, (size_t)n));
+    return h.sync();
 }
 
 // ------------------------------------------------------------------ SOG writer numeric core (host buffers)
-int gsx_lexsort3_dev(gsx_ctx *c, const float *k0, const float *k1, const float *k2, int64_t stride, int64_t n, uint32_t *perm_out_dev);
-int gsx_sog_quats_dev(gsx_ctx *c, const float *rot_rows_dev, int64_t n, uint8_t *out4_dev);
-
 int gsx_lexsort3(const float *k0, const float *k1, const float *k2, int64_t n, uint32_t *perm_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!k0 || !k1 || !k2 || !perm_out) GSX_FAIL("gsx_lexsort3: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * 3 * (size_t)n));
-    GSX_CHECK(c->scratch4.reserve(sizeof(uint32_t) * (size_t)n));
-    float *base = c->scratch.as<float>();
+    GSX_CHECK(h.open());
+    float *base;
+    uint32_t *d_perm;
+    GSX_CHECK(h.room(h.c->stage_in, 3 * (size_t)n, &base));
+    GSX_CHECK(h.room(h.c->stage_out, (size_t)n, &d_perm));
     const float *src[3] = {k0, k1, k2};
-    for (int a = 0; a < 3; ++a) GSX_HIP(hipMemcpyAsync(base + (size_t)a * n, src[a], sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_lexsort3_dev(c, base, base + n, base + 2 * (size_t)n, 1, n, c->scratch4.as<uint32_t>()));
-    GSX_HIP(hipMemcpyAsync(perm_out, c->scratch4.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    for (int a = 0; a < 3; ++a) GSX_CHECK(h.put(base + (size_t)a * n, src[a], (size_t)n));
+    GSX_CHECK(gsx_lexsort3_dev(h.c, base, base + n, base + 2 * (size_t)n, 1, n, d_perm));
+    GSX_CHECK(h.down(perm_out, d_perm, (size_t)n));
+    return h.sync();
 }
+
+}  // extern "C"
+
+// a texel column and its uncertain bytes behind it: the outputs of gsx_rgb_from_sh, gsx_sog_positions and gsx_sog_alpha
+template <class T>
+static int texel_room(HostCall &h, size_t n, T **d_out, uint8_t **d_unc)
+{
+    return carve(h.c->stage_out, [&](Carve &a) {
+        *d_out = a.take<T>(n);
+        *d_unc = a.take<uint8_t>(n, 1);
+        a.take<uint8_t>(TEXEL_TAIL, 1);
+    });
+}
+
+extern "C" {
 
 int gsx_rgb_from_sh(const float *f_dc, int64_t n, uint8_t *out, uint8_t *uncertain_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!f_dc || !out || !uncertain_out) GSX_FAIL("gsx_rgb_from_sh: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch4.reserve(2 * (size_t)n + 16));
-    uint8_t *d_out = c->scratch4.as<uint8_t>(), *d_unc = d_out + (size_t)n;
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, f_dc, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_rgb_from_sh_dev(c, c->scratch.as<float>(), n, d_out, d_unc));
-    GSX_HIP(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipMemcpyAsync(uncertain_out, d_unc, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    GSX_CHECK(h.open());
+    float *d_in;
+    uint8_t *d_out = nullptr, *d_unc = nullptr;
+    GSX_CHECK(h.up(h.c->stage_in, f_dc, (size_t)n, &d_in));
+    GSX_CHECK(texel_room(h, (size_t)n, &d_out, &d_unc));
+    GSX_CHECK(gsx_rgb_from_sh_dev(h.c, d_in, n, d_out, d_unc));
+    GSX_CHECK(h.down(out, d_out, (size_t)n));
+    GSX_CHECK(h.down(uncertain_out, d_unc, (size_t)n));
+    return h.sync();
 }
 
 int gsx_rgb_from_sh_list(const float *f_dc, int64_t n, uint8_t *out, uint32_t *list_out, int64_t cap, int64_t *count_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!f_dc || !out || !count_out || (cap > 0 && !list_out)) GSX_FAIL("gsx_rgb_from_sh_list: null argument");
     *count_out = 0;
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch4.reserve((size_t)n + 16 + 16 + 4 * (size_t)cap));
-    uint8_t *d_out = c->scratch4.as<uint8_t>();
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(c->scratch4.as<char>() + (((size_t)n + 15) & ~(size_t)15));
-    uint32_t *d_list = d_cnt + 4;
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, f_dc, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_rgb_from_sh_list_dev(c, c->scratch.as<float>(), n, d_out, d_list, cap, d_cnt));
+    GSX_CHECK(h.open());
+    float *d_in;
+    uint8_t *d_out = nullptr;
+    uint32_t *d_cnt = nullptr, *d_list = nullptr;
+    GSX_CHECK(h.up(h.c->stage_in, f_dc, (size_t)n, &d_in));
+    GSX_CHECK(carve(h.c->stage_out, [&](Carve &a) {
+        d_out = a.take<uint8_t>((size_t)n);
+        d_cnt = a.take<uint32_t>(4, 16);   // the count word, on a 16-byte boundary
+        d_list = a.take<uint32_t>((size_t)cap, 4);
+        a.take<uint8_t>(TEXEL_TAIL, 1);
+    }));
+    GSX_CHECK(gsx_rgb_from_sh_list_dev(h.c, d_in, n, d_out, d_list, cap, d_cnt));
     uint32_t hc = 0;
-    GSX_HIP(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipMemcpyAsync(&hc, d_cnt, 4, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
+    GSX_CHECK(h.down(out, d_out, (size_t)n));
+    GSX_CHECK(h.down(&hc, d_cnt, 1));
+    GSX_CHECK(h.sync());
     *count_out = hc;
     const size_t m = std::min<size_t>(hc, (size_t)cap);
     if (m) {
-        GSX_HIP(hipMemcpyAsync(list_out, d_list, 4 * m, hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(hipStreamSynchronize(c->stream));
+        GSX_CHECK(h.down(list_out, d_list, m));
+        GSX_CHECK(h.sync());
     }
     return 0;
 }
 
 int gsx_sog_positions(const float *v, int64_t n, float log_min, float log_max, uint16_t *out, uint8_t *uncertain_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!v || !out || !uncertain_out) GSX_FAIL("gsx_sog_positions: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch4.reserve(3 * (size_t)n + 16));
-    uint16_t *d_out = c->scratch4.as<uint16_t>();
-    uint8_t *d_unc = c->scratch4.as<uint8_t>() + 2 * (size_t)n;
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, v, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_sog_positions_dev(c, c->scratch.as<float>(), n, log_min, log_max, d_out, d_unc));
-    GSX_HIP(hipMemcpyAsync(out, d_out, 2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipMemcpyAsync(uncertain_out, d_unc, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    GSX_CHECK(h.open());
+    float *d_in;
+    uint16_t *d_out = nullptr;
+    uint8_t *d_unc = nullptr;
+    GSX_CHECK(h.up(h.c->stage_in, v, (size_t)n, &d_in));
+    GSX_CHECK(texel_room(h, (size_t)n, &d_out, &d_unc));
+    GSX_CHECK(gsx_sog_positions_dev(h.c, d_in, n, log_min, log_max, d_out, d_unc));
+    GSX_CHECK(h.down(out, d_out, (size_t)n));
+    GSX_CHECK(h.down(uncertain_out, d_unc, (size_t)n));
+    return h.sync();
 }
 
 int gsx_sog_alpha(const float *opacity, int64_t n, uint8_t *out, uint8_t *uncertain_out)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!opacity || !out || !uncertain_out) GSX_FAIL("gsx_sog_alpha: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * (size_t)n));
-    GSX_CHECK(c->scratch4.reserve(2 * (size_t)n + 16));
-    uint8_t *d_out = c->scratch4.as<uint8_t>(), *d_unc = d_out + (size_t)n;
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, opacity, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_sog_alpha_dev(c, c->scratch.as<float>(), n, d_out, d_unc));
-    GSX_HIP(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipMemcpyAsync(uncertain_out, d_unc, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    GSX_CHECK(h.open());
+    float *d_in;
+    uint8_t *d_out = nullptr, *d_unc = nullptr;
+    GSX_CHECK(h.up(h.c->stage_in, opacity, (size_t)n, &d_in));
+    GSX_CHECK(texel_room(h, (size_t)n, &d_out, &d_unc));
+    GSX_CHECK(gsx_sog_alpha_dev(h.c, d_in, n, d_out, d_unc));
+    GSX_CHECK(h.down(out, d_out, (size_t)n));
+    GSX_CHECK(h.down(uncertain_out, d_unc, (size_t)n));
+    return h.sync();
 }
 
 int gsx_sog_quats(const float *rot_rows, int64_t n, uint8_t *out4)
 {
-    std::lock_guard<std::mutex> lk(g_host_mu);
+    HostCall h;
     if (!rot_rows || !out4) GSX_FAIL("gsx_sog_quats: null argument");
     if (n <= 0) return 0;
-    gsx_ctx *c;
-    GSX_CHECK(host_ctx(&c));
-    GSX_CHECK(c->scratch.reserve(sizeof(float) * 4 * (size_t)n));
-    GSX_CHECK(c->scratch4.reserve(4 * (size_t)n));
-    GSX_HIP(hipMemcpyAsync(c->scratch.p, rot_rows, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    GSX_CHECK(gsx_sog_quats_dev(c, c->scratch.as<float>(), n, c->scratch4.as<uint8_t>()));
-    GSX_HIP(hipMemcpyAsync(out4, c->scratch4.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    GSX_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    GSX_CHECK(h.open());
+    float *d_in;
+    uint8_t *d_out;
+    GSX_CHECK(h.up(h.c->stage_in, rot_rows, 4 * (size_t)n, &d_in));
+    GSX_CHECK(h.room(h.c->stage_out, 4 * (size_t)n, &d_out));
+    GSX_CHECK(gsx_sog_quats_dev(h.c, d_in, n, d_out));
+    GSX_CHECK(h.down(out4, d_out, 4 * (size_t)n));
+    return h.sync();
 }
 
 }  // extern "C"

@@ -177,21 +177,6 @@ __global__ __launch_bounds__(256) void mo_active_kernel(const unsigned *__restri
     newseg[j] = p - (j - h);
 }
 
-struct Bump {
-    char *p;
-    size_t left;
-    template <class T>
-    T *take(size_t count)
-    {
-        const size_t bytes = (sizeof(T) * count + 255) & ~(size_t)255;
-        if (bytes > left) return nullptr;
-        T *r = reinterpret_cast<T *>(p);
-        p += bytes;
-        left -= bytes;
-        return r;
-    }
-};
-
 static int morton_order_dev(gsx_ctx *c, const float *x, const float *y, const float *z, int64_t stride, int64_t n64,
                             unsigned *order, int *levels_out)
 {
@@ -208,18 +193,20 @@ static int morton_order_dev(gsx_ctx *c, const float *x, const float *y, const fl
     const size_t temp_bytes = std::max(t_sort, std::max(t_scan, t_sel)) + 256;
     const size_t per = (size_t)n + 64;
     // pos/seg (x2, ping-pong), bbox 6, key x2 (u64), val x2, flag, count
-    const size_t total = 256 * 16 + temp_bytes + per * (4 * 4 + 6 * 4 + 2 * 8 + 2 * 4 + 1) + 1024;
-    GSX_CHECK(c->scratch5.reserve(total));
-    Bump bump{c->scratch5.as<char>(), total};
-    unsigned *posA = bump.take<unsigned>(per), *segA = bump.take<unsigned>(per);
-    unsigned *posB = bump.take<unsigned>(per), *segB = bump.take<unsigned>(per);
-    unsigned *bb = bump.take<unsigned>(6 * per);
-    unsigned long long *keyA = bump.take<unsigned long long>(per), *keyB = bump.take<unsigned long long>(per);
-    unsigned *valA = bump.take<unsigned>(per), *valB = bump.take<unsigned>(per);
-    uint8_t *flag = bump.take<uint8_t>(per);
-    unsigned *count = bump.take<unsigned>(64);
-    void *temp = bump.take<char>(temp_bytes);
-    if (!temp) GSX_FAIL("morton_order: scratch layout overflow");
+    unsigned *posA = nullptr, *segA = nullptr, *posB = nullptr, *segB = nullptr, *bb = nullptr, *valA = nullptr, *valB = nullptr, *count = nullptr;
+    unsigned long long *keyA = nullptr, *keyB = nullptr;
+    uint8_t *flag = nullptr;
+    void *temp = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        posA = a.take<unsigned>(per), segA = a.take<unsigned>(per);
+        posB = a.take<unsigned>(per), segB = a.take<unsigned>(per);
+        bb = a.take<unsigned>(6 * per);
+        keyA = a.take<unsigned long long>(per), keyB = a.take<unsigned long long>(per);
+        valA = a.take<unsigned>(per), valB = a.take<unsigned>(per);
+        flag = a.take<uint8_t>(per);
+        count = a.take<unsigned>(64);
+        temp = a.take<char>(temp_bytes);
+    }));
 
     hipLaunchKernelGGL(mo_iota_kernel, dim3(div_up((int64_t)n, 256)), dim3(256), 0, c->stream, order, posA, segA, n);
     unsigned m = n;

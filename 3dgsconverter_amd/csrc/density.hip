@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "gsx_common.h"
+#include "gsx_internal.h"
 
 namespace gsx {
 
@@ -331,7 +332,7 @@ static int compute_frame(gsx_ctx *c, const float *x, const float *y, const float
     return 0;
 }
 
-// ---- the voxel table of one call: keys | counts | second key word (wide) in scratch2, then room for `cap` exported entries
+// ---- the voxel table of one call: keys | counts | second key word (wide) in work_sub, then room for `cap` exported entries
 struct VoxTable {
     bool wide;
     uint64_t tsize;
@@ -351,18 +352,15 @@ static int alloc_table(gsx_ctx *c, const VoxelFrame &hvf, int64_t n_items, size_
     while (tsize < 2 * need) tsize <<= 1;
     if (tsize > (1ull << 31)) GSX_FAIL("density: too many points for the voxel table");
     t->tsize = tsize;
-    const size_t off_cnt = sizeof(unsigned long long) * tsize;
-    const size_t off_kb = off_cnt + sizeof(unsigned) * tsize;
-    size_t off_out = off_kb + (t->wide ? sizeof(unsigned) * tsize : 0);
-    off_out = (off_out + 15) & ~(size_t)15;
-    GSX_CHECK(c->scratch2.reserve(off_out + out_bytes + 64));
-    char *base = c->scratch2.as<char>();
-    t->tkeys = reinterpret_cast<unsigned long long *>(base);
-    t->tcnt = reinterpret_cast<unsigned *>(base + off_cnt);
-    t->tkb = t->wide ? reinterpret_cast<unsigned *>(base + off_kb) : nullptr;
-    t->out_base = base + off_out;
-    t->table_bytes = off_out;
-    GSX_HIP(hipMemsetAsync(base, 0, off_out, c->stream));
+    GSX_CHECK(carve(c->work_sub, [&](Carve &a) {
+        t->tkeys = a.take<unsigned long long>(tsize);
+        t->tcnt = a.take<unsigned>(tsize, 4);
+        t->tkb = t->wide ? a.take<unsigned>(tsize, 4) : nullptr;
+        t->out_base = a.take<char>(out_bytes, 16);
+        a.take<char>(64, 1);   // slack the table always had behind the callers' area; no kernel was found to read it
+    }));
+    t->table_bytes = (size_t)(t->out_base - reinterpret_cast<char *>(t->tkeys));   // one memset clears keys, counts and second words
+    GSX_HIP(hipMemsetAsync(t->tkeys, 0, t->table_bytes, c->stream));
     return 0;
 }
 
@@ -531,8 +529,8 @@ int density_voxels_dev(gsx_ctx *c, const float *x, const float *y, const float *
     if (!(voxel > 0.0f)) GSX_FAIL("density: voxel_size must be > 0");
     if (dense_cap < 0) GSX_FAIL("density: bad dense_cap");
     GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
-    GSX_CHECK(c->scratch5.reserve(sizeof(VoxelFrame) + 64));
-    VoxelFrame *dvf = c->scratch5.as<VoxelFrame>();
+    GSX_CHECK(c->work.reserve(sizeof(VoxelFrame) + 64));
+    VoxelFrame *dvf = c->work.as<VoxelFrame>();
     VoxelFrame hvf;
     GSX_CHECK(compute_frame(c, x, y, z, stride, n, voxel, dvf, &hvf));
     VoxTable t;
@@ -582,8 +580,8 @@ int density_hist_dev(gsx_ctx *c, const float *x, const float *y, const float *z,
     if (!(voxel > 0.0f)) GSX_FAIL("density: voxel_size must be > 0");
     if (cap < 1) GSX_FAIL("density: bad cap");
     GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
-    GSX_CHECK(c->scratch5.reserve(sizeof(VoxelFrame) + 64));
-    VoxelFrame *dvf = c->scratch5.as<VoxelFrame>();
+    GSX_CHECK(c->work.reserve(sizeof(VoxelFrame) + 64));
+    VoxelFrame *dvf = c->work.as<VoxelFrame>();
     VoxelFrame hvf;
     GSX_CHECK(compute_frame(c, x, y, z, stride, n, voxel, dvf, &hvf));
     VoxTable t;
@@ -656,8 +654,8 @@ int density_merge_dev(gsx_ctx *c, const int64_t *keys3_dev, const int64_t *count
     *n_unique_out = *n_dense_out = 0;
     if (m == 0) return 0;
     GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
-    GSX_CHECK(c->scratch5.reserve(64));
-    long long *mm = c->scratch5.as<long long>();
+    GSX_CHECK(c->work.reserve(64));
+    long long *mm = c->work.as<long long>();
     const long long init[6] = {0x7fffffffffffffffll, 0x7fffffffffffffffll, 0x7fffffffffffffffll,
                                -0x7fffffffffffffffll, -0x7fffffffffffffffll, -0x7fffffffffffffffll};
     GSX_HIP(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
@@ -698,8 +696,8 @@ int density_mask_dev(gsx_ctx *c, const float *x, const float *y, const float *z,
     const float voxel = (float)voxel_size;
     if (!(voxel > 0.0f)) GSX_FAIL("density: voxel_size must be > 0");
     GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
-    GSX_CHECK(c->scratch5.reserve(sizeof(VoxelFrame) + 64));
-    VoxelFrame *dvf = c->scratch5.as<VoxelFrame>();
+    GSX_CHECK(c->work.reserve(sizeof(VoxelFrame) + 64));
+    VoxelFrame *dvf = c->work.as<VoxelFrame>();
     VoxelFrame hvf;
     GSX_CHECK(compute_frame(c, x, y, z, stride, n, voxel, dvf, &hvf));
     const bool wide = hvf.ok == 2;
@@ -727,10 +725,12 @@ int density_mask_dev(gsx_ctx *c, const float *x, const float *y, const float *z,
         pa[i] = packed[i].first;
         pb[i] = packed[i].second;
     }
-    const size_t off_b = sizeof(unsigned long long) * (size_t)std::max(nk, 1);
-    GSX_CHECK(c->scratch2.reserve(off_b + sizeof(unsigned) * (size_t)std::max(nk, 1)));
-    unsigned long long *dka = c->scratch2.as<unsigned long long>();
-    unsigned *dkb = reinterpret_cast<unsigned *>(c->scratch2.as<char>() + off_b);
+    unsigned long long *dka = nullptr;
+    unsigned *dkb = nullptr;
+    GSX_CHECK(carve(c->work_sub, [&](Carve &a) {   // (sized by the frame that came back: dvf in `work` stays where it is)
+        dka = a.take<unsigned long long>((size_t)std::max(nk, 1));
+        dkb = a.take<unsigned>((size_t)std::max(nk, 1), 4);
+    }));
     if (nk) {
         GSX_HIP(hipMemcpyAsync(dka, pa.data(), sizeof(unsigned long long) * nk, hipMemcpyHostToDevice, c->stream));
         GSX_HIP(hipMemcpyAsync(dkb, pb.data(), sizeof(unsigned) * nk, hipMemcpyHostToDevice, c->stream));
@@ -1014,9 +1014,12 @@ int density_filter_dev(gsx_ctx *c, const float *x, const float *y, const float *
     const float voxel = (float)voxel_size;
     if (!(voxel > 0.0f)) GSX_FAIL("density: voxel_size must be > 0");
     GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
-    GSX_CHECK(c->scratch5.reserve(sizeof(VoxelFrame) + sizeof(ClusterOut) + 64));
-    VoxelFrame *dvf = c->scratch5.as<VoxelFrame>();
-    ClusterOut *dco = reinterpret_cast<ClusterOut *>(c->scratch5.as<char>() + 64);
+    VoxelFrame *dvf = nullptr;
+    ClusterOut *dco = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        dvf = a.take<VoxelFrame>(1);
+        dco = a.take<ClusterOut>(1, 64);
+    }));
     VoxelFrame hvf;
     bool from_box = box6 != nullptr;
     if (from_box) {
@@ -1390,13 +1393,17 @@ struct CcClock {
     }
 };
 
-// kernels 1-4 on a filled table; parent | size live in scratch3
+// kernels 1-4 on a filled table; parent | size live in work_leaf
 static int cc_components(gsx_ctx *c, const VoxelFrame &hvf, const VoxTable &t, int64_t min_points, int keep_multi, CcOut *dco,
                          unsigned **parent_out, unsigned **size_out, CcClock &clk)
 {
     const unsigned tsize = (unsigned)t.tsize;
-    GSX_CHECK(c->scratch3.reserve(2 * sizeof(unsigned) * (size_t)t.tsize + 64));
-    unsigned *parent = c->scratch3.as<unsigned>(), *size = parent + t.tsize;
+    unsigned *parent = nullptr, *size = nullptr;
+    GSX_CHECK(carve(c->work_leaf, [&](Carve &a) {
+        parent = a.take<unsigned>((size_t)t.tsize);
+        size = a.take<unsigned>((size_t)t.tsize, 4);
+        a.take<char>(64, 1);   // slack the buffer always had; no kernel was found to read it
+    }));
     const unsigned mp = (unsigned)std::min<int64_t>(std::max<int64_t>(min_points, 0), 0xffffffffll);
     const dim3 grid(blocks_for(c, (int64_t)t.tsize, 1024)), block(256);
     hipLaunchKernelGGL(cc_init_kernel, grid, block, 0, c->stream, t.tkeys, t.tcnt, tsize, mp, parent, size, dco);
@@ -1458,9 +1465,12 @@ int density_filter_large_dev(gsx_ctx *c, const float *x, const float *y, const f
     GSX_CHECK(timing_begin(c, GSX_T_DENSITY));
     CcClock clk(c);
     GSX_CHECK(clk.mark());
-    GSX_CHECK(c->scratch5.reserve(sizeof(VoxelFrame) + sizeof(CcOut) + 64));
-    VoxelFrame *dvf = c->scratch5.as<VoxelFrame>();
-    CcOut *dco = reinterpret_cast<CcOut *>(c->scratch5.as<char>() + 64);
+    VoxelFrame *dvf = nullptr;
+    CcOut *dco = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        dvf = a.take<VoxelFrame>(1);
+        dco = a.take<CcOut>(1, 64);
+    }));
     VoxelFrame hvf;
     const bool from_box = box6 != nullptr && frame_from_box(box6, voxel, &hvf);
     if (from_box)
@@ -1517,13 +1527,16 @@ int voxel_clusters_dev(gsx_ctx *c, const int64_t *keys3, int64_t m, int keep_mul
     CcClock clk(c);
     GSX_CHECK(clk.mark());
     const size_t key_bytes = sizeof(long long) * 3 * (size_t)m;
-    GSX_CHECK(c->scratch.reserve(key_bytes + 64));
-    GSX_CHECK(c->scratch4.reserve((size_t)m + 16));
-    GSX_CHECK(c->scratch5.reserve(64 + sizeof(CcOut) + 64));
-    long long *dk = c->scratch.as<long long>();
-    long long *dmin = c->scratch5.as<long long>();
-    CcOut *dco = reinterpret_cast<CcOut *>(c->scratch5.as<char>() + 64);
-    uint8_t *dkeep = c->scratch4.as<uint8_t>();
+    long long *dk = nullptr, *dmin = nullptr;
+    CcOut *dco = nullptr;
+    uint8_t *dkeep = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        dmin = a.take<long long>(3);
+        dco = a.take<CcOut>(1, 64);
+        dk = a.take<long long>(3 * (size_t)m);
+        dkeep = a.take<uint8_t>((size_t)m);
+        a.take<uint8_t>(16, 1);   // slack the keep bytes always had; no kernel was found to touch it
+    }));
     GSX_HIP(hipMemcpyAsync(dk, keys3, key_bytes, hipMemcpyHostToDevice, c->stream));
     GSX_HIP(hipMemcpyAsync(dmin, kmin, sizeof(kmin), hipMemcpyHostToDevice, c->stream));
     GSX_HIP(hipMemsetAsync(dco, 0, sizeof(CcOut), c->stream));

@@ -24,6 +24,7 @@
 
 #include "grid_policy.h"
 #include "gsx_common.h"
+#include "gsx_internal.h"
 #include "sor_grid_params.h"
 
 namespace gsx {
@@ -273,14 +274,6 @@ __global__ __launch_bounds__(256) void slab_pack_pieces_kernel(const float *__re
         o += p.count[q];
     }
 }
-
-int launch_sor_mask(gsx_ctx *ctx, const float *md, int64_t n, const float *thr_dev, uint8_t *mask);
-
-int launch_knn_slab(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride, int64_t n_own,
-                    int64_t n_halo, int k, float *mean_out, double *kth_out, const SlabKnn *sk = nullptr);
-int launch_sor_piece_sums(gsx_ctx *ctx, const float *a, int64_t n, const float *mean_dev, float *piece_out);
-int launch_sor_stats_from_pieces(gsx_ctx *ctx, const float *pieces, int64_t npieces, int64_t n_total, int mode, double factor,
-                                 float *stats_dev);
 
 }  // namespace gsx
 
@@ -576,21 +569,21 @@ static int slab_step_body(gsx_ctx *c, const float *rows_dev, int64_t n_local, in
     const float *x = rows_dev, *y = rows_dev + 1, *z = rows_dev + 2;
     // ---- 1./2. box, histogram (device-resident between them), gathered into plan_in
     const size_t plan_words = 8 + (size_t)SLAB_BINS * G;
-    GSX_CHECK(w.plan_in.reserve(4 * plan_words));
+    float *b7 = nullptr, *stats = nullptr;
+    unsigned *hist_all = nullptr, *cursor = nullptr, *unc = nullptr, *unc_total = nullptr;
+    GSX_CHECK(carve(w.plan_in, [&](Carve &a) {   // one block: it goes to the host (and to gsx_slab_plan) in one copy
+        b7 = a.take<float>(8);
+        hist_all = a.take<unsigned>((size_t)SLAB_BINS * G, 4);
+    }));
     GSX_CHECK(w.hist.reserve(4 * SLAB_BINS));
-    GSX_CHECK(w.small.reserve(1024));
-    if (w.host_cap < 4 * plan_words) {
-        if (w.host) (void)hipHostFree(w.host);
-        w.host = nullptr;
-        GSX_HIP(hipHostMalloc(&w.host, 4 * plan_words, hipHostMallocDefault));
-        w.host_cap = 4 * plan_words;
-    }
-    float *b7 = w.plan_in.as<float>();
-    unsigned *hist_all = w.plan_in.as<unsigned>() + 8;
+    GSX_CHECK(carve(w.small, [&](Carve &a) {
+        cursor = a.take<unsigned>(32);
+        unc = a.take<unsigned>(2, 8);         // right behind the cursors: slab_clear_kernel zeroes the 34 words as one run
+        unc_total = a.take<unsigned>(2, 8);   // read as one int64
+        stats = a.take<float>(4, 16);
+    }));
+    GSX_CHECK(w.host.reserve(4 * plan_words));
     unsigned *hist_mine = G > 1 ? w.hist.as<unsigned>() : hist_all;
-    unsigned *cursor = w.small.as<unsigned>();
-    unsigned *unc = cursor + 32;
-    float *stats = reinterpret_cast<float *>(cursor + 36);
     GSX_CHECK(timing_begin(c, GSX_T_SLAB_PREP));
     hipLaunchKernelGGL(slab_clear_kernel, dim3(1), dim3(256), 0, c->stream, b7, hist_mine, cursor);
     if (n_local > 0) {
@@ -616,10 +609,10 @@ static int slab_step_body(gsx_ctx *c, const float *rows_dev, int64_t n_local, in
         GSX_CHECK(gsx_comm_all_gather(c, hist_mine, hist_all, 4 * SLAB_BINS));
         GSX_CHECK(timing_end(c, GSX_T_SLAB_COLL));
     }
-    GSX_HIP(hipMemcpyAsync(w.host, w.plan_in.p, 4 * plan_words, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(hipMemcpyAsync(w.host.p, b7, 4 * plan_words, hipMemcpyDeviceToHost, c->stream));
     GSX_HIP(hipStreamSynchronize(c->stream));                                    // <- the step's host synchronisation
     gsx_slab_plan_t &p = out->plan;
-    GSX_CHECK(gsx_slab_plan(static_cast<const uint32_t *>(w.host), G, r, n_local, k, halo_cells, &p));
+    GSX_CHECK(gsx_slab_plan(static_cast<const uint32_t *>(w.host.p), G, r, n_local, k, halo_cells, &p));
     out->status = p.status;
     if (p.status != 0) return 0;
     // ---- 3. scatter into the send buffer, rows to the slab owners (own + reference-only halo) in ONE group
@@ -726,16 +719,20 @@ static int slab_step_body(gsx_ctx *c, const float *rows_dev, int64_t n_local, in
     // piece buffer: the sums, then 2 words = this rank's certificate count (even offset: 8-byte aligned)
     const int stride = ((max_pieces + 1) & ~1) + 2;
     pk.stride = stride;
-    GSX_CHECK(w.pieces.reserve(4 * (size_t)stride));
+    float *piece_sums = nullptr;
+    unsigned *piece_cert = nullptr;
+    GSX_CHECK(carve(w.pieces, [&](Carve &a) {   // one block of `stride` words: it is all-gathered in one piece
+        piece_sums = a.take<float>((size_t)stride - 2);
+        piece_cert = a.take<unsigned>(2, 8);
+    }));
     GSX_CHECK(w.allpieces.reserve(4 * (size_t)stride * G));
     GSX_CHECK(w.packed.reserve(4 * (size_t)std::max(total_pieces, 1)));
-    unsigned *unc_total = cursor + 34;
     if (n_local > 0) {   // (also hands this rank's certificate count to the tail of the piece buffer)
         GSX_CHECK(timing_begin(c, GSX_T_SLAB_PREP));
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n_local, 1024), (int64_t)c->num_cu * 8));
         const int64_t self_lo = wire ? p.own_off[r] : 0, self_hi = wire ? p.own_off[r] + p.own_cnt[r] : 0;
         hipLaunchKernelGGL(slab_unpermute_kernel, dim3(blocks), dim3(256), 0, c->stream, ret, w.send_src.as<unsigned>(), n_local, md,
-                           unc, w.pieces.as<unsigned>() + (stride - 2), self_lo, self_hi,
+                           unc, piece_cert, self_lo, self_hi,
                            w.md_slab.as<float>() + (p.r_own_off[r] - p.own_off[r]));
         GSX_HIP(hipGetLastError());
         GSX_CHECK(timing_end(c, GSX_T_SLAB_PREP));
@@ -765,12 +762,12 @@ static int slab_step_body(gsx_ctx *c, const float *rows_dev, int64_t n_local, in
     }
     for (int mode = 0; mode < 2; ++mode) {
         GSX_CHECK(timing_begin(c, GSX_T_SOR_STATS));
-        if (n_mine > 0) GSX_CHECK(launch_sor_piece_sums(c, st_in, n_mine, mode ? stats : nullptr, w.pieces.as<float>()));
+        if (n_mine > 0) GSX_CHECK(launch_sor_piece_sums(c, st_in, n_mine, mode ? stats : nullptr, piece_sums));
         GSX_CHECK(timing_end(c, GSX_T_SOR_STATS));
-        const float *pieces = w.pieces.as<float>();
+        const float *pieces = piece_sums;
         if (G > 1) {
             GSX_CHECK(timing_begin(c, GSX_T_SLAB_COLL));
-            GSX_CHECK(gsx_comm_all_gather(c, w.pieces.p, w.allpieces.p, 4 * (int64_t)stride));
+            GSX_CHECK(gsx_comm_all_gather(c, piece_sums, w.allpieces.p, 4 * (int64_t)stride));
             GSX_CHECK(timing_end(c, GSX_T_SLAB_COLL));
             hipLaunchKernelGGL(slab_pack_pieces_kernel, dim3(4), dim3(256), 0, c->stream, w.allpieces.as<float>(), pk, w.packed.as<float>(),
                                mode == 0 ? reinterpret_cast<unsigned long long *>(unc_total) : nullptr);

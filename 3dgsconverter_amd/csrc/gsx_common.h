@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/gsx_hip.h"
+#include "dev_carve.h"
 
 namespace gsx {
 
@@ -41,14 +42,33 @@ void set_error(const char *fmt, ...);
         return 1;                    \
     } while (0)
 
-// A grow-only device buffer owned by the context (no hipMalloc inside a timed step once warm).
+// A grow-only device buffer owned by the context (no hipMalloc inside a timed step once warm).  It frees its memory when it
+// dies, so a buffer added to a struct below needs no second mention anywhere; it cannot be copied (one owner).
+// reserve() frees and re-allocates on growth: every pointer into the buffer is dead after it.  A buffer of several regions is
+// therefore sized and placed by ONE carve() (dev_carve.h), never by a reserve followed by offsets.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t bytes);
     void release();
     template <class T>
     T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// DevBuf's pinned-host twin (exact size: no headroom)
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    int reserve(size_t bytes);
+    void release();
 };
 
 // Buffers of one grid-binned KNN run (sor_grid.hip).  Refinement levels > 0 re-run the pipeline on the
@@ -58,14 +78,15 @@ struct KnnWs {
     DevBuf packed;      // float4[n_ref]  (brute: original order; grid: cell-sorted refs)
     DevBuf qsorted;     // float4[q_count] cell-sorted queries when q != all refs
     DevBuf bucketpts;   // float4[n_ref] points grouped by bucket (between the two sort levels)
-    DevBuf bkcnt;       // u32 bucket sizes | starts
+    DevBuf bkcnt;       // u32 bucket sizes | starts: a block of fixed size, carved once (level_reserve) into ...
+    unsigned *bk_size = nullptr, *bk_start = nullptr;   // ... u32[MAX_BUCKETS] | u32[MAX_BUCKETS + 1]
     DevBuf tilecnt;     // u16[slot][bucket]: points of each coarse-pass tile in each bucket
     DevBuf tileoff;     // u32[slot][bucket]: where each tile's run starts inside its bucket
     DevBuf cellstart;   // u32[cap+1]
     DevBuf qcellstart;
     DevBuf gridparams;  // GridParams + work counters
     DevBuf bboxpart;    // float[7 * blocks]
-    DevBuf faillist;    // u32[q_count]
+    DevBuf faillist;    // u32[q_count] queries knn_brick could not certify | u32[q_count] knn_ring_fast's leftovers
     DevBuf extraitems;  // uint2[q_count/64 + 64]: (brick, first query) of every batch beyond a brick's first
     DevBuf finestart;   // u32[4 * cap + 1]: cell_start at quarter-cell steps along x (planned bricks only)
     DevBuf bricklist;   // uint2[n / 16 + 4096]: (bundle, first | last << 16 quarter) of every planned brick
@@ -82,13 +103,6 @@ struct KnnWs {
     DevBuf heavypart;   // double[batch * chunks * KCAP] per-chunk partial top lists
     DevBuf probe;       // u32[G^3 + 32]: density probe of a sub-cloud (counts of a coarse grid, point-weighted histogram of them)
     uint64_t refined_total = 0;  // host-side: points gathered into sub-clouds by the current call
-    void release_all()
-    {
-        DevBuf *all[] = {&packed, &qsorted, &bucketpts, &bkcnt, &tilecnt, &tileoff, &cellstart, &qcellstart, &gridparams, &bboxpart,
-                         &faillist, &extraitems, &finestart, &bricklist, &bundleoff, &wavestamps, &deferred, &cellflag, &subxyz, &submap, &submean, &subkth,
-                         &heavylist, &heavypart, &probe};
-        for (auto b : all) b->release();
-    }
 };
 
 constexpr int GSX_TREE_UNSUITABLE = 2;   // launch_knn_tree(guard = true): the cloud exhausts the key resolution, nothing was computed
@@ -109,19 +123,13 @@ struct TreeWs {
     DevBuf bboxpart;    // float[7 * blocks]
     DevBuf params;      // TreeParams
     DevBuf temp;        // rocprim temporary storage
-    void release_all()
-    {
-        DevBuf *all[] = {&keys[0], &keys[1], &vals[0], &vals[1], &refs, &samples, &blockboxes, &flags, &tilecnt, &tileoff, &leafstart, &leafbl,
-                         &faillist, &failbound, &bboxpart, &params, &temp};
-        for (auto b : all) b->release();
-    }
 };
 
 // Buffers of one multi-GPU slab step (dist_slab.hip: gsx_sor_slab_step_dev); grow-only like the rest
 struct SlabWs {
     DevBuf plan_in;    // 8 words (global box) + 4096 u32 per rank (all-gathered histograms)
     DevBuf hist;       // u32[4096]: this rank's histogram (send side of the all-gather)
-    DevBuf small;      // u32 cursor[32] | u32 uncertain[2] (all-reduced as one int64) | f32 stats[4] | i64 pack table
+    DevBuf small;      // u32 cursor[32] | u32 uncertain[2] | u32 uncertain_total[2] (one int64 each) | f32 stats[4]
     DevBuf send;       // float[3 * n_send]: rows grouped by destination slab (own rows, then halo copies)
     DevBuf send_src;   // u32[n_local]: local index of every own row of the send buffer
     DevBuf slab;       // float[3 * (n_own + n_halo)]: what this rank received
@@ -132,16 +140,7 @@ struct SlabWs {
     DevBuf md_stats;   // aligned copy for piece sums when the first own piece starts off a 16-byte boundary
     DevBuf pieces, allpieces, packed;   // numpy's 8192-element piece sums: mine | all-gathered (padded) | packed
     DevBuf mask;       // u8[n_local] when the caller brings no buffer
-    void *host = nullptr;   // pinned staging of plan_in (the step's one host synchronisation)
-    size_t host_cap = 0;
-    void release_all()
-    {
-        DevBuf *all[] = {&plan_in, &hist, &small, &send, &send_src, &slab, &md_slab, &kth, &ret, &md, &md_stats, &pieces, &allpieces, &packed, &mask};
-        for (auto b : all) b->release();
-        if (host) (void)hipHostFree(host);
-        host = nullptr;
-        host_cap = 0;
-    }
+    PinnedBuf host;    // pinned staging of plan_in (the step's one host synchronisation)
 };
 
 struct TimingSlot {
@@ -202,11 +201,37 @@ struct gsx_ctx {
     gsx::DevBuf vox_ids;     // u16[n]: dense voxel index of every point between the two passes of the density filter (density.hip)
     gsx::DevBuf nzmask;      // one 64-bit word: gsx_fields_nonzero_dev's result before it is copied out (cply.hip)
     gsx::DevBuf statspart;   // float chunk sums
-    gsx::DevBuf scratch;     // host-API staging
-    gsx::DevBuf scratch2;
-    gsx::DevBuf scratch3;
-    gsx::DevBuf scratch4;
-    gsx::DevBuf scratch5;
+    // Staging and work buffers, named by the tier of the call chain that may take them.  Two rules: the stage_* buffers are
+    // touched in api.hip only, and no function takes a buffer that a function it calls (directly or not) also takes.
+    //   buffer     taken by
+    //   stage_in   api.hip: Staging (every host-pointer entry point's uploaded inputs: xyz, data, values, keys, rows)
+    //   stage_aux  api.hip: Staging (the second device array: centroids / codebook in and out, gsx_sor_filter's distances + stats)
+    //   stage_out  api.hip: Staging (downloaded results: masks, labels, permutations, texels + uncertain bytes + lists)
+    //   work       the implementation an entry point dispatches to: kmeans_lloyd_dev, lloyd_batch_mfma (kmeans.hip),
+    //              gsx_kmeans_pp_dev, kmeans1d_dev, lexsort3_dev (sog.hip), gsx_sog_scan_dev, gsx_sog_extremes_dev,
+    //              gsx_sog_order_dev (sog_table.hip), morton_order_dev (cply.hip), gsx_rows_transform_dev, gsx_dev_patch_u8
+    //              (resident_rows.hip), and density.hip's density_voxels_dev, density_hist_dev, density_merge_dev,
+    //              density_mask_dev, density_filter_dev, density_filter_large_dev, voxel_clusters_dev (the last three end in a
+    //              retry of themselves at most once, as a tail call: nothing of the first attempt is used after it)
+    //   work_sub   helpers of those, sized by what their caller computed into `work` first: launch_assign_mfma_t (kmeans.hip),
+    //              alloc_table (density.hip: the voxel table), density_mask_dev's key list (sized after the frame came back)
+    //   work_leaf  cc_components (density.hip: parent | size of a table in work_sub)
+    // The named buffers around them belong to leaf functions that call nothing which takes a buffer:
+    //   commscratch  gsx_comm_barrier (comm.hip)
+    //   devflags     written by the pack / KNN kernels (sor_brute.hip, sor_grid.hip, sor_tree.hip) and launch_sor_stats' ticket,
+    //                read and cleared by gsx_ctx_check
+    //   vox_ids      density_filter_dev
+    //   nzmask       nzmask_word (row_tile.h), gsx_table_profile_dev, gsx_rows_take_dev
+    //   statspart    launch_sor_stats, gsx_limit_select_dev, gsx_compact_rows_dev
+    //   ksplat_keys  gsx_ksplat_centres_dev
+    //   splat_sort   gsx_splat_order_dev
+    // The KNN paths keep their own structs above (ws[], tree_ws, slab_ws); compute_frame (density.hip) borrows ws[0].bboxpart.
+    gsx::DevBuf stage_in;
+    gsx::DevBuf stage_aux;
+    gsx::DevBuf stage_out;
+    gsx::DevBuf work;
+    gsx::DevBuf work_sub;
+    gsx::DevBuf work_leaf;
     gsx::DevBuf ksplat_keys; // u32[7 * tiles]: the straddling buckets' min / max keys and NaN flags (ksplat.hip)
     gsx::DevBuf splat_sort;  // u32[n] sorted keys + rocprim temporary storage (splat.hip)
 };

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "gsx_common.h"
+#include "gsx_internal.h"
 #include "sog_math.h"
 
 namespace gsx {
@@ -936,15 +937,21 @@ static int launch_assign_mfma_t(gsx_ctx *c, const float *data, int64_t n, float 
     const unsigned P = (unsigned)nprob;
     const KmBatch kb{off_dev, n};
     const int ktiles = (k + 31) / 32;
-    const size_t opnd_bytes = sizeof(ku32x4) * (size_t)ktiles * NS * 2 * 64 * P;
     // operand words | meta (per problem 2 x 16 words, alternating by iteration) | uncertain list / permutation (n_total words)
-    // | starts (k per problem) | cursor (k per problem)
-    GSX_CHECK(c->scratch5.reserve(opnd_bytes + sizeof(unsigned) * ((size_t)KM_META_WORDS * P + (size_t)n_total + 2 * (size_t)k * P + 16)));
-    ku32x4 *opnd = c->scratch5.as<ku32x4>();
-    unsigned *meta2 = reinterpret_cast<unsigned *>(c->scratch5.as<char>() + opnd_bytes);
+    // | starts (k per problem) | cursor (k per problem).  The same layout every iteration of a run: what iteration it - 1 left
+    // in opnd and meta is read here.
+    ku32x4 *opnd = nullptr;
+    unsigned *meta2 = nullptr, *list = nullptr, *starts = nullptr, *cursor = nullptr;
+    GSX_CHECK(carve(c->work_sub, [&](Carve &a) {
+        opnd = a.take<ku32x4>((size_t)ktiles * NS * 2 * 64 * P);
+        meta2 = a.take<unsigned>((size_t)KM_META_WORDS * P, 16);
+        list = a.take<unsigned>((size_t)n_total, 4);
+        starts = a.take<unsigned>((size_t)k * P, 4);
+        cursor = a.take<unsigned>((size_t)k * P, 4);
+        a.take<unsigned>(16, 4);   // slack the buffer always had; no kernel was found to read it
+    }));
     unsigned *meta = meta2 + 16 * (it & 1);            // [0] = max |c|^2 (float bits), [1] = list length, [2] = histogram ticket
     unsigned *meta_next = meta2 + 16 * ((it + 1) & 1);
-    unsigned *list = meta2 + (size_t)KM_META_WORDS * P, *starts = list + n_total, *cursor = starts + (size_t)k * P;
     const bool fused_update = D <= 64;                 // (always: D is 9, 24 or 45)
     const int per = std::max(1, c->num_cu / nprob);    // workgroups per problem where one launch used to fill the chip
     if (it == 0 || !fused_update) {
@@ -1047,9 +1054,13 @@ int kmeans_lloyd_dev(gsx_ctx *c, const float *data_dev, int64_t n, int d, int k,
 {
     if (n <= 0 || d <= 0 || k <= 0) GSX_FAIL("kmeans: bad shape n=%lld d=%d k=%d", (long long)n, d, k);
     const size_t kd = (size_t)k * d;
-    GSX_CHECK(c->scratch3.reserve(sizeof(double) * kd + sizeof(unsigned) * (size_t)k + 64));
-    double *sums = c->scratch3.as<double>();
-    unsigned *counts = reinterpret_cast<unsigned *>(c->scratch3.as<char>() + sizeof(double) * kd);
+    double *sums = nullptr;
+    unsigned *counts = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        sums = a.take<double>(kd);
+        counts = a.take<unsigned>((size_t)k, 4);   // right behind the sums: one memset clears both
+        a.take<char>(64, 1);                       // slack the buffer always had; no kernel was found to read it
+    }));
     const int acc_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n * d, 256), (int64_t)c->num_cu * 16));
     GSX_HIP(hipMemsetAsync(sums, 0, sizeof(double) * kd + sizeof(unsigned) * (size_t)k, c->stream));
     for (int it = 0; it < max_iter; ++it) {
@@ -1069,6 +1080,33 @@ int kmeans_lloyd_dev(gsx_ctx *c, const float *data_dev, int64_t n, int d, int k,
     return 0;
 }
 
+// every iteration of ALL problems of a batch in one set of launches (kmeans_lloyd_batch_dev's matrix-core case)
+static int lloyd_batch_mfma(gsx_ctx *c, const float *data_dev, const int64_t *off_host, int nprob, int64_t n_max, int d, int k,
+                            int max_iter, float *cent_dev, int32_t *labels_dev)
+{
+    const int64_t n_total = off_host[nprob];
+    const size_t kd = (size_t)k * d * nprob, kk = (size_t)k * nprob;
+    double *sums = nullptr;
+    unsigned *counts = nullptr;
+    int64_t *off_dev = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        sums = a.take<double>(kd);
+        counts = a.take<unsigned>(kk, 4);   // right behind the sums: one memset clears both
+        off_dev = a.take<int64_t>((size_t)(nprob + 1), 64);
+        a.take<char>(64, 1);                // slack the buffer always had; no kernel was found to read it
+    }));
+    GSX_HIP(hipMemcpyAsync(off_dev, off_host, sizeof(int64_t) * (size_t)(nprob + 1), hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(hipMemsetAsync(sums, 0, sizeof(double) * kd + sizeof(unsigned) * kk, c->stream));
+    for (int it = 0; it < max_iter; ++it) {
+        GSX_CHECK(timing_begin(c, GSX_T_KMEANS_ASSIGN));
+        if (d == 9) GSX_CHECK(launch_assign_mfma_t<9>(c, data_dev, n_max, cent_dev, k, labels_dev, sums, counts, it, nprob, off_dev, n_total));
+        else if (d == 24) GSX_CHECK(launch_assign_mfma_t<24>(c, data_dev, n_max, cent_dev, k, labels_dev, sums, counts, it, nprob, off_dev, n_total));
+        else GSX_CHECK(launch_assign_mfma_t<45>(c, data_dev, n_max, cent_dev, k, labels_dev, sums, counts, it, nprob, off_dev, n_total));
+    }
+    GSX_HIP(hipStreamSynchronize(c->stream));   // off_host (the caller's, possibly pageable) must outlive its async copy
+    return 0;
+}
+
 // nprob independent problems of the same d and k, rows concatenated: problem p = rows [off[p], off[p+1]) of data_dev / labels_dev,
 // centroids p * k * d ... of cent_dev (in: init, out: result).  The matrix-core path runs every iteration of ALL problems in
 // one set of launches (launch_assign_mfma_t); other shapes run the problems one after the other -- the same kernels, launch
@@ -1083,7 +1121,6 @@ int kmeans_lloyd_batch_dev(gsx_ctx *c, const float *data_dev, const int64_t *off
         if (rows <= 0 || off_host[0] != 0) GSX_FAIL("kmeans batch: problem %d has %lld rows (offsets must start at 0 and increase)", p, (long long)rows);
         n_max = std::max(n_max, rows);
     }
-    const int64_t n_total = off_host[nprob];
     const bool batched = c->kmeans_mfma && k >= 64 && (d == 9 || d == 24 || d == 45) && nprob > 1 && nprob <= 65535;
     if (!batched) {
         for (int p = 0; p < nprob; ++p)
@@ -1115,22 +1152,7 @@ int kmeans_lloyd_batch_dev(gsx_ctx *c, const float *data_dev, const int64_t *off
         }
         if (first >= nprob) return 0;
     }
-    const size_t kd = (size_t)k * d * nprob, kk = (size_t)k * nprob;
-    const size_t off_at = (sizeof(double) * kd + sizeof(unsigned) * kk + 63) & ~(size_t)63;
-    GSX_CHECK(c->scratch3.reserve(off_at + sizeof(int64_t) * (size_t)(nprob + 1) + 64));
-    double *sums = c->scratch3.as<double>();
-    unsigned *counts = reinterpret_cast<unsigned *>(c->scratch3.as<char>() + sizeof(double) * kd);
-    int64_t *off_dev = reinterpret_cast<int64_t *>(c->scratch3.as<char>() + off_at);
-    GSX_HIP(hipMemcpyAsync(off_dev, off_host, sizeof(int64_t) * (size_t)(nprob + 1), hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(hipMemsetAsync(sums, 0, sizeof(double) * kd + sizeof(unsigned) * kk, c->stream));
-    for (int it = 0; it < max_iter; ++it) {
-        GSX_CHECK(timing_begin(c, GSX_T_KMEANS_ASSIGN));
-        if (d == 9) GSX_CHECK(launch_assign_mfma_t<9>(c, data_dev, n_max, cent_dev, k, labels_dev, sums, counts, it, nprob, off_dev, n_total));
-        else if (d == 24) GSX_CHECK(launch_assign_mfma_t<24>(c, data_dev, n_max, cent_dev, k, labels_dev, sums, counts, it, nprob, off_dev, n_total));
-        else GSX_CHECK(launch_assign_mfma_t<45>(c, data_dev, n_max, cent_dev, k, labels_dev, sums, counts, it, nprob, off_dev, n_total));
-    }
-    GSX_HIP(hipStreamSynchronize(c->stream));   // off_host (the caller's, possibly pageable) must outlive its async copy
-    return 0;
+    return lloyd_batch_mfma(c, data_dev, off_host, nprob, n_max, d, k, max_iter, cent_dev, labels_dev);
 }
 
 int quantize_dev(gsx_ctx *c, const float *vals_dev, int64_t n, const float *cb_dev, int kcb, uint8_t *out_dev)

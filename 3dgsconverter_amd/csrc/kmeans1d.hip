@@ -355,24 +355,21 @@ static int kmeans1d_dev(gsx_ctx *c, const float *vals, int64_t n, int k, int ite
     unsigned *nul = nullptr;
     if (rocprim::radix_sort_keys(nullptr, temp_bytes, nul, nul, (size_t)n, 0, 32, c->stream) != hipSuccess)
         GSX_FAIL("kmeans1d: rocprim size query failed");
-    // layout: keys A | keys B | xs | p1 | p2 | tiles (2 x (ntiles + 1)) | flags + inertia | temp
-    const size_t un = sizeof(unsigned) * (size_t)n, dn = sizeof(double) * (size_t)n;
-    const size_t bytes = 3 * un + 2 * dn + sizeof(double) * 2 * (size_t)(ntiles + 2) + 256 + temp_bytes + 1024 + sizeof(float) * 2 * K1_MAXK + 256;
-    GSX_CHECK(c->scratch5.reserve(bytes));
-    char *p = c->scratch5.as<char>();
-    auto take = [&](size_t b) {
-        char *r = p;
-        p += (b + 255) & ~(size_t)255;
-        return r;
-    };
-    unsigned *ka = reinterpret_cast<unsigned *>(take(un)), *kb = reinterpret_cast<unsigned *>(take(un));
-    float *xs = reinterpret_cast<float *>(take(un));
-    double *p1 = reinterpret_cast<double *>(take(dn)), *p2 = reinterpret_cast<double *>(take(dn));
-    double *tiles = reinterpret_cast<double *>(take(sizeof(double) * 2 * (size_t)(ntiles + 2)));
-    unsigned *flags = reinterpret_cast<unsigned *>(take(128));    // [0]: non-finite input, [8]: k1_lloyd's arrival ticket
-    double *inertia = reinterpret_cast<double *>(flags + 16);     // [3]; a start that does not run leaves its slot 0.0
-    float *cent_tmp = reinterpret_cast<float *>(take(sizeof(float) * 2 * K1_MAXK));
-    void *temp = take(temp_bytes);
+    // layout: keys A | keys B | xs | p1 | p2 | tiles (2 x (ntiles + 2)) | flags + inertia | centroids of both starts | temp
+    unsigned *ka = nullptr, *kb = nullptr, *flags = nullptr;
+    float *xs = nullptr, *cent_tmp = nullptr;
+    double *p1 = nullptr, *p2 = nullptr, *tiles = nullptr, *inertia = nullptr;
+    void *temp = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        ka = a.take<unsigned>((size_t)n), kb = a.take<unsigned>((size_t)n);
+        xs = a.take<float>((size_t)n);
+        p1 = a.take<double>((size_t)n), p2 = a.take<double>((size_t)n);
+        tiles = a.take<double>(2 * (size_t)(ntiles + 2));
+        flags = a.take<unsigned>(16);         // [0]: non-finite input, [8]: k1_lloyd's arrival ticket
+        inertia = a.take<double>(8, 8);       // [3]; a start that does not run leaves its slot 0.0 (zeroed with the flags: 128 bytes)
+        cent_tmp = a.take<float>(2 * (size_t)K1_MAXK);
+        temp = a.take<char>(temp_bytes);
+    }));
     GSX_HIP(hipMemsetAsync(flags, 0, 128, c->stream));
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n, 1024), (int64_t)c->num_cu * 8));
     hipLaunchKernelGGL(k1_keys_kernel, dim3(blocks), dim3(256), 0, c->stream, vals, n, ka, flags);

@@ -187,11 +187,15 @@ int gsx_kmeans_pp_dev(gsx_ctx *c, const float *data_dev, int64_t n, int d, int k
         if (!(uniforms_host[t] >= 0.0 && uniforms_host[t] < 1.0)) GSX_FAIL("gsx_kmeans_pp_dev: uniforms must lie in [0, 1)");
     GSX_HIP(hipSetDevice(c->device));
     const int64_t ntiles = (n + KPP_TILE - 1) / KPP_TILE;
-    GSX_CHECK(c->scratch3.reserve(sizeof(float) * (size_t)n + sizeof(double) * (size_t)ntiles * (1 + KPP_MAXL) + 1024));
-    float *mind2 = c->scratch3.as<float>();
-    double *tiles = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(mind2 + n) + 255) & ~(uintptr_t)255);
-    double *pot = tiles + ntiles;
-    int64_t *cand = reinterpret_cast<int64_t *>(pot + ntiles * KPP_MAXL);
+    float *mind2 = nullptr;
+    double *tiles = nullptr, *pot = nullptr;
+    int64_t *cand = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        mind2 = a.take<float>((size_t)n);
+        tiles = a.take<double>((size_t)ntiles);
+        pot = a.take<double>((size_t)ntiles * KPP_MAXL, 8);
+        cand = a.take<int64_t>(KPP_MAXL, 8);   // (it used to live in the buffer's 1024 bytes of slack)
+    }));
     // centroid 0: a uniformly random row
     int64_t first = (int64_t)(uniforms_host[0] * (double)n);
     if (first >= n) first = n - 1;

@@ -255,13 +255,15 @@ extern "C" int gsx_dev_patch_u8(gsx_ctx *c, uint8_t *dst_dev, int64_t dst_len, c
         if ((int64_t)idx[i] >= dst_len) GSX_FAIL("gsx_dev_patch_u8: entry %lld at byte %u of %lld", (long long)i, idx[i], (long long)dst_len);
     GSX_HIP(hipSetDevice(c->device));
     if (cnt == 0) return 0;
-    const size_t val_at = ((size_t)cnt * 4 + 15) & ~(size_t)15;
-    GSX_CHECK(c->scratch5.reserve(val_at + (size_t)cnt));
-    char *d = c->scratch5.as<char>();
-    GSX_HIP(hipMemcpyAsync(d, idx, (size_t)cnt * 4, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(hipMemcpyAsync(d + val_at, val, (size_t)cnt, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(patch_u8_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, dst_dev, dst_len,
-                       reinterpret_cast<const unsigned *>(d), reinterpret_cast<const unsigned char *>(d + val_at), cnt);
+    unsigned *d_idx = nullptr;
+    unsigned char *d_val = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        d_idx = a.take<unsigned>((size_t)cnt);
+        d_val = a.take<unsigned char>((size_t)cnt, 16);
+    }));
+    GSX_HIP(hipMemcpyAsync(d_idx, idx, (size_t)cnt * 4, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(hipMemcpyAsync(d_val, val, (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(patch_u8_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, dst_dev, dst_len, d_idx, d_val, cnt);
     GSX_HIP(hipGetLastError());
     GSX_HIP(hipStreamSynchronize(c->stream));   // (the host arrays are the caller's again)
     return 0;

@@ -71,10 +71,15 @@ static int lexsort3_dev(gsx_ctx *c, const float *k0, const float *k1, const floa
     unsigned *nul = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, temp_bytes, nul, nul, nul, nul, (size_t)n, 0, 32, c->stream) != hipSuccess)
         GSX_FAIL("lexsort: rocprim size query failed");
-    const size_t col = sizeof(unsigned) * (size_t)n;
-    GSX_CHECK(c->scratch5.reserve(4 * col + temp_bytes + 256));
-    unsigned *ka = c->scratch5.as<unsigned>(), *kb = ka + n, *va = kb + n, *vb = va + n;
-    void *temp = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(vb + n) + 255) & ~(uintptr_t)255);
+    unsigned *ka = nullptr, *kb = nullptr, *va = nullptr, *vb = nullptr;
+    void *temp = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        ka = a.take<unsigned>((size_t)n);
+        kb = a.take<unsigned>((size_t)n, 4);
+        va = a.take<unsigned>((size_t)n, 4);
+        vb = a.take<unsigned>((size_t)n, 4);
+        temp = a.take<char>(temp_bytes);
+    }));
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n, 1024), (int64_t)c->num_cu * 8));
     const float *cols[3] = {k0, k1, k2};   // least significant first, like np.lexsort's argument order
     const unsigned *perm = nullptr;

@@ -391,8 +391,9 @@ int gsx_sog_scan_dev(gsx_ctx *c, const void *rows_dev, const gsx_sog_layout *lay
     GSX_CHECK(layout_to_dev(layout, layout ? layout->n_rest : 0, &L, "gsx_sog_scan_dev"));
     if (reinterpret_cast<uintptr_t>(rows_dev) & 3) GSX_FAIL("gsx_sog_scan_dev: rows must be 4-byte aligned");
     GSX_HIP(hipSetDevice(c->device));
-    GSX_CHECK(c->scratch3.reserve(256));
-    SogScanDev *d = c->scratch3.as<SogScanDev>();
+    static_assert(sizeof(SogScanDev) <= 256, "SogScanDev outgrew its block");
+    GSX_CHECK(c->work.reserve(256));
+    SogScanDev *d = c->work.as<SogScanDev>();
     hipLaunchKernelGGL(sog_scan_init_kernel, dim3(1), dim3(64), 0, c->stream, d);
     const int64_t ntiles = (n + SOGT_ROWS - 1) / SOGT_ROWS;
     const int blocks = (int)std::min<int64_t>(ntiles, (int64_t)c->num_cu * 5);
@@ -424,10 +425,12 @@ int gsx_sog_extremes_dev(gsx_ctx *c, const uint32_t *keys3_dev, int64_t n, const
     if (!c || !keys3_dev || !lo3 || !hi3 || !vals_out || !counts6_out) GSX_FAIL("gsx_sog_extremes_dev: null argument");
     if (n <= 0 || cap < 1 || cap > (1 << 24)) GSX_FAIL("gsx_sog_extremes_dev: bad size");
     GSX_HIP(hipSetDevice(c->device));
-    const size_t list_bytes = sizeof(float) * 6 * (size_t)cap;
-    GSX_CHECK(c->scratch3.reserve(256 + list_bytes));
-    unsigned *counts = c->scratch3.as<unsigned>();
-    float *vals = reinterpret_cast<float *>(c->scratch3.as<char>() + 256);
+    unsigned *counts = nullptr;
+    float *vals = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        counts = a.take<unsigned>(8);   // six list lengths (32 bytes are zeroed)
+        vals = a.take<float>(6 * (size_t)cap);
+    }));
     GSX_HIP(hipMemsetAsync(counts, 0, 32, c->stream));
     SogExtremeArgs t;
     for (int a = 0; a < 3; ++a) {
@@ -457,10 +460,15 @@ int gsx_sog_order_dev(gsx_ctx *c, const uint32_t *keys3_dev, int64_t n, uint32_t
     unsigned *nul = nullptr;
     if (rocprim::radix_sort_pairs(nullptr, temp_bytes, nul, nul, nul, nul, (size_t)n, 0, 32, c->stream) != hipSuccess)
         GSX_FAIL("gsx_sog_order_dev: rocprim size query failed");
-    const size_t col = sizeof(unsigned) * (size_t)n;
-    GSX_CHECK(c->scratch5.reserve(4 * col + temp_bytes + 256));
-    unsigned *ka = c->scratch5.as<unsigned>(), *kb = ka + n, *va = kb + n, *vb = va + n;
-    void *temp = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(vb + n) + 255) & ~(uintptr_t)255);
+    unsigned *ka = nullptr, *kb = nullptr, *va = nullptr, *vb = nullptr;
+    void *temp = nullptr;
+    GSX_CHECK(carve(c->work, [&](Carve &a) {
+        ka = a.take<unsigned>((size_t)n);
+        kb = a.take<unsigned>((size_t)n, 4);
+        va = a.take<unsigned>((size_t)n, 4);
+        vb = a.take<unsigned>((size_t)n, 4);
+        temp = a.take<char>(temp_bytes);
+    }));
     const int blocks = stream_blocks(c, n);
     const unsigned *perm = nullptr;
     for (int pass = 0; pass < 3; ++pass) {   // np.lexsort((z, y, x)): z is the least significant key (:264)

@@ -12,6 +12,7 @@
 // rare after the first few hundred candidates.
 // Bound: FP32 VALU issue (7 lane-ops per pair), not HBM -- see DESIGN.md.
 #include "gsx_common.h"
+#include "gsx_internal.h"
 #include "knn_common.h"
 
 namespace gsx {

@@ -42,6 +42,7 @@
 
 #include "grid_policy.h"
 #include "gsx_common.h"
+#include "gsx_internal.h"
 #include "knn_common.h"
 #include "knn_mfma.h"
 #include "sor_grid_params.h"
@@ -2853,27 +2854,16 @@ static int dispatch_ring(gsx_ctx *ctx, const BrickLaunch &a)
     return launch_ring<65>(ctx, a);
 }
 
-// Multi-GPU slab: points [0, n_own) are queries, [n_own, n_own + n_halo) reference-only; kth_out (nullable) receives
-// every query's (k+1)-th squared distance so that the caller can certify it against the slab's open faces.
-int launch_knn_slab(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride, int64_t n_own,
-                    int64_t n_halo, int k, float *mean_out, double *kth_out, const SlabKnn *sk = nullptr);
-
-// csrc/sor_tree.hip: the path for clouds this grid cannot resolve
-int launch_knn_tree(gsx_ctx *ctx, const float *x, const float *y, const float *z, int64_t stride, int64_t n_ref, int64_t q_begin,
-                    int64_t q_count, int k, float *mean_out, double *kth_out, gsx_sor_info *info, int64_t ref_only_from, int share,
-                    int nshares, bool guard);
-
 // The coarse histogram of (x,y,z)[first, first+n): per-tile bucket counts, their per-bucket scans and bk_start.
 static int bin_hist(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, const float *z, int64_t stride, int64_t first,
                     int64_t n, GridParams *gp)
 {
     const BinTiles bt = BinTiles::of((int)n);
     if ((size_t)bt.slots() * MAX_BUCKETS * sizeof(unsigned) > w.tileoff.cap) GSX_FAIL("sor: bin tables not reserved for %lld points", (long long)n);
-    unsigned *bk_size = w.bkcnt.as<unsigned>();
     hipLaunchKernelGGL(bucket_hist_kernel, dim3(std::max(bt.ntiles, 1)), dim3(256), 0, ctx->stream, x, y, z, stride, (int)first, (int)n, gp,
                        w.tilecnt.as<unsigned short>());
     hipLaunchKernelGGL(bucket_offsets_kernel, dim3(MAX_BUCKETS / OFFSETS_BUCKETS), dim3(OFFSETS_THREADS), 0, ctx->stream, (int)n, gp, w.tilecnt.as<unsigned short>(),
-                       w.tileoff.as<unsigned>(), bk_size, bk_size + MAX_BUCKETS);   // its last workgroup scans the bucket sizes
+                       w.tileoff.as<unsigned>(), w.bk_size, w.bk_start);   // its last workgroup scans the bucket sizes
     GSX_HIP(hipGetLastError());
     return 0;
 }
@@ -2894,7 +2884,7 @@ static int bin_points(gsx_ctx *ctx, KnnWs &w, const float *x, const float *y, co
                       int64_t ref_only_from = INT32_MAX, bool hist_done = false, unsigned *fine = nullptr)
 {
     const bool big_path = cursor != nullptr;  // adaptive mode: oversized buckets are sorted by all workgroups
-    unsigned *bk_start = w.bkcnt.as<unsigned>() + MAX_BUCKETS;
+    unsigned *bk_start = w.bk_start;
     float4 *tmp = w.bucketpts.as<float4>();
     if (!hist_done) GSX_CHECK(bin_hist(ctx, w, x, y, z, stride, first, n, gp));
     hipLaunchKernelGGL(bucket_scatter_kernel, dim3(std::max(BinTiles::of((int)n).ntiles, 1)), dim3(SCATTER_THREADS), 0, ctx->stream, x, y, z, stride,
@@ -2953,6 +2943,7 @@ struct GridLevel {
     const float4 *qpts = nullptr;
     unsigned *rstart = nullptr;
     const unsigned *qstart = nullptr;
+    unsigned *fail = nullptr, *fail_rest = nullptr;   // the fail list | knn_ring_fast's leftovers (both regions of w.faillist)
     GridParams hgp;   // the grid parameters and counters as the host read them after knn_brick (have_hgp)
 };
 
@@ -2971,9 +2962,15 @@ static int level_reserve(GridLevel &L)
     GSX_CHECK(w.packed.reserve(sizeof(float4) * (size_t)n_ref));
     GSX_CHECK(w.bucketpts.reserve(sizeof(float4) * (size_t)n_ref));
     GSX_CHECK(w.cellstart.reserve(sizeof(unsigned) * (size_t)(cap + 1)));
-    if (!w.bkcnt.p) {  // bucket sizes | bucket starts
-        GSX_CHECK(w.bkcnt.reserve(sizeof(unsigned) * (2 * MAX_BUCKETS + 8)));
-        GSX_HIP(hipMemsetAsync(w.bkcnt.p, 0, sizeof(unsigned) * (2 * MAX_BUCKETS + 8), ctx->stream));
+    if (!w.bkcnt.p) {  // bucket sizes | bucket starts (one past the last bucket), zeroed once
+        const auto layout = [&](Carve &a) {
+            w.bk_size = a.take<unsigned>(MAX_BUCKETS);
+            w.bk_start = a.take<unsigned>(MAX_BUCKETS + 1, 4);
+            a.take<unsigned>(7, 4);   // words the block always had behind the starts; no kernel was found to touch them
+        };
+        const size_t bytes = carve_measure(layout);   // (before the carve: the layout's last pass must be the placing one)
+        GSX_CHECK(carve(w.bkcnt, layout));
+        GSX_HIP(hipMemsetAsync(w.bkcnt.p, 0, bytes, ctx->stream));
     }
     GSX_CHECK(reserve_bin_tables(w, n_ref));   // (the queries of a partial call are a subset of the refs: fewer tiles)
     if (!w.gridparams.p) {   // the arrival tickets inside must start at zero (they reset themselves afterwards)
@@ -2981,7 +2978,10 @@ static int level_reserve(GridLevel &L)
         GSX_HIP(hipMemsetAsync(w.gridparams.p, 0, sizeof(GridParams), ctx->stream));
     }
     GSX_CHECK(w.bboxpart.reserve(sizeof(float) * 7 * (size_t)L.bbox_blocks));
-    GSX_CHECK(w.faillist.reserve(sizeof(unsigned) * 2 * (size_t)std::max<int64_t>(q_count, 1)));   // fail list | knn_ring_fast's leftovers
+    GSX_CHECK(carve(w.faillist, [&](Carve &a) {
+        L.fail = a.take<unsigned>((size_t)std::max<int64_t>(q_count, 1));
+        L.fail_rest = a.take<unsigned>((size_t)std::max<int64_t>(q_count, 1), 4);   // knn_ring_fast's leftovers
+    }));
     GSX_CHECK(w.extraitems.reserve(sizeof(uint2) * (size_t)(std::max(q_count, L.slab ? n_ref : q_count) / 64 + 64)));
     if (L.adaptive) {
         GSX_CHECK(w.deferred.reserve(sizeof(unsigned) * (size_t)(cap + 64)));  // nbricks <= ncells <= cap
@@ -3053,7 +3053,7 @@ static int level_histogram(GridLevel &L, bool *done)
     if (!L.tree_ok) return 0;
     GSX_CHECK(bin_hist(ctx, w, L.x, L.y, L.z, L.stride, 0, L.n_ref, L.gp));
     static thread_local std::vector<unsigned> starts(MAX_BUCKETS + 1);
-    GSX_HIP(hipMemcpyAsync(starts.data(), w.bkcnt.as<unsigned>() + MAX_BUCKETS, sizeof(unsigned) * (MAX_BUCKETS + 1), hipMemcpyDeviceToHost, ctx->stream));
+    GSX_HIP(hipMemcpyAsync(starts.data(), w.bk_start, sizeof(unsigned) * (MAX_BUCKETS + 1), hipMemcpyDeviceToHost, ctx->stream));
     GSX_HIP(hipStreamSynchronize(ctx->stream));
     const HistVerdict v = grid_hist_verdict(starts.data(), L.n_ref, L.nshares);
     L.hist_done = true;
@@ -3330,8 +3330,7 @@ static int knn_grid_level(gsx_ctx *ctx, int level, const float *x, const float *
     int rc = level_histogram(L, &done);
     if (rc != 0 || done) return rc;
     GSX_CHECK(level_bin(L));
-    BrickLaunch a{L.gp, L.refs, L.rstart, L.qpts, L.qstart, k, q_begin, mean_out, kth_out, w.faillist.as<unsigned>(),
-                  w.faillist.as<unsigned>() + std::max<int64_t>(q_count, 1),
+    BrickLaunch a{L.gp, L.refs, L.rstart, L.qpts, L.qstart, k, q_begin, mean_out, kth_out, L.fail, L.fail_rest,
                   w.extraitems.as<uint2>(), w.deferred.as<unsigned>(), w.heavylist.as<unsigned>(), q_count, n_ref,
                   L.plan ? w.finestart.as<unsigned>() : nullptr, L.plan ? w.bricklist.as<uint2>() : nullptr};
     if (anyk) {

@@ -15,6 +15,7 @@
 // each, 16-byte loads), the 64 leaf sums combine in the balanced tree the recursion produces for 8192.  The ragged last piece is split into its (irregular) leaves by lane 0
 // and combined by the same recursion.  HBM-bound and tiny: 4 B/splat per pass, 3 passes.
 #include "gsx_common.h"
+#include "gsx_internal.h"
 
 namespace gsx {
 

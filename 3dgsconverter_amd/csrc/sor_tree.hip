@@ -44,6 +44,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gsx_common.h"
+#include "gsx_internal.h"
 #include "knn_common.h"
 #include "knn_mfma.h"
 #include "sor_grid_params.h"
@@ -1641,8 +1642,11 @@ int launch_knn_tree(gsx_ctx *ctx, const float *x, const float *y, const float *z
     GSX_CHECK(w.tileoff.reserve(sizeof(unsigned) * ((size_t)ntiles + 1)));
     GSX_CHECK(w.leafstart.reserve(sizeof(unsigned) * (n + 1)));
     GSX_CHECK(w.leafbl.reserve(n));
-    GSX_CHECK(w.faillist.reserve(sizeof(unsigned) * 2 * n));    // knn_leaf's list | knn_tree_near's leftovers
-    GSX_CHECK(w.failbound.reserve(sizeof(double) * 2 * n));
+    // knn_leaf's list | knn_tree_near's leftovers, and the bound of every entry of either
+    unsigned *fail = nullptr, *fail_rest = nullptr;
+    double *bound = nullptr, *bound_rest = nullptr;
+    GSX_CHECK(carve(w.faillist, [&](Carve &a) { fail = a.take<unsigned>(n), fail_rest = a.take<unsigned>(n, 4); }));
+    GSX_CHECK(carve(w.failbound, [&](Carve &a) { bound = a.take<double>(n), bound_rest = a.take<double>(n, 8); }));
     GSX_CHECK(w.bboxpart.reserve(sizeof(float) * 7 * (size_t)bbox_blocks));
     if (!w.params.p) {
         GSX_CHECK(w.params.reserve(sizeof(TreeParams)));
@@ -1713,12 +1717,12 @@ int launch_knn_tree(gsx_ctx *ctx, const float *x, const float *y, const float *z
     GSX_CHECK(timing_end(ctx, GSX_T_SOR_KNN));
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_FALLBACK));
     hipLaunchKernelGGL(knn_tree_near_kernel, dim3(ctx->num_cu * 6), dim3(TREE_THREADS), 0, ctx->stream, tp, k1,
-                       w.samples.as<unsigned long long>(), w.refs.as<float4>(), w.blockboxes.as<float4>(), w.faillist.as<unsigned>(),
-                       w.failbound.as<double>(), k, (int)q_begin, mean_out, kth_out, w.faillist.as<unsigned>() + n, w.failbound.as<double>() + n,
+                       w.samples.as<unsigned long long>(), w.refs.as<float4>(), w.blockboxes.as<float4>(), fail, bound, k, (int)q_begin, mean_out,
+                       kth_out, fail_rest, bound_rest,
                        ctx->tree_near_cell);
     hipLaunchKernelGGL(knn_tree_query_kernel, dim3(ctx->num_cu * 3), dim3(TREE_THREADS), 0, ctx->stream, tp, k1,
                        w.samples.as<unsigned long long>(), w.refs.as<float4>(), w.blockboxes.as<float4>(),
-                       w.faillist.as<unsigned>() + n, w.failbound.as<double>() + n, k, (int)q_begin, (int)q_count, mean_out, kth_out);
+                       fail_rest, bound_rest, k, (int)q_begin, (int)q_count, mean_out, kth_out);
     GSX_HIP(hipGetLastError());
     GSX_CHECK(timing_end(ctx, GSX_T_SOR_FALLBACK));
 

@@ -239,11 +239,11 @@ extern "C" int gsx_rows_transform_dev(gsx_ctx *c, const void *rows_dev, int64_t 
     if (n == 0) return 0;
     const int rb = (int)stride, tr = spz_tile_rows(rb);
     const int64_t tiles = (n + tr - 1) / tr;
-    GSX_CHECK(c->scratch5.reserve(sizeof(TfDev)));
-    GSX_HIP(hipMemcpyAsync(c->scratch5.p, &P, sizeof(TfDev), hipMemcpyHostToDevice, c->stream));
+    GSX_CHECK(c->work.reserve(sizeof(TfDev)));
+    GSX_HIP(hipMemcpyAsync(c->work.p, &P, sizeof(TfDev), hipMemcpyHostToDevice, c->stream));
     GSX_HIP(hipStreamSynchronize(c->stream));   // (P is this frame's)
     hipLaunchKernelGGL(rows_transform_kernel, dim3((unsigned)tiles), dim3(TF_THREADS), spz_in_bytes(tr, rb), c->stream,
-                       static_cast<const uint4 *>(rows_dev), rb, tr, first_byte, n, c->scratch5.as<unsigned>(), static_cast<unsigned char *>(out_dev));
+                       static_cast<const uint4 *>(rows_dev), rb, tr, first_byte, n, c->work.as<unsigned>(), static_cast<unsigned char *>(out_dev));
     GSX_HIP(hipGetLastError());
     return 0;
 }

@@ -425,6 +425,9 @@ SIGNATURES = {
     "gsx_rows_render_work_dev": (_I, [_P, _I64, C.c_int32, C.c_int32, C.POINTER(_I64)]),
     "gsx_rows_render_plan_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(RenderLayout), _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float)]),
     "gsx_rows_render_draw_dev": (_I, [_P, _I64, C.POINTER(RenderLayout), _P, _I64, _P, _I64, _P, C.POINTER(C.c_float)]),
+    "gsx_rows_render_score_dev": (_I, [_P, _I64, C.POINTER(RenderLayout), _P, _I64, _P, _I64, _P, _P, C.POINTER(C.c_float)]),
+    "gsx_view_keys_dev": (_I, [_P, _P, _I64, _P]),
+    "gsx_view_keys_host": (_I, [_P, _I64, _P]),
 }
 
 _lib = None
@@ -1726,6 +1729,90 @@ class ResidentRows:
         self.render_info = {"visible": visible, "instances": instances, "rows": self.n}
         return image
 
+    def view_scores_into(self, plans, peak_ptr, total_ptr, stage_ms: "dict | None" = None, ctx: "Context | None" = None) -> dict:
+        """The view scores of these rows under every plan of `plans` (views.plan_scores of this dtype, one per
+        view) ADDED into the caller's device arrays: `peak_ptr` n uint32 (float32 bits), `total_ptr` n uint64, both zeroed
+        before the first view -- the variant that leaves the scores in HBM for a chain.  Per view gsx_rows_render_plan_dev
+        and gsx_rows_render_score_dev on `ctx` (this object's own context without one).  The fixed workspace is allocated
+        once, for the largest image; the instance workspace grows to the largest view.  A view whose instances exceed its
+        plan's max_work_bytes raises render.RenderRefused before anything of that view is allocated (the arrays then hold the
+        views before it: the caller drops them).  -> dict(views, visible: per view, instances: per view, rows).  stage_ms: the
+        six RENDER_STAGES clocks summed over the views, "blend" being the score kernel's."""
+        from . import render as _render
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        plans = list(plans)
+        ctx = ctx if ctx is not None else self._ctx
+        lays = []
+        for plan in plans:
+            if np.dtype(plan.dtype) != self.dtype:
+                raise ValueError("ResidentRows.view_scores: a plan for %s, rows of %s" % (plan.dtype, self.dtype))
+            lays.append(render_layout(plan))
+        clocks = (C.c_float * len(RENDER_STAGES))() if stage_ms is not None else None
+        info = {"views": len(plans), "visible": [], "instances": [], "rows": self.n}
+        work_bytes = 0
+        for lay in lays:
+            need = C.c_int64(0)
+            check(ctx.lib.gsx_rows_render_work_dev(ctx.handle, self.n, lay.width, lay.height, C.byref(need)), "gsx_rows_render_work_dev")
+            work_bytes = max(work_bytes, int(need.value))
+        work = ctx.alloc(work_bytes) if plans else None
+        inst = None
+        try:
+            for plan, lay in zip(plans, lays):
+                words = (C.c_int64 * RENDER_INFO_WORDS)()
+                check(ctx.lib.gsx_rows_render_plan_dev(ctx.handle, self.ptr, self.first_byte, self.dtype.itemsize, self.n, C.byref(lay), work.ptr,
+                                                       work_bytes, words, clocks), "gsx_rows_render_plan_dev")
+                visible, instances, inst_bytes = int(words[1]), int(words[2]), int(words[3])
+                if words[0] != RENDER_OK or inst_bytes > plan.max_work_bytes:
+                    raise _render.RenderRefused("view %d of %d: an image of %d x %d needs %d (tile, splat) instances and %d bytes of workspace "
+                                                "for them; max_work_bytes is %d" % (len(info["visible"]) + 1, len(plans), lay.width, lay.height,
+                                                                                   instances, inst_bytes, plan.max_work_bytes))
+                if inst_bytes and (inst is None or inst.nbytes < inst_bytes):
+                    if inst is not None:
+                        inst.free()
+                        inst = None
+                    inst = ctx.alloc(inst_bytes)
+                check(ctx.lib.gsx_rows_render_score_dev(ctx.handle, self.n, C.byref(lay), work.ptr, work_bytes, inst.ptr if inst_bytes else None,
+                                                        inst.nbytes if inst_bytes else 0, peak_ptr, total_ptr, clocks),
+                      "gsx_rows_render_score_dev")
+                info["visible"].append(visible)
+                info["instances"].append(instances)
+        except BaseException:
+            try:
+                ctx.synchronize()       # (a launch before the failure may still write into what is freed next)
+            except GsxError:
+                pass
+            raise
+        finally:
+            for buf in (inst, work):
+                if buf is not None:
+                    buf.free()
+        if stage_ms is not None:
+            for name, ms in zip(RENDER_STAGES, clocks):
+                stage_ms[name] = round(stage_ms.get(name, 0.0) + float(ms), 3)
+        return info
+
+    def view_scores(self, plans, stage_ms: "dict | None" = None, ctx: "Context | None" = None):
+        """-> (peak float32[n], total uint64[n]) of these rows over the views `plans`: the largest blending weight of every row
+        and the sum of its weights in units of 2^-24 (view_scores_into on two arrays that live for the call, and one download
+        of each).  ``view_scores_info``: views, visible and instances per view, rows.  These rows stay as they are and open."""
+        if self.ptr is None:
+            raise ValueError("ResidentRows: closed")
+        ctx = ctx if ctx is not None else self._ctx
+        n = self.n
+        d_peak, d_total = ctx.alloc(max(4 * n, 16)), None
+        try:
+            d_total = ctx.alloc(max(8 * n, 16))
+            check(ctx.lib.gsx_dev_memset(ctx.handle, d_peak.ptr, 0, d_peak.nbytes), "gsx_dev_memset")
+            check(ctx.lib.gsx_dev_memset(ctx.handle, d_total.ptr, 0, d_total.nbytes), "gsx_dev_memset")
+            self.view_scores_info = self.view_scores_into(plans, d_peak.ptr, d_total.ptr, stage_ms=stage_ms, ctx=ctx)
+            with stage_clock(stage_ms, "download"):
+                return d_peak.download(np.float32, n), d_total.download(np.uint64, n)
+        finally:
+            for buf in (d_total, d_peak):
+                if buf is not None:
+                    buf.free()
+
     def profile(self) -> dict:
         """-> the profile dict of these rows: one gsx_table_profile_dev where they lie (no rows: empty_profile)"""
         if self.ptr is None:
@@ -2037,6 +2124,35 @@ def render_table(data: np.ndarray, plan, stage_ms: "dict | None" = None, device:
         return image
     finally:
         rr.close()
+
+
+def view_scores_table(data: np.ndarray, plans, stage_ms: "dict | None" = None, device: int = 0, info: "dict | None" = None):
+    """The view scores of a host table: the rows uploaded once (ResidentRows.from_host) and ResidentRows.view_scores.  data: 1-D
+    structured table of the plans' dtype; the caller's array is left alone.  -> (peak float32[n], total uint64[n]); `info`
+    receives view_scores_info.  stage_ms: upload, the RENDER_STAGES clocks, download."""
+    plans = list(plans)
+    data = np.ascontiguousarray(data)
+    if data.ndim != 1 or any(data.dtype != np.dtype(p.dtype) for p in plans):
+        raise ValueError("view_scores_table: a 1-D table of the plans' dtype")
+    require_hip()
+    with stage_clock(stage_ms, "upload"):
+        rr = ResidentRows.from_host(data, device)
+    try:
+        out = rr.view_scores(plans, stage_ms=stage_ms)
+        if info is not None:
+            info.update(rr.view_scores_info)
+        return out
+    finally:
+        rr.close()
+
+
+def view_keys_host(total: np.ndarray) -> np.ndarray:
+    """gsx_view_keys_host: the ranking keys of summed contributions (uint64) -> uint32, smallest = most visible, 0 -> 0xffffffff
+    (csrc/view_key.h, the function gsx_view_keys_dev runs).  No device is touched."""
+    total = np.ascontiguousarray(total, dtype=np.uint64)
+    keys = np.empty(total.shape, np.uint32)
+    check(load().gsx_view_keys_host(total.ctypes.data, total.size, keys.ctypes.data), "gsx_view_keys_host")
+    return keys
 
 
 def rows_decimate_table(data: np.ndarray, plan, zero_names=(), stage_ms: "dict | None" = None, device: int = 0):
@@ -4357,16 +4473,57 @@ class DeviceChain:
         finally:
             self._free(dev)
 
-    def limit_keep(self, max_count: int, columns: "np.ndarray | None" = None) -> dict:
+    def view_prune(self, plans, rows: "ResidentRows | None" = None, min_contribution: "float | None" = None,
+                   max_count: "int | None" = None, stage_ms: "dict | None" = None) -> dict:
+        """One scoring pass and what is asked of it, on a chain no filter has removed a row from: the view scores
+        of `rows` -- the resident rows the chain started from, or other rows in HBM that are the chain's table row for row --
+        over `plans` into the chain's "view_peak" and "view_total" (ResidentRows.view_scores_into on the chain's context); then
+        with `min_contribution` the rows whose peak is >= float32(min_contribution) are kept (ge_keep with the peaks as the
+        column), and with `max_count` the budget ranks what is left by that pass's totals (gsx_view_keys_dev into "limit_keys",
+        limit_keep(keys=)).  The scoring comes first and is all that can refuse (render.RenderRefused): the chain is then as it
+        was.  -> the scoring's info and never_seen (rows whose peak is 0), after_filter (rows the threshold left, None without
+        one), limit (limit_keep's dict, None without a budget)."""
+        rows = rows if rows is not None else self.resident
+        n0 = self.n0
+        if self.n != n0 or self.orig is not None or self.empty or rows is None or rows.n != n0:
+            raise ValueError("DeviceChain.view_prune: a chain that has removed no row, and rows that are its table's")
+        d_peak, d_total = self._alloc(max(4 * n0, 16), "view_peak"), self._alloc(max(8 * n0, 16), "view_total")
+        d_keys = None
+        try:
+            check(self.ctx.lib.gsx_dev_memset(self.ctx.handle, d_peak.ptr, 0, max(4 * n0, 16)), "gsx_dev_memset")
+            check(self.ctx.lib.gsx_dev_memset(self.ctx.handle, d_total.ptr, 0, max(8 * n0, 16)), "gsx_dev_memset")
+            out = rows.view_scores_into(plans, d_peak.ptr, d_total.ptr, stage_ms=stage_ms, ctx=self.ctx)
+            out["never_seen"] = int(np.count_nonzero(d_peak.download(np.uint32, n0) == 0))
+            out["after_filter"] = out["limit"] = None
+            if min_contribution is not None:
+                peaks, d_peak = d_peak, None        # (ge_keep releases its column)
+                out["after_filter"] = self.ge_keep(peaks, float(np.float32(min_contribution)))
+            if max_count is not None:
+                if limit_count(max_count) < self.n:
+                    d_keys = self._alloc(max(4 * n0, 16), "limit_keys")
+                    check(self.ctx.lib.gsx_view_keys_dev(self.ctx.handle, d_total.ptr, n0, d_keys.ptr), "gsx_view_keys_dev")
+                out["limit"] = self.limit_keep(max_count, keys=d_keys)
+            return out
+        finally:
+            for b in (d_peak, d_total, d_keys):
+                self._free(b)
+
+    def limit_keep(self, max_count: int, columns: "np.ndarray | None" = None, keys: "DeviceArray | None" = None) -> dict:
         """the splat budget (csrc/limit.hip): of the rows the chain has, the `max_count` with the smallest .splat sort keys, equal
         keys by row index, in input order.  The keys are those of EVERY row the chain started from: their (n0, 4) LIMIT_FIELDS
         gathered out of the resident rows on the device, or `columns` (limit_columns_host of the host table) uploaded once, into
         the chain's "limit_cols"; the keys go to "limit_keys" and the select reads them through the survivor list.  Both buffers
-        are released like "column".  -> dict(kept, threshold, ties_kept, threshold_key)"""
+        are released like "column".  keys: a device array of one uint32 per ORIGINAL row (the caller's: not released here), used
+        instead of the metric's keys -- gsx_view_keys_dev's for the ranking by views.  -> dict(kept, threshold, ties_kept,
+        threshold_key)"""
         max_count = limit_count(max_count)
         n0 = self.n0
         if max_count >= self.n:             # nothing to remove: no device work
             return {"kept": self.n, "threshold": None, "ties_kept": 0, "threshold_key": None}
+        if keys is not None:
+            out = limit_select_dev(self.ctx, keys.ptr, self.orig.ptr if self.orig is not None else None, self.n, max_count, self.mask.ptr)
+            out["kept"] = self._compact()
+            return out
         d_cols, d_keys = self._alloc(max(16 * n0, 16), "limit_cols"), self._alloc(max(4 * n0, 16), "limit_keys")
         try:
             rr = self.resident

@@ -8,7 +8,9 @@ the compressed-PLY chunk count from the reader's metadata.  In conversion mode t
 share one load.  ``--merge FILE`` (repeatable, with ``--merge_rotate / --merge_scale / --merge_translate`` once per file) adds
 further scenes to the input: ``Converter.run(merge=...)``.  ``--preview FILE`` (with ``--preview_size / _view / _up / _camera /
 _fov``) renders the table that was written to a PNG on the GPU: ``Converter.run(preview=...)``; it counts as an action in the
-no-op check, and the other preview flags are refused without it.
+no-op check, and the other preview flags are refused without it.  ``--min_contribution W`` and ``--rank_by views`` (with ``--views /
+--views_size / _elevation / _up`` or ``--view_camera``) score the splats by what they contribute to rendered views:
+``Converter.run(min_contribution=, rank_by=)``; both count as actions, and the other view flags are refused without one of them.
 """
 from __future__ import annotations
 
@@ -237,6 +239,21 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min_opacity", type=int, help="Drop splats whose opacity is below this value (0-255).")
     p.add_argument("--max_splats", type=int, metavar="N",
                    help="Keep at most N splats: the most visible ones by the .splat writer's metric (size times opacity), after every other filter.")
+    p.add_argument("--min_contribution", type=float, metavar="W",
+                   help="Render the scene from a ring of views and drop every splat whose largest blending weight (alpha times transmittance) "
+                        "over all pixels stays under W, between 0 and 1. Every splat that no view ever blends goes: hidden ones, splats outside "
+                        "every view, and splats with non-finite geometry. After --decimate_voxel_size, before --max_splats.")
+    p.add_argument("--rank_by", choices=("size", "views"),
+                   help="What --max_splats keeps: the largest splats by size times opacity (size, the default), or the splats the views see most, "
+                        "by summed blending weight (views). With --min_contribution both come from one scoring pass.")
+    p.add_argument("--views", type=int, metavar="N", help="Number of scoring views on a ring about the scene's bounding box, 1-1024 (default 32).")
+    p.add_argument("--views_size", nargs=2, type=int, metavar=("W", "H"), help="Scoring image size in pixels, 1-8192 per side (default 512 512).")
+    p.add_argument("--views_elevation", nargs=2, type=float, metavar=("LO", "HI"),
+                   help="Elevation band of the ring in degrees, -90 <= LO <= HI <= 90 (default -10 70).")
+    p.add_argument("--views_up", metavar="AXIS", help="Up axis of the ring: +x -x +y -y +z -z (default -y; write --views_up=-y).")
+    p.add_argument("--view_camera", action="append", nargs=6, type=float, metavar=("EX", "EY", "EZ", "TX", "TY", "TZ"),
+                   help="Score from this camera (eye and target) instead of the ring; repeatable. For inside-out captures, where outside views "
+                        "only see the backs of the walls.")
     p.add_argument("--decimate_voxel_size", type=float, metavar="H",
                    help="Replace all splats of every voxel of side H by one splat with their combined weight, mean and covariance: a lighter "
                         "scene without holes. After SOR, before --max_splats; shares its cells with --density_voxel_size.")
@@ -286,6 +303,48 @@ def check_preview_args(args):
     return None
 
 
+VIEW_OPTIONS = ("views", "views_size", "views_elevation", "views_up", "view_camera")
+
+
+def check_view_args(args):
+    """-> the error line of the first view-scoring flag that cannot be used, or None (no counterpart in the reference)"""
+    given = [name for name in VIEW_OPTIONS if getattr(args, name) is not None]
+    by_views = args.rank_by == "views"
+    if by_views and args.max_splats is None:
+        return "Error: --rank_by views ranks the splats for --max_splats N; give --max_splats too."
+    if args.min_contribution is None and not by_views:
+        return f"Error: --{given[0]} needs --min_contribution W or --rank_by views." if given else None
+    if args.info:
+        return "Error: --min_contribution and --rank_by views act on a conversion; they cannot be combined with --info."
+    if args.min_contribution is not None and not (0.0 < args.min_contribution < 1.0):
+        return f"Error: --min_contribution must be between 0 and 1 (exclusive). Got {args.min_contribution}."
+    if args.views is not None and not (1 <= args.views <= 1024):
+        return f"Error: --views must be between 1 and 1024. Got {args.views}."
+    if args.views_size is not None and not all(1 <= v <= 8192 for v in args.views_size):
+        return f"Error: --views_size must be between 1 and 8192 per side. Got {args.views_size[0]} {args.views_size[1]}."
+    if args.views_elevation is not None:
+        lo, hi = args.views_elevation
+        if not (-90.0 <= lo <= hi <= 90.0):
+            return f"Error: --views_elevation must be two angles with -90 <= LO <= HI <= 90. Got {lo} {hi}."
+    if args.views_up is not None and args.views_up.lower() not in PREVIEW_UP + ("x", "y", "z"):
+        return f"Error: --views_up must be one of {' '.join(PREVIEW_UP)}. Got {args.views_up}."
+    for c in args.view_camera or []:
+        if not all(np.isfinite(v) for v in c) or list(c[:3]) == list(c[3:]):
+            return f"Error: --view_camera must be six finite numbers with the eye apart from the target. Got {' '.join(f'{v:g}' for v in c)}."
+    if args.view_camera is not None and (args.views is not None or args.views_elevation is not None):
+        return "Error: --view_camera replaces the ring; it cannot be combined with --views or --views_elevation."
+    return None
+
+
+def view_kwargs(args) -> dict:
+    """Converter.run's view-scoring keywords: only the flags that were given"""
+    out = {name: getattr(args, name) for name in ("min_contribution", "rank_by", "views", "views_size", "views_elevation", "views_up")
+           if getattr(args, name) is not None}
+    if args.view_camera is not None:
+        out["view_cameras"] = [tuple(c) for c in args.view_camera]
+    return out
+
+
 def preview_kwargs(args) -> dict:
     """Converter.run's preview keywords: none at all without --preview, and only the flags that were given"""
     if args.preview is None:
@@ -319,7 +378,7 @@ def main(argv=None):
     if args.compression_level < 0 or args.compression_level > 9:
         print(f"Error: --compression_level must be between 0 and 9. Got {args.compression_level}.")
         return
-    preview_error = check_preview_args(args)
+    preview_error = check_preview_args(args) or check_view_args(args)
     if preview_error:
         print(preview_error)
         return
@@ -373,6 +432,7 @@ def main(argv=None):
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
                           args.rotate is not None, args.scale is not None, args.translate is not None, args.max_splats is not None,
                           args.decimate_voxel_size is not None, bool(merge_files), args.preview is not None,
+                          args.min_contribution is not None, args.rank_by == "views",
                           has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
@@ -409,7 +469,7 @@ def main(argv=None):
                       maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate,
                       max_splats=args.max_splats, **({"merge": merge_files, "merge_transforms": merge_transforms} if merge_files else {}),
                       **({"decimate_voxel_size": args.decimate_voxel_size} if args.decimate_voxel_size is not None else {}),
-                      **preview_kwargs(args))
+                      **preview_kwargs(args), **view_kwargs(args))
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

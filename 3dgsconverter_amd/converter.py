@@ -12,6 +12,7 @@ readers, filter chain and writers: a file is converted on a machine that has thi
   | (none: the reference cannot move a scene)         | run(rotate=, scale=, translate=): apply_transform before the filters|
   | :263-288 extra elements, the handler's write      | the format's write_*                                                |
   | (none: the reference renders nothing)             | run(preview=...): the written table as a PNG (_write_preview)       |
+  | (none: the reference ranks nothing by visibility) | run(min_contribution=, rank_by="views"): prune_by_views             |
 
 The decoded rows stay in HBM from the reader to the end of the run (``Converter(..., resident=True)``, the default; readers'
 ``keep=``, _lib.ResidentRows): the chain's coordinates, the alpha filter's column and the colours' f_dc are gathered from them
@@ -36,6 +37,9 @@ EXTENSIONS = {"3dgs": ".ply", "cc": ".ply", "compressed_ply": ".ply", "sog": ".s
 FORMATS_NEEDING_RGB = ["cc", "splat", "ksplat", "sogs", "sog"]                                             # :244
 EXTRA_ELEMENT_FORMATS = ["3dgs", "cc"]                                                                     # :275
 CC_MARKERS = ("property float scal_f_dc_0", "property float scalar_scal_f_dc_0", "property float scalar_f_dc_0")   # :56
+
+
+VIEW_KEYWORDS = {"views": "views", "size": "views_size", "elevation": "views_elevation", "up": "views_up", "cameras": "view_cameras"}
 
 
 def detect_format(path: str):
@@ -250,6 +254,10 @@ class Converter:
         and ``decimate_voxel_size=H``: one moment-matched splat per occupied voxel of side H (DataProcessor.decimate), applied
         after SOR and before the budget;
         and ``max_splats=N``: keep the N most visible splats (DataProcessor.limit_splats), applied after every other filter;
+        and ``min_contribution=W``: drop every splat whose largest blending weight over a ring of rendered views stays under W
+        (DataProcessor.prune_by_views), after the decimation and before the budget; ``rank_by="views"``: the budget keeps the
+        splats the views see most instead of the largest ones; both from one scoring pass, whose views are ``views=N``,
+        ``views_size=(w, h)``, ``views_elevation=(lo, hi)``, ``views_up=``, or ``view_cameras=[(ex, ey, ez, tx, ty, tz), ...]``;
         and ``merge=[path, ...]`` with ``merge_transforms=[None | {"rotate":, "scale":, "translate":}, ...]``: further sources
         whose rows follow the main source's in one table (_merge_sources), before everything else;
         and ``preview=PATH`` with ``preview_size=(w, h)``, ``preview_view=(azimuth, elevation)``, ``preview_up=``,
@@ -437,9 +445,28 @@ class Converter:
             if decimate_voxel_size is not None:
                 pbar.set_description("Decimating")
                 processor.decimate(decimate_voxel_size)
+            # the view scores follow the decimation: they belong to the geometry that is written.  With both options one scoring
+            # pass serves the threshold and the budget, which ranks the threshold's survivors
+            min_contribution, rank_by = kwargs.pop("min_contribution", None), kwargs.pop("rank_by", None)
+            view_kw = {name: kwargs.pop(key) for name, key in VIEW_KEYWORDS.items() if kwargs.get(key) is not None}
+            for key in VIEW_KEYWORDS.values():
+                kwargs.pop(key, None)
             # the splat budget is the last filter: the box that is printed and the colours belong to what is written
             max_splats = kwargs.pop("max_splats", None)
-            if max_splats is not None:
+            by_views = rank_by == "views"
+            if rank_by not in (None, "size", "views"):
+                raise ValueError(f"rank_by must be 'size' or 'views', got {rank_by!r}")
+            if by_views and max_splats is None:
+                raise ValueError("rank_by='views' ranks the rows for max_splats: give max_splats too")
+            if view_kw and min_contribution is None and not by_views:
+                raise ValueError(f"{', '.join(VIEW_KEYWORDS[k] for k in view_kw)} need min_contribution or rank_by='views'")
+            if min_contribution is not None:
+                pbar.set_description("Scoring Views")
+                processor.prune_by_views(min_contribution, max_count=max_splats if by_views else None, **view_kw)
+            elif by_views:
+                pbar.set_description("Scoring Views")
+                processor.limit_splats(max_splats, rank_by="views", **view_kw)
+            if max_splats is not None and not by_views:
                 processor.limit_splats(max_splats)
             pbar.update(10)
             if kwargs.get("auto_bbox"):

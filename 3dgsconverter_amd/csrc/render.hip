@@ -7,6 +7,8 @@
 //   gsx_rows_render_work_dev   bytes of the fixed workspace for n rows and a width x height image
 //   gsx_rows_render_plan_dev   (a) project  (b) count + scan; the one readback of the step
 //   gsx_rows_render_draw_dev   (c) emit  (d) stable order  (e) tile ranges  (f) blend
+//   gsx_rows_render_score_dev  (c) (d) (e) as above, then (g) score: what every row contributed to the pixels
+//   gsx_view_keys_dev          the ranking key of a row's summed contribution (view_key.h)
 //
 // (a) one lane per row: the eleven geometry fields and the colour source from the packed rows where they lie (any stride, any first
 //     byte) -> a record of 16 words (centre, conic, opacity, colour, depth, the pixel rectangle, visible); an invisible row's
@@ -24,6 +26,13 @@
 //     finished or outside the image adds nothing more; a wave leaves a batch and the workgroup leaves the loop when all their
 //     lanes are finished -- lanes only ever stop adding, so this is the per-pixel stop rule.
 //
+// (g) the blend's loop with the colour left out: per (pixel, splat) pair the weight alpha * T the colour sum uses.  256 lanes hold a
+//     weight for the same record at once; a wave whose ballot of contributing lanes is empty moves on, else it reduces the
+//     float bits (non-negative floats order as their bits) by max and the weights' 24-bit fixed-point truncations by sum, and
+//     its first lane adds both to the record's two LDS words.  After the batch, lane t sends record t's words on: at most
+//     one global atomicMax (u32) and one atomicAdd (u64) per (tile, record), none when the record added nothing.  Integer
+//     atomics only: the result does not depend on arrival order.
+//
 // The one shortcut: a splat with power < -5.6 is skipped without evaluating E.  E is numpy's float32 exp, within 2 ulp of the
 // nearest float32 of exp (np_exp.h: verified over all 2^32 inputs), so E(power) < exp(-5.6) (1 + 3e-7) < 0.0036980 for every such
 // power; the opacity is 1 / (1 + E(.)) <= 1 and the product is rounded once, so alpha < 0.0036981 < 1/255 = 0.0039215...: the
@@ -35,6 +44,7 @@
 
 #include "np_exp.h"
 #include "row_tile.h"
+#include "view_key.h"
 
 namespace gsx {
 
@@ -145,7 +155,8 @@ __device__ __forceinline__ void rnd_colour(const unsigned char *__restrict__ row
 {
     if (L.dc_offset[0] < 0) {
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) col[ch] = __double2float_rn(__ddiv_rn((double)rows[rb + L.rgb_offset[ch]], 255.0));
+        for (int ch = 0; ch < 3; ++ch)                                      // (rgb_offset[0] < 0: a scoring plan reads no colour)
+            col[ch] = L.rgb_offset[0] < 0 ? 0.0f : __double2float_rn(__ddiv_rn((double)rows[rb + L.rgb_offset[ch]], 255.0));
         return;
     }
     double Y[16];
@@ -393,6 +404,85 @@ __global__ __launch_bounds__(256) void rnd_blend_kernel(const uint4 *__restrict_
     }
 }
 
+// ---- (g) score
+
+constexpr float RND_SCORE_UNIT = 16777216.0f;    // 2^24: a weight in [3.9e-7, 0.99] times it truncates to an integer below 2^24
+
+__global__ __launch_bounds__(256) void rnd_score_kernel(const uint4 *__restrict__ rec, const unsigned *__restrict__ srows,
+                                                        const uint2 *__restrict__ ranges, int width, int height, int tiles_x,
+                                                        unsigned *__restrict__ peak, unsigned long long *__restrict__ total)
+{
+    __shared__ uint4 s_rec[RND_BATCH * RND_QUADS];
+    __shared__ unsigned s_peak[RND_BATCH], s_sum[RND_BATCH];     // per record of the batch: max of the float bits | sum, < 256 * 2^24
+    const int t = threadIdx.x;
+    const int tile = blockIdx.x;
+    const int px = (tile % tiles_x) * RND_TILE + (t & (RND_TILE - 1)), py = (tile / tiles_x) * RND_TILE + t / RND_TILE;
+    const float fpx = (float)px, fpy = (float)py;
+    float T = 1.0f;
+    bool done = !(px < width && py < height);
+    s_peak[t] = 0u;
+    s_sum[t] = 0u;
+    const uint2 rg = ranges[tile];
+    for (unsigned base = rg.x; base < rg.y; base += RND_BATCH) {
+        if (__syncthreads_and(done)) break;               // (also: the last batch's readers have left s_rec)
+        const int cnt = (int)min((unsigned)RND_BATCH, rg.y - base);
+        for (int q = t; q < cnt * RND_QUADS; q += 256) s_rec[q] = rec[(size_t)srows[base + (unsigned)(q / RND_QUADS)] * RND_QUADS + (q % RND_QUADS)];
+        __syncthreads();
+        for (int j = 0; j < cnt; ++j) {
+            if (__ballot(!done) == 0ull) break;           // this wave's strip is finished
+            float wgt = 0.0f;                             // (a weight that is added is >= 1/255 * 1e-4 > 0)
+            if (!done) {
+                const uint4 q2 = s_rec[j * RND_QUADS + 2], q3 = s_rec[j * RND_QUADS + 3];
+                if (!(px < (int)q2.z || px > (int)q2.w || py < (int)q3.x || py > (int)q3.y)) {
+                    const uint4 q0 = s_rec[j * RND_QUADS], q1 = s_rec[j * RND_QUADS + 1];
+                    const float dx = __fsub_rn(__uint_as_float(q0.x), fpx), dy = __fsub_rn(__uint_as_float(q0.y), fpy);
+                    const float a = __uint_as_float(q0.z), b = __uint_as_float(q0.w), c = __uint_as_float(q1.x);
+                    const float power = __fsub_rn(__fmul_rn(-0.5f, __fadd_rn(__fmul_rn(a, __fmul_rn(dx, dx)), __fmul_rn(c, __fmul_rn(dy, dy)))),
+                                                  __fmul_rn(__fmul_rn(b, dx), dy));
+                    if (power <= 0.0f && !(power < RND_POWER_CUT)) {
+                        const float alpha = fminf(RND_ALPHA_MAX, __fmul_rn(__uint_as_float(q1.y), np_expf(power)));
+                        if (!(alpha < RND_ALPHA_MIN)) {
+                            const float Tn = __fmul_rn(T, __fsub_rn(1.0f, alpha));
+                            if (Tn < RND_T_MIN) {
+                                done = true;
+                            } else {
+                                wgt = __fmul_rn(alpha, T);
+                                T = Tn;
+                            }
+                        }
+                    }
+                }
+            }
+            if (__ballot(wgt > 0.0f) == 0ull) continue;  // most records miss most strips
+            unsigned mx = __float_as_uint(wgt), sum = (unsigned)__fmul_rn(wgt, RND_SCORE_UNIT);     // 64 sums below 2^24: below 2^30
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) {
+                mx = max(mx, (unsigned)__shfl_xor((int)mx, d, 64));
+                sum += (unsigned)__shfl_xor((int)sum, d, 64);
+            }
+            if ((t & 63) == 0) {
+                atomicMax(&s_peak[j], mx);
+                atomicAdd(&s_sum[j], sum);
+            }
+        }
+        __syncthreads();
+        // lane t owns record t of the batch: it sends the words on and clears them for the next batch
+        const unsigned sum = s_sum[t];
+        if (sum) {                                        // (t < cnt: no wave wrote a word at or above cnt)
+            const unsigned row = srows[base + (unsigned)t];
+            atomicMax(&peak[row], s_peak[t]);
+            atomicAdd(&total[row], (unsigned long long)sum);
+            s_peak[t] = 0u;
+            s_sum[t] = 0u;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void view_keys_kernel(const unsigned long long *__restrict__ total, int64_t n, unsigned *__restrict__ keys)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) keys[i] = view_key_of(total[i]);
+}
+
 // the layout's refusals: every field inside a row, a degree the coefficients cover, an image and a camera the kernels can use
 static int rnd_check_layout(const gsx_render_layout *l, int64_t stride, const char *who)
 {
@@ -411,7 +501,7 @@ static int rnd_check_layout(const gsx_render_layout *l, int64_t stride, const ch
     for (int a = 0; a < 4; ++a) GSX_CHECK(inside(l->rot_offset[a], 4, "rotation", a));
     GSX_CHECK(inside(l->opacity_offset, 4, "opacity", 0));
     if (l->dc_offset[0] < 0) {
-        for (int a = 0; a < 3; ++a) GSX_CHECK(inside(l->rgb_offset[a], 1, "colour", a));
+        for (int a = 0; a < 3 && l->rgb_offset[0] >= 0; ++a) GSX_CHECK(inside(l->rgb_offset[a], 1, "colour", a));
     } else {
         const int used = (l->degree + 1) * (l->degree + 1) - 1;
         if (l->degree < 0 || l->degree > 3 || (l->rest_m != 0 && l->rest_m != 3 && l->rest_m != 8 && l->rest_m != 15) || used > l->rest_m)
@@ -467,6 +557,55 @@ static int rnd_common(gsx_ctx *c, int64_t n, const void *work_dev, const char *w
     if (!c || !work_dev) GSX_FAIL("%s: null argument", who);
     if (n < 0 || n >= (1LL << 31)) GSX_FAIL("%s: %lld rows (fewer than 2^31)", who, (long long)n);
     if (reinterpret_cast<uintptr_t>(work_dev) & 15) GSX_FAIL("%s: the workspace must be 16-byte aligned", who);
+    return 0;
+}
+
+// (c) (d) (e) of a plan, for the draw call and the score call alike: the plan's own total read again, the instance workspace
+// carved, emit, the stable sort and the tile ranges, with the clock's marks before emit and after each -> the workspace, the
+// sorted rows (null without instances) and the total
+static int rnd_order(gsx_ctx *c, int64_t n, const gsx_render_layout *layout, void *work_dev, int64_t work_bytes, void *inst_dev, int64_t inst_bytes,
+                     const char *who, RndClock *clock, RndWs *w, const unsigned **sorted_rows, unsigned long long *total_out)
+{
+    GSX_CHECK(rnd_check_layout(layout, 0, who));
+    if (reinterpret_cast<uintptr_t>(inst_dev) & 15) GSX_FAIL("%s: the instance workspace must be 16-byte aligned", who);
+    GSX_HIP(hipSetDevice(c->device));
+    const int width = layout->width, height = layout->height, tiles_x = rnd_tiles(width), tiles = tiles_x * rnd_tiles(height);
+    GSX_CHECK(rnd_carve(n, width, height, work_dev, c->stream, w));
+    if ((int64_t)w->total > work_bytes) GSX_FAIL("%s: a workspace of %lld bytes, %zu are needed", who, (long long)work_bytes, w->total);
+    // the plan's own total, read again: the launches below are sized by it, not by the caller's word
+    unsigned long long total = 0;
+    if (n > 0) {
+        GSX_HIP(hipMemcpyAsync(&total, w->offsets + n, 8, hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(hipStreamSynchronize(c->stream));
+    }
+    if (total >= (1ull << 31)) GSX_FAIL("%s: %llu instances (fewer than 2^31)", who, total);
+    RndInst inst = {};
+    if (total) {
+        GSX_CHECK(rnd_carve_inst((int64_t)total, rnd_key_bits(width, height), inst_dev, c->stream, &inst));
+        if (!inst_dev || (int64_t)inst.total > inst_bytes)
+            GSX_FAIL("%s: an instance workspace of %lld bytes, %zu are needed", who, (long long)(inst_dev ? inst_bytes : 0), inst.total);
+    }
+    GSX_HIP(hipMemsetAsync(w->ranges, 0, 8 * (size_t)tiles, c->stream));
+    GSX_CHECK(clock->mark());
+    *sorted_rows = nullptr;
+    if (total) {
+        hipLaunchKernelGGL(rnd_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, w->rec, w->offsets, n, tiles_x, inst.keys0, inst.rows0);
+        GSX_HIP(hipGetLastError());
+    }
+    GSX_CHECK(clock->mark());
+    if (total) {
+        size_t tb = inst.temp_bytes;
+        GSX_HIP(rocprim::radix_sort_pairs(inst.temp, tb, inst.keys0, inst.keys1, inst.rows0, inst.rows1, (size_t)total, 0, rnd_key_bits(width, height),
+                                          c->stream));                                                                    // stable
+        *sorted_rows = inst.rows1;
+    }
+    GSX_CHECK(clock->mark());
+    if (total) {
+        hipLaunchKernelGGL(rnd_ranges_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, inst.keys1, (int64_t)total, w->ranges);
+        GSX_HIP(hipGetLastError());
+    }
+    GSX_CHECK(clock->mark());
+    *total_out = total;
     return 0;
 }
 
@@ -543,53 +682,65 @@ int gsx_rows_render_draw_dev(gsx_ctx *c, int64_t n, const gsx_render_layout *lay
     const char *who = "gsx_rows_render_draw_dev";
     GSX_CHECK(rnd_common(c, n, work_dev, who));
     if (!image_dev) GSX_FAIL("%s: null argument", who);
-    GSX_CHECK(rnd_check_layout(layout, 0, who));
-    if (reinterpret_cast<uintptr_t>(inst_dev) & 15) GSX_FAIL("%s: the instance workspace must be 16-byte aligned", who);
-    GSX_HIP(hipSetDevice(c->device));
-    const int width = layout->width, height = layout->height, tiles_x = rnd_tiles(width), tiles = tiles_x * rnd_tiles(height);
     RndWs w;
-    GSX_CHECK(rnd_carve(n, width, height, work_dev, c->stream, &w));
-    if ((int64_t)w.total > work_bytes) GSX_FAIL("%s: a workspace of %lld bytes, %zu are needed", who, (long long)work_bytes, w.total);
-    // the plan's own total, read again: the launches below are sized by it, not by the caller's word
-    unsigned long long total = 0;
-    if (n > 0) {
-        GSX_HIP(hipMemcpyAsync(&total, w.offsets + n, 8, hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(hipStreamSynchronize(c->stream));
-    }
-    if (total >= (1ull << 31)) GSX_FAIL("%s: %llu instances (fewer than 2^31)", who, total);
-    RndInst inst = {};
-    if (total) {
-        GSX_CHECK(rnd_carve_inst((int64_t)total, rnd_key_bits(width, height), inst_dev, c->stream, &inst));
-        if (!inst_dev || (int64_t)inst.total > inst_bytes)
-            GSX_FAIL("%s: an instance workspace of %lld bytes, %zu are needed", who, (long long)(inst_dev ? inst_bytes : 0), inst.total);
-    }
     RndClock clock(stage_ms != nullptr, c->stream);
-    GSX_HIP(hipMemsetAsync(w.ranges, 0, 8 * (size_t)tiles, c->stream));
-    GSX_CHECK(clock.mark());
     const unsigned *sorted_rows = nullptr;
-    if (total) {
-        hipLaunchKernelGGL(rnd_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, w.rec, w.offsets, n, tiles_x, inst.keys0, inst.rows0);
-        GSX_HIP(hipGetLastError());
-    }
-    GSX_CHECK(clock.mark());
-    if (total) {
-        size_t tb = inst.temp_bytes;
-        GSX_HIP(rocprim::radix_sort_pairs(inst.temp, tb, inst.keys0, inst.keys1, inst.rows0, inst.rows1, (size_t)total, 0, rnd_key_bits(width, height),
-                                          c->stream));                                                                    // stable
-        sorted_rows = inst.rows1;
-    }
-    GSX_CHECK(clock.mark());
-    if (total) {
-        hipLaunchKernelGGL(rnd_ranges_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, inst.keys1, (int64_t)total, w.ranges);
-        GSX_HIP(hipGetLastError());
-    }
-    GSX_CHECK(clock.mark());
-    hipLaunchKernelGGL(rnd_blend_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, w.rec, sorted_rows, w.ranges, width, height, tiles_x,
-                       layout->background[0], layout->background[1], layout->background[2], static_cast<unsigned char *>(image_dev));
+    unsigned long long total = 0;
+    GSX_CHECK(rnd_order(c, n, layout, work_dev, work_bytes, inst_dev, inst_bytes, who, &clock, &w, &sorted_rows, &total));
+    const int tiles_x = rnd_tiles(layout->width), tiles = tiles_x * rnd_tiles(layout->height);
+    hipLaunchKernelGGL(rnd_blend_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, w.rec, sorted_rows, w.ranges, layout->width, layout->height,
+                       tiles_x, layout->background[0], layout->background[1], layout->background[2], static_cast<unsigned char *>(image_dev));
     GSX_HIP(hipGetLastError());
     GSX_CHECK(clock.mark());
     if (stage_ms) GSX_CHECK(clock.read(stage_ms + 2));
     GSX_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int gsx_rows_render_score_dev(gsx_ctx *c, int64_t n, const gsx_render_layout *layout, void *work_dev, int64_t work_bytes, void *inst_dev,
+                              int64_t inst_bytes, uint32_t *peak_dev, uint64_t *total_dev, float *stage_ms)
+{
+    const char *who = "gsx_rows_render_score_dev";
+    GSX_CHECK(rnd_common(c, n, work_dev, who));
+    if (n > 0 && (!peak_dev || !total_dev)) GSX_FAIL("%s: null argument", who);
+    if ((reinterpret_cast<uintptr_t>(peak_dev) & 3) || (reinterpret_cast<uintptr_t>(total_dev) & 7))
+        GSX_FAIL("%s: the peaks must be 4-byte aligned, the totals 8-byte aligned", who);
+    RndWs w;
+    RndClock clock(stage_ms != nullptr, c->stream);
+    const unsigned *sorted_rows = nullptr;
+    unsigned long long total = 0;
+    GSX_CHECK(rnd_order(c, n, layout, work_dev, work_bytes, inst_dev, inst_bytes, who, &clock, &w, &sorted_rows, &total));
+    if (total) {                                 // (no instance: no row is blended, nothing to add)
+        const int tiles_x = rnd_tiles(layout->width), tiles = tiles_x * rnd_tiles(layout->height);
+        hipLaunchKernelGGL(rnd_score_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, w.rec, sorted_rows, w.ranges, layout->width,
+                           layout->height, tiles_x, peak_dev, reinterpret_cast<unsigned long long *>(total_dev));
+        GSX_HIP(hipGetLastError());
+    }
+    GSX_CHECK(clock.mark());
+    if (stage_ms) GSX_CHECK(clock.read(stage_ms + 2));
+    GSX_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int gsx_view_keys_dev(gsx_ctx *c, const uint64_t *total_dev, int64_t n, uint32_t *keys_dev)
+{
+    if (!c || (n > 0 && (!total_dev || !keys_dev))) GSX_FAIL("gsx_view_keys_dev: null argument");
+    if (n < 0 || n >= (1LL << 32)) GSX_FAIL("gsx_view_keys_dev: 0 <= n < 2^32");
+    if ((reinterpret_cast<uintptr_t>(total_dev) & 7) || (reinterpret_cast<uintptr_t>(keys_dev) & 3))
+        GSX_FAIL("gsx_view_keys_dev: the totals must be 8-byte aligned, the keys 4-byte aligned");
+    GSX_HIP(hipSetDevice(c->device));
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(view_keys_kernel, dim3(tile_blocks(c, n, 1024, 8)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const unsigned long long *>(total_dev), n, keys_dev);
+    GSX_HIP(hipGetLastError());
+    return 0;
+}
+
+int gsx_view_keys_host(const uint64_t *total, int64_t n, uint32_t *keys)
+{
+    if (n > 0 && (!total || !keys)) GSX_FAIL("gsx_view_keys_host: null argument");
+    if (n < 0) GSX_FAIL("gsx_view_keys_host: n >= 0");
+    for (int64_t i = 0; i < n; ++i) keys[i] = view_key_of(total[i]);
     return 0;
 }
 

@@ -32,6 +32,7 @@ from .. import _lib
 from .. import decimate as _decimate
 from .. import render as _render
 from .. import transform as _transform
+from .. import views as _views
 from ..utils import debug_print, status_print
 from . import clusters as _clusters
 
@@ -563,14 +564,23 @@ class DataProcessor:
         return None if self.lazy else self.data
 
     # ------------------------------------------------------------------ splat budget (no counterpart in the reference)
-    def limit_splats(self, max_count):
+    def limit_splats(self, max_count, rank_by="size", **view_options):
         """Keep the `max_count` most visible splats, in input order (csrc/limit.hip).  Visibility is the .splat writer's metric,
         exp((scale_0 + scale_1) + scale_2) * (1 / (1 + exp(-opacity))) in float32 with the exp of csrc/np_exp.h; rows are ranked
         by the writer's sort key of its negative -- a NaN metric goes first, an infinite one last --, equal keys by row index.
         Refusals come before any device work: ValueError for a budget that is no integer >= 1, TypeError for a field that is
         not float32; a table without the four fields is left as it is, with a warning.  Lazy: one more step of the device
         chain (the keys from the resident rows when there are some), returns None; eager: updates and returns ``.data``.
-        ``last_limit``: the metric of the last row kept and how many rows of exactly that metric were kept."""
+        ``last_limit``: the metric of the last row kept, how many rows of exactly that metric were kept, and rank_by.
+        rank_by="views": the rows are ranked by what they contributed to a set of rendered views instead (prune_by_views'
+        scoring pass and its options views, size, elevation, up, fov, cameras, max_work_bytes: the N rows with the largest
+        summed blending weight are kept, equal sums by row index; ``last_limit["threshold"]`` is then that sum in units of
+        2^-24, rounded toward zero to float32)."""
+        _views.check_rank_by(rank_by)
+        if rank_by == "views":
+            return self._view_pass(None, max_count, view_options)
+        if view_options:
+            raise ValueError(f"limit_splats: {', '.join(sorted(view_options))} need rank_by='views'")
         debug_print(f"[DEBUG] Executing 'limit_splats' with max={max_count}")
         self._flush_rgb()
         N = _lib.limit_count(max_count)
@@ -606,8 +616,124 @@ class DataProcessor:
             res = _lib.limit_mask(_lib.limit_columns_host(data), N)
             self.data = _lib.host_compact_rows(data, res["mask"])
             kept = len(self.data)
-        self.last_limit = {"threshold": res["threshold"], "ties_kept": res["ties_kept"]}
+        self.last_limit = {"threshold": res["threshold"], "ties_kept": res["ties_kept"], "rank_by": "size"}
         status_print(f"Splat Limit (max {N}): Retained {kept} out of {n} splats.")
+        return None if self.lazy else self.data
+
+    # ------------------------------------------------------------------ view-based pruning (no counterpart in the reference)
+    def prune_by_views(self, min_contribution, views=_views.DEFAULT_VIEWS, size=_views.DEFAULT_SIZE, elevation=_views.DEFAULT_ELEVATION,
+                       up="-y", fov=50, cameras=None, max_work_bytes=_render.DEFAULT_MAX_WORK_BYTES, max_count=None):
+        """Drop what no view ever sees: the table as it stands -- the rows render_preview would render -- is rendered from
+        `views` cameras on a ring about its bounding box (views.plan_views: golden-angle azimuths, equal-area elevation bands
+        between the two `elevation` angles, each framed like the preview), or from the explicit `cameras`
+        [(ex, ey, ez, tx, ty, tz), ...], which replace the ring (the answer for inside-out captures), and every splat whose
+        largest blending weight alpha * T over all pixels of all views stays under `min_contribution` (0 < w < 1) is removed
+        (csrc/render.hip's score kernel).  EVERY row that no view blends goes -- hidden ones, rows outside every
+        image, and rows with non-finite geometry.  max_count: the budget of limit_splats(max_count, rank_by="views") applied to
+        the survivors from the same scoring pass.
+        Every refusal comes before any device work: ValueError for `views` not a whole number in 1 ... 1024, a threshold
+        outside (0, 1), elevations not -90 <= lo <= hi <= 90, and render.plan_render's (TypeError for a geometry field that is
+        not '<f4'); a table without x y z, scale_0..2, rot_0..3 or opacity is left as it is, with a warning.  A view that
+        needs more instance workspace than `max_work_bytes` prints a warning and leaves the table exactly as it was.
+        A pending survivor list and deferred fills are materialised first (in HBM when the rows are resident); the compaction
+        is one more step of the device chain, and with resident rows ``.data`` owes one download.  Lazy returns None, eager
+        updates and returns ``.data``.  ``last_view_scores``: views, visible (rows per view), never_seen, removed, rows."""
+        return self._view_pass(_views.check_min_contribution(min_contribution), max_count,
+                               dict(views=views, size=size, elevation=elevation, up=up, fov=fov, cameras=cameras, max_work_bytes=max_work_bytes))
+
+    def _settle_in_hbm(self):
+        """the pending survivor list and the deferred fills applied to the resident rows where they lie: one take into new
+        resident rows, no download -- ``.data`` owes it (the state decimate leaves).  -> False when this object has no resident
+        rows or they cannot be taken: the caller materialises on the host"""
+        if not (self.lazy and self._rr is not None) or self._pending_rgb is not None:
+            return False
+        ch, zero = self._chain, self._pending_zero
+        if not (self._compaction_pending() or zero):
+            if ch is not None and ch.orig is not None:      # (a filter ran and removed nothing: the next chain starts from no list)
+                self._chain = None
+                ch.close()
+            return True
+        taken = ch.take(zero, None, stage_ms=self.resident_ms) if ch is not None else self._rr.take(None, self._rr.n, zero, stage_ms=self.resident_ms)
+        if taken is None:
+            return False
+        self._chain, self._pending_zero = None, []
+        if ch is not None:
+            ch.close()
+        self._drop_resident()
+        self._rr, self._host_stale = taken, True
+        return True
+
+    def _view_pass(self, min_contribution, max_count, options):
+        """prune_by_views and limit_splats(rank_by="views"): one scoring pass, then the threshold on the peaks, the budget on the
+        totals, or both (DeviceChain.view_prune)"""
+        debug_print(f"[DEBUG] Executing view scoring pass (min={min_contribution}, max={max_count})")
+        self._flush_rgb()
+        N = _lib.limit_count(max_count) if max_count is not None else None
+        if not isinstance(self._data, np.ndarray) or self._data.dtype.fields is None:
+            raise TypeError("self.data must be a numpy structured array.")
+        what = "View Prune" if min_contribution is not None else "Splat Limit"
+        unknown = set(options) - {"views", "size", "elevation", "up", "fov", "cameras", "max_work_bytes"}
+        if unknown:
+            raise TypeError(f"view scores: unknown option {', '.join(sorted(unknown))}")
+        if any(nm not in self._data.dtype.names for nm in _render.GEOMETRY):
+            # (the options are still checked: a refusal does not depend on the table)
+            _views.plan_views((0, 0, 0), (0, 0, 0), **{k: v for k, v in options.items() if k != "max_work_bytes"})
+            status_print(f"Warning: View scores need x y z, scale_0..2, rot_0..3 and opacity. {what} skipped.")
+            return None if self.lazy else self.data
+        opts = dict(options)
+        budget = opts.pop("max_work_bytes", _render.DEFAULT_MAX_WORK_BYTES)
+        _views.check_options(self._data.dtype, max_work_bytes=budget, **opts)
+        head = _views.describe(opts.get("views", _views.DEFAULT_VIEWS), opts.get("size", _views.DEFAULT_SIZE), opts.get("cameras"))
+        n = len(self)
+        if n == 0:
+            status_print(f"{what} ({head}): no splats.")
+            return None if self.lazy else self.data
+        if min_contribution is None and N >= n:     # (the budget alone, and the table meets it: no scoring pass)
+            status_print(f"Splat Limit (max {N}, by {head}): {n} splats, nothing to remove.")
+            return None if self.lazy else self.data
+        # --- device work from here on
+        temp = local = None
+        try:
+            if not self._settle_in_hbm():
+                self._materialize()
+            if self.lazy and self._rr is not None:
+                rows, ch = self._rr, self._chain_for(self._data)
+                prof = rows.profile()
+            else:
+                data = self.data
+                prof = _lib.host_table_profile(data)
+                temp = rows = _lib.ResidentRows.from_host(data)
+                ch = self._chain_for(data) if self.lazy else _lib.DeviceChain(table=data)
+                local = None if self.lazy else ch
+            plans = [_views.plan_scores(self._data.dtype, cam, budget) for cam in _views.plan_views(prof["lo"], prof["hi"], **opts)]
+            try:
+                res = ch.view_prune(plans, rows, min_contribution, N, stage_ms=self.resident_ms)
+            except _render.RenderRefused as e:
+                status_print(f"Warning: {what} skipped, the table is unchanged: {e}")
+                return None if self.lazy else self.data
+            if local is not None:
+                if local.n != local.n0:
+                    self.data = _lib.host_take_rows(self._data, local.survivors())
+        finally:
+            if temp is not None:
+                temp.close()
+            if local is not None:
+                local.close()
+        kept = len(self)
+        self.last_view_scores = {"views": res["views"], "visible": list(res["visible"]), "never_seen": res["never_seen"], "removed": n - kept,
+                                 "rows": n}
+        if min_contribution is not None:
+            status_print(f"View Prune ({head}, min {min_contribution:g}): Retained {res['after_filter']} out of {n} splats "
+                         f"({res['never_seen']} never seen).")
+        if N is not None:
+            lim = res["limit"]
+            thr = None if lim["threshold_key"] is None else np.array([0xffffffff - lim["threshold_key"]], np.uint32).view(np.float32)[0]
+            self.last_limit = {"threshold": thr, "ties_kept": lim["ties_kept"], "rank_by": "views"}
+            before = res["after_filter"] if res["after_filter"] is not None else n
+            if lim["threshold_key"] is None:
+                status_print(f"Splat Limit (max {N}, by {head}): {before} splats, nothing to remove.")
+            else:
+                status_print(f"Splat Limit (max {N}, by {head}): Retained {lim['kept']} out of {before} splats.")
         return None if self.lazy else self.data
 
     # ------------------------------------------------------------------ voxel decimation (no counterpart in the reference)

@@ -161,13 +161,15 @@ class RenderPlan:
         self.max_work_bytes = DEFAULT_MAX_WORK_BYTES
 
 
-def plan_render(dtype, camera, sh_degree=None, background=(0, 0, 0), max_work_bytes=DEFAULT_MAX_WORK_BYTES) -> RenderPlan:
+def plan_render(dtype, camera, sh_degree=None, background=(0, 0, 0), max_work_bytes=DEFAULT_MAX_WORK_BYTES, colour=True) -> RenderPlan:
     """The rendering of a table of `dtype` through `camera` (a Camera).  sh_degree caps the SH degree the table carries (45 / 24
     / 9 / 0 f_rest fields: 3 / 2 / 1 / 0; channel c, coefficient k is f_rest_(c m + k) as in transform.plan_transform);
     background: three numbers in 0 ... 1.  Every refusal is raised here, before any device work: ValueError for a missing
     geometry field, no colour source (f_dc_0..2, or red green blue as u1), f_rest fields that are no whole bands of three
     channels, rows above 512 bytes, an image side outside 1 ... 8192, a camera whose numbers are not finite or whose near is
-    not above 0; TypeError, naming the field, for a field the kernels read as float32 that is not '<f4' (no silent casts)."""
+    not above 0; TypeError, naming the field, for a field the kernels read as float32 that is not '<f4' (no silent casts).
+    colour=False: a plan of the geometry alone, for the view scores (views.plan_scores) -- no colour field is asked for or
+    read, ``dc`` and ``rgb`` stay (-1, -1, -1)."""
     dtype = np.dtype(dtype)
     fields = dtype.fields or {}
     p = RenderPlan()
@@ -175,9 +177,9 @@ def plan_render(dtype, camera, sh_degree=None, background=(0, 0, 0), max_work_by
     for nm in GEOMETRY:
         if nm not in fields:
             raise ValueError(f"render: the table has no field {nm!r}; x y z, scale_0..2, rot_0..3 and opacity are needed")
-    has_dc = all(nm in fields for nm in DC)
-    has_rgb = all(nm in fields and fields[nm][0] == np.dtype("u1") for nm in RGB)
-    if not has_dc and not has_rgb:
+    has_dc = bool(colour) and all(nm in fields for nm in DC)
+    has_rgb = bool(colour) and all(nm in fields and fields[nm][0] == np.dtype("u1") for nm in RGB)
+    if colour and not has_dc and not has_rgb:
         raise ValueError("render: the table has no colour source: f_dc_0..2, or red green blue as unsigned bytes, are needed")
     if not 1 <= dtype.itemsize <= MAX_ROW_BYTES:
         raise ValueError(f"render: rows of {dtype.itemsize} bytes (1 ... {MAX_ROW_BYTES} are supported)")
@@ -221,7 +223,7 @@ def plan_render(dtype, camera, sh_degree=None, background=(0, 0, 0), max_work_by
     if has_dc:
         p.dc = off(DC)
         p.rest = tuple(int(fields[f"f_rest_{i}"][1]) for i in range(3 * p.m))
-    else:
+    elif has_rgb:
         p.rgb = off(RGB)
     p.background, p.max_work_bytes = bg, int(max_work_bytes)
     return p

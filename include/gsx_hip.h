@@ -1324,6 +1324,29 @@ int gsx_rows_render_plan_dev(gsx_ctx *ctx, const void *rows_dev, int64_t first_b
 int gsx_rows_render_draw_dev(gsx_ctx *ctx, int64_t n, const gsx_render_layout *layout, void *work_dev, int64_t work_bytes, void *inst_dev,
                              int64_t inst_bytes, void *image_dev, float *stage_ms);
 
+/* ---- view scores: what every row contributed to the pixels of a view (csrc/render.hip) ----
+ * The definition is tests/view_scores_numpy.py, a twin of the image's loop: for every (pixel, splat) pair the blend adds, the
+ * float32 weight wgt = alpha * T the colour sum uses.  peak[row] = max(peak[row], wgt) as float32 bits (non-negative floats order
+ * as their bit patterns), total[row] += (uint64)(wgt * 2^24) -- an exact truncation to an integer below 2^24.  Integer atomics
+ * only: the two arrays are the definition's bits on every run, whatever the order the tiles arrive in.
+ *
+ * Runs after gsx_rows_render_plan_dev, in place of the draw call and with its arguments: the same emit, stable sort and tile
+ * ranges, then the score kernel -- one workgroup per tile, one pixel per lane, the blend's tests and early exits; the weights of
+ * a record are reduced inside each wave, combined per batch in LDS, and leave as at most one atomicMax and one atomicAdd per
+ * (tile, record).  ADDS into peak_dev (n uint32) and total_dev (n uint64, 8-byte aligned): the caller zeroes both before the
+ * first view, and after the last they hold the maximum and the sum over the views.  No image is written; a plan without
+ * instances launches nothing.  A layout whose dc_offset[0] and rgb_offset[0] are both -1 reads no colour (the records' are 0).
+ * stage_ms: the clocks of emit, sort, ranges and score are ADDED to entries 2 ... 5.  Synchronises the context's stream. */
+int gsx_rows_render_score_dev(gsx_ctx *ctx, int64_t n, const gsx_render_layout *layout, void *work_dev, int64_t work_bytes, void *inst_dev,
+                              int64_t inst_bytes, uint32_t *peak_dev, uint64_t *total_dev, float *stage_ms);
+/* The ranking key of a summed contribution for gsx_limit_select_*: keys[i] = 0xffffffff - fbits(total[i]), fbits the bit pattern
+ * of total converted to float32 rounding toward zero, computed in integers (csrc/view_key.h): 0 for 0, else with
+ * e = bit_length(total) - 1 and m = total >> (e - 23) (e >= 23) or total << (23 - e): ((e + 127) << 23) | (m & 0x7fffff).  The most
+ * visible row has the smallest key, a row no view blended 0xffffffff.  One launch.  Asynchronous. */
+int gsx_view_keys_dev(gsx_ctx *ctx, const uint64_t *total_dev, int64_t n, uint32_t *keys_dev);
+/* the same on the HOST, from the same function; HOST pointers, serial. */
+int gsx_view_keys_host(const uint64_t *total, int64_t n, uint32_t *keys);
+
 #ifdef __cplusplus
 }
 #endif

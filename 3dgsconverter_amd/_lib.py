@@ -243,6 +243,8 @@ class RenderLayout(C.Structure):
                 ("tan_fovx", C.c_double), ("tan_fovy", C.c_double), ("near", C.c_double), ("background", C.c_float * 3)]
 
 
+FIDELITY_WORDS, FIDELITY_TILE, FIDELITY_MAX_SIDE = 9, 32, 8192            # GSX_FIDELITY_*
+
 DENSITY_OK, DENSITY_EMPTY, DENSITY_HOST = range(3)
 DENSITY_STAGES = ("table", "init", "hook", "flatten", "reduce", "membership")   # GSX_DENSITY_STAGES
 SLAB_OK, SLAB_EMPTY, SLAB_NONFINITE, SLAB_SMALL_SHARD, SLAB_NO_STRUCTURE = range(5)
@@ -426,6 +428,8 @@ SIGNATURES = {
     "gsx_rows_render_plan_dev": (_I, [_P, _P, _I64, _I64, _I64, C.POINTER(RenderLayout), _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float)]),
     "gsx_rows_render_draw_dev": (_I, [_P, _I64, C.POINTER(RenderLayout), _P, _I64, _P, _I64, _P, C.POINTER(C.c_float)]),
     "gsx_rows_render_score_dev": (_I, [_P, _I64, C.POINTER(RenderLayout), _P, _I64, _P, _I64, _P, _P, C.POINTER(C.c_float)]),
+    "gsx_image_compare_dev": (_I, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(_I64), C.POINTER(C.c_float)]),
+    "gsx_image_compare_host": (_I, [_P, _P, C.c_int32, C.c_int32, C.POINTER(_I64)]),
     "gsx_view_keys_dev": (_I, [_P, _P, _I64, _P]),
     "gsx_view_keys_host": (_I, [_P, _I64, _P]),
 }
@@ -1697,6 +1701,21 @@ class ResidentRows:
         above plan.max_work_bytes raises render.RenderRefused, naming the image size and the instance count, before that
         workspace or the image is allocated.  ``render_info``: visible, instances, rows.  stage_ms: the six RENDER_STAGES
         clocks, joined, and "download".  These rows stay as they are and open."""
+        ctx = ctx if ctx is not None else self._ctx
+        image_dev = self.render_dev(plan, ctx=ctx, stage_ms=stage_ms)
+        try:
+            cam = plan.camera
+            with stage_clock(stage_ms, "download"):
+                image = image_dev.download(np.uint8, cam.width * cam.height * 3).reshape(cam.height, cam.width, 3)
+        finally:
+            image_dev.free()
+        return image
+
+    def render_dev(self, plan, ctx: "Context | None" = None, stage_ms: "dict | None" = None) -> "DeviceArray":
+        """render() up to and including gsx_rows_render_draw_dev, without the download: -> the image where the rasteriser left
+        it, height * width * 3 bytes of HBM allocated on `ctx` (this object's own context without one), which the caller frees
+        (``.free()``) -- for a consumer on the device (fidelity.compare_rows).  The workspaces live for the call; the refusal,
+        ``render_info`` and the six RENDER_STAGES clocks are render()'s.  These rows stay as they are and open."""
         from . import render as _render
         ctx = ctx if ctx is not None else self._ctx
         clocks = (C.c_float * len(RENDER_STAGES))() if stage_ms is not None else None
@@ -1711,23 +1730,23 @@ class ResidentRows:
             image_dev = ctx.alloc(lay.width * lay.height * 3)
             check(ctx.lib.gsx_rows_render_draw_dev(ctx.handle, self.n, C.byref(lay), work.ptr, work_bytes, inst.ptr if inst else None, inst_bytes,
                                                    image_dev.ptr, clocks), "gsx_rows_render_draw_dev")
-            with stage_clock(stage_ms, "download"):
-                image = image_dev.download(np.uint8, lay.width * lay.height * 3).reshape(lay.height, lay.width, 3)
         except BaseException:
             try:
                 ctx.synchronize()       # (a launch before the failure may still write into what is freed next)
             except GsxError:
                 pass
+            if image_dev is not None:
+                image_dev.free()
             raise
         finally:
-            for buf in (image_dev, inst, work):
+            for buf in (inst, work):
                 if buf is not None:
                     buf.free()
         if stage_ms is not None:
             for name, ms in zip(RENDER_STAGES, clocks):
                 stage_ms[name] = round(stage_ms.get(name, 0.0) + float(ms), 3)
         self.render_info = {"visible": visible, "instances": instances, "rows": self.n}
-        return image
+        return image_dev
 
     def view_scores_into(self, plans, peak_ptr, total_ptr, stage_ms: "dict | None" = None, ctx: "Context | None" = None) -> dict:
         """The view scores of these rows under every plan of `plans` (views.plan_scores of this dtype, one per
@@ -2153,6 +2172,64 @@ def view_keys_host(total: np.ndarray) -> np.ndarray:
     keys = np.empty(total.shape, np.uint32)
     check(load().gsx_view_keys_host(total.ctypes.data, total.size, keys.ctypes.data), "gsx_view_keys_host")
     return keys
+
+
+def image_compare_words(words) -> dict:
+    """the nine words of gsx_image_compare_* -> dict(sse: three ints, windows, ssim: three ints -- the sums of the windows' 32.32
+    fixed-point values), Python ints throughout"""
+    w = [int(v) for v in words]
+    return {"sse": tuple(w[0:3]), "windows": w[3], "ssim": tuple(w[4:7])}
+
+
+def _image_pair(a, b, who: str):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
+        raise ValueError("%s: two (height, width, 3) uint8 images of the same size" % who)
+    h, w = a.shape[:2]
+    if not (1 <= h <= FIDELITY_MAX_SIDE and 1 <= w <= FIDELITY_MAX_SIDE):
+        raise ValueError("%s: an image of %d x %d (1 ... %d per side)" % (who, w, h, FIDELITY_MAX_SIDE))
+    return a, b, w, h
+
+
+def image_compare_dev(ctx: "Context", a_ptr: int, b_ptr: int, width: int, height: int, stage_ms: "dict | None" = None) -> dict:
+    """gsx_image_compare_dev on two images that lie in HBM (height * width * 3 bytes each) -> image_compare_words.
+    stage_ms["compare"]: the launch's stream clock, added."""
+    words = (C.c_int64 * FIDELITY_WORDS)()
+    clock = C.c_float(0.0) if stage_ms is not None else None
+    check(ctx.lib.gsx_image_compare_dev(ctx.handle, a_ptr, b_ptr, int(width), int(height), words, C.byref(clock) if clock is not None else None),
+          "gsx_image_compare_dev")
+    if stage_ms is not None:
+        stage_ms["compare"] = round(stage_ms.get("compare", 0.0) + float(clock.value), 3)
+    return image_compare_words(words)
+
+
+def image_compare(a: np.ndarray, b: np.ndarray, ctx: "Context | None" = None) -> dict:
+    """The fidelity sums of two host images: both uploaded, one gsx_image_compare_dev on `ctx` (a context that
+    lives for the call without one) -> dict(sse, windows, ssim).  For tests and small uses; fidelity.compare_rows compares
+    images where the rasteriser left them."""
+    a, b, w, h = _image_pair(a, b, "image_compare")
+    require_hip()
+    own = ctx is None
+    ctx = Context() if own else ctx
+    bufs = []
+    try:
+        for img in (a, b):
+            bufs.append(ctx.alloc(img.nbytes))
+            bufs[-1].upload(img)
+        return image_compare_dev(ctx, bufs[0].ptr, bufs[1].ptr, w, h)
+    finally:
+        for buf in bufs:
+            buf.free()
+        if own:
+            ctx.close()
+
+
+def image_compare_host(a: np.ndarray, b: np.ndarray) -> dict:
+    """gsx_image_compare_host: the same sums from the same per-window function on the host.  No device is touched."""
+    a, b, w, h = _image_pair(a, b, "image_compare_host")
+    words = (C.c_int64 * FIDELITY_WORDS)()
+    check(load().gsx_image_compare_host(a.ctypes.data, b.ctypes.data, w, h, words), "gsx_image_compare_host")
+    return image_compare_words(words)
 
 
 def rows_decimate_table(data: np.ndarray, plan, zero_names=(), stage_ms: "dict | None" = None, device: int = 0):

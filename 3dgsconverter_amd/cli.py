@@ -11,6 +11,10 @@ _fov``) renders the table that was written to a PNG on the GPU: ``Converter.run(
 no-op check, and the other preview flags are refused without it.  ``--min_contribution W`` and ``--rank_by views`` (with ``--views /
 --views_size / _elevation / _up`` or ``--view_camera``) score the splats by what they contribute to rendered views:
 ``Converter.run(min_contribution=, rank_by=)``; both count as actions, and the other view flags are refused without one of them.
+``--fidelity [written|source]`` (with ``--fidelity_views / _size / _up / _image`` or ``--fidelity_camera``) reads the output file
+back and reports its PSNR and SSIM over a ring of rendered views against the table that was written (the format's loss) or
+against the moved source (everything the run did): ``Converter.run(fidelity=...)``; it counts as an action, and the other fidelity
+flags are refused without it.
 """
 from __future__ import annotations
 
@@ -267,6 +271,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--preview_camera", nargs=6, type=float, metavar=("EX", "EY", "EZ", "TX", "TY", "TZ"),
                    help="Preview camera given as eye and target points instead of --preview_view.")
     p.add_argument("--preview_fov", type=float, metavar="DEG", help="Preview vertical field of view in degrees, between 0 and 170 (default 50).")
+    p.add_argument("--fidelity", nargs="?", const="written", choices=("written", "source"), metavar="written|source",
+                   help="After the conversion, read the output file back and report PSNR and SSIM of its rendering over a ring of views: against "
+                        "the table that was written (written, the default: the target format's loss alone) or against the input file moved by "
+                        "--rotate / --scale / --translate (source: filters, decimation, budget, SH reduction and format together).")
+    p.add_argument("--fidelity_views", type=int, metavar="N", help="Number of fidelity views on a ring about the reference's bounding box, 1-1024 (default 8).")
+    p.add_argument("--fidelity_size", nargs=2, type=int, metavar=("W", "H"), help="Fidelity image size in pixels, 1-8192 per side (default 512 512).")
+    p.add_argument("--fidelity_up", metavar="AXIS", help="Up axis of the fidelity ring: +x -x +y -y +z -z (default -y; write --fidelity_up=-y).")
+    p.add_argument("--fidelity_camera", action="append", nargs=6, type=float, metavar=("EX", "EY", "EZ", "TX", "TY", "TZ"),
+                   help="Measure from this camera (eye and target) instead of the ring; repeatable.")
+    p.add_argument("--fidelity_image", metavar="FILE",
+                   help="Save the worst view as one PNG: the reference, the output file and four times their difference side by side.")
     p.add_argument("--keep_multicluster", action="store_true", help="Density filter: keep every dense cluster, not only the largest.")
     p.add_argument("--compression_level", type=int, default=0,
                    help="0-9, per format: .ksplat 0 = float32, 1 = float16 blocks, 2+ = 8-bit SH; .spz the gzip level; .sog the palette size.")
@@ -336,6 +351,45 @@ def check_view_args(args):
     return None
 
 
+FIDELITY_OPTIONS = ("fidelity_views", "fidelity_size", "fidelity_up", "fidelity_camera", "fidelity_image")
+
+
+def check_fidelity_args(args):
+    """-> the error line of the first fidelity flag that cannot be used, or None (no counterpart in the reference)"""
+    given = [name for name in FIDELITY_OPTIONS if getattr(args, name) is not None]
+    if args.fidelity is None:
+        return f"Error: --{given[0]} needs --fidelity." if given else None
+    if args.info:
+        return "Error: --fidelity measures a conversion's result; it cannot be combined with --info."
+    if args.fidelity == "source" and args.merge:
+        return "Error: --fidelity source compares against the one input file; it cannot be combined with --merge (use --fidelity written)."
+    if args.fidelity_views is not None and not (1 <= args.fidelity_views <= 1024):
+        return f"Error: --fidelity_views must be between 1 and 1024. Got {args.fidelity_views}."
+    if args.fidelity_size is not None and not all(1 <= v <= 8192 for v in args.fidelity_size):
+        return f"Error: --fidelity_size must be between 1 and 8192 per side. Got {args.fidelity_size[0]} {args.fidelity_size[1]}."
+    if args.fidelity_up is not None and args.fidelity_up.lower() not in PREVIEW_UP + ("x", "y", "z"):
+        return f"Error: --fidelity_up must be one of {' '.join(PREVIEW_UP)}. Got {args.fidelity_up}."
+    for c in args.fidelity_camera or []:
+        if not all(np.isfinite(v) for v in c) or list(c[:3]) == list(c[3:]):
+            return f"Error: --fidelity_camera must be six finite numbers with the eye apart from the target. Got {' '.join(f'{v:g}' for v in c)}."
+    if args.fidelity_camera is not None and args.fidelity_views is not None:
+        return "Error: --fidelity_camera replaces the ring; it cannot be combined with --fidelity_views."
+    return None
+
+
+def fidelity_kwargs(args) -> dict:
+    """Converter.run's fidelity keywords: none at all without --fidelity, and only the flags that were given"""
+    if args.fidelity is None:
+        return {}
+    out = {"fidelity": args.fidelity}
+    out.update({name: getattr(args, name) for name in ("fidelity_views", "fidelity_up", "fidelity_image") if getattr(args, name) is not None})
+    if args.fidelity_size is not None:
+        out["fidelity_size"] = tuple(args.fidelity_size)
+    if args.fidelity_camera is not None:
+        out["fidelity_cameras"] = [tuple(c) for c in args.fidelity_camera]
+    return out
+
+
 def view_kwargs(args) -> dict:
     """Converter.run's view-scoring keywords: only the flags that were given"""
     out = {name: getattr(args, name) for name in ("min_contribution", "rank_by", "views", "views_size", "views_elevation", "views_up")
@@ -378,7 +432,7 @@ def main(argv=None):
     if args.compression_level < 0 or args.compression_level > 9:
         print(f"Error: --compression_level must be between 0 and 9. Got {args.compression_level}.")
         return
-    preview_error = check_preview_args(args) or check_view_args(args)
+    preview_error = check_preview_args(args) or check_view_args(args) or check_fidelity_args(args)
     if preview_error:
         print(preview_error)
         return
@@ -432,7 +486,7 @@ def main(argv=None):
                           args.sh_level is not None, args.min_opacity, args.keep_multicluster,
                           args.rotate is not None, args.scale is not None, args.translate is not None, args.max_splats is not None,
                           args.decimate_voxel_size is not None, bool(merge_files), args.preview is not None,
-                          args.min_contribution is not None, args.rank_by == "views",
+                          args.min_contribution is not None, args.rank_by == "views", args.fidelity is not None,
                           has_source_extras and not args.extra_elements])
     is_same_extension = in_ext == os.path.splitext(args.output)[1].lower()
     if is_same_extension and args.target_format == "3dgs" and not filters_active and args.compression_level == 0 and not args.force:
@@ -469,7 +523,7 @@ def main(argv=None):
                       maintain_extra_elements=args.extra_elements, rotate=args.rotate, scale=args.scale, translate=args.translate,
                       max_splats=args.max_splats, **({"merge": merge_files, "merge_transforms": merge_transforms} if merge_files else {}),
                       **({"decimate_voxel_size": args.decimate_voxel_size} if args.decimate_voxel_size is not None else {}),
-                      **preview_kwargs(args), **view_kwargs(args))
+                      **preview_kwargs(args), **view_kwargs(args), **fidelity_kwargs(args))
         print("\n>>> TARGET FILE INFO")
         report_info(args.output)
     except Exception as e:   # noqa: BLE001  (:502)

@@ -13,6 +13,7 @@ readers, filter chain and writers: a file is converted on a machine that has thi
   | :263-288 extra elements, the handler's write      | the format's write_*                                                |
   | (none: the reference renders nothing)             | run(preview=...): the written table as a PNG (_write_preview)       |
   | (none: the reference ranks nothing by visibility) | run(min_contribution=, rank_by="views"): prune_by_views             |
+  | (none: the reference measures no loss)            | run(fidelity=...): PSNR and SSIM of the file (_measure_fidelity)    |
 
 The decoded rows stay in HBM from the reader to the end of the run (``Converter(..., resident=True)``, the default; readers'
 ``keep=``, _lib.ResidentRows): the chain's coordinates, the alpha filter's column and the colours' f_dc are gathered from them
@@ -40,6 +41,7 @@ CC_MARKERS = ("property float scal_f_dc_0", "property float scalar_scal_f_dc_0",
 
 
 VIEW_KEYWORDS = {"views": "views", "size": "views_size", "elevation": "views_elevation", "up": "views_up", "cameras": "view_cameras"}
+FIDELITY_KEYWORDS = ("views", "size", "up", "cameras", "image")     # run(fidelity_views=, ...): they need fidelity=
 
 
 def detect_format(path: str):
@@ -213,6 +215,7 @@ class Converter:
         self.profile = None
         self.stage_ms = {}          # the last run's stage clocks: read_*, process, write_*
         self.last_preview = {}      # the last run's preview: visible, instances, rows and the render plan (run(preview=...))
+        self.last_fidelity = {}     # the last run's fidelity.summarise result (run(fidelity=...)); {}: none asked for, or not measured
         self._loaded = None         # (path, handler, data, profile) of load_source_only: run() decodes the source no second time
 
     def _detect_format(self, path):
@@ -262,7 +265,10 @@ class Converter:
         whose rows follow the main source's in one table (_merge_sources), before everything else;
         and ``preview=PATH`` with ``preview_size=(w, h)``, ``preview_view=(azimuth, elevation)``, ``preview_up=``,
         ``preview_camera=(ex, ey, ez, tx, ty, tz)``, ``preview_fov=``: a PNG of the written table, rendered after the writer has
-        returned (_write_preview)"""
+        returned (_write_preview);
+        and ``fidelity="written" | "source"`` with ``fidelity_views=N``, ``fidelity_size=(w, h)``, ``fidelity_up=``,
+        ``fidelity_cameras=[(ex, ey, ez, tx, ty, tz), ...]``, ``fidelity_image=PATH``: PSNR and SSIM of the output file, read
+        back, against the written table or the moved source over a ring of views (_measure_fidelity), after the preview"""
         debug_print(f"[DEBUG] Starting conversion: {self.input_path} -> {self.output_path} ({self.target_format})")
         clocks = self.stage_ms = {}
         held = []                   # the processor of this run: whatever it still holds in HBM is freed on every exit path
@@ -378,9 +384,91 @@ class Converter:
         status_print(f"Preview: {image.shape[1]} x {image.shape[0]}, {info.get('visible', 0):,} of {info.get('rows', len(self.data)):,} splats visible, "
                      f"saved to {path}")
 
+    def _measure_fidelity(self, processor, source_format, opts, image_path, moved, clocks):
+        """``run(fidelity="written" | "source", fidelity_views=, fidelity_size=, fidelity_up=, fidelity_cameras=,
+        fidelity_image=)``: after the writer (and the preview) the output file is read back by this package's own reader for
+        the target format -- a fresh handler, its rows kept in HBM on the resident path -- and compared in image space with a
+        reference (fidelity.compare_tables).  'written': the reference is the table that was written, the rows
+        _write_preview renders, so the figures are the format's loss alone.  'source': the reference is the input file read a
+        second time by a fresh handler (the first load was changed in place), moved by the run's own transform and nothing
+        else, so the figures are everything the run did.  The cameras frame the reference's bounds.  ``last_fidelity``: the
+        result ({} when nothing was measured); clocks: fidelity_read, fidelity_transform, the render stages summed,
+        fidelity_compare.  fidelity_image: the worst view rendered once more for both tables and stored as one PNG of the
+        reference, the test and four times their difference side by side.  A view that needs more instance workspace than the
+        renderer's budget, or a table the renderer cannot take (render.plan_render's refusals: a missing geometry field, a
+        field that is not float32), prints a warning and the conversion still completes; any other error propagates.
+        Everything the comparison holds in HBM is freed on every exit path."""
+        from . import _lib, fidelity, render, transform, views
+        ms = {}
+        mode = opts["mode"]
+        view_kw = {k: opts[k] for k in ("views", "size", "elevation", "up", "fov", "cameras")}
+        handlers = []
+        try:
+            test_handler = self._get_format_handler(self.target_format)
+            handlers.append(test_handler)
+            with _lib.stage_clock(ms, "read"):
+                test = test_handler.read(self.output_path)
+            test = test_handler.resident if test_handler.resident is not None else test
+            if mode == "written":
+                rr = getattr(processor, "resident", None)
+                ref = rr if rr is not None else processor.data
+                what = f"written table vs {self.output_path}"
+            else:
+                ref_handler = self._get_format_handler(source_format)
+                handlers.append(ref_handler)
+                with _lib.stage_clock(ms, "read"):
+                    ref = ref_handler.read(self.input_path)
+                if moved is not None:
+                    plan = transform.plan_transform(ref.dtype, *moved)
+                    with _lib.stage_clock(ms, "transform"):
+                        if ref_handler.resident is not None:
+                            ref_handler.resident.transform(plan)
+                        else:
+                            ref = _lib.rows_transform_table(ref, plan)
+                ref = ref_handler.resident if ref_handler.resident is not None else ref
+                what = f"{self.input_path} vs {self.output_path}"
+            try:                    # (what the renderer cannot take of either table: asked before any device work)
+                probe = views.plan_views((0, 0, 0), (0, 0, 0), **view_kw)[0]
+                for t in (ref, test):
+                    render.plan_render(t.dtype, probe, background=fidelity.BACKGROUND)
+            except (ValueError, TypeError) as e:
+                status_print(f"Warning: fidelity not measured: {e}")
+                return
+            try:
+                res = fidelity.compare_tables(ref, test, stage_ms=ms, max_work_bytes=fidelity.MAX_WORK_BYTES, **view_kw)
+                if image_path is not None:
+                    cam = res["cameras"][res["worst_view"]]
+                    pair = []
+                    for t in (ref, test):
+                        plan = render.plan_render(t.dtype, cam, background=fidelity.BACKGROUND)
+                        pair.append(t.render(plan) if isinstance(t, _lib.ResidentRows) else _lib.render_table(t, plan))
+                    with _lib.stage_clock(ms, "png"):
+                        render.write_png(image_path, fidelity.side_by_side(*pair))
+            except render.RenderRefused as e:
+                status_print(f"Warning: fidelity not measured: {e}")
+                return
+        finally:
+            for h in handlers:
+                h.close()
+            clocks.update({"fidelity_" + k: v for k, v in ms.items()})
+        self.last_fidelity = res
+        status_print(fidelity.report_line(res, what))
+        if image_path is not None:
+            status_print(f"Fidelity image: view {res['worst_view']}, reference | test | 4 x difference, saved to {image_path}")
+
     def _run(self, clocks, held, kwargs):
         import time
         from .processing.data_processor import ChainedDataProcessor
+        # the fidelity options are checked first: a refusal comes before any file is read
+        fidelity_kw = {k: kwargs.pop("fidelity_" + k, None) for k in FIDELITY_KEYWORDS}
+        fidelity_mode = kwargs.pop("fidelity", None)
+        self.last_fidelity = {}
+        if fidelity_mode is None and any(v is not None for v in fidelity_kw.values()):
+            raise ValueError(f"{', '.join('fidelity_' + k for k, v in fidelity_kw.items() if v is not None)} need fidelity='written' or 'source'")
+        if fidelity_mode is not None:
+            from . import fidelity as _fidelity
+            fidelity_image = fidelity_kw.pop("image")
+            fidelity_opts = _fidelity.check_options(fidelity_mode, merge=kwargs.get("merge"), **fidelity_kw)
         with progress_bar() as pbar:
             source_format = self._detect_format(self.input_path)
             if not source_format:
@@ -417,11 +505,13 @@ class Converter:
             processor.cap_sh_degree(plan["final_degree"])
             # the scene transform is the first processing step: the box, the voxel size and SOR all work in the output frame
             rotate, scale, translate = kwargs.pop("rotate", None), kwargs.pop("scale", None), kwargs.pop("translate", None)
+            moved = None            # (rotation, s, translation) of the run's own transform: the fidelity's source reference takes it too
             if rotate is not None or scale is not None or translate is not None:
                 from . import transform
                 (rx, ry, rz), s, (tx, ty, tz) = transform_values(rotate, scale, translate)
                 status_print(f"Transform: {transform_text((rx, ry, rz), s, (tx, ty, tz))}")
-                processor.apply_transform(rotation=transform.rotation_from_euler_deg(rx, ry, rz), translation=(tx, ty, tz), scale=s)
+                moved = (transform.rotation_from_euler_deg(rx, ry, rz), s, (tx, ty, tz))
+                processor.apply_transform(rotation=moved[0], translation=moved[2], scale=s)
             pbar.update(5)
 
             pbar.set_description("Filtering")
@@ -498,6 +588,9 @@ class Converter:
             if preview_path is not None:
                 pbar.set_description("Rendering Preview")
                 self._write_preview(processor, preview_path, preview, clocks)
+            if fidelity_mode is not None:
+                pbar.set_description("Measuring Fidelity")
+                self._measure_fidelity(processor, source_format, fidelity_opts, fidelity_image, moved, clocks)
             pbar.update(40)
             pbar.refresh()
             pbar.set_description("Completed")

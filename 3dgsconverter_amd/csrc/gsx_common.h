@@ -210,7 +210,7 @@ struct gsx_ctx {
     //   work       the implementation an entry point dispatches to: kmeans_lloyd_dev, lloyd_batch_mfma (kmeans.hip),
     //              gsx_kmeans_pp_dev, kmeans1d_dev, lexsort3_dev (sog.hip), gsx_sog_scan_dev, gsx_sog_extremes_dev,
     //              gsx_sog_order_dev (sog_table.hip), morton_order_dev (cply.hip), gsx_rows_transform_dev, gsx_dev_patch_u8
-    //              (resident_rows.hip), and density.hip's density_voxels_dev, density_hist_dev, density_merge_dev,
+    //              (resident_rows.hip), gsx_image_compare_dev (fidelity.hip: its six sums), and density.hip's density_voxels_dev, density_hist_dev, density_merge_dev,
     //              density_mask_dev, density_filter_dev, density_filter_large_dev, voxel_clusters_dev (the last three end in a
     //              retry of themselves at most once, as a tail call: nothing of the first attempt is used after it)
     //   work_sub   helpers of those, sized by what their caller computed into `work` first: launch_assign_mfma_t (kmeans.hip),

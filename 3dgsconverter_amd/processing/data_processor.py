@@ -30,6 +30,7 @@ import numpy as np
 
 from .. import _lib
 from .. import decimate as _decimate
+from .. import fidelity as _fidelity
 from .. import render as _render
 from .. import transform as _transform
 from .. import views as _views
@@ -807,6 +808,28 @@ class DataProcessor:
             image = _lib.render_table(data, plan, stage_ms=stage_ms, info=info)
         self.last_preview = dict(info, plan=plan)
         return image
+
+    # ------------------------------------------------------------------ fidelity against another table (no counterpart in the reference)
+    def compare_with(self, other, views=_fidelity.DEFAULT_VIEWS, size=_fidelity.DEFAULT_SIZE, elevation=_views.DEFAULT_ELEVATION, up="-y",
+                     fov=50, cameras=None, lo=None, hi=None, stage_ms=None, max_work_bytes=_render.DEFAULT_MAX_WORK_BYTES):
+        """-> the image-space loss of `other` (a host table or _lib.ResidentRows, left as it is) against this processor's
+        table as it stands, the reference: both are rendered through views.plan_views of this table's bounding box (or of the
+        box `lo` ... `hi`; explicit `cameras` replace the ring) and compared on the device (fidelity.compare_tables; DESIGN.md
+        6u).  With resident rows they are rendered where they lie; otherwise the host table is uploaded once, as
+        render_preview does.  ``.data`` is unchanged.  Every refusal of the options and of render.plan_render for either table
+        comes before any device work; render.RenderRefused when a view needs more instance workspace than `max_work_bytes`.
+        ``last_fidelity``: the result."""
+        debug_print("[DEBUG] Executing 'compare_with'...")
+        data, rr = self.data, self.resident
+        if not isinstance(data, np.ndarray) or data.dtype.fields is None:
+            raise TypeError("self.data must be a numpy structured array.")
+        opts = _fidelity.check_options(views=None if cameras is not None else views, size=size, elevation=elevation, up=up, fov=fov,
+                                       cameras=cameras)
+        res = _fidelity.compare_tables(rr if rr is not None else data, other, views=opts["views"], size=opts["size"],
+                                       elevation=opts["elevation"], up=opts["up"], fov=opts["fov"], cameras=opts["cameras"], lo=lo, hi=hi,
+                                       max_work_bytes=max_work_bytes, stage_ms=stage_ms)
+        self.last_fidelity = res
+        return res
 
     # ------------------------------------------------------------------ table-shaping methods (SURVEY.md 8(f) rank 4)
     def cap_sh_degree(self, degree):

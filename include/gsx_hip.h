@@ -1347,6 +1347,30 @@ int gsx_view_keys_dev(gsx_ctx *ctx, const uint64_t *total_dev, int64_t n, uint32
 /* the same on the HOST, from the same function; HOST pointers, serial. */
 int gsx_view_keys_host(const uint64_t *total, int64_t n, uint32_t *keys);
 
+
+/* ---- fidelity: two rendered images compared in integers (csrc/fidelity.hip; --fidelity) ----
+ * No reference counterpart: the definition is this project's own (tests/fidelity_numpy.py) and the device
+ * reproduces it bit for bit.  A and B are height x width x 3 uint8 images (RGB, row 0 the top, rows packed).  Nine words:
+ *   out_words[0..2]  sse[c]: the sum over all pixels of (A - B)^2 in channel c (< 2^43)
+ *   out_words[3]     windows: (height - 7) * (width - 7) when both sides are at least 8, else 0 -- every 8 x 8 box at stride 1
+ *   out_words[4..6]  ssim[c]: the sum over the windows of q = floor(r1 * r2 * 2^32), a signed 32.32 fixed-point SSIM.  With the
+ *                    window's integer sums Sa, Sb, Saa, Sbb, Sab over its N = 64 pixels, c1 = 26634 and c2 = 239708:
+ *                    r1 = f64(2 Sa Sb + c1) / f64(Sa^2 + Sb^2 + c1), r2 = f64(2 (N Sab - Sa Sb) + c2) / f64((N Saa - Sa^2) +
+ *                    (N Sbb - Sb^2) + c2): four integers below 2^31, two correctly rounded divisions, one product, no fma
+ *   out_words[7..8]  0
+ * The addends are integers, so the words do not depend on the order of summation. */
+enum { GSX_FIDELITY_WORDS = 9, GSX_FIDELITY_TILE = 32, GSX_FIDELITY_MAX_SIDE = 8192 };
+/* a_dev, b_dev: the images in HBM (any alignment; only their height * width * 3 bytes are read).  One launch over tiles of
+ * GSX_FIDELITY_TILE x GSX_FIDELITY_TILE pixels and window origins: both images' (T + 7) x (T + 7) x 3 bytes staged in LDS, the
+ * window sums built separably, the six sums reduced in the wave, then in LDS, then by one 64-bit integer atomicAdd per workgroup
+ * and quantity.  Tiles over the right and bottom edge and images narrower or shorter than 8 (windows = 0) are the kernel's to
+ * handle.  out_words: HOST, GSX_FIDELITY_WORDS int64.  stage_ms (HOST, one float, or NULL): the stream clock of the launch is
+ * ADDED to it.  width, height in 1 ... GSX_FIDELITY_MAX_SIDE.  Synchronises the context's stream (the one readback). */
+int gsx_image_compare_dev(gsx_ctx *ctx, const void *a_dev, const void *b_dev, int32_t width, int32_t height, int64_t *out_words,
+                          float *stage_ms);
+/* the same on the HOST, from the same per-window function; HOST pointers, serial, only the images' bytes are read. */
+int gsx_image_compare_host(const void *a, const void *b, int32_t width, int32_t height, int64_t *out_words);
+
 #ifdef __cplusplus
 }
 #endif

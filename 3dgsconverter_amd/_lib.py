@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("GSX_LIB_PATH") or os.path.join(_HERE, "libgsx_hip.so"
 
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_TREE = 0, 1, 2, 3
 PROBE_ROOT_DIST2, PROBE_ROOT_DSQRT = 0, 1                                    # gsx_knn_probe_root_dev modes
+PROBE_SHORT_ROOT, PROBE_SHORT_SEED = 0, 1                                    # gsx_knn_probe_root_short_dev modes
 PROBE_MEAN_NET, PROBE_MEAN_LIST, PROBE_MEAN_LE128, PROBE_MEAN_NP = 0, 1, 2, 3   # gsx_knn_probe_mean_dev forms
 T_SOR_KNN, T_SOR_BIN, T_SOR_FALLBACK, T_SOR_STATS, T_DENSITY, T_KMEANS_ASSIGN, T_KMEANS_UPDATE, T_QUANTIZE = range(8)
 T_SLAB_PREP, T_SLAB_ROWS, T_SLAB_MEANS, T_SLAB_COLL = range(8, 12)   # multi-GPU slab step (round 5)
@@ -306,6 +307,7 @@ SIGNATURES = {
     "gsx_sor_debug_group_bricks": (_I, [_P, _I64, _I, _I, _I, _P, C.POINTER(C.c_int32)]),
     "gsx_sor_debug_refine_sizing": (_I, [C.POINTER(RefineSizingIn), C.POINTER(RefineSizingOut)]),
     "gsx_knn_probe_root_dev": (_I, [_P, _P, _I64, _I, _P]),
+    "gsx_knn_probe_root_short_dev": (_I, [_P, _P, _I64, _I, _P]),
     "gsx_knn_probe_mean_dev": (_I, [_P, _P, _I64, _I64, _I, _I, _I, _P]),
     "gsx_sor_stats_dev": (_I, [_P, _P, _I64, _D, _P]),
     "gsx_sor_mask_dev": (_I, [_P, _P, _I64, _P, _P]),
@@ -3993,6 +3995,11 @@ class Context:
     def knn_probe_root(self, values: int, n: int, mode: int, out: int):
         """debug / tests: out[i] = float64 root of values[i] (device pointers); mode 0 sqrt_rn_dist2, 1 __dsqrt_rn"""
         check(self.lib.gsx_knn_probe_root_dev(self.handle, values, int(n), int(mode), out), "gsx_knn_probe_root_dev")
+
+    def knn_probe_root_short(self, values: int, n: int, mode: int, out: int):
+        """debug / tests: out[i] = sqrt_short_dist2(values[i]) (PROBE_SHORT_ROOT, the certified epilogue's root) or the
+        v_rsq_f64 seed it starts from (PROBE_SHORT_SEED); device pointers"""
+        check(self.lib.gsx_knn_probe_root_short_dev(self.handle, values, int(n), int(mode), out), "gsx_knn_probe_root_short_dev")
 
     def knn_probe_mean(self, d2: int, m: int, stride: int, k: int, form: int, cap: int, out: int):
         """debug / tests: float32 row means of m rows of ascending float64 squared distances (device pointers) through one

@@ -282,6 +282,8 @@ int gsx_ctx_set_param(gsx_ctx *c, const char *name, double value)
         c->defer_words = (int)value;
     } else if (!strcmp(name, "brick_plan")) {
         c->brick_plan = value != 0.0;
+    } else if (!strcmp(name, "epilogue_cert")) {
+        c->epilogue_cert = value != 0.0;
     } else if (!strcmp(name, "filter_mfma")) {
         c->filter_mfma = value != 0.0;
     } else {

@@ -187,6 +187,8 @@ struct gsx_ctx {
     int phase2_net = 1;  // knn_brick phase 2: 1 = sorting-network block selection (TopNet), 0 = per-candidate bubble insert (A/B only)
     int brick_plan = 1;  // knn_brick on planned bricks (runs of quarter-cell slabs holding at most 64 queries) where the call allows it: the plain
                          // single-cloud call, k <= 16, MFMA filter + network selection (0: the fixed 2x2x2-cell bricks everywhere; A/B)
+    int epilogue_cert = 1;   // knn_brick, k = 16 on the network list: certify the float32 mean of short roots, re-sort and round exactly only
+                             // where the certificate fails (0: full merge and mean_from_net throughout; A/B and tests)
     int ws_cap = 0;      // -DGSX_WAVE_STAMPS builds: record slots per kernel of the last grid KNN call
     int wq_grid[4] = {0, 0, 0, 0};   // workgroups of the last knn_brick, knn_brick (second batches), knn_ring and knn_ring_fast launches (debug)
     int filter_mfma = 1; // knn_brick phase 1: 1 = bf16-split MFMA filter for batches whose mask words fit LDS, 0 = scalar-load f32 VALU filter only

@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "knn_mean_cert.h"
+
 namespace gsx {
 
 // Relative slack on f32 squared distances.  fl32 error of ((dx*dx)+dy*dy)+dz*dz with
@@ -243,6 +245,38 @@ struct TopNet {
             for (int p = OFF; p < P; ++p)   // (positions below OFF hold -inf)
                 if ((p & half) == 0) ce_f64(a[p - OFF], a[p + half - OFF]);
     }
+    // The wave's LAST block of a batch, where nothing downstream needs the order (mean_from_net_cert): the block's minima are
+    // taken as in merge_block and the half-cleaner stages are left out.  The list then holds the L smallest as a SET --
+    // a[0 .. L-BS-1] ascending, a[L-BS .. L-1] bitonic -- until sort_set() runs the stages after all.
+    __device__ __forceinline__ void merge_block_last(double (&b)[BS])
+    {
+        oe_sort<BS, 0, BS>(b);
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            double c;
+            asm("v_min_f64 %0, %1, %2" : "=v"(c) : "v"(a[L - BS + i]), "v"(b[BS - 1 - i]));
+            a[L - BS + i] = c;
+        }
+    }
+    // the largest entry of a list merge_block_last (or nothing: a sorted list) left as a set: what a[L - 1] is once sorted,
+    // bit for bit (max is exact)
+    __device__ __forceinline__ double kth_of_set() const
+    {
+        static_assert(L > BS, "the set form needs a sorted head");
+        double r = a[L - BS - 1];
+#pragma unroll
+        for (int i = L - BS; i < L; ++i) asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(r), "v"(a[i]));
+        return r;
+    }
+    // merge_block's half-cleaner stages on their own: a set form comes out sorted, a sorted list passes through untouched
+    __device__ __forceinline__ void sort_set()
+    {
+#pragma unroll
+        for (int half = P / 2; half >= 1; half /= 2)
+#pragma unroll
+            for (int p = OFF; p < P; ++p)
+                if ((p & half) == 0) ce_f64(a[p - OFF], a[p + half - OFF]);
+    }
 };
 
 // Correctly rounded float64 square root for the squared distances of knn_brick's epilogue: the compiler's own
@@ -266,6 +300,21 @@ __device__ __forceinline__ double sqrt_rn_dist2(double x)
     g = __builtin_fma(d, h, g);
     d = __builtin_fma(-g, g, x);
     return __builtin_fma(d, h, g);
+}
+
+// sqrt_rn_dist2 up to and including its first Goldschmidt line, no residual correction (and no second line for h, which only the
+// corrections read): 6 instead of 11 float64-rate instructions.  With a seed y = (1 + e0) / sqrt(x) the result is sqrt(x) (1 - 1.5 e0^2 + O(u)); what e0 is on this hardware
+// is measured (gsx_knn_probe_root_short_dev, profiles/epilogue_cert_ab.txt), and the bound the certificate works with
+// (knn_mean_cert.h: KNN_SHORT_ROOT_BOUND) is 64 times the largest error seen.  x = 0 still gives 0.
+__device__ __forceinline__ double sqrt_short_dist2(double x)
+{
+    double xs;
+    asm("v_max_f64 %0, %1, %2" : "=v"(xs) : "v"(x), "v"(1e-300));
+    const double y = __builtin_amdgcn_rsq(xs);
+    double g = x * y;
+    const double h = 0.5 * y;
+    const double r = __builtin_fma(-h, g, 0.5);
+    return __builtin_fma(g, r, g);
 }
 
 // the last line of every epilogue: the f64 sum of the k roots -> (float)(sum / k), an IEEE f64 divide and one rounding to f32
@@ -315,6 +364,32 @@ __device__ __forceinline__ float mean_from_net(const TopNet<L> &lst, int k_arg)
             if (j >= nfull && j < k) res = __dadd_rn(res, b[j]);
     }
     return mean_finish(res, k);
+}
+
+// knn_brick's epilogue for k = L = 16 on a list left as a set (TopNet::merge_block_last) or sorted: short roots, one sum in
+// the 8-accumulator shape (the order does not matter here), and the certificate of knn_mean_cert.h.  Where any lane of the
+// wave is not certain -- a float32 rounding boundary within 2^-41.8 (relative) of its mean, some six queries in a million -- the wave sorts the
+// list after all and takes mean_from_net: the parent's path, the parent's bits.  `exact` reports that branch (wave-uniform;
+// read by profiling builds only).
+template <int L>
+__device__ __forceinline__ float mean_from_net_cert(TopNet<L> &lst, bool &exact)
+{
+    static_assert(L == 16, "the certificate is derived for 16 roots");
+    double r[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) r[t] = sqrt_short_dist2(lst.a[t]);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) r[t] = __dadd_rn(r[t], sqrt_short_dist2(lst.a[8 + t]));
+    const double sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
+                                 __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
+    const MeanCert c = mean_cert16<KnnMeanEps>(sum);
+    float f = c.f;
+    exact = __any(!c.certain);
+    if (exact) {
+        lst.sort_set();
+        f = mean_from_net(lst, L);
+    }
+    return f;
 }
 
 // numpy pairwise sum of n <= 128 doubles read through a functor (loops_utils.h.src);

@@ -24,6 +24,23 @@ __global__ __launch_bounds__(256) void probe_root_kernel(const double *__restric
         out[i] = MODE == 0 ? sqrt_rn_dist2(in[i]) : __dsqrt_rn(in[i]);
 }
 
+// the short root of the certified epilogue (MODE 0) and the hardware seed it starts from (MODE 1: what sqrt_short_dist2 and
+// sqrt_rn_dist2 both take v_rsq_f64 of)
+template <int MODE>
+__global__ __launch_bounds__(256) void probe_root_short_kernel(const double *__restrict__ in, int64_t n, double *__restrict__ out)
+{
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        if constexpr (MODE == 0) {
+            out[i] = sqrt_short_dist2(in[i]);
+        } else {
+            double xs;
+            asm("v_max_f64 %0, %1, %2" : "=v"(xs) : "v"(in[i]), "v"(1e-300));
+            out[i] = __builtin_amdgcn_rsq(xs);
+        }
+    }
+}
+
 // knn_brick / knn_leaf: the list holds the L nearest NEIGHBOURS' squared distances (entries past the row: +inf, as init() leaves them)
 template <int L>
 __global__ __launch_bounds__(PROBE_THREADS) void probe_net_kernel(const double *__restrict__ d2, int64_t m, int64_t stride, int k,
@@ -109,6 +126,18 @@ int gsx_knn_probe_root_dev(gsx_ctx *c, const double *in_dev, int64_t n, int mode
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n, 256), (int64_t)c->num_cu * 8));
     if (mode == GSX_PROBE_ROOT_DIST2) hipLaunchKernelGGL(probe_root_kernel<0>, dim3(blocks), dim3(256), 0, c->stream, in_dev, n, out_dev);
     else hipLaunchKernelGGL(probe_root_kernel<1>, dim3(blocks), dim3(256), 0, c->stream, in_dev, n, out_dev);
+    GSX_HIP(hipGetLastError());
+    return 0;
+}
+
+int gsx_knn_probe_root_short_dev(gsx_ctx *c, const double *in_dev, int64_t n, int mode, double *out_dev)
+{
+    if (!c || !in_dev || !out_dev || n <= 0) GSX_FAIL("gsx_knn_probe_root_short_dev: bad arguments");
+    if (mode != GSX_PROBE_SHORT_ROOT && mode != GSX_PROBE_SHORT_SEED) GSX_FAIL("gsx_knn_probe_root_short_dev: unknown mode %d", mode);
+    GSX_HIP(hipSetDevice(c->device));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(div_up(n, 256), (int64_t)c->num_cu * 8));
+    if (mode == GSX_PROBE_SHORT_ROOT) hipLaunchKernelGGL(probe_root_short_kernel<0>, dim3(blocks), dim3(256), 0, c->stream, in_dev, n, out_dev);
+    else hipLaunchKernelGGL(probe_root_short_kernel<1>, dim3(blocks), dim3(256), 0, c->stream, in_dev, n, out_dev);
     GSX_HIP(hipGetLastError());
     return 0;
 }

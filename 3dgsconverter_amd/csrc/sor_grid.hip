@@ -1075,13 +1075,18 @@ constexpr int brick_min_waves(int kcap, bool mf, bool net)
 // quarter indices of p and q differ by at most 4 -- the cell argument of r_safe with dim = 4 nx.  Where brick_plan withdrew
 // the plan (gp->plan == 0) the same kernel takes the fixed bricks as the aligned runs [8 bx, 8 bx + 7]: fine_start[4 c] is
 // cell_start[c], the rows are the fixed brick's.
-template <int KCAP, bool EXTRA, bool MF, bool NET, bool PLAN = false>
+// CERT (k = 16 on the 16-entry network list, no kth_out; the context's epilogue_cert): the wave's last block of a batch is
+// merged without the re-sort (TopNet::merge_block_last) and the epilogue certifies the float32 mean of short roots
+// (mean_from_net_cert, knn_mean_cert.h), recomputing exactly in the same wave where it cannot.  Acceptance sees the same k-th
+// distance, so the fail list is the same.
+template <int KCAP, bool EXTRA, bool MF, bool NET, bool PLAN = false, bool CERT = false>
 __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void knn_brick_kernel(
     GridParams *__restrict__ gp, const float4 *__restrict__ refs, const unsigned *__restrict__ rstart,
     const float4 *__restrict__ qpts, const unsigned *__restrict__ qstart, int k, int q_begin,
     float *__restrict__ mean_out, unsigned *__restrict__ faillist, uint2 *__restrict__ extra,
     unsigned *__restrict__ deferred, double *__restrict__ kth_out, const uint2 *__restrict__ plist)
 {
+    static_assert(!CERT || (NET && KCAP == 17), "the certified epilogue is derived for the 16-entry network list");
     constexpr int WCAP = KCAP > 33 ? GSX_WCAP_BIG : (KCAP > 17 ? GSX_WCAP_MID : gsx::WCAP);
     __shared__ unsigned s_mask[BRICK_THREADS / 64][WCAP][64];
     // per mask word: first candidate (index into refs); (c1, b2 - c1): candidates of the first row segment and the
@@ -1370,7 +1375,9 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
             unsigned nzw = 0;
 
             // ---- phase 2: walk this lane's set bits, exact f64 distance, sorted insert
-            auto drain = [&]() __attribute__((always_inline)) {
+            // (final_drain: std::true_type for the batch's last call -- CERT leaves the list as a set there)
+            auto drain = [&](auto final_drain) __attribute__((always_inline)) {
+                constexpr bool SET_FORM = CERT && decltype(final_drain)::value;
                 // widened here, not before phase 1: six registers that the filter loop does not have to carry
                 const double qxd = (double)qx, qyd = (double)qy, qzd = (double)qz;
                 wave_sync();  // wbase[] written by lane 0 is visible to every lane
@@ -1422,9 +1429,19 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                                 blk[h0 + j] = (ok[j] && __float_as_uint(pt[j].w) != self_w) ? d : __builtin_inf();
                             }
                         }
+                        if constexpr (SET_FORM) {
+                            // merge_block in its two halves, the loop's exit between them: the wave's last block leaves
+                            // the list as a set
+                            const bool first = uniform((int)lst_empty);
+                            if (first) lst.assign_block(blk); else lst.merge_block_last(blk);
+                            lst_empty = false;
+                            if (!__any(m != 0 || nzw != 0)) break;
+                            if (!first) lst.sort_set();
+                        } else {
                         if (uniform((int)lst_empty)) lst.assign_block(blk); else lst.merge_block(blk);
                         lst_empty = false;
                         if (!__any(m != 0 || nzw != 0)) break;
+                        }
                     }
                 } else {
                 // software pipeline: the gather of candidate n+1 is in flight while candidate n goes
@@ -1456,7 +1473,7 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                     have_cur = have_next;
                 }
                 }
-                tau = fminf(tau, bound_from(lst.kth(kq)));
+                if constexpr (!SET_FORM) tau = fminf(tau, bound_from(lst.kth(kq)));   // (nothing filters after the final drain)
                 widx = 0;
                 nzw = 0;
                 wave_sync();  // all reads of mask/wbase done before they are overwritten
@@ -1642,7 +1659,7 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 const int gs = __builtin_amdgcn_readlane(rs_start, r);
                 const int len = __builtin_amdgcn_readlane(rs_len, r);
                 for (int w0 = 0; w0 < len; w0 += 32) {
-                    if (widx == WCAP) drain();
+                    if (widx == WCAP) drain(std::false_type{});
                     const int c = min(32, len - w0);
                     const float4 *__restrict__ p = refs + gs + w0;
                     const float neg_tau = -tau;  // dead lanes: tau = -1 => t > 0 => bit 0
@@ -1674,19 +1691,30 @@ __global__ __launch_bounds__(BRICK_THREADS, brick_min_waves(KCAP, MF, NET)) void
                 }
             }
             }
-            drain();
+            drain(std::true_type{});
 
             // ---- exact iff the (k+1)-th distance lies inside the searched cells
             if (is_query) {
-                const double kth_d2 = lst.kth(kq);
+                double kth_d2;
+                if constexpr (CERT) kth_d2 = lst.kth_of_set();   // k = 16 = the list's length: its largest entry, sorted or not
+                else kth_d2 = lst.kth(kq);
                 if (dbg & 8) {
                     if (kth_d2 == 12345.0) mean_out[0] = 1.0f;  // keeps the list live, writes nothing
                 } else if (dbg & 4) {
                     mean_out[(int)__float_as_uint(qp.w) - q_begin] = (float)kth_d2;
                 } else if (kth_d2 <= racc_sq) {
+                    if constexpr (CERT) {   // (kth_out is null here: dispatch_bricks)
+                        bool exact;
+                        mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_from_net_cert(lst, exact);
+#ifdef GSX_ABLATE
+                        if ((dbg & 128) && exact && lane == __builtin_ctzll(__ballot(1))) atomicAdd(&gp->exhaustive_count, 1u);   // profiling: batches on the exact branch
+#endif
+                        (void)exact;
+                    } else {
                     kth_emit<NET>(gp, kth_out, (int)__float_as_uint(qp.w) - q_begin, kth_d2, qx, qy, qz);
                     if constexpr (NET) mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_from_net(lst, k);
                     else mean_out[(int)__float_as_uint(qp.w) - q_begin] = mean_from_list<KCAP>(lst, k);
+                    }
                 } else {
                     unsigned slot = atomicAdd(&gp->fail_count, 1u);
                     faillist[slot] = (unsigned)qidx;
@@ -2439,7 +2467,7 @@ struct BrickLaunch {
     const uint2 *plist = nullptr;
 };
 
-template <int KCAP, bool MF, bool NET, bool PLAN = false>
+template <int KCAP, bool MF, bool NET, bool PLAN = false, bool CERT = false>
 static int launch_bricks(gsx_ctx *ctx, const BrickLaunch &a)
 {
     const unsigned *rstart = PLAN ? a.fstart : a.rstart, *qstart = PLAN ? a.fstart : a.qstart;
@@ -2448,18 +2476,18 @@ static int launch_bricks(gsx_ctx *ctx, const BrickLaunch &a)
     // workgroup would run its share only after a resident one has finished all of its own).
     static int occ_brick = 0, occ_extra = 0;
     if (!occ_brick) {
-        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_brick, knn_brick_kernel<KCAP, false, MF, NET, PLAN>, BRICK_THREADS, 0));
-        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_extra, knn_brick_kernel<KCAP, true, MF, NET, PLAN>, BRICK_THREADS, 0));
+        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_brick, knn_brick_kernel<KCAP, false, MF, NET, PLAN, CERT>, BRICK_THREADS, 0));
+        GSX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_extra, knn_brick_kernel<KCAP, true, MF, NET, PLAN, CERT>, BRICK_THREADS, 0));
         occ_brick = std::max(1, std::min(occ_brick, 8));
         occ_extra = std::max(1, std::min(occ_extra, 8));
     }
     ctx->wq_grid[0] = ctx->num_cu * occ_brick;
     ctx->wq_grid[1] = ctx->num_cu * occ_extra;
     GSX_CHECK(timing_begin(ctx, GSX_T_SOR_KNN));
-    hipLaunchKernelGGL((knn_brick_kernel<KCAP, false, MF, NET, PLAN>), dim3(ctx->num_cu * occ_brick), dim3(BRICK_THREADS), 0, ctx->stream,
+    hipLaunchKernelGGL((knn_brick_kernel<KCAP, false, MF, NET, PLAN, CERT>), dim3(ctx->num_cu * occ_brick), dim3(BRICK_THREADS), 0, ctx->stream,
                        a.gp, a.refs, rstart, a.qpts, qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
                        a.deferred, a.kth_out, a.plist);
-    hipLaunchKernelGGL((knn_brick_kernel<KCAP, true, MF, NET, PLAN>), dim3(ctx->num_cu * occ_extra), dim3(BRICK_THREADS), 0, ctx->stream,
+    hipLaunchKernelGGL((knn_brick_kernel<KCAP, true, MF, NET, PLAN, CERT>), dim3(ctx->num_cu * occ_extra), dim3(BRICK_THREADS), 0, ctx->stream,
                        a.gp, a.refs, rstart, a.qpts, qstart, a.k, (int)a.q_begin, a.mean_out, a.faillist, a.extra,
                        a.deferred, a.kth_out, a.plist);
     GSX_HIP(hipGetLastError());
@@ -2808,10 +2836,12 @@ static int dispatch_heavy(gsx_ctx *ctx, KnnWs &w, const BrickLaunch &a, int64_t 
 static int dispatch_bricks(gsx_ctx *ctx, const BrickLaunch &a, bool mf, bool net)
 {
     const int kk = a.k + 1;
+    // the certified epilogue: the 16-entry network list at k = 16, mean distances only
+    const bool cert = ctx->epilogue_cert != 0 && a.k == 16 && !a.kth_out;
     if (a.plist) {   // planned bricks: knn_grid_level allows them for the MFMA + network kernels of 2x2x2-cell bricks only
         if (kk <= 9) return launch_bricks<9, true, true, true>(ctx, a);
         if (GSX_CAP4 && kk <= 13) return launch_bricks<13, true, true, true>(ctx, a);
-        return launch_bricks<17, true, true, true>(ctx, a);
+        return cert ? launch_bricks<17, true, true, true, true>(ctx, a) : launch_bricks<17, true, true, true>(ctx, a);
     }
     if (net) {
 #define GSX_BRICKS(K) (mf ? launch_bricks<K, true, true>(ctx, a) : launch_bricks<K, false, true>(ctx, a))
@@ -2819,6 +2849,7 @@ static int dispatch_bricks(gsx_ctx *ctx, const BrickLaunch &a, bool mf, bool net
         //  and the default is 25: -5 % of the step at k = 25 with 28 entries instead of 32, profiles/r05_variants.txt)
         if (kk <= 9) return GSX_BRICKS(9);
         if (GSX_CAP4 && kk <= 13) return GSX_BRICKS(13);
+        if (cert) return mf ? launch_bricks<17, true, true, false, true>(ctx, a) : launch_bricks<17, false, true, false, true>(ctx, a);
         if (kk <= 17) return GSX_BRICKS(17);
         if (GSX_CAP4 && kk <= 21) return GSX_BRICKS(21);
         if (kk <= 25) return GSX_BRICKS(25);   // 24 and 48 entries: the reference CLI's k = 18 ... 24 and 33 ... 48

@@ -111,7 +111,9 @@ int  gsx_ctx_get_timing(gsx_ctx *ctx, int slot, uint64_t *launches, double *tota
  * "tree_scale" (0, default: the tree path's density probe stretches the key grid by up to 2x so that the leaves of
  * a cloud with one dominant density are cubes of ~50 points; f > 0: that factor, no probe -- A/B; results are
  * bit-identical for every value), "filter_mfma" (1 = matrix-core phase-1 filter, default), "brick_plan" (1 = knn_brick on planned bricks where the call allows them, default; 0 = the fixed bricks; bit-identical
- * either way), "timing_mask" (bit s set = slot
+ * either way), "epilogue_cert" (1 = knn_brick at k = 16 certifies the float32 mean of short float64 roots and
+ * recomputes exactly where it cannot, default; 0 = the exact epilogue throughout; bit-identical either way),
+ * "timing_mask" (bit s set = slot
  * GSX_T_s records events while timing is enabled; default all -- every event pair costs stream time),
  * "tree_leaf_cap" (0, default: points per leaf of the tree path by k -- 64 up to k = 28, 96 up to 34, 128 above; 64 ... 256: that
  * capacity; results are bit-identical for every value), "tree_cand_limit" (candidates per 64 points of leaf capacity above which
@@ -299,6 +301,10 @@ int gsx_sor_debug_refine_sizing(const gsx_refine_sizing_in *in, gsx_refine_sizin
  * SPZ / compressed-PLY readers take it (__dsqrt_rn). */
 enum { GSX_PROBE_ROOT_DIST2 = 0, GSX_PROBE_ROOT_DSQRT = 1 };
 int gsx_knn_probe_root_dev(gsx_ctx *ctx, const double *in_dev, int64_t n, int mode, double *out_dev);
+/* The short root of knn_brick's certified epilogue (sqrt_short_dist2: no residual correction; same domain) or its seed alone:
+ * out[i] = v_rsq_f64(max(in[i], 1e-300)), whose relative error against 1 / sqrt decides the short root's. */
+enum { GSX_PROBE_SHORT_ROOT = 0, GSX_PROBE_SHORT_SEED = 1 };
+int gsx_knn_probe_root_short_dev(gsx_ctx *ctx, const double *in_dev, int64_t n, int mode, double *out_dev);
 /* Mean: d2_dev holds m rows of `stride` >= k ascending squared distances of a query's neighbours (the query itself is not
  * in the row); out_dev[r] = (float)(sum of the roots of row r's first k entries / k), summed the way `form` does:
  *   NET    mean_from_net<cap>: cap = a list length of knn_brick / knn_leaf (8, 12, 16, ... 56, 64), k <= cap; row entries
